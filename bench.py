@@ -8,6 +8,11 @@ One *step* = one minibatch policy update exactly as examples/torchrl/train.py:25
 (HEPi actor + DeepSets critic + projection), actor and critic backward, gradient all-reduce when N > 1, two Adam updates.
 Workload: rigid_insertion_multi_hepi_trpl, 4096 envs x 128 steps, minibatch = 4096 frames (one frame per env), fp32.
 Multi-GPU: the 4096-frame minibatch is sharded over the ranks (strong scaling), one RCCL all-reduce of the flat gradient.
+
+A plain run sets up, warms up, times --steps steps once and prints the line.  --full adds everything else the line can carry: box
+calibration before and after the timed region, the determinism self-check, seven repeats of the timed region, warm advantage-pass and GAE
+timings, the data-parallel collective log, the per-kernel roofline leg and (N = 1) the parity gate and the CPU baseline.
+--dump-outputs DIR writes the last timed step's outputs as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -270,13 +275,37 @@ def syn_fields(B, A):
     return syn.make_ppo_fields(B, A, seed=1)
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """``arrays`` {name: tensor} -> out_dir/<name>.npy, float64 tensors as float64 and every other one as float32.  An array larger than its
+    equal share of DUMP_BYTES is replaced by a fixed, seeded sample of its rows (same rows in every run), so that the dump stays within
+    DUMP_BYTES at any minibatch size."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    share = DUMP_BYTES // len(arrays)
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach().cpu()
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        if t.numel() * t.element_size() > share:
+            row_bytes = (t[0].numel() if t.dim() > 1 else 1) * t.element_size()
+            keep = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:max(1, share // row_bytes)]
+            t = t[keep.sort().values]
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=8)
-    ap.add_argument("--repeats", type=int, default=7, help="the timed region of --steps steps is repeated this many times back to back; "
-                    "`value` is the MEDIAN repeat (every repeat is listed in the line)")
+    ap.add_argument("--full", action="store_true", help="measure and check everything beyond the headline figure (see the module docstring)")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed region of --steps steps is repeated this many times back to back; "
+                    "`value` is the MEDIAN repeat (every repeat is listed in the line); default 1, with --full 7")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed region, write what its last step returned (every "
+                    "entry of the loss dict: losses, loc, sigma, state_value, ...) and the updated flat parameter vector as DIR/<name>.npy")
     ap.add_argument("--workload", default="rigid_hepi")
     ap.add_argument("--minibatch", type=int, default=4096, help="global frames per policy update (= num_envs)")
     ap.add_argument("--pool", type=int, default=128, help="time steps of the synthetic device-resident rollout the minibatches are "
@@ -293,6 +322,8 @@ def main():
     ap.add_argument("--dp-plan", action="store_true", help="one GPU, but the DATA-PARALLEL program of the step: a one-rank RCCL process group, "
                     "every collective issued, graph segments between them -- what a shard's step costs before any inter-GPU latency")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 7 if args.full else 1
 
     # ---- `python bench.py --gpus N` outside a launcher: start the N ranks ourselves.  Nothing above has touched the GPU (no HIP call,
     #      no torch.cuda query), so the child launcher and its ranks are ordinary fresh processes; this process only relays their
@@ -344,13 +375,13 @@ def main():
     from geometry_rl_amd import agent, hip, synthetic as syn
     spec, cfg, make_obs, cfg_name = workload(args.workload)
     calib = None
-    if rank == 0:   # before anything else has warmed or loaded the chip (a library without the calibration kernels -- an older build loaded
-        try:        # through GRL_LIB for an A/B -- simply has no calibration block)
+    if rank == 0 and args.full:   # before anything else has warmed or loaded the chip (a library without the calibration kernels -- an
+        try:                      # older build loaded through GRL_LIB for an A/B -- simply has no calibration block)
             calib = box_calibration(dev)
         except AttributeError:
             calib = None
     det = None
-    if rank == 0 and not os.environ.get("GRL_BENCH_NO_SELFCHECK"):   # (the override is for timing knock-out builds, whose results are garbage)
+    if rank == 0 and args.full and not os.environ.get("GRL_BENCH_NO_SELFCHECK"):   # (the override is for timing knock-out builds, whose results are garbage)
         det = determinism_selfcheck(dev, "_bf16" if cfg.precision == "bf16" else "")
     assert args.minibatch % world == 0
     B = args.minibatch // world
@@ -383,13 +414,13 @@ def main():
     drv = RolloutDriver(upd, spec, ppo_epochs=5, seed=rank)
     next_last = {k: first_frame[k].unsqueeze(1) for k in spec.in_features}
     adv_times = []
-    for _ in range(2):   # first call: cold (topology of the rollout-sized batch, lazy initialisation); second: what every later rollout pays
-        torch.cuda.synchronize()
+    for _ in range(2 if args.full else 1):   # first call: cold (topology of the rollout-sized batch, lazy initialisation); second (--full):
+        torch.cuda.synchronize()             # what every later rollout pays
         t_adv = time.perf_counter()
         drv.compute_advantages(buf, next_last)
         torch.cuda.synchronize()
         adv_times.append(1e3 * (time.perf_counter() - t_adv))
-    adv_ms_cold, adv_ms = adv_times
+    adv_ms_cold, adv_ms = adv_times[0], (adv_times[1] if args.full else None)
 
     def sampler():   # sampling without replacement, reshuffled every epoch
         while True:
@@ -460,8 +491,10 @@ def main():
         calib_after = {"mfma_tflops": _mf, "vs_start_of_process": _mf / calib["mfma_tflops"],
                        "box_throttled": bool(_mf < 0.93 * calib["mfma_tflops"]),
                        "what": "grl_calib_mfma again, median of 5 launches directly behind the timed region; box_throttled: below 0.93 of the figure at process start"}
+    if rank == 0 and args.dump_outputs:   # before any further step overwrites the recorded step's outputs and the parameters
+        dump_outputs(args.dump_outputs, {**out, "params_flat": upd.flat})
     dp_info = None
-    if world > 1 or args.dp_plan:
+    if (world > 1 or args.dp_plan) and args.full:
         import torch.distributed as dist
         own = torch.tensor([dt_own], device=dev, dtype=torch.float64)
         every = [torch.zeros_like(own) for _ in range(world)]
@@ -508,7 +541,7 @@ def main():
 
     # ---- GAE + shifted critic pass over the whole 4096 x 128 rollout (once per 640 updates; outside the timed region)
     gae_ms = None
-    if rank == 0:
+    if rank == 0 and args.full:
         N, T = args.minibatch, 128
         g = syn.make_gae_inputs(N, T, seed=0)
         gd = {k: v.to(dev) for k, v in g.items()}
@@ -521,11 +554,12 @@ def main():
         gae_ms = 1e3 * (time.perf_counter() - t1) / 5
 
     roof = None
-    if rank != 0 and not args.no_roofline:   # the profiled steps are collective when data parallel: every rank runs them
+    roofline = args.full and not args.no_roofline
+    if rank != 0 and roofline:   # the profiled steps are collective when data parallel: every rank runs them
         upd.use_graph = False
         for i in range(6):
             upd.step_from(buf, next(mb))
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and roofline:
         # HIP events around every C-ABI launch, on the launch stream; one profiled step is discarded (first-use cost of
         # timed events lands on a random kernel) and the per-step totals are reduced with the median over the other steps.
         n_prof = 6
@@ -689,7 +723,7 @@ def main():
                 "per_kernel_ms_per_step": {k: v[1] for k, v in sorted(summ.items(), key=lambda kv: -kv[1][1])}}
 
     cpu, gate = None, None
-    if rank == 0 and world == 1 and not (args.no_cpu_baseline or args.no_parity_gate):   # N = 1 only
+    if rank == 0 and world == 1 and args.full and not (args.no_cpu_baseline or args.no_parity_gate):   # N = 1 only
         cpu, gate = cpu_baseline_and_parity(args.workload, args.minibatch, dev)
 
     if rank == 0:

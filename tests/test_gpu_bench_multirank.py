@@ -26,7 +26,7 @@ def _bench(*args, env_extra=None, timeout=900):
 
 
 def test_two_rank_bench_line():
-    two = _bench("--gpus", "2", "--minibatch", "1024", "--steps", "3", "--warmup", "1", "--pool", "4",
+    two = _bench("--gpus", "2", "--full", "--minibatch", "1024", "--steps", "3", "--warmup", "1", "--pool", "4",
                  env_extra={"GRL_BENCH_ONE_GPU": "1"})
     assert two["n_gpus"] == 2 and two["steps"] == 3 and two["warmup"] == 1
     assert two["scaling"] == "strong" and two["config"]["parallelism"] == "dp2"

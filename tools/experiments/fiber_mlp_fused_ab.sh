@@ -9,11 +9,11 @@ import sys,json; d=json.loads(sys.stdin.read()); print('%-10s %5s : %8.2f steps/
 for r in 1 2 3; do
   for mb in 512 4096; do
     for f in 0 1; do
-      GRL_FUSE_FIBER_MLP=$f python bench.py --minibatch $mb --steps 40 --warmup 8 --pool 16 --no-parity-gate --no-roofline 2>/dev/null | grep "^{" | tail -1 | line fuse$f $mb >> $OUT
+      GRL_FUSE_FIBER_MLP=$f python bench.py --full --minibatch $mb --steps 40 --warmup 8 --pool 16 --no-parity-gate --no-roofline 2>/dev/null | grep "^{" | tail -1 | line fuse$f $mb >> $OUT
     done
   done
 done
 for f in 0 1; do
-  GRL_FUSE_FIBER_MLP=$f python bench.py --workload rope_hepi_bf16 --steps 20 --warmup 5 --no-parity-gate --no-roofline 2>/dev/null | grep "^{" | tail -1 | line bf16_fuse$f 4096 >> $OUT
+  GRL_FUSE_FIBER_MLP=$f python bench.py --full --workload rope_hepi_bf16 --steps 20 --warmup 5 --no-parity-gate --no-roofline 2>/dev/null | grep "^{" | tail -1 | line bf16_fuse$f 4096 >> $OUT
 done
 cat $OUT

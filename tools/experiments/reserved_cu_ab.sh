@@ -9,7 +9,7 @@ line() { python -c "
 import sys,json; d=json.loads(sys.stdin.read()); print('%-22s %5s : %8.2f steps/s  %.4f ms/step  %s' % ('$1', '$2', d['value'], d['ms_per_step'], d['config'].get('mode','')[:60]))"; }
 run() { # name frames env... -- extra args
   name=$1; mb=$2; shift 2
-  env "$@" python bench.py --minibatch $mb --steps 40 --warmup 8 --pool 16 --no-parity-gate --no-roofline $EXTRA 2>/dev/null | grep "^{" | tail -1 | line $name $mb >> $OUT
+  env "$@" python bench.py --full --minibatch $mb --steps 40 --warmup 8 --pool 16 --no-parity-gate --no-roofline $EXTRA 2>/dev/null | grep "^{" | tail -1 | line $name $mb >> $OUT
 }
 for r in 1 2; do
   for mb in 128 512 1024 2048 4096; do

@@ -14,7 +14,7 @@ T=${GRL_MG_TIMEOUT:-420}
 
 run_line() {   # tag, n, workload, extra env...
   local tag=$1 n=$2 wl=$3; shift 3
-  env "$@" timeout $T python bench.py --gpus $n --workload $wl --steps 40 --warmup 8 --no-roofline > $O/$tag.json 2> $O/$tag.err
+  env "$@" timeout $T python bench.py --gpus $n --full --workload $wl --steps 40 --warmup 8 --no-roofline > $O/$tag.json 2> $O/$tag.err
   local rc=$?
   echo "$tag rc=$rc $(tail -c 300 $O/$tag.json | tr -d '\n' | cut -c1-120)"
   return $rc

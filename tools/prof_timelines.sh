@@ -13,7 +13,7 @@ for mb in ${GRL_TL_SIZES:-32 512 4096}; do
 done
 cd $GRAFT_REPO_ROOT
 for mb in 32 256 512 1024 2048 4096; do
-  python bench.py --minibatch $mb --steps 40 --warmup 8 --pool 16 --no-parity-gate --no-roofline --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+  python bench.py --full --minibatch $mb --steps 40 --warmup 8 --pool 16 --no-parity-gate --no-roofline --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); print('rigid_hepi minibatch %5d : %8.2f steps/s  %.3f ms/step  mode %s' % ($mb, d['value'], d['ms_per_step'], d['mode']))"
 done > $OUT/sizes.txt 2>&1
 cat $OUT/sizes.txt

@@ -23,7 +23,7 @@ PY
 line() { python -c "
 import sys,json; d=json.loads(sys.stdin.read()); print('%-14s %-22s %5s : %8.2f steps/s  %.4f ms/step  %s' % ('$1', '$2', '$3', d['value'], d['ms_per_step'], d.get('mode','')[:70]))"; }
 run() { w=$1; name=$2; mb=$3; shift 3
-  python bench.py --workload $w --minibatch $mb --steps 40 --warmup 8 --pool 16 --no-parity-gate --no-roofline --no-cpu-baseline "$@" 2>/dev/null | grep "^{" | tail -1 | line $w $name $mb >> $OUT
+  python bench.py --full --workload $w --minibatch $mb --steps 40 --warmup 8 --pool 16 --no-parity-gate --no-roofline --no-cpu-baseline "$@" 2>/dev/null | grep "^{" | tail -1 | line $w $name $mb >> $OUT
 }
 for r in 1 2; do
   for w in cloth_hepi rigid2_empn rope_hepi_bf16; do
