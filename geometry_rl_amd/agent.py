@@ -43,6 +43,9 @@ class AgentConfig:
     max_grad_norm: float = 1.0
     aggr: str = "add"         # "AttentionalAggregation": configs/algorithm/pyg_agent/model/hepi_attention.yaml
     precision: str = "fp32"   # "bf16": BASELINE config 5 -- node latents stored as bf16, one bf16 MFMA per dense product, fp32 accumulation
+    # the actor's HyperData only (configs/rigid_pushing_multi_empn_trpl_cfg.yaml:105-106; every upstream critic config keeps it False)
+    training_noise: bool = False
+    training_noise_std: float = 0.01
 
 
 def build_agent(spec: TaskSpec, cfg: AgentConfig, device="cuda", group=None):
@@ -70,7 +73,8 @@ def build_agent(spec: TaskSpec, cfg: AgentConfig, device="cuda", group=None):
     else:
         raise ValueError(cfg.model)
     post_fc = cfg.model == "transformer"
-    a_data = HyperData(spec, full_graph_obs=False, dist_as_pos=True, output_mask_key=spec.actuator, concat_input_vector=post_fc)
+    a_data = HyperData(spec, full_graph_obs=False, dist_as_pos=True, output_mask_key=spec.actuator, concat_input_vector=post_fc,
+                       training_noise=cfg.training_noise, training_noise_std=cfg.training_noise_std)
     A = spec.num_actuators * cfg.output_dim_vec * 3
     actor = GNNGaussianPolicyDiag(gnn=gnn, hyper_data=a_data, action_dim=A, num_actuators=spec.num_actuators, init="orthogonal",
                                   hidden_sizes=(64, 64), contextual_std=True, init_std=cfg.init_std, minimal_std=cfg.minimal_std,
@@ -234,6 +238,10 @@ class PolicyUpdater:
                 self._oneshot = oneshot.ipc_rank(group, self.gbuf[:self._rec + self.n_actor])
         if group is not None:
             self.sync_replicas()
+        # data parallel: every rank's actor draws its training noise from a stream of its own (the rank folded into the key)
+        hd = getattr(loss_module.actor_network, "hyper_data", None)
+        if hd is not None and self.rank:
+            hd.fold_noise_rank(self.rank)
 
     # ---- hyper-parameters.  ``lr`` lives in device memory (no re-recording); the others are baked into recorded launches as
     #      scalars, so changing one drops the recorded program (it is re-recorded by the next step)

@@ -715,6 +715,19 @@ __global__ __launch_bounds__(256) void step_head_kernel(FeatDescs feat, int n_de
   b -= nwi;
   build_features_body(feat, bump, b % nfx, nfx, b / nfx, b == 0);
 }
+// ... with training noise in the feature role (grl_feat.h build_features_body_t<true>; nz.n_blocks = its nfx * n_desc workgroups take the
+// draw's tickets, the fiber-basis and weight-image workgroups take none)
+__global__ __launch_bounds__(256) void step_head_noise_kernel(FeatDescs feat, int n_desc, int nfx, int* __restrict__ bump, FbFwd fb, WimgJobs jobs,
+                                                              FeatNoise nz) {
+  __shared__ float fb_smem[FB_SMEM_FLOATS];
+  const int nfb = fb.wf.n > 0 ? FB_ROWS / FB_RPB : 0, nwi = WIMG_PARTS * jobs.n;
+  int b = (int)blockIdx.x;
+  if (b < nfb) { fiber_basis_fwd_body(fb, b, fb_smem); return; }
+  b -= nfb;
+  if (b < nwi) { weight_images_body(jobs, b / WIMG_PARTS, b % WIMG_PARTS); return; }
+  b -= nwi;
+  build_features_body_t<true>(feat, bump, b % nfx, nfx, b / nfx, b == 0, &nz);
+}
 // End of the actor's backward: the lift's weight gradient (all node types) | the fiber basis backward -- both only feed the tail's fold.
 __global__ __launch_bounds__(256) void lift_fiber_basis_bwd_kernel(LiftMulti m, const float* __restrict__ grid, float* __restrict__ partial,
                                                                    int S, int V, FbBwd fb) {
@@ -1154,9 +1167,10 @@ int grl_fiber_basis_bwd(const float* poly, const float* W2, const float* const* 
 // ---- merged launches (round 6).  grl_step_head: grl_build_features_bump (descs, n_desc, bump) + grl_fiber_basis_fwd (n_conv may be 0:
 // role absent) + grl_weight_images (n_img may be 0) in ONE launch; arguments as in those three entry points.  The images depend on the
 // build's precision, hence the _bf16 twin.
-int GRL_ENTRY(grl_step_head)(const long long* descs, int n_desc, int* bump, const float* poly, const float* W1, const float* b1,
-                             const float* W2, const float* b2, const float* const* wf, int n_conv, float* saved, float* const* fk,
-                             int n_img, const int* kinds, const float* const* srcs, void* const* outs, hipStream_t stream) {
+static int step_head_launch(const long long* descs, int n_desc, int* bump, const long long* noise, unsigned long long* state, float std,
+                            int advance, const float* poly, const float* W1, const float* b1, const float* W2, const float* b2,
+                            const float* const* wf, int n_conv, float* saved, float* const* fk, int n_img, const int* kinds,
+                            const float* const* srcs, void* const* outs, hipStream_t stream) {
   if (n_desc < 0 || n_desc > FEAT_MAX || n_img < 0) return -2;
   FeatDescs feat{};
   const int max_nodes = n_desc > 0 ? feat_fill(feat, descs, n_desc) : 1;
@@ -1172,9 +1186,30 @@ int GRL_ENTRY(grl_step_head)(const long long* descs, int n_desc, int* bump, cons
   if (nfx > 64) nfx = 64;
   const int blocks = (n_conv > 0 ? FB_ROWS / FB_RPB : 0) + WIMG_PARTS * jobs.n + nfx * n_desc;
   if (blocks <= 0) return 0;
-  hipLaunchKernelGGL(step_head_kernel, dim3(blocks), dim3(256), 0, stream, feat, n_desc, nfx, bump, A, jobs);
+  if (noise && n_desc > 0) {
+    FeatNoise nz{};
+    if (const int rc = feat_noise_fill(nz, noise, n_desc, state, std, nfx * n_desc, advance)) return rc;
+    hipLaunchKernelGGL(step_head_noise_kernel, dim3(blocks), dim3(256), 0, stream, feat, n_desc, nfx, bump, A, jobs, nz);
+  } else {
+    hipLaunchKernelGGL(step_head_kernel, dim3(blocks), dim3(256), 0, stream, feat, n_desc, nfx, bump, A, jobs);
+  }
   GRL_CHECK_LAUNCH();
   return 0;
+}
+int GRL_ENTRY(grl_step_head)(const long long* descs, int n_desc, int* bump, const float* poly, const float* W1, const float* b1,
+                             const float* W2, const float* b2, const float* const* wf, int n_conv, float* saved, float* const* fk,
+                             int n_img, const int* kinds, const float* const* srcs, void* const* outs, hipStream_t stream) {
+  return step_head_launch(descs, n_desc, bump, nullptr, nullptr, 0.f, 0, poly, W1, b1, W2, b2, wf, n_conv, saved, fk, n_img, kinds, srcs,
+                          outs, stream);
+}
+// the same with training noise in the feature role: noise, state, std, advance as in grl_build_features_noise (train_ops.hip)
+int GRL_ENTRY(grl_step_head_noise)(const long long* descs, int n_desc, int* bump, const long long* noise, unsigned long long* state, float std,
+                                   int advance, const float* poly, const float* W1, const float* b1, const float* W2, const float* b2,
+                                   const float* const* wf, int n_conv, float* saved, float* const* fk, int n_img, const int* kinds,
+                                   const float* const* srcs, void* const* outs, hipStream_t stream) {
+  if (!noise || !state) return -2;
+  return step_head_launch(descs, n_desc, bump, noise, state, std, advance, poly, W1, b1, W2, b2, wf, n_conv, saved, fk, n_img, kinds, srcs,
+                          outs, stream);
 }
 // grl_lift_encode_bwd_multi + grl_fiber_basis_bwd in ONE launch (n_conv may be 0: the lift alone); arguments as in those two entry points
 int GRL_ENTRY(grl_lift_fiber_basis_bwd)(int n_types, const float* const* scal, const float* const* vec, const float* grid,

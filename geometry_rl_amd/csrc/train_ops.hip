@@ -200,6 +200,10 @@ __global__ __launch_bounds__(128) void knn_kernel(const float* __restrict__ pos 
 __global__ __launch_bounds__(256) void build_features_kernel(FeatDescs all, int* __restrict__ bump) {
   build_features_body(all, bump, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.y, blockIdx.x == 0 && blockIdx.y == 0);
 }
+// ... with training noise (grl_feat.h build_features_body_t<true>): every workgroup is a feature workgroup and takes a ticket
+__global__ __launch_bounds__(256) void build_features_noise_kernel(FeatDescs all, int* __restrict__ bump, FeatNoise nz) {
+  build_features_body_t<true>(all, bump, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.y, blockIdx.x == 0 && blockIdx.y == 0, &nz);
+}
 
 // ---- lane gate as a kernel: one thread waits until flag[0] >= count[0] + add (both device int32), at most timeout_ticks of the 100 MHz wall clock
 // -- what hipStreamWaitValue32 does on this runtime as well (its __amd_rocclr_streamOpsWait is a one-thread kernel), but capturable into a
@@ -408,7 +412,7 @@ extern "C" {
 
 // ABI version of this library: major * 10000 + minor * 100 + patch.  Bumped whenever a declared signature changes
 // (include/grl_hip.h GRL_HIP_VERSION must agree: geometry_rl_amd/hip.py checks it at load time).
-int grl_version(void) { return 205; }
+int grl_version(void) { return 206; }
 // The current stream waits (a one-thread kernel: capturable) until flag[0] >= count[0] + add, at most timeout_us microseconds.
 int grl_wait_flag_ge(const int* flag, const int* count, int add, int timeout_us, hipStream_t stream) {
   if (!flag || !count) return -2;
@@ -491,6 +495,22 @@ int grl_build_features_bump(const long long* descs, int n_desc, int* bump, hipSt
   const int max_nodes = feat_fill(all, descs, n_desc);
   const int bx = (max_nodes + 255) / 256 < 256 ? (max_nodes + 255) / 256 : 256;
   hipLaunchKernelGGL(build_features_kernel, dim3(bx, n_desc), dim3(256), 0, stream, all, bump);
+  GRL_CHECK_LAUNCH();
+  return 0;
+}
+// the same with training noise: noise = HOST array of n_desc noise words, state = device uint64 {seed, draw, ticket}; advance != 0: the draw
+// advances by one in stream order (the ticket of grl_feat.h)
+int grl_build_features_noise(const long long* descs, int n_desc, int* bump, const long long* noise, unsigned long long* state, float std,
+                             int advance, hipStream_t stream) {
+  if (n_desc <= 0) return 0;
+  if (n_desc > FEAT_MAX) return -2;
+  FeatDescs all{};
+  const int max_nodes = feat_fill(all, descs, n_desc);
+  // (at most 64 workgroups per descriptor, grid-stride as in the merged head launch: every workgroup takes one ticket of the draw)
+  const int bx = (max_nodes + 255) / 256 < 64 ? (max_nodes + 255) / 256 : 64;
+  FeatNoise nz{};
+  if (const int rc = feat_noise_fill(nz, noise, n_desc, state, std, bx * n_desc, advance)) return rc;
+  hipLaunchKernelGGL(build_features_noise_kernel, dim3(bx, n_desc), dim3(256), 0, stream, all, bump, nz);
   GRL_CHECK_LAUNCH();
   return 0;
 }

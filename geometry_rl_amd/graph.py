@@ -131,6 +131,22 @@ class GraphBatch:
         return list(self.edges.keys())
 
 
+_MASK64 = (1 << 64) - 1
+
+
+def _signed64(x: int) -> int:
+    x &= _MASK64
+    return x - (1 << 64) if x >> 63 else x
+
+
+def _mix64(x: int) -> int:
+    """splitmix64's finaliser: a 64-bit seed from a small integer."""
+    x = (x + 0x9E3779B97F4A7C15) & _MASK64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _MASK64
+    return x ^ (x >> 31)
+
+
 import os as _os
 BALANCE_NODE_ORDER = _os.environ.get("GRL_BALANCE_NODE_ORDER", "1") == "1"   # module attribute: tests / A/B tools flip it
 
@@ -188,10 +204,21 @@ class HyperData:
     (concat_input_vector=True; the reference returns the per-type dict that DeepSets concatenates, deepsets.py:41-49)."""
 
     def __init__(self, spec: TaskSpec, *, full_graph_obs=False, dist_as_pos=False, output_mask_key=None, training_noise=False,
-                 training_noise_std=1e-2, concat_input_vector=True, drop_padding=True, **ignored):
-        if training_noise:
-            raise NotImplementedError("training_noise is False in every reference config on the hot path")
+                 training_noise_std=1e-2, concat_input_vector=True, drop_padding=True, noise_seed=None, **ignored):
         self.spec = spec
+        # training noise (rigid_tasks_data.py:178-214, rope_tasks_data.py:168-186): N(0, std^2) on the input vectors of every build_data with
+        # train=True, drawn on the device by the feature launch itself (csrc/grl_feat.h) -- see _noise_words for which slots.  cloth: the flag
+        # is accepted and changes nothing, as upstream (cloth_tasks_data.py adds no noise).  DELIBERATE DEVIATION: upstream adds the noise in
+        # place (``pos_vec += ...``), which writes into the caller's observation tensor where a reshape is a view (a group of one term); the
+        # kernel never writes its inputs.
+        self.training_noise, self.training_noise_std = bool(training_noise), float(training_noise_std)
+        self._noise_on = self.training_noise and spec.family != "cloth"
+        if noise_seed is None:   # from torch's initial seed (torch.manual_seed before construction reproduces a run; no draw is consumed)
+            noise_seed = _mix64(torch.initial_seed() ^ (int(dist_as_pos) << 1 | int(concat_input_vector) << 2 | int(full_graph_obs) << 3))
+        self._noise_host = (int(noise_seed) & _MASK64, 0)   # (seed, draw) until the device state exists
+        self._noise_dev = None        # device int64[4] = uint64 {seed, draw, ticket, unused}, allocated by the first noisy build_data
+        self._noise_advance = True    # False: the launches read the draw and leave it (policy.GNNGaussianPolicyDiag's calibrating pass)
+        self._noise_rank = None
         self.full_graph_obs = full_graph_obs
         self.dist_as_pos = dist_as_pos
         self._output_mask_key = output_mask_key
@@ -208,6 +235,62 @@ class HyperData:
         self._cache = {}
         self.bump_next = None   # one-shot: a device int32[1] the NEXT build_data's feature launch advances by one (PolicyUpdater: step count)
         self.check_topology_always = False   # debugging: True = every eager build_data re-validates the cached topology (one device sync each)
+
+    # ---- training noise: the device-side generator state {seed, draw}
+    def _noise_state_tensor(self, dev) -> torch.Tensor:
+        if self._noise_dev is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("HyperData: the noise state must exist before a capture (run one eager build_data with train=True first)")
+            seed, draw = self._noise_host
+            self._noise_dev = torch.tensor([_signed64(seed), _signed64(draw), 0, 0], dtype=torch.int64, device=dev)
+        return self._noise_dev
+
+    def noise_state(self):
+        """(seed, draw) of the training-noise generator: the next noisy feature launch draws with these (one device sync)."""
+        if self._noise_dev is None:
+            return self._noise_host
+        seed, draw = self._noise_dev[:2].tolist()
+        return seed & _MASK64, draw & _MASK64
+
+    def set_noise_state(self, seed: int, draw: int = 0) -> None:
+        """Put the generator at (seed, draw): stream-ordered behind the work already enqueued (one host-to-device copy)."""
+        self._noise_host = (int(seed) & _MASK64, int(draw) & _MASK64)
+        if self._noise_dev is not None:
+            self._noise_dev.copy_(torch.tensor([_signed64(self._noise_host[0]), _signed64(self._noise_host[1]), 0, 0], dtype=torch.int64))
+
+    def fold_noise_rank(self, rank: int) -> None:
+        """Data parallel: rank r > 0 draws from its own stream (key = mix(seed, r)); rank 0 keeps the key.  Applied once per HyperData."""
+        if not rank or self._noise_rank is not None:
+            return
+        self._noise_rank = rank
+        seed, draw = self.noise_state()
+        self.set_noise_state(_mix64(seed ^ _mix64(rank)), draw)
+
+    def share_noise(self, other: "HyperData", advance: bool) -> None:
+        """Draw from ``other``'s generator state (same device words); ``advance`` False: this object's launches only read the draw."""
+        self._noise_on = other._noise_on
+        self.training_noise, self.training_noise_std = other.training_noise, other.training_noise_std
+        self._noise_host, self._noise_dev, self._noise_advance = other._noise_host, other._noise_dev, advance
+
+    def _noise_words(self, t, n_t, B):
+        """Noise word per vector slot of node type t (include/grl_hip.h grl_build_features_noise), the rules of rigid_tasks_data.py:178-214 /
+        rope_tasks_data.py:168-186: the position always; ``corr`` only for the type that has a target (with dist_as_pos its value is computed
+        from the NOISY position: the position's noise is added as well); ``vel`` / ``ang`` only for types with a velocity observation --
+        ``ang`` even without an angular velocity (upstream adds noise to its zeros); everything else stays exact."""
+        spec = self.spec
+        has_vel = t in spec.obs_names["velocity_vectors"]
+        terms = self._feature_terms(t, n_t)
+        head = (spec.node_types.index(t) << 24) | (spec.n_vec << 16) | (B << 32)
+        words = []
+        for v, (ta, _tb) in enumerate(terms):
+            if v == 0:
+                on, pos_too = True, False
+            elif v == 1:
+                on, pos_too = ta is not None, ta is not None and self.dist_as_pos
+            else:
+                on, pos_too = has_vel, False
+            words.append(_signed64(head | (v << 8) | (2 if pos_too else 0) | 1) if on else 0)
+        return words
 
     # ---- cached topology: invariant and guards
     def reset_cache(self):
@@ -398,7 +481,8 @@ class HyperData:
 
     def build_data(self, *args, train=True, **kw):
         """rigid_tasks_data.py / base_data.py:45-55.  Positional obs tensors in ``spec.in_features`` order.  All node features
-        (and the raw positions) are written by ONE launch of ``grl_build_features``."""
+        (and the raw positions) are written by ONE launch of ``grl_build_features``; with ``train`` and training noise on, that launch
+        (``grl_build_features_noise``) also adds the noise of the generator's current draw and advances the draw."""
         import ctypes
         spec = self.spec
         obs = {k: (v if v.dtype == torch.float32 and v.is_contiguous() else v.float().contiguous())
@@ -420,6 +504,8 @@ class HyperData:
             x_dense = torch.empty(B, n_total, d, device=dev, dtype=torch.float32) if dense else None
             graph_pos, scalar_dict, vector_dict = {}, {}, {}
             words = []
+            noisy = train and self._noise_on
+            nwords = [] if noisy else None
 
             def term(tn, n_t):
                 if tn is None:
@@ -454,8 +540,12 @@ class HyperData:
                     scalar_dict[t] = topo["one_hot"][t]
                     pa = term(("position_vectors", t), n_t)
                     words += [graph_pos[t].data_ptr(), pa[0], 0, gather, 3, 0, 0, 0, n_nodes, n_t, pa[1], pa[2], pa[3], 0, 0, 0, -1, 0]
+                    if noisy:
+                        nwords.append(0)   # (raw positions: geometry, never noisy)
                 terms = self._feature_terms(t, n_t)
                 assert len(terms) == n_vec
+                if noisy:
+                    nwords += self._noise_words(t, n_t, B)
                 for v, (ta, tb) in enumerate(terms):
                     A, Bt = term(ta, n_t), term(tb, n_t)
                     if dense:
@@ -472,8 +562,14 @@ class HyperData:
             if bump is None and self.bump_next is not None:
                 bump, self.bump_next = self.bump_next, None
             from . import ops
+            # noise: (host noise words, device state, std, advance) -- the draw advances by one per launch, in stream order
+            noise = None
+            if noisy:
+                noise = ((ctypes.c_longlong * n_desc)(*nwords), self._noise_state_tensor(dev), self.training_noise_std, int(self._noise_advance))
             if ops.HEAD is not None and ops.HEAD.feat is None:   # rides in the merged head launch of this forward (ops.HeadLaunch)
-                ops.HEAD.feat = ((ctypes.c_longlong * len(words))(*words), n_desc, bump)
+                ops.HEAD.feat = ((ctypes.c_longlong * len(words))(*words), n_desc, bump, noise)
+            elif noise is not None:
+                hip.call("grl_build_features_noise", (ctypes.c_longlong * len(words))(*words), n_desc, bump, *noise)
             else:
                 hip.call("grl_build_features_bump", (ctypes.c_longlong * len(words))(*words), n_desc, bump)
             self._keepalive = obs  # the launch reads these buffers asynchronously

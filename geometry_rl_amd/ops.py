@@ -278,7 +278,7 @@ class HeadLaunch:
         import ctypes
         if self.feat is None and self.fiber is None and self.wimg is None:
             return
-        words, n_desc, bump = self.feat if self.feat is not None else (None, 0, None)
+        words, n_desc, bump, noise = self.feat if self.feat is not None else (None, 0, None, None)
         if self.fiber is not None:
             poly2, P, W, saved, fks = self.fiber
             n = len(W)
@@ -291,7 +291,10 @@ class HeadLaunch:
             wargs = [n_img, (ctypes.c_int * n_img)(*kinds), (ctypes.c_void_p * (6 * n_img))(*ptrs), (ctypes.c_void_p * n_img)(*outs)]
         else:
             wargs = [0, None, None, None]
-        hip.call("grl_step_head" + prec, words, n_desc, bump, *fargs, *wargs)
+        if noise is not None:   # (training noise in the feature role: graph.HyperData.build_data)
+            hip.call("grl_step_head_noise" + prec, words, n_desc, bump, *noise, *fargs, *wargs)
+        else:
+            hip.call("grl_step_head" + prec, words, n_desc, bump, *fargs, *wargs)
         self.feat = self.fiber = self.wimg = None
 
 

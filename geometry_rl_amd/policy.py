@@ -66,13 +66,21 @@ class GNNGaussianPolicyDiag(nn.Module):
 
     def _maybe_calibrate(self, args):
         """First training call: data-dependent re-initialisation of every conv that sees edges (conv.py:104-105).  Convs whose
-        edge set is empty are skipped by the reference too (hetero_fiber_conv.py:48-49) and stay un-calibrated."""
+        edge set is empty are skipped by the reference too (hetero_fiber_conv.py:48-49) and stay un-calibrated.
+
+        Training noise: upstream calibrates inside the first training forward, on its noisy features.  The calibrating pass here draws from
+        the actor's own generator WITHOUT advancing it: it reads the draw that the training forward right behind it (same call) consumes,
+        so both see the same noise for every (sample, point, slot) -- the padded points this pass keeps get theirs as well -- and the
+        draw sequence is that of the training forwards alone."""
         gnn = self.gnn
         self._calib_checked = True
         if hasattr(gnn, "calibrated") and not gnn.calibrated:
             hd = self.hyper_data
             full = HyperData(hd.spec, full_graph_obs=hd.full_graph_obs, dist_as_pos=hd.dist_as_pos,
                              output_mask_key=hd._output_mask_key, concat_input_vector=False, drop_padding=False)
+            if hd._noise_on:
+                hd._noise_state_tensor(args[0].device)   # (the shared device words must exist first)
+                full.share_noise(hd, advance=False)
             graph, u = full.build_data(*args, train=True)
             gnn.calibrate(graph, u, group=self.group)
 

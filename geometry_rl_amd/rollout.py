@@ -167,16 +167,20 @@ class PolicyActor:
 
     ``use_graph``: after the first call (which builds the cached topology and, on a fresh policy, calibrates the convolutions --
     the collector calls the module with its default ``train=True``, gnn_gaussian_policy_diag.py:65) the pass is recorded into a
-    hipGraph and replayed on static input buffers."""
+    hipGraph and replayed on static input buffers.
 
-    def __init__(self, policy, spec, use_graph: bool = True, seed: int = 0, deterministic: bool = False):
+    ``train``: the pass's ``train`` flag (True, as the collector's default call).  With the policy's training noise on, every pass -- every
+    replay -- draws a fresh noise set from the actor's generator; ``train=False`` (evaluation) is noiseless."""
+
+    def __init__(self, policy, spec, use_graph: bool = True, seed: int = 0, deterministic: bool = False, train: bool = True):
         self.policy, self.spec, self.use_graph, self.deterministic = policy, spec, use_graph, deterministic
+        self.train = bool(train)
         self.gen, self.seed = None, seed
         self._graph, self._static, self._out, self._calls = None, None, None, 0
 
     def _pass(self, obs):
         from . import hip
-        loc, sigma = self.policy.forward_diag(*[obs[k] for k in self.spec.in_features], train=True)
+        loc, sigma = self.policy.forward_diag(*[obs[k] for k in self.spec.in_features], train=self.train)
         B, A = loc.shape
         eps = torch.zeros_like(loc) if self.deterministic else torch.randn(loc.shape, device=loc.device, dtype=loc.dtype, generator=self.gen)
         action, var = torch.empty_like(loc), torch.empty_like(loc)

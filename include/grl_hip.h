@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 /* ABI version (major*10000 + minor*100 + patch); grl_version() returns the value the library was built with. */
-#define GRL_HIP_VERSION 205   /* 205 (round 6): grl_source_hash added; 204 (round 5): grl_head_fused / grl_head_fused_rows removed, grl_calib_mfma / grl_calib_copy added; the exports are exactly this header */
+#define GRL_HIP_VERSION 206   /* 206: grl_build_features_noise, grl_step_head_noise[_bf16] added (training noise); 205 (round 6): grl_source_hash added; 204 (round 5): grl_head_fused / grl_head_fused_rows removed, grl_calib_mfma / grl_calib_copy added; the exports are exactly this header */
 int grl_version(void);
 /* The hash of the sources this binary was built from (16 hex digits + NUL into buf; returns the length).  geometry_rl_amd/hip.py
    source_hash() recomputes it from csrc/, this header and the build's flag tables and refuses a library that disagrees. */
@@ -360,6 +360,18 @@ int grl_gae_scan(const float* reward, const unsigned char* done, const unsigned 
 int grl_build_features(const long long* descs, int n_desc, hipStream_t stream);
 /* (ABI 203) the same; bump (device int[1] or NULL) is advanced by one by the launch: the optimizer's step count of a recorded step */
 int grl_build_features_bump(const long long* descs, int n_desc, int* bump, hipStream_t stream);
+/* (ABI 206) the same with training noise (rigid_tasks_data.py:178-214, rope_tasks_data.py:168-186, pyg_data/utils.py:13-15): N(0, std^2)
+ * added per descriptor as its noise word says.  noise: HOST array of n_desc words (uint64): bit 0 = add the noise of (type, slot), bit 1 =
+ * also add the noise of (type, slot 0) (the corr slot under dist_as_pos: computed from the noisy position), bits 8-15 = slot, 16-23 = n_slots,
+ * 24-31 = type index, 32-63 = B; a zero word = no noise (raw positions, noise-free slots).  state: device uint64[3] {seed, draw, ticket}
+ * (ticket 0 between launches).  advance != 0: the launch advances draw by one, in stream order (the last feature workgroup to finish
+ * stores it, csrc/grl_feat.h); 0: it only reads it.  The noise of element e = ((type * B + b) * n_per + j) * n_slots + slot -- (b, j) the
+ * natural (sample, point) index, independent of the output row (dropped padding, renumbered nodes, dense or per-type layout) -- at draw d:
+ *   (r0, r1, r2, r3) = Philox4x32-10(counter = (e mod 2^32, e >> 32, d mod 2^32, d >> 32), key = (seed mod 2^32, seed >> 32));
+ *   u1 = ((r0 >> 8) + 1) * 2^-24, u2 = (r1 >> 8) * 2^-24, u3 = ((r2 >> 8) + 1) * 2^-24, u4 = (r3 >> 8) * 2^-24;
+ *   (x, y, z) += std * (sqrt(-2 ln u1) cos(2 pi u2), sqrt(-2 ln u1) sin(2 pi u2), sqrt(-2 ln u3) cos(2 pi u4))   (fp32) */
+int grl_build_features_noise(const long long* descs, int n_desc, int* bump, const long long* noise, unsigned long long* state, float std,
+                             int advance, hipStream_t stream);
 
 /* ---- (ABI 205, round 6) merged launches of the recorded policy-update step and lane signals -----------------------------------------
  * Replaces nothing of the reference (it has no launches to merge: examples/torchrl/train.py:279-316 runs eager PyTorch); these shorten the
@@ -374,6 +386,15 @@ int grl_step_head(const long long* descs, int n_desc, int* bump, const float* po
 int grl_step_head_bf16(const long long* descs, int n_desc, int* bump, const float* poly, const float* W1, const float* b1, const float* W2,
                        const float* b2, const float* const* wf, int n_conv, float* saved, float* const* fk, int n_img, const int* kinds,
                        const float* const* srcs, void* const* outs, hipStream_t stream);
+/* (ABI 206) grl_step_head with training noise in its feature role: noise, state, std, advance as in grl_build_features_noise */
+int grl_step_head_noise(const long long* descs, int n_desc, int* bump, const long long* noise, unsigned long long* state, float std,
+                        int advance, const float* poly, const float* W1, const float* b1, const float* W2, const float* b2,
+                        const float* const* wf, int n_conv, float* saved, float* const* fk, int n_img, const int* kinds,
+                        const float* const* srcs, void* const* outs, hipStream_t stream);
+int grl_step_head_noise_bf16(const long long* descs, int n_desc, int* bump, const long long* noise, unsigned long long* state, float std,
+                             int advance, const float* poly, const float* W1, const float* b1, const float* W2, const float* b2,
+                             const float* const* wf, int n_conv, float* saved, float* const* fk, int n_img, const int* kinds,
+                             const float* const* srcs, void* const* outs, hipStream_t stream);
 /* grl_lift_fiber_basis_bwd: grl_lift_encode_bwd_multi (n_types .. n_vec; n_types = 0: absent) + grl_fiber_basis_bwd (poly .. fb_partial;
  * n_conv = 0: absent) in ONE launch at the end of the actor's backward; arguments and results as in those two entry points. */
 int grl_lift_fiber_basis_bwd(int n_types, const float* const* scal, const float* const* vec, const float* grid, const float* const* dx,
