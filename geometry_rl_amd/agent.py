@@ -15,6 +15,7 @@ from . import hip, ops
 from .graph import HyperData, TaskSpec
 from .hepi import HEPi, FiberBundleConv
 from .policy import BaseCritic, DeepSets, GNNGaussianPolicyDiag, GNNVFNet
+from .ppo import ClipPPOLoss2
 from .trpl import KLProjectionLayer, TRPLLoss
 
 
@@ -46,10 +47,16 @@ class AgentConfig:
     # the actor's HyperData only (configs/rigid_pushing_multi_empn_trpl_cfg.yaml:105-106; every upstream critic config keeps it False)
     training_noise: bool = False
     training_noise_std: float = 0.01
+    # configs/algorithm/{trpl,ppo}.yaml: "trpl" (TRPLLoss + projection) or "ppo" (ClipPPOLoss2, no projection; objective/default.yaml)
+    algorithm: str = "trpl"
+    clip_epsilon: float = 0.2
 
 
 def build_agent(spec: TaskSpec, cfg: AgentConfig, device="cuda", group=None):
-    """-> (actor GNNGaussianPolicyDiag, critic BaseCritic, projection, loss_module)  (agent.py:31-52)."""
+    """-> (actor GNNGaussianPolicyDiag, critic BaseCritic, projection, loss_module)  (agent.py:31-64).  ``cfg.algorithm == "ppo"``: the
+    projection is None and the loss a ClipPPOLoss2 (utils_algo_graph.py:244-257 builds no projection for PPO)."""
+    if cfg.algorithm not in ("trpl", "ppo"):
+        raise ValueError(f"algorithm '{cfg.algorithm}': trpl | ppo (kl_ppo is not built)")
     n_in = len(spec.node_types) + spec.n_vec  # utils_algo_graph.py:79
     if cfg.model == "hepi":
         mp = []  # utils_algo_graph.py:29-47: one fresh conv per (level, active round)
@@ -84,10 +91,15 @@ def build_agent(spec: TaskSpec, cfg: AgentConfig, device="cuda", group=None):
     c_gnn = DeepSets(input_dim_node=len(spec.node_types) + 3 * spec.n_vec, output_dim=64, hidden_dim=64, device=device)
     critic = BaseCritic(GNNVFNet(gnn=c_gnn, hyper_data=c_data))
     critic._network1.group = group
-    projection = KLProjectionLayer(proj_type=cfg.proj_type, mean_bound=cfg.mean_bound, cov_bound=cfg.cov_bound,
-                                   trust_region_coeff=cfg.trust_region_coeff, scale_prec=True, entropy_schedule=False, action_dim=A)
     # config 1 hands its actor the NORMALISED vectors in the raw-vector slots (configs/rigid_insertion_multi_transformer_trpl_cfg.yaml:88-94)
     a_in = [k if k.startswith("norm_") or "vectors" not in k else "norm_" + k for k in spec.in_features] if post_fc else spec.in_features
+    if cfg.algorithm == "ppo":   # builders/agent.py:53-64
+        loss = ClipPPOLoss2(actor, critic, clip_epsilon=cfg.clip_epsilon, entropy_coef=cfg.entropy_coef, critic_coef=cfg.critic_coef,
+                            clip_value=cfg.clip_value, loss_critic_type="l2", normalize_advantage=True, in_features=a_in,
+                            critic_in_features=spec.in_features, group=group)
+        return actor, critic, None, loss
+    projection = KLProjectionLayer(proj_type=cfg.proj_type, mean_bound=cfg.mean_bound, cov_bound=cfg.cov_bound,
+                                   trust_region_coeff=cfg.trust_region_coeff, scale_prec=True, entropy_schedule=False, action_dim=A)
     loss = TRPLLoss(actor, critic, projection=projection, entropy_coef=cfg.entropy_coef, critic_coef=cfg.critic_coef,
                     clip_value=cfg.clip_value, loss_critic_type="l2", normalize_advantage=True, in_features=a_in,
                     critic_in_features=spec.in_features, group=group)
@@ -123,9 +135,14 @@ class PolicyUpdater:
     The step is laid out as an explicit program (``_plan``) of device-only segments, each free of host synchronisation, so with
     ``use_graph=True`` they are recorded once into hipGraphs (torch.cuda.CUDAGraph) and replayed -- the ~3 ms of per-step launch
     overhead disappears, which is what strong scaling over 8 GPUs needs (512 frames per GPU are < 1 ms of device time).  One program per
-    case (``_plan_one_stream`` / ``_plan_lanes`` / ``_plan_dp``): see the comment above ``_plan``."""
+    case (``_plan_one_stream`` / ``_plan_lanes`` / ``_plan_dp``): see the comment above ``_plan``.
 
-    def __init__(self, loss_module: TRPLLoss, lr=3e-4, eps=1e-5, betas=(0.9, 0.999), clip_grad_norm=False, max_grad_norm=1.0,
+    ``loss_module`` is a TRPLLoss or a ClipPPOLoss2: every program runs either (the fused loss kernel is the only launch that differs).
+    PPO's ``clip_epsilon`` buffer is read from device memory by that launch, so an in-place write (``loss.clip_epsilon.copy_(eps)``)
+    takes effect at the next step or replay without recording again; within one ``run_minibatches`` launch of several steps it is
+    constant, like ``lr``.  Replacing the buffer by another tensor drops the recorded program (it is recorded again)."""
+
+    def __init__(self, loss_module, lr=3e-4, eps=1e-5, betas=(0.9, 0.999), clip_grad_norm=False, max_grad_norm=1.0,
                  group=None, use_graph=False, overlap_critic=True, allow_eager_fallback=False, force_dp_plan=False,
                  critic_after_first_conv=True):
         self.loss_module, self.group = loss_module, group
@@ -264,6 +281,18 @@ class PolicyUpdater:
     betas = property(lambda self: self._hyper["betas"], lambda self, v: self._set_hyper("betas", tuple(v)))
     clip = property(lambda self: self._hyper["clip"], lambda self, v: self._set_hyper("clip", bool(v)))
     max_norm = property(lambda self: self._hyper["max_norm"], lambda self, v: self._set_hyper("max_norm", float(v)))
+
+    def _loss_storage(self):
+        """Device storage the recorded launches read from the loss module itself (PPO's clip_epsilon), or None."""
+        eps = getattr(self.loss_module, "clip_epsilon", None)
+        return eps.data_ptr() if torch.is_tensor(eps) else None
+
+    def _check_loss_storage(self):
+        """A loss buffer REPLACED by another tensor (not written in place) drops the recorded programs: they read the old storage."""
+        ptr = self._loss_storage()
+        if ptr != getattr(self, "_loss_ptr", ptr):
+            self._program, self._epoch = None, None
+        self._loss_ptr = ptr
 
     def anneal_lr(self, base_lr: float, iteration: int, total_iterations: int) -> float:
         """train.py:264-271: ``alpha = 1 - i / total; lr = base_lr * alpha`` for both optimisers."""
@@ -522,7 +551,7 @@ class PolicyUpdater:
                                                 dict(slots=fold_.slots, batch=fold_.batch, sums=fold_.sums, maxes=fold_.maxes,
                                                      ent_coef=ent, out14=o14), signal=(self.lane_flag, self.step_dev) if (gate and ops.SIGNAL_IN_KERNEL) else None)
                     if done:
-                        a_loss, mt = report_dict(o14)
+                        a_loss, mt = report_dict(o14, m)
                 if not done:
                     ops.flush_deferred_grads(overwrite=ow)
                     self._adam(st, 0, na, 0)
@@ -644,7 +673,7 @@ class PolicyUpdater:
 
         # (the reported values live in ONE buffer per recorded program: the tail may run as an eager launch behind the collective, below)
         o14 = torch.empty(14, device=self.flat.device, dtype=torch.float32)
-        st["lv_main"] = report_dict(o14)
+        st["lv_main"] = report_dict(o14, m)
 
         def p_tail():   # behind the lane's collective: Adam on the reduced gradient, reported values of the delivered records
             with torch.no_grad():
@@ -1001,6 +1030,7 @@ class PolicyUpdater:
         step; ``self.last_outs`` holds the dicts of the last launch's steps."""
         M, B = int(idx_rows.shape[0]), int(idx_rows.shape[1])
         U = int(unroll or self.epoch_unroll)
+        self._check_loss_storage()
         out, j = None, 0
         if not self._epoch_ok() or U <= 1:
             for j in range(M):
@@ -1176,6 +1206,7 @@ class PolicyUpdater:
 
     def _step(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         B = next(v.shape[0] for v in batch.values() if torch.is_tensor(v))
+        self._check_loss_storage()
         seen = getattr(self, "_eager_sizes", None)
         if seen is None:
             seen = self._eager_sizes = set()

@@ -205,6 +205,11 @@ struct TrplCfg {
 // ------------------------------------------------------------------------------------------------ TRPL, lane-parallel form (round 4)
 // PROJ: 0 = KL (kl_projection_layer.py + ITPAL), 1 = Frobenius (frob_projection_layer.py:10-88), 2 = Wasserstein, commutative,
 //       precision-scaled (w2_projection_layer.py:15-76, projection_utils.py:107-149); diagonal policy throughout.
+//       3 = no projection, the clipped PPO surrogate (objectives/ppo.py ClipPPOLoss2 on torchrl 0.3.1 ClipPPOLoss.forward):
+//       lw = log N(action; mean, diag(S)) - old log-prob, gain = min(e^lw adv, e^clamp(lw, log1p(-eps), log1p(eps)) adv), loss = -gain;
+//       d(-gain)/d lw = -e^lw adv, exactly 0 where the clamp is active on the side that wins the min (lw > hi with adv > 0, lw < lo with
+//       adv < 0).  eps is read from a DEVICE float (the loss module's clip_epsilon buffer): a recorded step sees every write to it.  No
+//       trust-region terms: those columns of the slot stay zero; the entropy column (8) carries the policy's own MVN entropy.
 // Covariance projection (KL): eta >= 0 with KL_cov(eta) = cov_bound.  With rho_i = v_i/o_i = (eta+1)/(eta+c_i), c_i = o_i/t_i:
 //   KL = 1/2 sum(rho_i - 1 - log rho_i),  dKL/deta = -1/2 sum (1-c_i)^2 / ((eta+1)(eta+c_i)^2) < 0, KL convex in eta: Newton from eta = 0
 //   approaches the root monotonically from the left (never overshoots).  Phase 1 runs the iteration in fp32 (hardware log2 / reciprocal)
@@ -260,6 +265,7 @@ struct TrplPtrs {
   double* slots;
   const float *tgt_mean, *tgt_S;
   int ms_row0;
+  const float* clip_eps;   // PROJ 3 only: device float[1]
 };
 // The body for workgroup `blk` of a launch whose workgroups have NT threads: the first TRPL_FPB * L of them carry the frames (whole waves:
 // 64 / 128 / 256 threads), the others only take part in the advantage sums and in the barriers.
@@ -308,14 +314,15 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
   __shared__ float redm[NWL][2];
   if (live) {   // (wave-uniform: the frames sit on whole waves)
   const size_t k = (size_t)b * A + ii, kms = (size_t)(b - q_.ms_row0) * A + ii;
-  const double mu = mean[kms], sg = sigma[kms], mo = old_mean[k], So = old_var[k], ac = action[k];
+  const double mu = mean[kms], sg = sigma[kms], ac = action[k];
+  const double mo = PROJ == 3 ? 0.0 : (double)old_mean[k], So = PROJ == 3 ? 1.0 : (double)old_var[k];   // (PPO: no old distribution)
   const double S = sg * sg;                  // policy covariance diagonal == "std" seen by the projection (trpl.py:241)
   const double t = S * S, o = So * So;       // kl_projection_layer.py:60-63: covariance(std) = std**2
   // ---- mean projection (base_projection_layer.py:71-100)
-  double mp;
-  { const double d = (mu - mo) / So; mp = gsum<L>(M(d * d)); }
+  double mp = 0.0;
+  if (PROJ != 3) { const double d = (mu - mo) / So; mp = gsum<L>(M(d * d)); }
   if (PROJ == 0) mp *= 0.5;
-  const bool m_act = mp > cfg.mean_bound;
+  const bool m_act = PROJ != 3 && mp > cfg.mean_bound;
   double omega = 0.0, D = 1.0;
   if (m_act) { omega = sqrt(mp / cfg.mean_bound) - 1.0; D = 1.0 + omega + 1e-16; }
   double pm = m_act ? (mu + omega * mo) / D : mu;
@@ -359,6 +366,10 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
     }
     v = (eta + 1.0) / (eta / o + 1.0 / t);
     pS = sqrt(v);
+  } else if (PROJ == 3) {
+    c_act = false;
+    v = t;
+    pS = S;
   } else {
     const double d = PROJ == 1 ? o - t : 1.0 - S / So;
     const double part = gsum<L>(M(d * d));
@@ -394,6 +405,16 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
   acc[4] = ratio;
   acc[5] = ratio * ratio;
   acc[2] = 0.5 * (A * (1.0 + LOG2PI) + sl);
+  double w_lw = -ratio * adv;   // d loss_objective / d lw of this frame (before the 1/B scale)
+  if (PROJ == 3) {   // clipped surrogate (the header above); the bounds in fp64 from the float32 buffer
+    const double ce = (double)q_.clip_eps[0], lo = log1p(-ce), hi = log1p(ce);
+    const double g1 = ratio * adv, g2 = exp(fmin(fmax(lw, lo), hi)) * adv;
+    acc[0] = -fmin(g1, g2);
+    if ((lw > hi && adv > 0.0) || (lw < lo && adv < 0.0)) w_lw = 0.0;
+  }
+  float mmax = 0.f, cmax = 0.f;
+  if (PROJ == 3) acc[8] = acc[2];   // "entropy": MultivariateNormal(mean, diag(S)).entropy (the reported PPO key)
+  else {
   // ---- trust-region regression loss and metrics
   const double dmk = (mu - pm) / pS, rr = S / pS;
   double mk = gsum<L>(M(dmk * dmk)), ck = gsum<L>(M(rr * rr));
@@ -414,9 +435,11 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
   const double c_ent = 0.5 * A * 2.8378770664093454836;
   acc[8] = c_ent + ldS;
   acc[9] = (c_ent + ldP) - (c_ent + ldS);
-  float mmax = (float)acc[6], cmax = (float)fmax(acc[7], 0.0);
+  mmax = (float)acc[6];
+  cmax = (float)fmax(acc[7], 0.0);
+  }
   // ---- gradients of actor_loss = objective + entropy bonus + trust region  (all already scaled by 1/B)
-  const double w_obj = -ratio * adv * cfg.inv_batch;
+  const double w_obj = w_lw * cfg.inv_batch;
   double g_pm = w_obj * da / pS;
   double g_pS = w_obj * 0.5 * (da * da / (pS * pS) - 1.0 / pS) - cfg.ent_coef * cfg.inv_batch * 0.5 / pS;
   const double ctr = cfg.tr_coeff * cfg.inv_batch;
@@ -454,7 +477,7 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
     const double dm = mu - pm;
     gmu += ctr * 2.0 * dm / (S * S);
     gS += ctr * (-2.0 * dm * dm / (S * S * S) + 2.0 * (S - pS));
-  } else {
+  } else if (PROJ == 2) {
     gmu += ctr * 2.0 * (mu - pm) / (pS * pS);
     gS += ctr * (-2.0 * (1.0 - S / pS) / pS);
   }
@@ -707,7 +730,7 @@ static int trpl_launch(const double* cfg9, int action_dim, const float* mean, co
   const int proj = (int)cfg9[8];
   if (proj < 0 || proj > 2) return -3;
   const TrplPtrs tp{mean, sigma, action, old_mean, old_var, old_logp, advantage, value, old_value, value_target, dmean, dsigma, dvalue,
-                    proj_mean, proj_var, adv_stats, slots, tgt_mean, tgt_S, 0};
+                    proj_mean, proj_var, adv_stats, slots, tgt_mean, tgt_S, 0, nullptr};
 #define GRL_TRPL_LAUNCH(LL, PJ)                                                                                                       \
   hipLaunchKernelGGL((trpl_lanes_kernel<LL, PJ>), dim3(trpl_blocks(batch)), dim3(TRPL_FPB * LL), 0, stream, c, tp, batch)
 #define GRL_TRPL_WIDTH(PJ)                                        \
@@ -723,6 +746,29 @@ static int trpl_launch(const double* cfg9, int action_dim, const float* mean, co
 #undef GRL_TRPL_LAUNCH
   GRL_CHECK_LAUNCH();
   if (sums) {   // sums == NULL: the caller folds the slots later (grl_trpl_fold, on a stream of its choice: the sums are reported values only)
+    hipLaunchKernelGGL(trpl_fold_kernel, dim3(1), dim3(FOLD_NT), 0, stream, slots, trpl_blocks(batch), sums, maxes);
+    GRL_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
+// cfg6 (HOST): {entropy_coef, critic_coef, clip_value, 1/B_global, B_global, adv_local}; clip_eps: DEVICE float[1], read by the kernel
+int grl_ppo_fwd_bwd(const double* cfg6, const float* clip_eps, int action_dim, const float* mean, const float* sigma, const float* action,
+                    const float* old_logp, const float* advantage, const float* value, const float* old_value, const float* value_target,
+                    float* dmean, float* dsigma, float* dvalue, const double* adv_stats, double* sums, unsigned int* maxes, double* slots,
+                    int batch, hipStream_t stream) {
+  if (action_dim > 16 || action_dim < 1 || batch < 1 || !slots || !clip_eps || !mean || !sigma || !action || !old_logp || !advantage ||
+      !dmean || !dsigma)
+    return -2;
+  if (value && (!old_value || !value_target || !dvalue)) return -2;
+  const TrplCfg c{0.0, 0.0, 0.0, cfg6[0], cfg6[1], cfg6[2], cfg6[3], cfg6[4], action_dim, (int)cfg6[5]};
+  const TrplPtrs tp{mean, sigma, action, nullptr, nullptr, old_logp, advantage, value, old_value, value_target, dmean, dsigma, dvalue,
+                    nullptr, nullptr, adv_stats, slots, nullptr, nullptr, 0, clip_eps};
+  if (action_dim <= 4) hipLaunchKernelGGL((trpl_lanes_kernel<4, 3>), dim3(trpl_blocks(batch)), dim3(TRPL_FPB * 4), 0, stream, c, tp, batch);
+  else if (action_dim <= 8) hipLaunchKernelGGL((trpl_lanes_kernel<8, 3>), dim3(trpl_blocks(batch)), dim3(TRPL_FPB * 8), 0, stream, c, tp, batch);
+  else hipLaunchKernelGGL((trpl_lanes_kernel<16, 3>), dim3(trpl_blocks(batch)), dim3(TRPL_FPB * 16), 0, stream, c, tp, batch);
+  GRL_CHECK_LAUNCH();
+  if (sums) {
     hipLaunchKernelGGL(trpl_fold_kernel, dim3(1), dim3(FOLD_NT), 0, stream, slots, trpl_blocks(batch), sums, maxes);
     GRL_CHECK_LAUNCH();
   }

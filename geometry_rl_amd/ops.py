@@ -968,6 +968,41 @@ def trpl_fwd_bwd(loc, sigma, batch, value, *, mean_bound, cov_bound, trust_regio
     return sums, maxes, dloc, dsigma, dvalue, pm, pv
 
 
+def ppo_fwd_bwd(loc, sigma, batch, value, *, clip_epsilon: torch.Tensor, entropy_coef, critic_coef, clip_value, global_batch: int,
+                adv_stats: Optional[torch.Tensor], sums=None, maxes=None, defer_fold: bool = False, adv_local: bool = False):
+    """The clipped PPO objective on the fused kernel (grl_ppo_fwd_bwd): the same returns as ``trpl_fwd_bwd`` without the projection
+    outputs, (sums, maxes, dloc, dsigma, dvalue).  ``clip_epsilon``: a device float32 tensor of one element, read by the kernel when it
+    runs (a recorded launch sees every in-place write to it)."""
+    import ctypes
+    hip.check_f32(loc, sigma, clip_epsilon)
+    if clip_epsilon.numel() != 1 or clip_epsilon.device != loc.device:
+        raise ValueError("clip_epsilon must be a one-element float32 tensor on the policy's device")
+    B, A = loc.shape
+    dev = loc.device
+    cfg = (ctypes.c_double * 6)(entropy_coef, critic_coef, clip_value if clip_value else 0.0, 1.0 / global_batch, float(global_batch),
+                                1.0 if adv_local else 0.0)
+    if sums is None:
+        sums = torch.empty(12, device=dev, dtype=torch.float64)
+        maxes = torch.empty(2, device=dev, dtype=torch.int32)
+    slots = torch.empty(hip.query("grl_trpl_slot_doubles", B), device=dev, dtype=torch.float64)
+    dloc, dsigma = torch.empty_like(loc), torch.empty_like(sigma)
+    dvalue = torch.empty(B, device=dev, dtype=torch.float32) if value is not None else None
+    f = lambda t: t.reshape(B, -1).contiguous()
+    hip.call("grl_ppo_fwd_bwd", cfg, clip_epsilon, A, loc.contiguous(), sigma.contiguous(), f(batch["action"]),
+             batch["sample_log_prob"].reshape(B).contiguous(), batch["advantage"].reshape(B).contiguous(),
+             value.reshape(B).contiguous() if value is not None else None,
+             batch["state_value"].reshape(B).contiguous() if value is not None else None,
+             batch["value_target"].reshape(B).contiguous() if value is not None else None,
+             dloc, dsigma, dvalue, adv_stats, None if defer_fold else sums, maxes, slots, B)
+    if defer_fold:
+        def fold(sums=sums, maxes=maxes, slots=slots):
+            hip.call("grl_trpl_fold", slots, B, sums, maxes)
+            return sums, maxes
+        fold.slots, fold.batch, fold.sums, fold.maxes = slots, B, sums, maxes
+        return fold, maxes, dloc, dsigma, dvalue
+    return sums, maxes, dloc, dsigma, dvalue
+
+
 def trpl_target_terms(loc, sigma, tgt_mean, tgt_S, *, mean_bound, cov_bound, trust_region_coeff, global_batch: int, proj_type: int = 0):
     """Trust-region measure of (p, detached target) with its gradient -- the fused kernel with the projection skipped
     (grl_trpl_target_terms).  ``sigma`` = sqrt of the policy's covariance diagonal, ``tgt_S`` = the target's covariance diagonal.

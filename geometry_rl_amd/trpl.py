@@ -260,7 +260,11 @@ def trpl_launch(m, loc, sigma, value, batch, adv_stats, sums=None, maxes=None, d
     """One launch of the fused kernel on detached inputs: rank-local (sums, maxes) and the gradients of the (1/B_global-scaled)
     losses with respect to loc, sigma and value.  ``defer_fold``: see ops.trpl_fwd_bwd (``sums`` comes back as the folding callable).
     ``adv_local`` (one rank): the advantage statistics are summed inside the kernel; ``value=None``: actor-only (the critic's share of
-    the loss comes from ``value_loss`` on the critic's lane)."""
+    the loss comes from ``value_loss`` on the critic's lane).  A PPO loss module (``m.algorithm == "ppo"``) takes the same launch in
+    its PPO mode (ppo.ppo_launch): same slots, same returns."""
+    if getattr(m, "algorithm", "trpl") == "ppo":
+        from .ppo import ppo_launch
+        return ppo_launch(m, loc, sigma, value, batch, adv_stats, sums=sums, maxes=maxes, defer_fold=defer_fold, adv_local=adv_local)
     p = m.projection
     B = loc.shape[0]
     sums, maxes, dloc, dsigma, dvalue, _, _ = ops.trpl_fwd_bwd(
@@ -287,8 +291,12 @@ def value_loss(m, value, batch):
     return dvalue, mean[0], out2
 
 
-def report_dict(o):
-    """The 14-float output of grl_trpl_report / grl_fold_adam_report as (actor loss, metrics dict of views)."""
+def report_dict(o, m=None):
+    """The 14-float output of grl_trpl_report / grl_fold_adam_report as (actor loss, metrics dict of views); the PPO loss module
+    ``m`` reports its own keys (ppo.report_dict)."""
+    if getattr(m, "algorithm", "trpl") == "ppo":
+        from .ppo import report_dict as ppo_report_dict
+        return ppo_report_dict(o, m)
     return o[0], {"loss_trust_region": o[2], "loss_entropy": o[3], "ESS": o[4], "kl": o[5], "constraint": o[13], "mean_constraint": o[6],
                   "mean_constraint_max": o[7], "cov_constraint": o[8], "cov_constraint_max": o[9], "entropy": o[10],
                   "entropy_diff": o[11], "loss_objective_value": o[12]}
@@ -300,10 +308,7 @@ def report_values(m, slots, B, sums, maxes):
     ent_coef = m.entropy_coef if m.entropy_bonus else 0.0
     o = torch.empty(14, device=sums.device, dtype=torch.float32)
     hip.call("grl_trpl_report", slots, B, sums, maxes, float(ent_coef), o)
-    metrics = {"loss_trust_region": o[2], "loss_entropy": o[3], "ESS": o[4], "kl": o[5], "constraint": o[13], "mean_constraint": o[6],
-               "mean_constraint_max": o[7], "cov_constraint": o[8], "cov_constraint_max": o[9], "entropy": o[10],
-               "entropy_diff": o[11], "loss_objective_value": o[12]}
-    return o[0], o[1], metrics
+    return o[0], o[1], report_dict(o, m)[1]
 
 
 def loss_values(m, sums, maxes):
@@ -312,10 +317,7 @@ def loss_values(m, sums, maxes):
     ent_coef = m.entropy_coef if m.entropy_bonus else 0.0
     o = torch.empty(14, device=sums.device, dtype=torch.float32)
     hip.call("grl_trpl_loss_values", sums, maxes, float(ent_coef), o)
-    metrics = {"loss_trust_region": o[2], "loss_entropy": o[3], "ESS": o[4], "kl": o[5], "constraint": o[13], "mean_constraint": o[6],
-               "mean_constraint_max": o[7], "cov_constraint": o[8], "cov_constraint_max": o[9], "entropy": o[10],
-               "entropy_diff": o[11], "loss_objective_value": o[12]}
-    return o[0], o[1], metrics
+    return o[0], o[1], report_dict(o, m)[1]
 
 
 def _run_trpl(m, loc, sigma, value, batch):
@@ -359,6 +361,18 @@ def _as_batch(td, in_features) -> Dict[str, torch.Tensor]:
     return out
 
 
+def _unwrap(m, attr):
+    """ProbabilisticActor(TensorDictModule(policy)) / ValueOperator(critic): the wrapped nn.Module that has ``attr``."""
+    for path in ("0.module", "module.0.module", "module"):
+        try:
+            inner = m.get_submodule(path)
+        except Exception:
+            continue
+        if hasattr(inner, attr):
+            return inner
+    return m
+
+
 class TRPLLoss(_LossBase):
     """trpl.py:105-321.  ``actor_network`` is a GNNGaussianPolicyDiag (the reference digs the same module out of the
     ProbabilisticActor, trpl.py:243: ``actor_network.get_submodule("0").module`` is tried first, so a ProbabilisticActor wrapping
@@ -369,6 +383,7 @@ class TRPLLoss(_LossBase):
     examples/torchrl/train.py:279-316 runs on it unchanged: ``loss.select(*loss_types).detach()``,
     ``loss["loss_objective"] (+= loss_entropy, loss_trust_region)`` carries the actor gradient, ``loss["loss_critic"]`` the critic
     gradient.  With torchrl importable the class is a ``torchrl.objectives.LossModule``."""
+    algorithm = "trpl"
 
     def __init__(self, actor_network, critic_network, *, projection: KLProjectionLayer, clip_epsilon=0.2, entropy_bonus=True,
                  samples_mc_entropy=1, entropy_coef=0.01, critic_coef=1.0, trust_region_coef=1.0, loss_critic_type="l2",
@@ -377,17 +392,8 @@ class TRPLLoss(_LossBase):
         super().__init__()
         if loss_critic_type != "l2":
             raise NotImplementedError("loss_critic_type is l2 in configs/algorithm/objective/trpl.yaml:12")
-        def unwrap(m, attr):   # ProbabilisticActor(TensorDictModule(policy)) / ValueOperator(critic): the wrapped nn.Module
-            for path in ("0.module", "module.0.module", "module"):
-                try:
-                    inner = m.get_submodule(path)
-                except Exception:
-                    continue
-                if hasattr(inner, attr):
-                    return inner
-            return m
-        actor_network = unwrap(actor_network, "forward_diag")
-        critic_network = unwrap(critic_network, "_network1")
+        actor_network = _unwrap(actor_network, "forward_diag")
+        critic_network = _unwrap(critic_network, "_network1")
         if getattr(projection, "entropy_schedule_type", None):
             raise NotImplementedError("an entropy schedule (base_projection_layer.py:266-283) is not applied by the fused update kernel; the "
                                       "projection layer offers it on its own (KLProjectionLayer.entropy_projection / __call__)")

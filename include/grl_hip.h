@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 /* ABI version (major*10000 + minor*100 + patch); grl_version() returns the value the library was built with. */
-#define GRL_HIP_VERSION 206   /* 206: grl_build_features_noise, grl_step_head_noise[_bf16] added (training noise); 205 (round 6): grl_source_hash added; 204 (round 5): grl_head_fused / grl_head_fused_rows removed, grl_calib_mfma / grl_calib_copy added; the exports are exactly this header */
+#define GRL_HIP_VERSION 207   /* 207: grl_ppo_fwd_bwd added (clipped PPO objective); 206: grl_build_features_noise, grl_step_head_noise[_bf16] added (training noise); 205 (round 6): grl_source_hash added; 204 (round 5): grl_head_fused / grl_head_fused_rows removed, grl_calib_mfma / grl_calib_copy added; the exports are exactly this header */
 int grl_version(void);
 /* The hash of the sources this binary was built from (16 hex digits + NUL into buf; returns the length).  geometry_rl_amd/hip.py
    source_hash() recomputes it from csrc/, this header and the build's flag tables and refuses a library that disagrees. */
@@ -271,6 +271,17 @@ int grl_trpl_fwd_bwd(const double* cfg9, int action_dim, const float* mean, cons
                      unsigned int* maxes, double* slots /* scratch, grl_trpl_slot_doubles(batch) doubles: per-workgroup sums, folded
                      in a fixed order into sums / maxes (written, not accumulated; bitwise reproducible) */, int batch,
                      hipStream_t stream);
+/* (ABI 207) the clipped PPO objective (objectives/ppo.py ClipPPOLoss2 -> torchrl 0.3.1 ClipPPOLoss.forward) on the same kernel, no projection:
+ * per frame lw = log N(action; mean, diag(sigma^2)) - old_logp, gain = min(e^lw adv, e^clamp(lw, log1p(-eps), log1p(eps)) adv).
+ * cfg6 (HOST): {entropy_coef, critic_coef, clip_value, 1/B_global, B_global, adv_local (as in cfg9)}; clip_eps: DEVICE float[1], read at
+ * run time (a recorded launch sees every write to it).  Slots / sums / maxes / adv_stats / value arguments as grl_trpl_fwd_bwd; sums[0] =
+ * sum of -gain, sums[2] = sums[8] = sum of the policy's entropy, sums[4..5] as TRPL (ESS), the trust-region and KL columns are zero, so
+ * every fold / report / record entry point serves it unchanged.  dmean / dsigma = gradient of (sum -gain - entropy_coef * sum entropy) /
+ * B_global, dvalue as grl_trpl_fwd_bwd. */
+int grl_ppo_fwd_bwd(const double* cfg6, const float* clip_eps, int action_dim, const float* mean, const float* sigma, const float* action,
+                    const float* old_logp, const float* advantage, const float* value, const float* old_value, const float* value_target,
+                    float* dmean, float* dsigma, float* dvalue, const double* adv_stats, double* sums, unsigned int* maxes, double* slots,
+                    int batch, hipStream_t stream);
 /* projection-layer boundary methods for an arbitrary DETACHED target (base_projection_layer.py:292-327 get_trust_region_loss,
  * :332-384 compute_metrics): the same kernel with its projection step skipped.  tgt_S = the target's "std" diagonal as the layer
  * sees it (= covariance diagonal of the policy).  sums[1] = trust_region_coeff * sum measure(p, target), sums[6..9,11] / maxes = the

@@ -1,0 +1,403 @@
+"""The clipped PPO objective (geometry_rl_amd.ppo.ClipPPOLoss2, grl_ppo_fwd_bwd) on the GPU:
+  (a) the kernel against the float64 restatement (tests/ppo_ref.py), frames on both sides of both bounds with both advantage signs;
+  (b) five consecutive PolicyUpdater updates against the PPO oracle (clip_grad_norm, objective/default.yaml), recorded from the third on;
+  (c) the recorded programs against the step-by-step loop (lanes, one stream, run_minibatches in its multi-step forms);
+  (d) an annealed clip epsilon written in place takes effect at the next replay without recording again;
+  (e) two data-parallel ranks against one rank on the whole batch;
+  (f) the reference loop protocol (loss_module(td), two backward passes, two Adam steps) against PolicyUpdater.step."""
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import step as ost
+from geometry_rl_amd import synthetic as syn
+from parity_util import adam_first_step_bound, grad_scales
+from ppo_ref import PPOOracleAgent, ppo_loss
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+
+
+# ------------------------------------------------------------------------------------------------------------- (a) kernel
+@pytest.mark.parametrize("A", [6, 12])
+def test_kernel_matches_the_restatement(A):
+    from geometry_rl_amd import ops
+    eps = 0.2
+    lo, hi = math.log1p(-eps), math.log1p(eps)
+    g = torch.Generator().manual_seed(11 + A)
+    regions = torch.tensor([lo - 0.6, lo - 0.05, 0.5 * lo, 0.0, 0.5 * hi, hi + 0.05, hi + 0.6], dtype=torch.float64)
+    B = 7 * 12 + 5   # not a multiple of the 16 frames per workgroup
+    lw_t = regions.repeat(13)[:B] + 0.01 * (torch.rand(B, generator=g, dtype=torch.float64) - 0.5)   # >= 0.04 from either bound
+    loc = torch.randn(B, A, generator=g).float()
+    sigma = (torch.rand(B, A, generator=g) + 0.4).float()
+    action = (loc.double() + sigma.double() * torch.randn(B, A, generator=g, dtype=torch.float64)).float()
+    var = sigma.double() ** 2
+    from oracle import trpl as otr
+    logp = (otr.mvn_diag_log_prob(action.double(), loc.double(), var) - lw_t).float()
+    adv = torch.randn(B, generator=g).float()
+    batch = {"action": action, "sample_log_prob": logp, "advantage": adv, "state_value": torch.randn(B, generator=g).float(),
+             "value_target": torch.randn(B, generator=g).float()}
+    value = (batch["state_value"] + 0.4 * torch.randn(B, generator=g)).float()
+    ent_coef, critic_coef, clip_value = 0.01, 0.5, 0.2
+    # reference (float64 autograd on the float32 inputs)
+    loc_r = loc.double().requires_grad_(True)
+    sig_r = sigma.double().requires_grad_(True)
+    val_r = value.double().requires_grad_(True)
+    bd = {k: v.double() for k, v in batch.items()}
+    ref = ppo_loss(loc_r, sig_r ** 2, bd, val_r, clip_epsilon=eps, entropy_coef=ent_coef, critic_coef=critic_coef, clip_value=clip_value)
+    d_loc, d_sig = torch.autograd.grad(ref["loss_objective"] + ref["loss_entropy"], [loc_r, sig_r])
+    (d_val,) = torch.autograd.grad(ref["loss_critic"], [val_r])
+    lw = ref["lw"]
+    assert bool(((lw - lo).abs() > 0.03).all() and ((lw - hi).abs() > 0.03).all())
+    a_n = (adv.double() - adv.double().mean()) / adv.double().std()
+    for side in ((lw > hi) & (a_n > 0), (lw < lo) & (a_n < 0), (lw > hi) & (a_n < 0), (lw < lo) & (a_n > 0), (lw > lo) & (lw < hi)):
+        assert int(side.sum()) >= 3   # every region is populated
+    # kernel
+    ce = torch.tensor(eps, dtype=torch.float32, device=DEV)
+    db = {k: v.to(DEV) for k, v in batch.items()}
+    sums, maxes, dloc, dsigma, dvalue = ops.ppo_fwd_bwd(loc.to(DEV), sigma.to(DEV), db, value.to(DEV), clip_epsilon=ce, entropy_coef=ent_coef,
+                                                        critic_coef=critic_coef, clip_value=clip_value, global_batch=B, adv_stats=None,
+                                                        adv_local=True)
+    s = sums.cpu()
+    n = float(s[10])
+    assert n == B
+    got = {"loss_objective": float(s[0]) / n, "entropy": float(s[2]) / n, "entropy_col8": float(s[8]) / n,
+           "loss_critic": float(s[3]) / n, "ESS": float(s[4] ** 2 / s[5]) / n}
+    want = {"loss_objective": float(ref["loss_objective"]), "entropy": float(ref["entropy"]), "entropy_col8": float(ref["entropy"]),
+            "loss_critic": float(ref["loss_critic"]), "ESS": float(ref["ESS"])}
+    for k in got:
+        assert abs(got[k] - want[k]) <= 1e-5 * max(1.0, abs(want[k])), (k, got[k], want[k])
+    for col in (1, 6, 7, 9, 11):   # trust-region / KL columns stay zero
+        assert float(s[col]) == 0.0, col
+    for name, a, b in (("dloc", dloc, d_loc), ("dsigma", dsigma, d_sig), ("dvalue", dvalue, d_val)):
+        a = a.cpu().double()
+        err = float((a - b).abs().max())
+        scale = float(b.abs().max())
+        print(f"A={A} {name}: max err {err:.3e} of scale {scale:.3e}")
+        assert err <= 1e-5 * scale, (name, err, scale)
+    zero = ((lw > hi) & (a_n > 0)) | ((lw < lo) & (a_n < 0))
+    assert bool((dloc.cpu()[zero] == 0).all())   # the clipped side wins: no objective gradient (and loc has no entropy term)
+    assert bool((dloc.cpu()[~zero].abs().sum(-1) > 0).all())
+
+
+# ------------------------------------------------------------------------------------------------------------- (b) vs oracle
+def _obs(name, B, seed):
+    if name == "rigid_g1":
+        return syn.make_rigid_obs(B, seed=seed)
+    if name == "cloth":
+        return syn.make_cloth_obs(B, n_particles=25, E_cloth=40, seed=seed)
+    return syn.make_rigid_obs(B, G=2, angular_velocity=False, object_velocity=False, seed=seed)
+
+
+PPO_KW = dict(algorithm="ppo", clip_epsilon=0.2, critic_coef=1.0, clip_value=0.2, clip_grad_norm=True, max_grad_norm=1.0)   # objective/default.yaml
+
+
+@pytest.mark.parametrize("name,B,K", [("rigid_g1", 64, 5), ("cloth", 16, 5), ("empn_g2", 32, 5)])
+def test_five_updates_match_the_ppo_oracle(name, B, K):
+    from geometry_rl_amd import agent
+    from test_gpu_step import load_params, make_case
+    torch.set_num_threads(min(32, os.cpu_count() or 1))
+    o_spec, spec, kw, _ = make_case(name, B)
+    o_cfg = ost.AgentConfig(**dict(kw, critic_coef=1.0, clip_value=0.2, clip_grad_norm=True))
+    cfg = agent.AgentConfig(**dict(kw, **PPO_KW))
+    a_par, c_par = ost.init_agent_params(o_spec, o_cfg, seed=21)
+    oracle = PPOOracleAgent(o_spec, o_cfg, a_par, c_par)
+    actor, critic, proj, loss = agent.build_agent(spec, cfg, device=DEV)
+    assert proj is None
+    load_params(actor, a_par, DEV)
+    load_params(critic, {"_network1." + k: v for k, v in c_par.items()}, DEV)
+    A = spec.num_actuators * cfg.output_dim_vec * 3
+    batches = []
+    for i in range(K):
+        b = dict(_obs(name, B, 30 + i))
+        b.update(syn.make_ppo_fields(B, A, seed=40 + i))
+        batches.append(b)
+    with torch.no_grad():
+        oracle.actor_forward({k: batches[0][k] for k in o_spec.in_features}, calibrate=True)
+    actor.load_state_dict({k: v.detach().to(DEV) for k, v in oracle.actor.items()}, strict=False)
+    for mod in actor.modules():
+        if hasattr(mod, "callibrated"):
+            mod.callibrated.fill_(True)
+    actor._calib_checked = True
+    upd = agent.PolicyUpdater(loss, lr=cfg.lr, clip_grad_norm=cfg.clip_grad_norm, max_grad_norm=cfg.max_grad_norm, use_graph=True)
+    g_scale = None
+    clipped_frac = []
+    for i, b in enumerate(batches):
+        ref, ref_grads = oracle.update(b)
+        out = upd.step({k: v.to(DEV) for k, v in b.items()})
+        assert set(out) >= {"loss_objective", "loss_critic", "ESS", "entropy", "loss_entropy"} and "kl" not in out
+        lw = ref["lw"]
+        clipped_frac.append(float(((lw > math.log1p(0.2)) | (lw < math.log1p(-0.2))).double().mean()))
+        sc = {net: grad_scales(ref_grads[net]) for net in ("actor", "critic")}
+        g_scale = sc if g_scale is None else {net: {k: max(v, g_scale[net].get(k, 0.0)) for k, v in sc[net].items()} for net in sc}
+        for k in ("loss_objective", "loss_critic", "loss_entropy", "entropy", "ESS"):
+            e = abs(float(out[k]) - float(ref[k]))
+            assert e <= 1e-4 * max(1.0, abs(float(ref[k]))), (i, k, e)
+    print("fraction of frames outside the clip bounds per update:", clipped_frac)
+    assert min(clipped_frac) > 0.0   # the clipped branch is exercised
+    assert upd.mode.startswith("graph") and upd._program is not None
+    torch.cuda.synchronize()
+    off = lambda p: (p.data_ptr() - upd.flat.data_ptr()) // 4
+    bad = []
+    for net, mod, ref_p, optim, strip in (("actor", actor, oracle.actor, oracle.actor_optim, 0),
+                                          ("critic", critic, oracle.critic, oracle.critic_optim, len("_network1."))):
+        states = {kk: optim.state.get(ref_p[kk], {}) for kk in ref_p}
+        m_ref = {kk: s_["exp_avg"] for kk, s_ in states.items() if "exp_avg" in s_}
+        v_ref = {kk: s_["exp_avg_sq"] for kk, s_ in states.items() if "exp_avg_sq" in s_}
+        m_sc, v_sc = grad_scales(m_ref), grad_scales(v_ref)
+        for k, p in mod.named_parameters():
+            kk = k[strip:]
+            if kk not in m_ref:
+                continue
+            o, n = off(p), p.numel()
+            em = float((upd.exp_avg[o:o + n].view_as(p).cpu().double() - m_ref[kk].double()).abs().max())
+            ev = float((upd.exp_avg_sq[o:o + n].view_as(p).cpu().double() - v_ref[kk].double()).abs().max())
+            ep = float((p.detach().cpu().double() - ref_p[kk].detach().double()).abs().max())
+            allowed_p = K * adam_first_step_bound(cfg.lr, 1e-5, g_scale[net].get(kk, 0.0), cfg.clip_grad_norm, p_ref=ref_p[kk])
+            if not (em <= 5e-4 * m_sc[kk] and ev <= 1e-3 * v_sc[kk] and ep <= allowed_p and np.isfinite(em + ev + ep)):
+                bad.append((net, kk, em / m_sc[kk], ev / v_sc[kk], ep, allowed_p))
+    assert not bad, bad
+
+
+# ------------------------------------------------------------------------------------------------------------- (c), (d)
+def _make(N, T, seed, **cfg_kw):
+    from geometry_rl_amd import agent, graph
+    spec = graph.rigid_spec()
+    cfg = agent.AgentConfig(only_upper_hemisphere=True, output_dim=2, output_dim_vec=2, **dict(PPO_KW, clip_grad_norm=False, **cfg_kw))
+    torch.manual_seed(0)
+    actor, critic, proj, loss = agent.build_agent(spec, cfg, device=DEV)
+    frames = []
+    for t in range(T + 1):
+        b = dict(syn.make_rigid_obs(N, seed=seed + t))
+        b.update(syn.make_ppo_fields(N, 6, seed=seed + t))
+        frames.append(b)
+    data = {k: torch.stack([f[k] for f in frames[:T]], dim=1).to(DEV) for k in frames[0]}
+    g = syn.make_gae_inputs(N, T, seed=seed)
+    data.update(reward=g["reward"].reshape(N, T, 1).to(DEV), done=g["done"].reshape(N, T, 1).to(DEV),
+                terminated=g["terminated"].reshape(N, T, 1).to(DEV))
+    next_last = {k: frames[T][k].unsqueeze(1).to(DEV) for k in spec.in_features}
+    with torch.no_grad():
+        actor.forward_diag(*[data[k][:, 0].contiguous() for k in spec.in_features], train=True)   # calibration
+    return spec, cfg, loss, data, next_last
+
+
+KEYS = ("loss_objective", "loss_critic", "ESS", "entropy", "loss_entropy")
+
+
+@pytest.mark.parametrize("form", ["unrolled", "per_step", "cursor"])
+def test_run_minibatches_equals_the_step_loop(form):
+    from geometry_rl_amd import agent
+    from geometry_rl_amd.rollout import RolloutBuffer, RolloutDriver
+    N, T = 8, 10
+    res = {}
+    for mode in ("loop", "launches"):
+        spec, cfg, loss, data, next_last = _make(N, T, seed=33)
+        upd = agent.PolicyUpdater(loss, lr=cfg.lr, use_graph=True)
+        upd.epoch_unroll = 4 if mode == "launches" else 1
+        if form == "per_step":
+            upd.form_by_size[N] = "per_step"
+        if form == "cursor":
+            upd.epoch_unroll_max_gated_frames, upd.epoch_gated_from_frames, upd.epoch_cursor = 0, 0, True
+        buf = RolloutBuffer(dict(data))
+        drv = RolloutDriver(upd, spec, ppo_epochs=2, seed=9)
+        drv.compute_advantages(buf, next_last)
+        outs = []
+        if mode == "loop":
+            for idx in drv.minibatches(buf):
+                o = upd.step_from(buf, idx)
+                outs.append({k: o[k].clone() for k in KEYS})
+        else:
+            for _ in range(2):
+                o = upd.run_minibatches(buf, torch.stack(drv.epoch_minibatches(buf.N, buf.T, DEV)))
+            assert (upd._epoch is not None) == (form != "per_step")
+            outs.append({k: o[k].clone() for k in KEYS})
+        torch.cuda.synchronize()
+        assert upd.steps == 2 * T
+        res[mode] = (upd.flat.detach().clone(), upd.exp_avg.detach().clone(), upd.exp_avg_sq.detach().clone(), outs)
+    for a, b in zip(res["loop"][:3], res["launches"][:3]):
+        assert torch.equal(a, b), (a - b).abs().max().item()
+    for k in KEYS:   # the last update's loss dict
+        assert torch.equal(res["loop"][3][-1][k], res["launches"][3][-1][k]), k
+
+
+def test_recorded_programs_equal_the_eager_loop():
+    """Eager steps, the recorded lanes program and the one-stream program (overlap_critic=False) over the same four updates: the replayed
+    lanes program is the eager loop's arithmetic; the one-stream program sums the advantage statistics in another launch (last bits)."""
+    from geometry_rl_amd import agent
+    N, T, k = 8, 2, 4
+    res = {}
+    for mode in ("eager", "graph", "one_stream", "one_stream_eager"):
+        spec, cfg, loss, data, next_last = _make(N, T, seed=41)
+        batch = {kk: v[:, 0].contiguous() for kk, v in data.items()}
+        upd = agent.PolicyUpdater(loss, lr=cfg.lr, use_graph=mode in ("graph", "one_stream"), overlap_critic=not mode.startswith("one_stream"))
+        outs = [{kk: v.clone() for kk, v in upd.step(batch).items() if kk in KEYS} for _ in range(k)]
+        torch.cuda.synchronize()
+        res[mode] = (upd.flat.detach().clone(), upd.exp_avg.detach().clone(), upd.exp_avg_sq.detach().clone(), outs)
+    for a, b in (("eager", "graph"), ("one_stream_eager", "one_stream")):
+        for x, y in zip(res[a][:3], res[b][:3]):
+            assert (x - y).abs().max().item() <= 1e-7, (a, b)
+        for oa, ob in zip(res[a][3], res[b][3]):
+            for kk in KEYS:
+                assert abs(float(oa[kk]) - float(ob[kk])) <= 1e-6 * max(1.0, abs(float(oa[kk]))), (a, b, kk)
+    assert (res["graph"][0] - res["one_stream"][0]).abs().max().item() <= 1e-6
+
+
+def test_annealed_clip_epsilon_takes_effect_on_replay():
+    from geometry_rl_amd import agent
+    N, T = 8, 4
+    res = {}
+    for mode in ("graph", "eager", "graph_unannealed"):
+        spec, cfg, loss, data, next_last = _make(N, T, seed=51)
+        upd = agent.PolicyUpdater(loss, lr=cfg.lr, use_graph=mode != "eager")
+        ptr = loss.clip_epsilon.data_ptr()
+        prog = None
+        outs = []
+        for t in range(T):
+            if t == 2:
+                prog = upd._program
+                assert (prog is not None) == (mode != "eager")
+                if mode != "graph_unannealed":
+                    loss.clip_epsilon.copy_(torch.tensor(0.1))   # train.py:272-274
+            outs.append({k: v.clone() for k, v in upd.step({kk: v[:, t].contiguous() for kk, v in data.items()}).items() if k in KEYS})
+        torch.cuda.synchronize()
+        if mode == "graph":
+            assert upd._program is prog and loss.clip_epsilon.data_ptr() == ptr   # replayed, not recorded again
+        res[mode] = (upd.flat.detach().clone(), outs)
+    assert (res["graph"][0] - res["eager"][0]).abs().max().item() <= 1e-7
+    for oa, ob in zip(res["graph"][1], res["eager"][1]):
+        for k in KEYS:
+            assert abs(float(oa[k]) - float(ob[k])) <= 1e-6 * max(1.0, abs(float(ob[k]))), k
+    # the write changed the update (epsilon was read): the unannealed replay differs from step 3 on
+    assert not torch.equal(res["graph"][1][2]["loss_objective"], res["graph_unannealed"][1][2]["loss_objective"])
+
+
+def test_replacing_the_clip_epsilon_buffer_records_again():
+    from geometry_rl_amd import agent
+    N, T = 8, 4
+    spec, cfg, loss, data, next_last = _make(N, T, seed=52)
+    upd = agent.PolicyUpdater(loss, lr=cfg.lr, use_graph=True)
+    for t in range(3):
+        upd.step({kk: v[:, t].contiguous() for kk, v in data.items()})
+    prog = upd._program
+    assert prog is not None
+    loss.clip_epsilon = torch.tensor(0.1, device=DEV)   # a new tensor, not an in-place write
+    upd.step({kk: v[:, 3].contiguous() for kk, v in data.items()})
+    assert upd._program is not prog
+
+
+# ------------------------------------------------------------------------------------------------------------- (e) data parallel
+def _dp_setup(B, group):
+    from geometry_rl_amd import agent, graph
+    spec = graph.rigid_spec(G=2, angular_velocity=False, object_velocity=False)
+    cfg = agent.AgentConfig(**PPO_KW)
+    torch.manual_seed(0)
+    actor, critic, proj, loss = agent.build_agent(spec, cfg, device=DEV, group=group)
+    batch = dict(syn.make_rigid_obs(B, G=2, angular_velocity=False, object_velocity=False, seed=4))
+    batch.update(syn.make_ppo_fields(B, 6, seed=4))
+    return spec, cfg, actor, loss, {k: v.to(DEV) for k, v in batch.items()}
+
+
+def _dp_worker(rank, world, port, B, ret):
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from geometry_rl_amd import agent
+    spec, cfg, actor, loss, batch = _dp_setup(B, dist.group.WORLD)
+    with torch.no_grad():
+        actor.forward_diag(*[batch[k] for k in spec.in_features], train=True)
+    lo, hi = rank * B // world, (rank + 1) * B // world
+    shard = {k: v[lo:hi].contiguous() for k, v in batch.items()}
+    upd = agent.PolicyUpdater(loss, lr=cfg.lr, clip_grad_norm=cfg.clip_grad_norm, group=dist.group.WORLD, use_graph=True)
+    for _ in range(3):
+        out = upd.step(shard)
+    ret[rank] = ({k: float(out[k].detach()) for k in KEYS}, upd.flat.detach().cpu())
+    dist.destroy_process_group()
+
+
+def test_two_ranks_match_single_rank():
+    import torch.multiprocessing as mp
+    from geometry_rl_amd import agent
+    from spawn_util import spawn_ranks
+    B, world = 16, 2
+    spec, cfg, actor, loss, batch = _dp_setup(B, None)
+    with torch.no_grad():
+        actor.forward_diag(*[batch[k] for k in spec.in_features], train=True)
+    upd = agent.PolicyUpdater(loss, lr=cfg.lr, clip_grad_norm=cfg.clip_grad_norm, use_graph=True)
+    for _ in range(3):
+        out = upd.step(batch)
+    ref_losses = {k: float(out[k].detach()) for k in KEYS}
+    ref_flat = upd.flat.detach().cpu()
+    ret = mp.Manager().dict()
+    spawn_ranks(_dp_worker, world, (world,), (B, ret))
+    assert all(r in ret for r in range(world))
+    for r in range(world):
+        losses, flat = ret[r]
+        for k, v in ref_losses.items():
+            assert abs(losses[k] - v) <= 1e-5 * max(1.0, abs(v)), (r, k, losses[k], v)
+        err = (flat - ref_flat).abs().max().item()
+        print(f"rank {r}: max |param - single-rank param| = {err:.3e}")
+        assert err <= 2e-6
+
+
+# ------------------------------------------------------------------------------------------------------------- (f) reference loop
+@pytest.mark.parametrize("model", ["hepi", "transformer"])
+def test_reference_loop_protocol_matches_the_updater(model):
+    """examples/torchrl/train.py:279-316 with algorithm=ppo on the loss module itself, against PolicyUpdater.step on a copy."""
+    from geometry_rl_amd import agent, graph
+    B = 32
+    spec = graph.rigid_spec()
+    kw = dict(model="transformer", output_dim=2, output_dim_vec=2) if model == "transformer" else \
+        dict(only_upper_hemisphere=True, output_dim=2, output_dim_vec=2)
+    cfg = agent.AgentConfig(**dict(kw, **PPO_KW))
+    batch = dict(syn.make_rigid_obs(B, seed=61))
+    batch.update(syn.make_ppo_fields(B, 6, seed=61))
+    batch = {k: v.to(DEV) for k, v in batch.items()}
+    sides = []
+    for _ in range(2):
+        torch.manual_seed(5)
+        actor, critic, proj, loss = agent.build_agent(spec, cfg, device=DEV)
+        with torch.no_grad():
+            actor.forward_diag(*[batch[k] for k in loss.in_features], train=True)   # calibration (HEPi), identical on both sides
+        sides.append((actor, critic, loss))
+    # the reference loop
+    actor, critic, loss = sides[0]
+    a_par = [p for p in actor.parameters() if p.requires_grad]
+    c_par = [p for p in critic.parameters() if p.requires_grad]
+    a_opt = torch.optim.Adam(a_par, lr=cfg.lr, eps=1e-5)
+    c_opt = torch.optim.Adam(c_par, lr=cfg.lr, eps=1e-5)
+    ref = []
+    for _ in range(2):
+        out = loss(dict(batch))
+        assert set(loss.out_keys) <= set(out.keys())
+        ref.append({k: float(out[k].detach()) for k in KEYS})
+        critic_loss = out["loss_critic"]
+        actor_loss = out["loss_objective"]
+        actor_loss += out["loss_entropy"]
+        actor_loss.backward()
+        critic_loss.backward()
+        torch.nn.utils.clip_grad_norm_(a_par, cfg.max_grad_norm)
+        torch.nn.utils.clip_grad_norm_(c_par, cfg.max_grad_norm)
+        a_opt.step()
+        c_opt.step()
+        a_opt.zero_grad()
+        c_opt.zero_grad()
+    # the updater
+    actor2, critic2, loss2 = sides[1]
+    upd = agent.PolicyUpdater(loss2, lr=cfg.lr, clip_grad_norm=True, max_grad_norm=cfg.max_grad_norm)
+    got = []
+    for _ in range(2):
+        o = upd.step(dict(batch))
+        got.append({k: float(o[k]) for k in KEYS})
+    for r, g_ in zip(ref, got):
+        for k in KEYS:
+            assert abs(r[k] - g_[k]) <= 1e-5 * max(1.0, abs(r[k])), (k, r[k], g_[k])
+    worst = 0.0
+    for (n1, p1), (n2, p2) in zip(list(actor.named_parameters()) + list(critic.named_parameters()),
+                                  list(actor2.named_parameters()) + list(critic2.named_parameters())):
+        assert n1 == n2
+        worst = max(worst, float((p1.detach() - p2.detach()).abs().max()))
+    print(f"{model}: max |param(reference loop) - param(updater)| = {worst:.3e}")
+    assert worst <= 2e-5
