@@ -540,8 +540,25 @@ __global__ __launch_bounds__(256) void softmax_agg_bwd_kernel(const float* __res
     const int e0 = rowptr[d], e1 = rowptr[d + 1];
     float mx = -3.0e38f, den = 0.f;
     for (int e = e0; e < e1; ++e) mx = fmaxf(mx, gate[((size_t)e * O + o) * C + c]);
+#if GRL_PREC
+    // bf16 build: x1 is recomputed in fp32 (the forward's operations in the forward's order) instead of read back from its bf16 store.
+    // d gate_e = alpha_e dx1 (msg_e - x1) sums to zero over the in-edges of d only with the x1 that the alphas produced: the stored
+    // x1 is off by up to half a bf16 ulp, the same offset for every edge of the destination, and that bias does not cancel in the
+    // gate network's weight gradient, a sum over edges of d gate_e msg_e whose true value is a small difference of large terms.
+    float num = 0.f;
+    for (int e = e0; e < e1; ++e) {
+      const size_t i = ((size_t)e * O + o) * C + c;
+      const float w = expf(gate[i] - mx);
+      den += w;
+      num = fmaf(w, ld1(msg + i), num);
+    }
+    const float xo = e1 > e0 ? num / (den + 1e-16f) : 0.f;
+    (void)x1;
+#else
     for (int e = e0; e < e1; ++e) den += expf(gate[((size_t)e * O + o) * C + c] - mx);
-    const float inv = 1.f / (den + 1e-16f), g = ld1(dx1 + (size_t)row * C + c), xo = ld1(x1 + (size_t)row * C + c);
+    const float xo = ld1(x1 + (size_t)row * C + c);
+#endif
+    const float inv = 1.f / (den + 1e-16f), g = ld1(dx1 + (size_t)row * C + c);
     for (int e = e0; e < e1; ++e) {
       const size_t i = ((size_t)e * O + o) * C + c;
       const float a = expf(gate[i] - mx) * inv;
