@@ -34,7 +34,7 @@ class AgentConfig:
     minimal_std: float = 1e-5
     mean_bound: float = 0.05
     cov_bound: float = 0.0025
-    proj_type: str = "kl"  # kl | frob | w2
+    proj_type: str = "kl"  # kl | frob | w2 | w2_non_com
     trust_region_coeff: float = 1.0
     entropy_coef: float = 0.005
     critic_coef: float = 0.5

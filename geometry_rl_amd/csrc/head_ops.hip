@@ -210,6 +210,14 @@ struct TrplCfg {
 //       d(-gain)/d lw = -e^lw adv, exactly 0 where the clamp is active on the side that wins the min (lw > hi with adv > 0, lw < lo with
 //       adv < 0).  eps is read from a DEVICE float (the loss module's clip_epsilon buffer): a recorded step sees every write to it.  No
 //       trust-region terms: those columns of the slot stay zero; the entropy column (8) carries the policy's own MVN entropy.
+//       4 = Wasserstein, non-commuting (w2_projection_layer_non_com.py:13-86, torch_utils.py sqrtm_newton), precision-scaled; on the
+//       diagonal policy every matrix of the layer is diagonal: mp, cp as for 2; ONE joint bound, ONE interpolation weight
+//       t = sqrt((eps + eps_cov) / (mp + cp + 1e-16)) where mp + cp > eps + eps_cov:  proj_mean = (1-t) mo + t mu,
+//       d = (1-t) + t S So, x = d^2 So^2, n = sqrt(sum x^2), then the reference's TEN Newton-Schulz steps from Y = x / n, Z = 1:
+//       T = (3 - Z Y) / 2, Y <- Y T, Z <- T Z; proj_S = Y sqrt(n).  Ten steps are its semantics, not an approximation to refine: where
+//       x_i / n is small they have not converged (1e-3: 2.4 %, 1e-4: 47 % below sqrt(x_i)).  The backward runs through t, d, n and the ten steps in
+//       reverse (their iterates kept in registers); frames inside the bound pass the gradient through.  Trust-region terms and metrics
+//       as 2 (trust_region_value = the non-commuting W2, which equals the commutative one on diagonal matrices).
 // Covariance projection (KL): eta >= 0 with KL_cov(eta) = cov_bound.  With rho_i = v_i/o_i = (eta+1)/(eta+c_i), c_i = o_i/t_i:
 //   KL = 1/2 sum(rho_i - 1 - log rho_i),  dKL/deta = -1/2 sum (1-c_i)^2 / ((eta+1)(eta+c_i)^2) < 0, KL convex in eta: Newton from eta = 0
 //   approaches the root monotonically from the left (never overshoots).  Phase 1 runs the iteration in fp32 (hardware log2 / reciprocal)
@@ -322,13 +330,14 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
   double mp = 0.0;
   if (PROJ != 3) { const double d = (mu - mo) / So; mp = gsum<L>(M(d * d)); }
   if (PROJ == 0) mp *= 0.5;
-  const bool m_act = PROJ != 3 && mp > cfg.mean_bound;
+  const bool m_act = PROJ != 3 && PROJ != 4 && mp > cfg.mean_bound;   // (4: one joint bound, below)
   double omega = 0.0, D = 1.0;
   if (m_act) { omega = sqrt(mp / cfg.mean_bound) - 1.0; D = 1.0 + omega + 1e-16; }
   double pm = m_act ? (mu + omega * mo) / D : mu;
   // ---- covariance projection (derivation: the header above)
   double eta = 0.0, v, pS;
   bool c_act;
+  double w_t = 1.0, w_tot = 0.0, w_d = 1.0, w_x = 0.0, w_n = 1.0, ys[10], zs[10];   // PROJ 4: the forward's intermediates
   if (PROJ == 0) {
     const double rho0 = t / o;
     c_act = 0.5 * gsum<L>(M(rho0 - 1.0 - log(rho0))) > cfg.cov_bound;
@@ -370,6 +379,29 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
     c_act = false;
     v = t;
     pS = S;
+  } else if (PROJ == 4) {
+    const double r = 1.0 - S / So;
+    w_tot = mp + gsum<L>(M(r * r));
+    c_act = w_tot > cfg.mean_bound + cfg.cov_bound;
+    pS = S;
+    if (c_act) {
+      w_t = sqrt((cfg.mean_bound + cfg.cov_bound) / (w_tot + 1e-16));
+      pm = (1.0 - w_t) * mo + w_t * mu;
+      w_d = (1.0 - w_t) + w_t * S * So;
+      w_x = w_d * w_d * (So * So);
+      w_n = sqrt(gsum<L>(M(w_x * w_x)));
+      double y = w_x / w_n, z = 1.0;
+#pragma unroll
+      for (int it = 0; it < 10; ++it) {
+        ys[it] = y;
+        zs[it] = z;
+        const double T = 0.5 * (3.0 - z * y);
+        y = y * T;
+        z = T * z;
+      }
+      pS = y * sqrt(w_n);
+    }
+    v = pS * pS;
   } else {
     const double d = PROJ == 1 ? o - t : 1.0 - S / So;
     const double part = gsum<L>(M(d * d));
@@ -424,14 +456,14 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
     const double f = pS * pS - S * S, dm = (mu - pm) / S, ds = S - pS;
     cd = gsum<L>(M(f * f)); mS = gsum<L>(M(dm * dm)); sq = gsum<L>(M(ds * ds));
   }
-  if (PROJ == 2) cd = gsum<L>(M((1.0 - rr) * (1.0 - rr)));
+  if (PROJ == 2 || PROJ == 4) cd = gsum<L>(M((1.0 - rr) * (1.0 - rr)));
   const double md = mk;
   mk *= 0.5;
   ck = 0.5 * (ck - A + 2.0 * ldP - 2.0 * ldS);
   acc[10] = mk + ck;
   if (PROJ == 0) { acc[1] = (mk + ck) * cfg.tr_coeff; acc[6] = mk; acc[7] = ck; }
   if (PROJ == 1) { acc[1] = (mS + sq) * cfg.tr_coeff; acc[6] = md; acc[7] = cd; }
-  if (PROJ == 2) { acc[1] = (md + cd) * cfg.tr_coeff; acc[6] = md; acc[7] = cd; }
+  if (PROJ == 2 || PROJ == 4) { acc[1] = (md + cd) * cfg.tr_coeff; acc[6] = md; acc[7] = cd; }
   const double c_ent = 0.5 * A * 2.8378770664093454836;
   acc[8] = c_ent + ldS;
   acc[9] = (c_ent + ldP) - (c_ent + ldS);
@@ -464,6 +496,25 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
       const double denom = gsum<L>(M(gk * dve)), num = gsum<L>(M(gv * dve));
       gS = (gv * dvt - num * gk * dvt / denom) * 2.0 * S;
     } else gS = gv * 2.0 * S;
+  } else if (PROJ == 4) {
+    gS = g_pS;   // (inside the bound: pass-through)
+    if (c_act) {   // reverse of: pS = Y10 sqrt(n); the ten steps; Y0 = x / n, n = |x|; x = d^2 So^2; d, pm <- t <- mp + cp
+      const double sn = sqrt(w_n);
+      double gy = g_pS * sn, gz = 0.0, gn = g_pS * pS * 0.5 / w_n;   // (pS * 0.5 / n = Y10 * 0.5 / sqrt(n))
+#pragma unroll
+      for (int it = 9; it >= 0; --it) {
+        const double y = ys[it], z = zs[it], T = 0.5 * (3.0 - z * y);
+        const double gT = gy * y + gz * z;
+        gy = gy * T - 0.5 * gT * z;
+        gz = gz * T - 0.5 * gT * y;
+      }
+      gn = gsum<L>(M(gn - gy * w_x / (w_n * w_n)));
+      const double gd = (gy / w_n + gn * w_x / w_n) * 2.0 * w_d * (So * So);
+      const double g_t = gsum<L>(M(g_pm * (mu - mo) + gd * (S * So - 1.0)));
+      const double g_tot = -0.5 * g_t * w_t / (w_tot + 1e-16);
+      gmu = g_pm * w_t + g_tot * 2.0 * (mu - mo) / (So * So);
+      gS = gd * w_t * So - g_tot * 2.0 * (1.0 - S / So) / So;
+    }
   } else if (c_act) {
     const double den = 1.0 + eta + 1e-16, deta = 1.0 / (2.0 * (eta + 1.0) * cfg.cov_bound);
     const double st_ = gsum<L>(M(PROJ == 1 ? g_pS / (2.0 * pS) * (o - v) / den : g_pS * (So - pS) / den));
@@ -477,7 +528,7 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
     const double dm = mu - pm;
     gmu += ctr * 2.0 * dm / (S * S);
     gS += ctr * (-2.0 * dm * dm / (S * S * S) + 2.0 * (S - pS));
-  } else if (PROJ == 2) {
+  } else if (PROJ == 2 || PROJ == 4) {
     gmu += ctr * 2.0 * (mu - pm) / (pS * pS);
     gS += ctr * (-2.0 * (1.0 - S / pS) / pS);
   }
@@ -703,7 +754,7 @@ int grl_adv_stats(const float* advantage, double* stats, int batch, hipStream_t 
 }
 
 // cfg9 (HOST pointer): TEN doubles since ABI 203 {mean_bound, cov_bound, trust_region_coeff, entropy_coef, critic_coef, clip_value,
-// 1/B_global, B_global, projection type (0 KL, 1 Frobenius, 2 Wasserstein), adv_local (1: the advantage statistics are summed inside the
+// 1/B_global, B_global, projection type (0 KL, 1 Frobenius, 2 Wasserstein, 4 non-commuting Wasserstein), adv_local (1: the advantage statistics are summed inside the
 // kernel from this launch's batch -- adv_stats is then ignored; 0: adv_stats as below)}.  adv_stats: device fp64[2] = (sum, sum of squares) of the GLOBAL batch's advantages (from
 // grl_adv_stats, all-reduced when data parallel) or NULL for no normalisation.  sums: fp64[12], maxes: u32[2], zeroed by the caller.  value/old_value/value_target/dvalue may be
 // NULL together (actor-only call); proj_mean/proj_var may be NULL.
@@ -728,7 +779,7 @@ static int trpl_launch(const double* cfg9, int action_dim, const float* mean, co
   if (action_dim > 16 || action_dim < 1 || batch < 1 || !slots) return -2;
   TrplCfg c{cfg9[0], cfg9[1], cfg9[2], cfg9[3], cfg9[4], cfg9[5], cfg9[6], cfg9[7], action_dim, (int)cfg9[9]};
   const int proj = (int)cfg9[8];
-  if (proj < 0 || proj > 2) return -3;
+  if (proj < 0 || proj > 4 || proj == 3) return -3;   // (3, the PPO mode, has its own entry point: grl_ppo_fwd_bwd)
   const TrplPtrs tp{mean, sigma, action, old_mean, old_var, old_logp, advantage, value, old_value, value_target, dmean, dsigma, dvalue,
                     proj_mean, proj_var, adv_stats, slots, tgt_mean, tgt_S, 0, nullptr};
 #define GRL_TRPL_LAUNCH(LL, PJ)                                                                                                       \
@@ -741,7 +792,8 @@ static int trpl_launch(const double* cfg9, int action_dim, const float* mean, co
   } while (0)
   if (proj == 0) GRL_TRPL_WIDTH(0);
   else if (proj == 1) GRL_TRPL_WIDTH(1);
-  else GRL_TRPL_WIDTH(2);
+  else if (proj == 2) GRL_TRPL_WIDTH(2);
+  else GRL_TRPL_WIDTH(4);
 #undef GRL_TRPL_WIDTH
 #undef GRL_TRPL_LAUNCH
   GRL_CHECK_LAUNCH();

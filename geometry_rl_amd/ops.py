@@ -934,7 +934,7 @@ TRPL_SUM_KEYS = ("loss_objective", "loss_trust_region", "entropy_dist", "loss_cr
 def trpl_fwd_bwd(loc, sigma, batch, value, *, mean_bound, cov_bound, trust_region_coeff, entropy_coef, critic_coef, clip_value,
                  global_batch: int, adv_stats: Optional[torch.Tensor], want_projection: bool = False, sums=None, maxes=None,
                  proj_type: int = 0, defer_fold: bool = False, adv_local: bool = False):
-    """Launches the fused TRPL kernel (proj_type 0 KL | 1 Frobenius | 2 Wasserstein).  Returns (sums fp64[12], maxes u32[2], dloc,
+    """Launches the fused TRPL kernel (proj_type 0 KL | 1 Frobenius | 2 Wasserstein | 4 non-commuting Wasserstein).  Returns (sums fp64[12], maxes u32[2], dloc,
     dsigma, dvalue, proj_mean, proj_var).  ``defer_fold``: the per-workgroup slots are not folded into ``sums`` / ``maxes`` by this call;
     the returned ``sums`` is then a callable that does it (on whatever stream is current when it is called) and returns (sums, maxes)."""
     import ctypes

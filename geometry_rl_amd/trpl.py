@@ -122,9 +122,10 @@ class KLProjectionLayer:
         self._entropy_proj = entropy_equality_projection if entropy_eq else entropy_inequality_projection
         self.target_entropy, self.temperature = float(target_entropy), float(temperature)
         self.entropy_first, self.entropy_eq = bool(entropy_first), bool(entropy_eq)
-        kinds = {"kl": 0, "frob": 1, "frobenius": 1, "w2": 2, "wasserstein": 2}
+        kinds = {"kl": 0, "frob": 1, "frobenius": 1, "w2": 2, "wasserstein": 2, "w2_non_com": 4}
         if proj_type.lower() not in kinds or mean_eq or not scale_prec:
-            raise NotImplementedError("projections: kl | frob | w2 (commutative), each with the Mahalanobis (scale_prec) mean bound")
+            raise NotImplementedError("projections: kl | frob | w2 (commutative) | w2_non_com, each with the Mahalanobis (scale_prec) "
+                                      "mean bound")
         self.proj_type, self.mean_bound, self.cov_bound = proj_type, float(mean_bound), float(cov_bound)
         self.proj_code = kinds[proj_type.lower()]
         self.trust_region_coeff = float(trust_region_coeff)
@@ -215,11 +216,30 @@ class WassersteinProjectionLayer(KLProjectionLayer):
         super().__init__(proj_type="w2", **kw)
 
 
+class WassersteinProjectionLayerNonCommuting(KLProjectionLayer):
+    """w2_projection_layer_non_com.py:13-86 (non-commuting W2, precision-scaled) on the diagonal policy: one joint bound on mean part +
+    covariance part, one interpolation weight for both, and the reference's ten Newton-Schulz steps for the square root (kernel code 4,
+    derivation in csrc/head_ops.hip).  The update path, ``__call__``, ``get_trust_region_loss`` and ``compute_metrics`` run on the fused
+    kernel like the other layers."""
+
+    def __init__(self, proj_type="w2_non_com", **kw):
+        super().__init__(proj_type="w2_non_com", **kw)
+
+    def trust_region_value(self, policy, p, q):
+        """projection_utils.py gaussian_wasserstein_non_commutative(scale_prec=True) -> per-frame (mean part, covariance part).  On
+        diagonal matrices the eigenvalues of S_o^-1 S^2 S_o^-1 are (S / S_o)^2, and the value is the commutative one: (maha(mean, mean_o,
+        S_o), sum (1 - S / S_o)^2).  Per-frame values for inspection, on the tensors as given (differentiable); the update path sums the
+        same terms inside the fused kernel."""
+        (mean, S), (mean_o, S_o) = p, q
+        S, S_o = _diag(S), _diag(S_o)
+        return ((mean - mean_o) / S_o).pow(2).sum(-1), (1.0 - S / S_o).pow(2).sum(-1)
+
+
 def get_projection_layer(proj_type: str = "", **kwargs) -> KLProjectionLayer:
     """projection_factory.py:9-48 -- the call builders/utils_algo_graph.py:246-253 makes (``action_dim``, ``total_train_steps``, ``cpu``,
-    ``dtype`` + the entries of configs/algorithm/projection/<type>.yaml as keyword arguments).  "kl" / "frob" / "w2": the fused-kernel
-    layers of this module; the reference's other branches are outside the TRPL hot path (PPO objective, PAPI,
-    non-commuting W2) and say so; anything else is the reference's ValueError."""
+    ``dtype`` + the entries of configs/algorithm/projection/<type>.yaml as keyword arguments).  "kl" / "frob" / "w2" / "w2_non_com": the
+    fused-kernel layers of this module; the reference's other branches are outside the TRPL hot path (PPO objective,
+    PAPI) and say so; anything else is the reference's ValueError."""
     key = (proj_type or "").lower()
     if key == "kl":
         return KLProjectionLayer(proj_type, **kwargs)
@@ -227,9 +247,11 @@ def get_projection_layer(proj_type: str = "", **kwargs) -> KLProjectionLayer:
         return FrobeniusProjectionLayer(proj_type, **kwargs)
     if key == "w2":
         return WassersteinProjectionLayer(proj_type, **kwargs)
-    if not key or key.isspace() or key in ("ppo", "sac", "td3", "mpo", "vlearn", "vtrace", "awr", "entropy", "w2_non_com", "papi"):
-        raise NotImplementedError(f"projection '{proj_type}': only the TRPL projections kl | frob | w2 are built (the PPO-style "
-                                  "BaseProjectionLayer, PAPI and the non-commuting W2 are outside the policy-update hot path)")
+    if key == "w2_non_com":
+        return WassersteinProjectionLayerNonCommuting(proj_type, **kwargs)
+    if not key or key.isspace() or key in ("ppo", "sac", "td3", "mpo", "vlearn", "vtrace", "awr", "entropy", "papi"):
+        raise NotImplementedError(f"projection '{proj_type}': only the TRPL projections kl | frob | w2 | w2_non_com are built (the "
+                                  "PPO-style BaseProjectionLayer and PAPI are outside the policy-update hot path)")
     raise ValueError(f"Invalid projection type {proj_type}. Choose one of None/' ', 'ppo', 'sac', 'td3', 'mpo', 'vtrace', 'papi', 'w2', "
                      "'w2_non_com', 'frob', 'kl', or 'entropy'.")
 

@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 /* ABI version (major*10000 + minor*100 + patch); grl_version() returns the value the library was built with. */
-#define GRL_HIP_VERSION 207   /* 207: grl_ppo_fwd_bwd added (clipped PPO objective); 206: grl_build_features_noise, grl_step_head_noise[_bf16] added (training noise); 205 (round 6): grl_source_hash added; 204 (round 5): grl_head_fused / grl_head_fused_rows removed, grl_calib_mfma / grl_calib_copy added; the exports are exactly this header */
+#define GRL_HIP_VERSION 208   /* 208: cfg9[8] = 4 accepted (non-commuting Wasserstein projection), no signature change; 207: grl_ppo_fwd_bwd added (clipped PPO objective); 206: grl_build_features_noise, grl_step_head_noise[_bf16] added (training noise); 205 (round 6): grl_source_hash added; 204 (round 5): grl_head_fused / grl_head_fused_rows removed, grl_calib_mfma / grl_calib_copy added; the exports are exactly this header */
 int grl_version(void);
 /* The hash of the sources this binary was built from (16 hex digits + NUL into buf; returns the length).  geometry_rl_amd/hip.py
    source_hash() recomputes it from csrc/, this header and the build's flag tables and refuses a library that disagrees. */
@@ -236,7 +236,8 @@ int grl_readout_bwd(const float* lat, const float* grid, const float* Wd, const 
  *      objectives/utils.py:5-28 ---------------------------------------------------------------------------------------------
  *      projections/frob_projection_layer.py:9-88, projections/w2_projection_layer.py:14-76 (diagonal policy, closed forms)
  * cfg9 (HOST, TEN doubles since ABI 203): {mean_bound, cov_bound, trust_region_coeff, entropy_coef, critic_coef, clip_value, 1/B_global, B_global,
- *               projection type: 0 KL | 1 Frobenius | 2 Wasserstein (commutative, precision-scaled),
+ *               projection type: 0 KL | 1 Frobenius | 2 Wasserstein (commutative, precision-scaled) | 4 (ABI 208) Wasserstein,
+ *               non-commuting (w2_projection_layer_non_com.py: one joint bound, ten Newton-Schulz steps; precision-scaled), 3 is refused,
  *               adv_local: 1 = the advantage statistics are summed inside the kernel from this launch's batch (one rank), 0 = adv_stats}
  * sums fp64[12]: loss_objective, loss_trust_region, entropy(dist), loss_critic, sum w, sum w^2, mean_constraint,
  *               cov_constraint, entropy(p), entropy_diff, count, kl  (per-frame sums; divide by count);  maxes u32[2] (float bits) */

@@ -1,0 +1,387 @@
+"""The non-commuting Wasserstein projection (proj_type "w2_non_com", kernel code 4) on the GPU:
+  (a) the kernel against the reference layer's own numbers (tier2f fixture): projection, trust-region loss and gradient, metrics;
+  (b) the ten Newton-Schulz steps, not an exact square root, on the fixture's unconverged frame;
+  (c) the whole fused loss (objective, entropy, trust region, critic) and its gradients against the float64 restatement
+      (tests/w2nc_ref.py through the oracle's TRPL loss) on random batches at A = 3, 6, 12, 16;
+  (d) five updates against the oracle with the restatement registered, rigid HEPi and two-agent EMPN;
+  (e) recorded programs against the step-by-step loop (lanes, one stream, run_minibatches in both forms);
+  (f) two data-parallel ranks against one rank; two runs bitwise identical."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import w2nc_ref
+from oracle import step as ost, trpl as otr
+from geometry_rl_amd import synthetic as syn
+from parity_util import adam_first_step_bound, grad_scales
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+EPS, EPS_COV = 0.05, 0.0025
+
+
+@pytest.fixture
+def registered(monkeypatch):
+    monkeypatch.setitem(otr.PROJECTIONS, "w2_non_com", (w2nc_ref.projection, otr.wasserstein_value))
+
+
+def _fixture(golden_dir, grp):
+    z = np.load(os.path.join(golden_dir, "tier2f_projection_w2_non_com.npz"))
+    out = {k[len(grp) + 1:]: torch.from_numpy(np.asarray(z[k])) for k in z.files if k.startswith(grp + ".")}
+    out.update({k: float(z[k]) for k in ("mean_bound", "cov_bound", "coeff")})
+    return out
+
+
+def _rel(name, got, want, tol, floor=1.0):
+    got, want = got.detach().cpu().double(), want.double()
+    err = float((got - want).abs().max())
+    scale = max(floor, float(want.abs().max()))
+    print(f"{name}: max err {err:.3e} of scale {scale:.3e}")
+    assert np.isfinite(err) and err <= tol * scale, (name, err, tol * scale)
+
+
+# ------------------------------------------------------------------------------------------------------------- (a), (b) fixture
+@pytest.mark.parametrize("grp", ["a6", "a3", "a12"])
+def test_kernel_matches_the_reference_fixture(golden_dir, grp):
+    from geometry_rl_amd import ops
+    from geometry_rl_amd.trpl import WassersteinProjectionLayerNonCommuting
+    z = _fixture(golden_dir, grp)
+    B, A = z["mean"].shape
+    layer = WassersteinProjectionLayerNonCommuting(mean_bound=z["mean_bound"], cov_bound=z["cov_bound"], trust_region_coeff=z["coeff"])
+    mean, S = z["mean"].float().to(DEV), z["S"].float().to(DEV)
+    q = (z["mean_o"].float().to(DEV), z["S_o"].float().to(DEV))
+    pm, pS = layer(None, (mean, S.diag_embed()), (q[0], q[1].diag_embed()))
+    assert pS.dim() == 3
+    _rel("proj_mean", pm, z["proj_mean"], 1e-5)
+    _rel("proj_S", pS.diagonal(dim1=-2, dim2=-1), z["proj_S"], 1e-5, floor=0.0)
+    # the same launch through ops directly (proj_type=4, want_projection=True): proj_var is the projected "std" diagonal
+    batch = {"action": mean, "loc": q[0], "var": q[1], "sample_log_prob": torch.zeros(B, device=DEV), "advantage": torch.zeros(B, device=DEV)}
+    out = ops.trpl_fwd_bwd(mean, S.sqrt(), batch, None, mean_bound=z["mean_bound"], cov_bound=z["cov_bound"], trust_region_coeff=z["coeff"],
+                           entropy_coef=0.0, critic_coef=0.0, clip_value=0.0, global_batch=B, adv_stats=None, want_projection=True, proj_type=4)
+    assert torch.equal(out[5], pm) and torch.equal(out[6], pS.diagonal(dim1=-2, dim2=-1))
+    # boundary methods: trust-region loss (value and gradient w.r.t. mean and S), metrics of (p, proj_p), trust_region_value
+    m_g = mean.clone().requires_grad_(True)
+    S_g = S.clone().requires_grad_(True)
+    p_g = (m_g, S_g.diag_embed())
+    tr = layer.get_trust_region_loss(None, p_g, (pm, pS))
+    tr.backward()
+    _rel("tr_loss", tr, z["tr_loss"], 1e-5)
+    _rel("tr_grad_mean", m_g.grad, z["tr_grad_mean"], 2e-5, floor=0.0)
+    _rel("tr_grad_S", S_g.grad, z["tr_grad_S"], 2e-5, floor=0.0)
+    mt = layer.compute_metrics(None, (mean, S.diag_embed()), (pm, pS), step=0)
+    for k in ("kl", "constraint", "mean_constraint", "cov_constraint", "mean_constraint_max", "cov_constraint_max", "entropy", "entropy_diff"):
+        _rel("metric." + k, mt[k], z["metric." + k], 2e-5)
+    vm, vc = layer.trust_region_value(None, (mean, S.diag_embed()), (q[0], q[1].diag_embed()))
+    _rel("value_mean", vm, z["value_mean"], 1e-5)
+    _rel("value_cov", vc, z["value_cov"], 1e-5)
+
+
+def test_kernel_runs_the_ten_steps_not_an_exact_square_root(golden_dir):
+    from geometry_rl_amd.trpl import WassersteinProjectionLayerNonCommuting
+    z = _fixture(golden_dir, "a6")
+    layer = WassersteinProjectionLayerNonCommuting(mean_bound=z["mean_bound"], cov_bound=z["cov_bound"], trust_region_coeff=z["coeff"])
+    _, pS = layer(None, (z["mean"].float().to(DEV), z["S"].float().to(DEV)), (z["mean_o"].float().to(DEV), z["S_o"].float().to(DEV)))
+    p64, q64 = (z["mean"], z["S"]), (z["mean_o"], z["S_o"])
+    _, exact = w2nc_ref.projection(p64, q64, z["mean_bound"], z["cov_bound"], sqrt_fn=torch.sqrt)
+    low = 1.0 - pS.cpu().double() / exact
+    print("kernel below the exact square root: x/n = 1e-3:", float(low[3, 0]), " 1e-4:", float(low[4, 0]))
+    assert abs(float(low[3, 0]) - 0.0243) < 1e-3 and abs(float(low[4, 0]) - 0.4706) < 2e-3
+    assert abs(float(pS[3, 0]) / float(z["proj_S"][3, 0]) - 1.0) < 1e-5 and abs(float(pS[4, 0]) / float(z["proj_S"][4, 0]) - 1.0) < 1e-5
+
+
+# ------------------------------------------------------------------------------------------------------------- (c) vs restatement
+def _random_case(B, A, seed):
+    """Frames on both sides of the bound: far outside, just outside (mp + cp in (eps + eps_cov, 1.2 (eps + eps_cov))), inside, in the
+    band (eps, eps + eps_cov] that a bound on eps alone would project, and outside with one dimension of tiny x_i / n."""
+    g = torch.Generator().manual_seed(seed)
+    loc = torch.randn(B, A, generator=g, dtype=torch.float64)
+    sigma = torch.rand(B, A, generator=g, dtype=torch.float64) + 0.5
+    S = sigma ** 2
+    old = loc + 0.4 * torch.randn(B, A, generator=g, dtype=torch.float64)
+    S_o = S * (1 + 0.3 * torch.randn(B, A, generator=g, dtype=torch.float64)).abs().clamp_min(0.3)
+    u = torch.randn(B, A, generator=g, dtype=torch.float64)
+    u = u / u.norm(dim=-1, keepdim=True)
+    kind = torch.arange(B) % 6
+    for b in range(B):
+        k = int(kind[b])
+        if k == 1:   # just outside: mean part only, 1.1 (eps + eps_cov)
+            S_o[b] = S[b]
+            old[b] = loc[b] + u[b] * S_o[b] * (1.1 * (EPS + EPS_COV)) ** 0.5
+        elif k == 2:   # inside: small steps with distinct ratios
+            S_o[b] = S[b] * (1 + 0.01 * u[b])
+            old[b] = loc[b] + 0.05 * u[b] * S_o[b]
+        elif k == 3:   # in the band (eps, eps + eps_cov]
+            S_o[b] = S[b]
+            old[b] = loc[b] + u[b] * S_o[b] * (EPS + 0.5 * EPS_COV) ** 0.5
+        elif k == 4:   # an unconverged dimension: its old "std" small
+            S_o[b, 0] = S_o[b, 0] * 0.02
+    sigma, S_o, old, loc = sigma.float(), S_o.float(), old.float(), loc.float()
+    var_f = S_o.double()
+    action = (old.double() + var_f.sqrt() * torch.randn(B, A, generator=g, dtype=torch.float64)).float()
+    logp = otr.mvn_diag_log_prob(action.double(), old.double(), var_f).float() + 0.1 * torch.randn(B, generator=g).float()
+    batch = {"action": action, "loc": old, "var": S_o, "sample_log_prob": logp, "advantage": torch.randn(B, generator=g).float(),
+             "state_value": torch.randn(B, generator=g).float(), "value_target": torch.randn(B, generator=g).float()}
+    value = (batch["state_value"] + 0.3 * torch.randn(B, generator=g)).float()
+    return loc, sigma, value, batch, kind
+
+
+@pytest.mark.parametrize("A", [3, 6, 12, 16])
+def test_kernel_matches_the_restatement(registered, A):
+    from geometry_rl_amd import ops
+    B = 6 * 11 + 5   # not a multiple of the 16 frames per workgroup
+    loc, sigma, value, batch, kind = _random_case(B, A, seed=100 + A)
+    kw = dict(mean_bound=EPS, cov_bound=EPS_COV, trust_region_coeff=1.7, entropy_coef=0.01, critic_coef=0.5, clip_value=0.2)
+    loc_r = loc.double().requires_grad_(True)
+    sig_r = sigma.double().requires_grad_(True)
+    val_r = value.double().requires_grad_(True)
+    bd = {k: v.double() for k, v in batch.items()}
+    ref = otr.trpl_loss(loc_r, sig_r ** 2, bd, val_r, proj_type="w2_non_com", **kw)
+    d_loc, d_sig = torch.autograd.grad(ref["loss_objective"] + ref["loss_entropy"] + ref["loss_trust_region"], [loc_r, sig_r])
+    (d_val,) = torch.autograd.grad(ref["loss_critic"], [val_r])
+    # the cases are where they are meant to be
+    mp, cp = w2nc_ref.value((loc.double(), sigma.double() ** 2), (bd["loc"], bd["var"]))
+    tot = mp + cp
+    assert bool((tot[kind == 2] < EPS).all()) and bool((tot[kind == 1] > EPS + EPS_COV).all())
+    assert bool(((tot[kind == 3] > EPS) & (tot[kind == 3] <= EPS + EPS_COV)).all())
+    r = w2nc_ref.x_over_n((loc.double(), sigma.double() ** 2), (bd["loc"], bd["var"]), EPS, EPS_COV)
+    assert float(r[kind == 4].min(-1).values.max()) < 2e-3
+    db = {k: v.to(DEV) for k, v in batch.items()}
+    sums, maxes, dloc, dsigma, dvalue, pm, pv = ops.trpl_fwd_bwd(loc.to(DEV), sigma.to(DEV), db, value.to(DEV), global_batch=B, adv_stats=None,
+                                                                 want_projection=True, proj_type=4, adv_local=True, **kw)
+    _rel("proj_mean", pm, ref["proj_mean"], 1e-5)
+    _rel("proj_S", pv, ref["proj_S"], 1e-5, floor=0.0)
+    s = sums.cpu()
+    n = float(s[10])
+    assert n == B
+    mx = maxes.cpu().view(torch.float32)
+    got = {"loss_objective": s[0] / n, "loss_trust_region": s[1] / n, "loss_critic": s[3] / n, "ESS": s[4] ** 2 / s[5] / n, "kl": s[11] / n,
+           "mean_constraint": s[6] / n, "cov_constraint": s[7] / n, "entropy": s[8] / n, "entropy_diff": s[9] / n,
+           "mean_constraint_max": mx[0], "cov_constraint_max": mx[1]}
+    for k, v in got.items():
+        want = float(ref[k])
+        assert abs(float(v) - want) <= 1e-5 * max(1.0, abs(want)), (k, float(v), want)
+    _rel("dloc", dloc, d_loc, 1e-5, floor=0.0)
+    _rel("dsigma", dsigma, d_sig, 1e-5, floor=0.0)
+    _rel("dvalue", dvalue, d_val, 1e-5, floor=0.0)
+    # per frame, so that one kind of frame cannot hide behind the largest gradient of another
+    for k in range(6):
+        sel = kind == k
+        _rel(f"dsigma[kind {k}]", dsigma.cpu()[sel], d_sig[sel], 2e-5, floor=0.0)
+        _rel(f"dloc[kind {k}]", dloc.cpu()[sel], d_loc[sel], 2e-5, floor=0.0)
+
+
+# ------------------------------------------------------------------------------------------------------------- (d) vs oracle
+@pytest.mark.parametrize("name,B,K", [("rigid_g1", 64, 5), ("empn_g2", 32, 5)])
+def test_five_updates_match_the_oracle(registered, name, B, K):
+    from geometry_rl_amd import agent
+    from test_gpu_step import load_params, make_case
+    torch.set_num_threads(min(16, os.cpu_count() or 1))
+    o_spec, spec, kw, _ = make_case(name, B)
+    kw = dict(kw, proj_type="w2_non_com", trust_region_coeff=2.0)
+    o_cfg, cfg = ost.AgentConfig(**kw), agent.AgentConfig(**kw)
+    a_par, c_par = ost.init_agent_params(o_spec, o_cfg, seed=21)
+    oracle = ost.OracleAgent(o_spec, o_cfg, a_par, c_par)
+    actor, critic, proj, loss = agent.build_agent(spec, cfg, device=DEV)
+    assert proj.proj_code == 4
+    load_params(actor, a_par, DEV)
+    load_params(critic, {"_network1." + k: v for k, v in c_par.items()}, DEV)
+    A = spec.num_actuators * cfg.output_dim_vec * 3
+    batches = []
+    for i in range(K):
+        b = dict(syn.make_rigid_obs(B, seed=30 + i) if name == "rigid_g1" else
+                 syn.make_rigid_obs(B, G=2, angular_velocity=False, object_velocity=False, seed=30 + i))
+        b.update(syn.make_ppo_fields(B, A, seed=40 + i))
+        batches.append(b)
+    with torch.no_grad():
+        oracle.actor_forward({k: batches[0][k] for k in o_spec.in_features}, calibrate=True)
+    actor.load_state_dict({k: v.detach().to(DEV) for k, v in oracle.actor.items()}, strict=False)
+    for mod in actor.modules():
+        if hasattr(mod, "callibrated"):
+            mod.callibrated.fill_(True)
+    actor._calib_checked = True
+    upd = agent.PolicyUpdater(loss, lr=cfg.lr, clip_grad_norm=cfg.clip_grad_norm, max_grad_norm=cfg.max_grad_norm, use_graph=True)
+    g_scale = None
+    for i, b in enumerate(batches):
+        ref, ref_grads = oracle.update(b)
+        out = upd.step({k: v.to(DEV) for k, v in b.items()})
+        sc = {net: grad_scales(ref_grads[net]) for net in ("actor", "critic")}
+        g_scale = sc if g_scale is None else {net: {k: max(v, g_scale[net].get(k, 0.0)) for k, v in sc[net].items()} for net in sc}
+        assert float(ref["kl"]) > 0.0   # frames were projected
+        for k in ("loss_objective", "loss_trust_region", "loss_critic", "kl", "constraint", "mean_constraint", "cov_constraint", "entropy"):
+            e = abs(float(out[k]) - float(ref[k]))
+            assert e <= 1e-4 * max(1.0, abs(float(ref[k]))), (i, k, e)
+    assert upd.mode.startswith("graph") and upd._program is not None
+    torch.cuda.synchronize()
+    off = lambda p: (p.data_ptr() - upd.flat.data_ptr()) // 4
+    bad = []
+    for net, mod, ref_p, optim, strip in (("actor", actor, oracle.actor, oracle.actor_optim, 0),
+                                          ("critic", critic, oracle.critic, oracle.critic_optim, len("_network1."))):
+        states = {kk: optim.state.get(ref_p[kk], {}) for kk in ref_p}
+        m_ref = {kk: s_["exp_avg"] for kk, s_ in states.items() if "exp_avg" in s_}
+        v_ref = {kk: s_["exp_avg_sq"] for kk, s_ in states.items() if "exp_avg_sq" in s_}
+        m_sc, v_sc = grad_scales(m_ref), grad_scales(v_ref)
+        for k, p in mod.named_parameters():
+            kk = k[strip:]
+            if kk not in m_ref:
+                continue
+            o, n = off(p), p.numel()
+            em = float((upd.exp_avg[o:o + n].view_as(p).cpu().double() - m_ref[kk].double()).abs().max())
+            ev = float((upd.exp_avg_sq[o:o + n].view_as(p).cpu().double() - v_ref[kk].double()).abs().max())
+            ep = float((p.detach().cpu().double() - ref_p[kk].detach().double()).abs().max())
+            allowed_p = K * adam_first_step_bound(cfg.lr, 1e-5, g_scale[net].get(kk, 0.0), cfg.clip_grad_norm, p_ref=ref_p[kk])
+            if not (em <= 5e-4 * m_sc[kk] and ev <= 1e-3 * v_sc[kk] and ep <= allowed_p and np.isfinite(em + ev + ep)):
+                bad.append((net, kk, em / m_sc[kk], ev / v_sc[kk], ep, allowed_p))
+    assert not bad, bad
+
+
+# ------------------------------------------------------------------------------------------------------------- (e) programs
+KEYS = ("loss_objective", "loss_trust_region", "loss_critic", "kl", "constraint", "entropy", "ESS")
+
+
+def _make(N, T, seed):
+    from geometry_rl_amd import agent, graph
+    spec = graph.rigid_spec()
+    cfg = agent.AgentConfig(only_upper_hemisphere=True, output_dim=2, output_dim_vec=2, proj_type="w2_non_com")
+    torch.manual_seed(0)
+    actor, critic, proj, loss = agent.build_agent(spec, cfg, device=DEV)
+    frames = []
+    for t in range(T + 1):
+        b = dict(syn.make_rigid_obs(N, seed=seed + t))
+        b.update(syn.make_ppo_fields(N, 6, seed=seed + t))
+        frames.append(b)
+    data = {k: torch.stack([f[k] for f in frames[:T]], dim=1).to(DEV) for k in frames[0]}
+    g = syn.make_gae_inputs(N, T, seed=seed)
+    data.update(reward=g["reward"].reshape(N, T, 1).to(DEV), done=g["done"].reshape(N, T, 1).to(DEV),
+                terminated=g["terminated"].reshape(N, T, 1).to(DEV))
+    next_last = {k: frames[T][k].unsqueeze(1).to(DEV) for k in spec.in_features}
+    with torch.no_grad():
+        actor.forward_diag(*[data[k][:, 0].contiguous() for k in spec.in_features], train=True)   # calibration
+    return spec, cfg, loss, data, next_last
+
+
+@pytest.mark.parametrize("form", ["unrolled", "cursor"])
+def test_run_minibatches_equals_the_step_loop(form):
+    from geometry_rl_amd import agent
+    from geometry_rl_amd.rollout import RolloutBuffer, RolloutDriver
+    N, T = 8, 10
+    res = {}
+    for mode in ("loop", "launches"):
+        spec, cfg, loss, data, next_last = _make(N, T, seed=33)
+        upd = agent.PolicyUpdater(loss, lr=cfg.lr, use_graph=True)
+        upd.epoch_unroll = 4 if mode == "launches" else 1
+        if form == "cursor":
+            upd.epoch_unroll_max_gated_frames, upd.epoch_gated_from_frames, upd.epoch_cursor = 0, 0, True
+        buf = RolloutBuffer(dict(data))
+        drv = RolloutDriver(upd, spec, ppo_epochs=2, seed=9)
+        drv.compute_advantages(buf, next_last)
+        outs = []
+        if mode == "loop":
+            for idx in drv.minibatches(buf):
+                o = upd.step_from(buf, idx)
+                outs.append({k: o[k].clone() for k in KEYS})
+        else:
+            for _ in range(2):
+                o = upd.run_minibatches(buf, torch.stack(drv.epoch_minibatches(buf.N, buf.T, DEV)))
+            assert upd._epoch is not None
+            outs.append({k: o[k].clone() for k in KEYS})
+        torch.cuda.synchronize()
+        assert upd.steps == 2 * T
+        res[mode] = (upd.flat.detach().clone(), upd.exp_avg.detach().clone(), upd.exp_avg_sq.detach().clone(), outs)
+    for a, b in zip(res["loop"][:3], res["launches"][:3]):
+        assert torch.equal(a, b), (a - b).abs().max().item()
+    for k in KEYS:
+        assert torch.equal(res["loop"][3][-1][k], res["launches"][3][-1][k]), k
+
+
+def test_recorded_programs_equal_the_eager_loop():
+    from geometry_rl_amd import agent
+    N, T, k = 8, 2, 4
+    res = {}
+    for mode in ("eager", "graph", "one_stream", "one_stream_eager"):
+        spec, cfg, loss, data, next_last = _make(N, T, seed=41)
+        batch = {kk: v[:, 0].contiguous() for kk, v in data.items()}
+        upd = agent.PolicyUpdater(loss, lr=cfg.lr, use_graph=mode in ("graph", "one_stream"), overlap_critic=not mode.startswith("one_stream"))
+        outs = [{kk: v.clone() for kk, v in upd.step(batch).items() if kk in KEYS} for _ in range(k)]
+        torch.cuda.synchronize()
+        if mode in ("graph", "one_stream"):
+            assert upd.mode.startswith("graph") and upd._program is not None
+        res[mode] = (upd.flat.detach().clone(), upd.exp_avg.detach().clone(), upd.exp_avg_sq.detach().clone(), outs)
+    for a, b in (("eager", "graph"), ("one_stream_eager", "one_stream")):
+        for x, y in zip(res[a][:3], res[b][:3]):
+            assert torch.equal(x, y), (a, b, (x - y).abs().max().item())
+        for oa, ob in zip(res[a][3], res[b][3]):
+            for kk in KEYS:
+                assert torch.equal(oa[kk], ob[kk]), (a, b, kk)
+    assert (res["graph"][0] - res["one_stream"][0]).abs().max().item() <= 1e-6
+
+
+def test_two_runs_are_bitwise_identical():
+    from geometry_rl_amd import agent
+    res = []
+    for _ in range(2):
+        spec, cfg, loss, data, next_last = _make(16, 3, seed=45)
+        upd = agent.PolicyUpdater(loss, lr=cfg.lr, use_graph=True)
+        outs = [{kk: v.clone() for kk, v in upd.step({k: v[:, t].contiguous() for k, v in data.items()}).items() if kk in KEYS}
+                for t in range(3)]
+        torch.cuda.synchronize()
+        res.append((upd.flat.detach().clone(), outs))
+    assert torch.equal(res[0][0], res[1][0])
+    for oa, ob in zip(res[0][1], res[1][1]):
+        for kk in KEYS:
+            assert torch.equal(oa[kk], ob[kk]), kk
+
+
+# ------------------------------------------------------------------------------------------------------------- (f) data parallel
+def _dp_setup(B, group):
+    from geometry_rl_amd import agent, graph
+    spec = graph.rigid_spec(G=2, angular_velocity=False, object_velocity=False)
+    cfg = agent.AgentConfig(proj_type="w2_non_com")
+    torch.manual_seed(0)
+    actor, critic, proj, loss = agent.build_agent(spec, cfg, device=DEV, group=group)
+    batch = dict(syn.make_rigid_obs(B, G=2, angular_velocity=False, object_velocity=False, seed=4))
+    batch.update(syn.make_ppo_fields(B, 6, seed=4))
+    return spec, cfg, actor, loss, {k: v.to(DEV) for k, v in batch.items()}
+
+
+def _dp_worker(rank, world, port, B, ret):
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from geometry_rl_amd import agent
+    spec, cfg, actor, loss, batch = _dp_setup(B, dist.group.WORLD)
+    with torch.no_grad():
+        actor.forward_diag(*[batch[k] for k in spec.in_features], train=True)
+    lo, hi = rank * B // world, (rank + 1) * B // world
+    shard = {k: v[lo:hi].contiguous() for k, v in batch.items()}
+    upd = agent.PolicyUpdater(loss, lr=cfg.lr, clip_grad_norm=cfg.clip_grad_norm, group=dist.group.WORLD, use_graph=True)
+    for _ in range(3):
+        out = upd.step(shard)
+    ret[rank] = ({k: float(out[k].detach()) for k in KEYS}, upd.flat.detach().cpu())
+    dist.destroy_process_group()
+
+
+def test_two_ranks_match_single_rank():
+    import torch.multiprocessing as mp
+    from geometry_rl_amd import agent
+    from spawn_util import spawn_ranks
+    B, world = 16, 2
+    spec, cfg, actor, loss, batch = _dp_setup(B, None)
+    with torch.no_grad():
+        actor.forward_diag(*[batch[k] for k in spec.in_features], train=True)
+    upd = agent.PolicyUpdater(loss, lr=cfg.lr, clip_grad_norm=cfg.clip_grad_norm, use_graph=True)
+    for _ in range(3):
+        out = upd.step(batch)
+    ref_losses = {k: float(out[k].detach()) for k in KEYS}
+    ref_flat = upd.flat.detach().cpu()
+    ret = mp.Manager().dict()
+    spawn_ranks(_dp_worker, world, (world,), (B, ret))
+    assert all(r in ret for r in range(world))
+    for r in range(world):
+        losses, flat = ret[r]
+        for k, v in ref_losses.items():
+            assert abs(losses[k] - v) <= 1e-5 * max(1.0, abs(v)), (r, k, losses[k], v)
+        err = (flat - ref_flat).abs().max().item()
+        print(f"rank {r}: max |param - single-rank param| = {err:.3e}")
+        assert err <= 2e-6

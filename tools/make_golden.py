@@ -522,9 +522,111 @@ def tier2e():
     print("tier2e:", len(rec), "arrays")
 
 
+def tier2f():
+    """The non-commuting Wasserstein projection layer (w2_projection_layer_non_com.py:13-86) on the diagonal policy, in the shape of
+    tier2c: projection outputs, gradients through the projection, trust-region loss + gradients, metrics, trust_region_value.  Run in
+    float64 on float32-representable inputs, in three groups (A = 3, 6, 12: every lane width of the kernel).
+
+    One shim beyond the name-only stubs of tier 2, and the only stub of any tier that does arithmetic: ``torch.symeig`` no longer exists
+    in this torch, and the layer calls it; ``symeig(c, eigenvectors, upper)`` is mapped onto its documented replacement
+    ``torch.linalg.eigh(c, UPLO="U" if upper else "L")``.
+
+    Group a6 holds frames inside the bound with distinct ratios S / S_o (rows 0, 1), one inside the bound whose ratios are all equal
+    (row 2: the reference's autograd through the eigendecomposition gives NaN there; the analytic gradient is the pass-through), and
+    frames outside it where one dimension's x_i / n is 1e-3 (row 3) and 1e-4 (row 4) -- there the ten Newton-Schulz steps are not
+    converged."""
+    from geometry_rl.algorithms.trust_region_projections.projections.w2_projection_layer_non_com import (
+        WassersteinProjectionLayerNonCommuting)
+    from geometry_rl.algorithms.trust_region_projections.models.policy.gnn_gaussian_policy_diag import GNNGaussianPolicyDiag
+    torch.symeig = lambda c, eigenvectors=False, upper=True: torch.linalg.eigh(c, UPLO="U" if upper else "L")   # (this torch: raises)
+
+    class FakeGNN(nn.Module):
+        device = "cpu"
+
+    class FakeData:
+        pass
+
+    eps, eps_cov, coeff = 0.05, 0.0025, 4.0
+
+    def x_over_n(mean, S, mean_o, S_o):   # the argument of the square root, relative to its norm (input tuning only)
+        mp = ((mean - mean_o) / S_o).pow(2).sum(-1)
+        cp = (1.0 - S / S_o).pow(2).sum(-1)
+        t = torch.sqrt((eps + eps_cov) / (mp + cp + 1e-16))[..., None]
+        x = ((1.0 - t) + t * S * S_o).pow(2) * S_o.pow(2)
+        return x / x.pow(2).sum(-1, keepdim=True).sqrt()
+
+    def spread_row(mean, S, mean_o, S_o, target):
+        """Scale dimension 0 of the old std until its x_0 / n is ``target`` (bisection on the log scale), float32-representable."""
+        lo, hi = -12.0, 0.0
+        for _ in range(200):
+            mid = 0.5 * (lo + hi)
+            so = S_o.clone()
+            so[0] = S_o[0] * 2.0 ** mid
+            r = float(x_over_n(mean, S, mean_o, so)[0])
+            lo, hi = (mid, hi) if r < target else (lo, mid)
+        so = S_o.clone()
+        so[0] = (S_o[0] * 2.0 ** (0.5 * (lo + hi))).float().double()
+        return so
+
+    torch.manual_seed(3)
+    rec = {"mean_bound": torch.tensor(eps, dtype=torch.float64), "cov_bound": torch.tensor(eps_cov, dtype=torch.float64),
+           "coeff": torch.tensor(coeff, dtype=torch.float64)}
+    for A, B, seed in ((6, 16, 23), (3, 5, 29), (12, 5, 31)):
+        policy = GNNGaussianPolicyDiag(gnn=FakeGNN(), hyper_data=FakeData(), action_dim=A, num_actuators=1, init="orthogonal",
+                                       hidden_sizes=(64, 64), contextual_std=True, init_std=1.0, minimal_std=1e-5,
+                                       share_action_dim=True, post_fc=False)
+        g = torch.Generator().manual_seed(seed)
+        f32 = lambda t: t.float().double()
+        mean = f32(torch.randn(B, A, generator=g, dtype=torch.float64))
+        S = f32(torch.rand(B, A, generator=g, dtype=torch.float64) + 0.5)
+        mean_o = f32(mean + 0.3 * torch.randn(B, A, generator=g, dtype=torch.float64))
+        S_o = f32(torch.rand(B, A, generator=g, dtype=torch.float64) + 0.5)
+        # inside the bound, distinct ratios
+        mean_o[0] = f32(mean[0] + 1e-3 * torch.linspace(-1, 1, A, dtype=torch.float64))
+        S_o[0] = f32(S[0] * (1 + 2e-3 * torch.linspace(-1, 1, A, dtype=torch.float64)))
+        if A == 6:
+            mean_o[1] = f32(mean[1] + 2e-2)
+            S_o[1] = f32(S[1] * (1 + 5e-3 * torch.linspace(0.2, 1, A, dtype=torch.float64)))
+            mean_o[2] = f32(mean[2] - 1e-2)     # inside the bound, the ratio S / S_o = 32 / 33 in every dimension (exact: short mantissas)
+            S[2] = torch.tensor([0.75, 0.875, 1.0, 1.25, 0.625, 1.125], dtype=torch.float64)
+            S_o[2] = S[2] * 1.03125
+            S_o[3] = spread_row(mean[3], S[3], mean_o[3], S_o[3], 1e-3)
+            S_o[4] = spread_row(mean[4], S[4], mean_o[4], S_o[4], 1e-4)
+        R1, R2 = torch.randn(B, A, generator=g, dtype=torch.float64), torch.randn(B, A, generator=g, dtype=torch.float64)
+        layer = WassersteinProjectionLayerNonCommuting(proj_type="w2_non_com", mean_bound=eps, cov_bound=eps_cov, trust_region_coeff=coeff,
+                                                       scale_prec=True, entropy_schedule=False, action_dim=A, total_train_steps=100,
+                                                       cpu=True, dtype=torch.float64)
+        mean_g = mean.clone().requires_grad_(True)
+        S_g = S.clone().requires_grad_(True)
+        p = (mean_g, S_g.diag_embed())
+        q = (mean_o, S_o.diag_embed())
+        pm, pS = layer(policy, p, q, 0)
+        r = {"mean": mean, "S": S, "mean_o": mean_o, "S_o": S_o, "R1": R1, "R2": R2, "proj_mean": pm,
+             "proj_S": pS.diagonal(dim1=-2, dim2=-1), "x_over_n": x_over_n(mean, S, mean_o, S_o)}
+        ((pm * R1).sum() + (pS.diagonal(dim1=-2, dim2=-1) * R2).sum()).backward(retain_graph=True)
+        r["grad_mean"], r["grad_S"] = mean_g.grad.clone(), S_g.grad.clone()
+        mean_g.grad = None
+        S_g.grad = None
+        trl = layer.get_trust_region_loss(policy, p, (pm, pS))
+        trl.backward()
+        r["tr_loss"], r["tr_grad_mean"], r["tr_grad_S"] = trl, mean_g.grad.clone(), S_g.grad.clone()
+        m = layer.compute_metrics(policy, (mean, S.diag_embed()), (pm.detach(), pS.detach()), step=0)
+        for k, v in m.items():
+            r["metric." + k] = v
+        mp, cp = layer.trust_region_value(policy, (mean, S.diag_embed()), q)
+        r["value_mean"], r["value_cov"] = mp, cp
+        rec.update({f"a{A}.{k}": v for k, v in r.items()})
+    np.savez(os.path.join(OUT, "tier2f_projection_w2_non_com.npz"), **npd(rec))
+    print("tier2f:", len(rec), "arrays,", os.path.getsize(os.path.join(OUT, "tier2f_projection_w2_non_com.npz")), "bytes")
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(4)
+    if len(sys.argv) > 1 and sys.argv[1] == "tier2f":
+        install_stubs()
+        tier2f()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "tier2e":
         install_stubs()
         tier2e()
@@ -545,5 +647,6 @@ if __name__ == "__main__":
     tier2d()
     tier2b(attention=True)
     tier2e()
+    tier2f()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
