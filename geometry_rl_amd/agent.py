@@ -148,27 +148,22 @@ class PolicyUpdater:
         self.loss_module, self.group = loss_module, group
         self.overlap_critic = overlap_critic   # one rank: False = everything on the caller's stream (_plan_one_stream)
         self.force_dp_plan = force_dp_plan     # a process group of ONE rank runs the data-parallel program (bench.py --dp-plan)
-        self.critic_delay_us = 0               # experiment knob (tools/critic_delay_ab.py): microseconds the critic's lane idles before it starts
-        # one rank, two lanes: the critic's lane starts when the actor's FIRST edge convolution has finished (a stream wait on a flag that a
-        # 4-byte copy behind that launch sets to the step count: _plan_lanes).  Beside that launch the critic's kernels cost it 60-90 us at 4096
-        # frames (DESIGN.md finding 42); beside the HBM-bound kernels that follow they cost less: -1.6 % on the step (finding 55).
+        # one rank, two lanes: the critic's lane starts when the actor's FIRST edge convolution has finished (a launch of the lane waits on a
+        # flag that the actor's lane sets to the step count behind that launch: _plan_lanes).  Beside that launch the critic's kernels cost it
+        # 60-90 us at 4096 frames (DESIGN.md finding 42); beside the HBM-bound kernels that follow they cost less: -1.6 % on the step (finding
+        # 55).  True: the size table of _gate_for; False: never gated; "edge0": always gated.
+        if not (isinstance(critic_after_first_conv, bool) or critic_after_first_conv == "edge0"):
+            raise ValueError(f"critic_after_first_conv={critic_after_first_conv!r}: True (size table) | False | \"edge0\"")
         self.critic_after_first_conv = critic_after_first_conv
-        # the critic lane's gate: a launch of the lane itself (grl_wait_flag_ge, default) or hipStreamWaitValue32 in front of its graph
-        # (round 5; GRL_GATE_STREAMWAIT=1 -- a BETA API: taken only where the device reports support)
-        self.gate_in_graph = os.environ.get("GRL_GATE_STREAMWAIT", "0") != "1"
-        self.epoch_unroll = int(os.environ.get("GRL_EPOCH_UNROLL", "8"))   # minibatch steps per recorded launch of run_minibatches
+        self.epoch_unroll = 8   # minibatch steps per recorded launch of run_minibatches
         # data parallel: gate the critic's lane behind the actor's first edge convolution from this shard size on (0: never).  One-rank RCCL
         # group, alternating on one box (profiles/r06_ab_dp_gate.txt): -4.1 % at 4096 frames per rank, -2 % at 2048, -1.3 % at 1024, 0 at 512
         self.dp_gate_from_frames = int(os.environ.get("GRL_DP_GATE_FROM", "1024"))
-        self.dp_eager_tail = os.environ.get("GRL_DP_EAGER_TAIL", "1") == "1"   # the actor lane's one-launch tail behind the collective: a plain launch, not a one-node graph
-        # gated sizes: one step per launch with the gathers inside (by device cursor).  Measured no better than the per-step program with its
-        # eager gather (256 / 512 frames: -0.5 % / +0.5 %) and 1 % slower at 4096 frames (gpurun_out -> profiles/r06_ab_forms.txt): OFF
-        self.epoch_cursor = os.environ.get("GRL_EPOCH_CURSOR", "0") == "1"
-        self.epoch_unroll_max_gated_frames = int(os.environ.get("GRL_EPOCH_UNROLL_MAX_GATED", "64"))   # ... above this many frames
-        self.epoch_gated_from_frames = int(os.environ.get("GRL_EPOCH_GATED_FROM", "3072"))   # run_minibatches: the gated per-step program from here on
+        self.epoch_unroll_max_gated_frames = 64   # run_minibatches: the gated multi-step launch up to this many work-frames ...
+        self.epoch_gated_from_frames = 3072       # ... and the gated per-step program from here on
         self._epoch = None
-        # which recorded form run_minibatches takes above 64 work-frames is measured once per size (_tune_form); GRL_AUTOTUNE_FORM=0: the table
-        self.autotune_form = os.environ.get("GRL_AUTOTUNE_FORM", "1") == "1"
+        # which recorded form run_minibatches takes above 64 work-frames is measured once per size (_tune_form); False: the table
+        self.autotune_form = True
         self.form_by_size, self.form_times = {}, {}
 
         self.allow_eager_fallback = allow_eager_fallback   # False: a failed hipGraph capture raises instead of degrading silently
@@ -182,8 +177,6 @@ class PolicyUpdater:
         n = sum(pad4(p.numel()) for p in self.params)
         dev = self.params[0].device
         self.flat = torch.zeros(n, device=dev, dtype=torch.float32)
-        if not self.gate_in_graph and self.flat.is_cuda and not hip.query("grl_can_stream_wait_value"):
-            self.gate_in_graph = True   # (no hipStreamWaitValue32 on this device: the gate as a launch)
         # the flat gradient, with room IN FRONT of it for the ranks' loss records ([world][14] (hi, lo) float pairs, grl_trpl_fold_record_pairs):
         # data parallel, ``gbuf[:rec + n_actor]`` is ONE all-reduce -- the records ride on the actor's gradient slice
         if group is not None:
@@ -375,9 +368,6 @@ class PolicyUpdater:
         sums, maxes = zw[10:22], zw[22:23].view(torch.int32)
         ops.DEFERRED = []   # leaf-gradient folds of this backward are queued and executed by one launch at the lane's end
         loc, sigma = actor.forward_diag(*st["obs"], train=True)
-        after_fwd = st.pop("after_forward", None)
-        if after_fwd is not None:
-            after_fwd()
         with torch.no_grad():
             fold_, _mx, dloc, dsigma, _ = trpl_launch(m, loc, sigma, None, st["b"], adv, sums=sums, maxes=maxes, defer_fold=True,
                                                       adv_local=adv_local)
@@ -467,7 +457,39 @@ class PolicyUpdater:
         return dict(grads=self.gflat[lo:hi], params=self.flat[lo:hi], exp_avg=self.exp_avg[lo:hi], exp_avg_sq=self.exp_avg_sq[lo:hi],
                     lr_dev=self.lr_dev, betas=self.betas, eps=self.eps, step_dev=cnt)
 
-    def _plan_lanes(self, batch, st, cbatch=None, gate_in_graph=None, gate_override=None):
+    def _signal_lane(self):
+        """lane_flag[0] = step_dev[0] on the current stream (one tiny launch): the critic's lane may start this step."""
+        import ctypes
+        hip.call("grl_copy_many", (ctypes.c_void_p * 1)(self.lane_flag.data_ptr()), (ctypes.c_void_p * 1)(self.step_dev.data_ptr()),
+                 (ctypes.c_longlong * 1)(4), 1)
+
+    @contextlib.contextmanager
+    def _actor_lane_head(self, gate: bool):
+        """Around the actor lane's forward + backward: the step count rides on the lane's first launch (grl_build_features_bump) and, ``gate``,
+        the critic's lane is signalled right behind the actor's first edge convolution -- by the fiber convolution launched behind it, which
+        writes the flag when it starts (ops.FiberConv, ops.SIGNAL_IN_KERNEL), or else by a copy launch of its own."""
+        hd = self.loss_module.actor_network.hyper_data
+        hd.bump_next = self.step_dev
+        if gate:
+            def signal():
+                if hd.bump_next is not None:   # the step count has not been advanced yet (a calibrating pass in front of the step's own
+                    return False               # forward): not this edge convolution
+                if ops.SIGNAL_IN_KERNEL:
+                    ops.PENDING_SIGNAL = (self.lane_flag, self.step_dev)
+                else:
+                    self._signal_lane()
+                return True
+            ops.AFTER_EDGE_HOOK = signal
+        try:
+            yield
+        finally:
+            ops.AFTER_EDGE_HOOK = None
+            unsent, ops.PENDING_SIGNAL = ops.PENDING_SIGNAL, None
+        if unsent is not None:   # (no fiber convolution followed the edge convolution: send the signal by itself)
+            self._signal_lane()
+        assert hd.bump_next is None, "the actor's feature launch did not take the step count"
+
+    def _plan_lanes(self, batch, st, cbatch=None, gate_override=None):
         """One rank as a two-lane PROGRAM of single-stream graphs.  This HIP runtime replays a captured graph with two branches through
         the host (hipGraphLaunch returned after 2/3 of the DEVICE time of a forked step; tools/ubench/graph_branches.py) and every
         cross-branch edge costs a 6-11 us gap; a graph boundary on a lane costs ~15 us as well.  So each lane is ONE graph and the lanes
@@ -481,15 +503,11 @@ class PolicyUpdater:
         accumulate (attention gate: torch's AccumulateGrad adds into .grad)."""
         from .trpl import report_dict, report_values, value_loss
         m = self.loss_module
-        actor, vf = m.actor_network, m.critic_network._network1
+        vf = m.critic_network._network1
         leaves = self._critic_leaves()
         ow = self._fold_overwrite
         na, n_all = self.n_actor, self.flat.numel()
         cb = cbatch if cbatch is not None else batch   # the critic lane's inputs (the epoch program gives each lane a private copy)
-        # the gate as a launch INSIDE the critic's lane (grl_wait_flag_ge: capturable, target read from the lane's own device-side count) or
-        # as a stream operation in front of its graph (hipStreamWaitValue32, round 5; GRL_GATE_STREAMWAIT=1)
-        if gate_in_graph is None:
-            gate_in_graph = self.gate_in_graph
         # the one-launch tail needs every leaf gradient of the lane in the fold queue (overwrite mode) and no clipping (which needs the
         # finished gradient norm before Adam)
         fuse_tail = not self.clip and ow
@@ -498,49 +516,12 @@ class PolicyUpdater:
         # slower): measured on rigid HEPi +1.1 % at 4096 frames, +3 % at 512, +1 % at 32, 0 at 2048, -1.5 % at 1024, where a forward of
         # 0.35 ms is too short for it (profiles/r05_ab_critic_gate.txt, r05_ab_critic_gate_points.txt).  True (default) = that table.
         frames = next(int(v.shape[0]) for v in batch.values() if torch.is_tensor(v))
-        mode = self.critic_after_first_conv
         gate = self._gate_for(frames) if gate_override is None else bool(gate_override)
-        gate_point = mode if isinstance(mode, str) else "edge0"   # "edge0" | "fwd_end" (experiment: bench.py --critic-gate)
-
-        def copy4(dst, src):   # dst[0] = src[0] (int32) on the current stream: one tiny launch
-            import ctypes
-            hip.call("grl_copy_many", (ctypes.c_void_p * 1)(dst.data_ptr()), (ctypes.c_void_p * 1)(src.data_ptr()), (ctypes.c_longlong * 1)(4), 1)
 
         def main_all():
             self._prep(batch, st, zero=self.gflat[:na])
-            actor.hyper_data.bump_next = self.step_dev   # the step count rides on the lane's first launch (grl_build_features_bump)
-            fired = []
-            if gate and gate_point == "edge0":   # the critic's lane starts on this signal: flag = the step count, written right behind the first edge convolution
-                def signal():
-                    if actor.hyper_data.bump_next is not None:   # the step count has not been advanced yet (a calibrating pass in front of
-                        return False                             # the step's own forward): not this edge convolution
-                    fired.append(1)
-                    # the signal rides on the NEXT launch of the lane (the fiber convolution behind this edge convolution writes the flag
-                    # when it starts, ops.FiberConv): no 4-us copy launch on the step's chain
-                    if ops.SIGNAL_IN_KERNEL:
-                        ops.PENDING_SIGNAL = (self.lane_flag, self.step_dev)
-                    else:
-                        copy4(self.lane_flag, self.step_dev)
-                    return True
-                ops.AFTER_EDGE_HOOK = signal
-            if gate and gate_point == "fwd_end":
-                st["after_forward"] = lambda: copy4(self.lane_flag, self.step_dev)
-            if gate and gate_point == "fiber0":   # experiment: the critic starts behind the first FIBER convolution (beside the ConvNeXt forward)
-                def signal_f():
-                    if actor.hyper_data.bump_next is not None:
-                        return False
-                    copy4(self.lane_flag, self.step_dev)
-                    return True
-                ops.AFTER_FIBER_HOOK = signal_f
-            try:
+            with self._actor_lane_head(gate):
                 fold_ = self._actor_head(st, None, bool(m.normalize_advantage and st["obs"][0].shape[0] > 1))
-            finally:
-                ops.AFTER_EDGE_HOOK = None
-                ops.AFTER_FIBER_HOOK = None
-                unsent, ops.PENDING_SIGNAL = ops.PENDING_SIGNAL, None
-            if unsent is not None:   # (no fiber convolution followed the edge convolution: send the signal by itself)
-                copy4(*unsent)
-            assert actor.hyper_data.bump_next is None, "the actor's feature launch did not take the step count"
             with torch.no_grad():
                 done = False
                 if fuse_tail:   # fold + Adam + reported values: ONE launch at the lane's end (ops.fold_adam_report)
@@ -558,15 +539,13 @@ class PolicyUpdater:
                     a_loss, _c, mt = report_values(m, fold_.slots, fold_.batch, fold_.sums, fold_.maxes)
                 ops.DEFERRED = None
                 if gate and not (done and ops.SIGNAL_IN_KERNEL):   # ... and once more at the lane's end, whatever happened above (an actor without an edge convolution; a
-                    copy4(self.lane_flag, self.step_dev)   # signal that carried a stale count): the critic's lane can be late, it can never be stuck
+                    self._signal_lane()                            # signal that carried a stale count): the critic's lane can be late, it can never be stuck
                 st.update(sums=fold_.sums, maxes=fold_.maxes, lv_main=(a_loss, mt))
 
         def critic_all():
             ops.DEFERRED = []
             with torch.no_grad():
-                if self.critic_delay_us:   # (experiment knob, default 0: an idle one-wave kernel in front of the critic's lane)
-                    hip.call("grl_calib_spin", int(self.critic_delay_us))
-                if gate and gate_in_graph:   # until the actor's lane has signalled THIS step: flag >= the steps this lane has finished + 1
+                if gate:   # until the actor's lane has signalled THIS step: flag >= the steps this lane has finished + 1
                     hip.call("grl_wait_flag_ge", self.lane_flag, self.step_dev_c, 1, 200000)
                 pre = st.pop("critic_pre", None)
                 if pre is not None:           # (epoch program: the lane's own minibatch gather)
@@ -591,9 +570,8 @@ class PolicyUpdater:
                 ops.DEFERRED = None
                 st["c_loss"] = c_loss
 
-        wait = [("wait_flag", None, "s", "critic_lane_start")] if (gate and not gate_in_graph) else []
         st["lanes"] = (main_all, critic_all)
-        return [("fork", None), ("run", main_all), *wait, ("run", critic_all, "s"), ("join", None), ("run_host", lambda: self._finish(st))]
+        return [("fork", None), ("run", main_all), ("run", critic_all, "s"), ("join", None), ("run_host", lambda: self._finish(st))]
 
     def _plan_dp(self, batch, st):
         """Several ranks: the same two lanes, graph segments between the collectives (which stay eager torch.distributed calls).
@@ -610,7 +588,7 @@ class PolicyUpdater:
         from .trpl import adv_stats_local, report_dict, value_loss
         m = self.loss_module
         world = m.world_size
-        actor, vf = m.actor_network, m.critic_network._network1
+        vf = m.critic_network._network1
         leaves = self._critic_leaves()
         ow = self._fold_overwrite
         na, n_all = self.n_actor, self.flat.numel()
@@ -636,31 +614,13 @@ class PolicyUpdater:
         frames_local = next((int(v.shape[0]) for v in batch.values() if torch.is_tensor(v)), 0)
         gate_dp = bool(self.dp_gate_from_frames) and self._work_frames(frames_local) >= self.dp_gate_from_frames   # (work-normalised, see _work_frames)
 
-        def copy4(dst, src):
-            import ctypes
-            hip.call("grl_copy_many", (ctypes.c_void_p * 1)(dst.data_ptr()), (ctypes.c_void_p * 1)(src.data_ptr()), (ctypes.c_longlong * 1)(4), 1)
-
         def p_main():
             if published:
                 p_stats()
-            actor.hyper_data.bump_next = self.step_dev
-            if gate_dp:
-                def signal():
-                    if actor.hyper_data.bump_next is not None:   # (a calibrating pass in front of the step's own forward: not this convolution)
-                        return False
-                    ops.PENDING_SIGNAL = (self.lane_flag, self.step_dev)   # rides on the fiber convolution behind the edge convolution
-                    return True
-                ops.AFTER_EDGE_HOOK = signal
-            try:
+            with self._actor_lane_head(gate_dp):
                 fold_ = self._actor_head(st, st["adv"], False)
-            finally:
-                ops.AFTER_EDGE_HOOK = None
-                unsent, ops.PENDING_SIGNAL = ops.PENDING_SIGNAL, None
-            if unsent is not None:
-                copy4(*unsent)
             if gate_dp:   # ... and once more at the end of the segment: the critic's lane can be late, never stuck (its wait is bounded as well)
-                copy4(self.lane_flag, self.step_dev)
-            assert actor.hyper_data.bump_next is None
+                self._signal_lane()
             st.update(sums=fold_.sums, maxes=fold_.maxes)
             with torch.no_grad():
                 # this rank's loss sums / maxes as ONE record of float pairs in front of the flat gradient (own row, zeros in the
@@ -686,8 +646,8 @@ class PolicyUpdater:
                              self.lr_dev, float(self.betas[0]), float(self.betas[1]), float(self.eps), self.step_dev,
                              self.gbuf[:self._rec], world, st["sums"], st["maxes"], float(ent), o14)
         # ONE launch is cheaper issued eagerly than replayed as a one-node graph (a graph launch behind a collective costs ~13 us of lane time,
-        # an eager kernel launch ~4): GRL_DP_EAGER_TAIL
-        p_tail.eager = bool(self.dp_eager_tail and not self.clip)
+        # an eager kernel launch ~4; -1.5 % at 512 frames per rank)
+        p_tail.eager = not self.clip
 
         def q_fwd1():
             with torch.no_grad():
@@ -931,7 +891,7 @@ class PolicyUpdater:
     def _epoch_ok(self) -> bool:
         m = self.loss_module
         return bool(self.use_graph and m.world_size == 1 and not (self.group is not None and self.force_dp_plan) and self.overlap_critic
-                    and m.critic_coef and self.gate_in_graph and self.epoch_unroll > 1)
+                    and m.critic_coef and self.epoch_unroll > 1)
 
     def _lane_keys(self, buf):
         m = self.loss_module
@@ -940,12 +900,16 @@ class PolicyUpdater:
         c = list(dict.fromkeys(list(m.critic_in_features) + ["state_value", "value_target"]))
         return a, c
 
-    EPOCH_ROWS = 512   # index rows the cursor form keeps on the device (minibatches per load)
+    def _epoch_key(self, buf, B, U):
+        """What a recorded multi-step launch depends on: its sizes and the rollout tensors its gathers read (RolloutDriver.compute_advantages
+        REPLACES the buffer's state_value / advantage / value_target, so the next rollout through the same buffer object records again)."""
+        ka, kc = self._lane_keys(buf)
+        # (four entries: bench.py reads key[1] as the steps per launch and key[2] as the flag of the retired cursor form, now always False)
+        return (B, U, False, tuple(buf.flat(k).data_ptr() for k in ka + kc))
 
-    def _compile_epoch(self, buf, idx0, U, cursor, gate=None):
-        """Record ``U`` consecutive steps into one graph per lane.  ``cursor`` False: step j of a launch gathers the FIXED row j of a static
-        [U, B] index matrix (filled per launch); True (U = 1): the launch gathers the row the lane's own device-side step count points at in
-        a static [EPOCH_ROWS, B] matrix loaded once per call -- nothing but graph launches per step."""
+    def _compile_epoch(self, buf, idx0, U, gate=None):
+        """Record ``U`` consecutive steps into one graph per lane: step j of a launch gathers the FIXED row j of a static [U, B] index
+        matrix (filled per launch)."""
         import ctypes
         m = self.loss_module
         B = int(idx0.numel())
@@ -953,32 +917,28 @@ class PolicyUpdater:
         sa, sc = buf.rows(idx0, ka), buf.rows(idx0, kc)      # static inputs, one private set per lane
         m.actor_network.hyper_data.check_topology(*[sa[k] for k in m.in_features])
         m.critic_network._network1.hyper_data.check_topology(*[sc[k] for k in m.critic_in_features])
-        rows = self.EPOCH_ROWS if cursor else U
-        idx_static = torch.zeros(rows, B, device=idx0.device, dtype=torch.int64)
-        base_a = torch.zeros(1, device=idx0.device, dtype=torch.int32)
-        base_c = torch.zeros(1, device=idx0.device, dtype=torch.int32)
+        idx_static = torch.zeros(U, B, device=idx0.device, dtype=torch.int64)
+        src = {k: buf.flat(k) for k in ka + kc}   # (held by the recording: its gathers read these storages)
 
         def gather_args(static, keys):
             n = len(keys)
             for k in keys:
-                if static[k].dtype != buf.flat(k).dtype or static[k][0].numel() != buf.flat(k).shape[1]:
+                if static[k].dtype != src[k].dtype or static[k][0].numel() != src[k].shape[1]:
                     raise RuntimeError(f"rollout tensor '{k}' cannot be gathered row-wise into the recorded step's inputs")
-            return ((ctypes.c_void_p * n)(*[static[k].data_ptr() for k in keys]), (ctypes.c_void_p * n)(*[buf.flat(k).data_ptr() for k in keys]),
-                    (ctypes.c_longlong * n)(*[buf.flat(k).shape[1] * buf.flat(k).element_size() for k in keys]), n)
+            return ((ctypes.c_void_p * n)(*[static[k].data_ptr() for k in keys]), (ctypes.c_void_p * n)(*[src[k].data_ptr() for k in keys]),
+                    (ctypes.c_longlong * n)(*[src[k].shape[1] * src[k].element_size() for k in keys]), n)
         ga, gc = gather_args(sa, ka), gather_args(sc, kc)
 
-        def gather(args, j, count, base):
-            if cursor:
-                return lambda: hip.call("grl_gather_rows_many_cur", *args, idx_static, B, count, base, rows)
+        def gather(args, j):
             row = idx_static[j]
             return lambda: hip.call("grl_gather_rows_many", *args, row, B)
         sts, mains, critics = [], [], []
         for j in range(U):
             st = {}
-            self._plan_lanes(sa, st, cbatch=sc, gate_in_graph=True, gate_override=gate)
+            self._plan_lanes(sa, st, cbatch=sc, gate_override=gate)
             main_all, critic_all = st.pop("lanes")
-            mains.append((gather(ga, j, self.step_dev, base_a), main_all))
-            critics.append((st, gather(gc, j, self.step_dev_c, base_c), critic_all))
+            mains.append((gather(ga, j), main_all))
+            critics.append((st, gather(gc, j), critic_all))
             sts.append(st)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -994,9 +954,27 @@ class PolicyUpdater:
         torch.cuda.current_stream().wait_stream(side)
         for st in sts:
             self._finish(st)
-        tail = [] if cursor else [("join", None, "m", None)]   # (cursor form: the lanes are joined once, when the call returns)
-        self._epoch = dict(key=(B, U, cursor, id(buf)), idx=idx_static, base=(base_a, base_c), sts=sts, keep=(sa, sc, ga, gc, buf),
-                           program=[("fork", None, "m", None), ("graph", ga_graph, "m", None), ("graph", gc_graph, "s", None)] + tail)
+        self._epoch = dict(key=self._epoch_key(buf, B, U), idx=idx_static, sts=sts, keep=(sa, sc, src),
+                           program=[("fork", None, "m", None), ("graph", ga_graph, "m", None), ("graph", gc_graph, "s", None),
+                                    ("join", None, "m", None)])
+
+    def _launch_epoch(self, buf, rows, key, gate):
+        """``rows`` [U, B] (device int64): U steps as ONE recorded launch per lane, recorded first when ``key`` (_epoch_key) is not the
+        recording's.  Returns the loss dict of the last step; ``self.last_outs`` holds those of all U."""
+        U = int(rows.shape[0])
+        if self._epoch is None or self._epoch["key"] != key:
+            self.loss_module._global_steps = self.steps
+            self._compile_epoch(buf, rows[0], U, gate=gate)
+        ep = self._epoch
+        ep["idx"].copy_(rows)
+        self.steps += U
+        try:
+            self._execute(ep["program"])
+        except BaseException:
+            self.steps -= U
+            raise
+        self.last_outs = [st["out"] for st in ep["sts"]]
+        return self.last_outs[-1]
 
     # The size thresholds of the lane policy (_gate_for, run_minibatches) were measured on rigid_insertion_multi HEPi, whose compact graph has
     # this many edges per frame (kNN + task edges); every other workload is placed on that scale by ITS edge count -- the edge kernels are
@@ -1022,10 +1000,9 @@ class PolicyUpdater:
         ``rollout.RolloutDriver.epoch_minibatches`` hands out).  One rank with recorded lanes takes one of two recorded forms:
           * ``unroll`` steps per launch where the critic's lane is not gated, or the launches are smaller than the chip (<= 64 frames):
             no boundary at all between the steps of a launch (-3 % at 32 frames, -1.5 % at 1024);
-          * one step per launch with the gathers inside (index row picked by the lane's device-side step count) where the lane IS gated:
-            a gate waiting inside a multi-step launch is a resident wave during the previous step's one-wave-per-SIMD backward kernels,
-            which then find 255 free compute units for 256 workgroups (+10 % at 512 frames, +20 % at 4096: DESIGN.md, round 6) -- here
-            the lanes are forked per step so that the gate starts with the step, and joined once at the end.
+          * the per-step program (a loop of ``step_from``) where the lane IS gated: a gate waiting inside a multi-step launch is a resident
+            wave during the previous step's one-wave-per-SIMD backward kernels, which then find 255 free compute units for 256 workgroups
+            (+10 % at 512 frames, +20 % at 4096: DESIGN.md, round 6).
         Otherwise, and for the first (eager) step of a size and the remainder, a loop of ``step_from``.  Returns the loss dict of the last
         step; ``self.last_outs`` holds the dicts of the last launch's steps."""
         M, B = int(idx_rows.shape[0]), int(idx_rows.shape[1])
@@ -1046,62 +1023,23 @@ class PolicyUpdater:
         # above 64 frames (a resident waiting wave during the previous step's one-wave-per-SIMD backward kernels).
         Bw = self._work_frames(B)   # (the thresholds are on the scale of the workload they were measured on)
         gate_here = self._gate_for(B) and (Bw <= self.epoch_unroll_max_gated_frames or Bw >= self.epoch_gated_from_frames)
-        gated_big = gate_here and Bw > self.epoch_unroll_max_gated_frames
-        cursor = gated_big and self.epoch_cursor
         # That table is ONE workload's; on the others the better of the two forms differs by 1-2 % either way (cloth and rope
         # prefer the gated per-step program at 512 frames, the two-agent EMPN the multi-step launch: profiles/r06_ab_policy.txt).  Both forms
         # give bitwise the same update, so above 64 work-frames the choice is MEASURED once per size on the running program (_tune_form:
         # alternating blocks of U steps of each, HIP events) whenever a call brings enough minibatches; until then the table decides.
         form = self.form_by_size.get(B)
-        if (form is None and self.autotune_form and not self.epoch_cursor and Bw > self.epoch_unroll_max_gated_frames
-                and M - j >= self.tune_minibatches(U)):
+        if form is None and self.autotune_form and Bw > self.epoch_unroll_max_gated_frames and M - j >= self.tune_minibatches(U):
             j, out = self._tune_form(buf, idx_rows, j, U)
             form = self.form_by_size[B]
-        per_step = (form == "per_step") if form is not None else (gated_big and not cursor)
-        if form == "unrolled":
-            cursor, gate_here = False, False   # (the measured multi-step launch is the ungated one)
-        if cursor:
-            U = 1
-        elif per_step:     # a gate inside a multi-step launch is a resident wave during the previous step's backward: the per-step program
-            while j < M:
-                out = self.step_from(buf, idx_rows[j])
-                j += 1
-            return out
-        if M - j >= U:
-            if self._epoch is None or self._epoch["key"] != (B, U, cursor, id(buf)):
-                self.loss_module._global_steps = self.steps
-                self._compile_epoch(buf, idx_rows[j], U, cursor, gate=gate_here)
-            ep = self._epoch
-            if cursor:
-                main = torch.cuda.current_stream()
-                while j < M:
-                    n = min(M - j, self.EPOCH_ROWS)
-                    main.wait_stream(self._critic_stream())          # every earlier step of BOTH lanes is behind us: the counts are final
-                    ep["idx"][:n].copy_(idx_rows[j:j + n])
-                    ep["base"][0].copy_(self.step_dev)
-                    ep["base"][1].copy_(self.step_dev_c)
-                    for _ in range(n):
-                        self.steps += 1
-                        try:
-                            self._execute(ep["program"])
-                        except BaseException:
-                            self.steps -= 1
-                            raise
-                    j += n
-                main.wait_stream(self._critic_stream())
-                self.last_outs = [ep["sts"][0]["out"]]
-                out = self.last_outs[-1]
-            while not cursor and M - j >= U:
-                ep["idx"].copy_(idx_rows[j:j + U])
-                self.steps += U
-                try:
-                    self._execute(ep["program"])
-                except BaseException:
-                    self.steps -= U
-                    raise
+        if form is None:
+            form = "per_step" if gate_here and Bw > self.epoch_unroll_max_gated_frames else "unrolled"
+        elif form == "unrolled":
+            gate_here = False   # (the measured multi-step launch is the ungated one)
+        if form == "unrolled" and M - j >= U:
+            key = self._epoch_key(buf, B, U)
+            while M - j >= U:
+                out = self._launch_epoch(buf, idx_rows[j:j + U], key, gate_here)
                 j += U
-                self.last_outs = [st["out"] for st in ep["sts"]]
-                out = self.last_outs[-1]
         while j < M:
             out = self.step_from(buf, idx_rows[j])
             j += 1
@@ -1123,21 +1061,10 @@ class PolicyUpdater:
         B = int(idx_rows.shape[1])
         main, cs = torch.cuda.current_stream(), self._critic_stream()
         out = None
+        key = self._epoch_key(buf, B, U)
 
         def unrolled(rows):
-            if self._epoch is None or self._epoch["key"] != (B, U, False, id(buf)):
-                self.loss_module._global_steps = self.steps
-                self._compile_epoch(buf, rows[0], U, False, gate=False)
-            ep = self._epoch
-            ep["idx"].copy_(rows)
-            self.steps += U
-            try:
-                self._execute(ep["program"])
-            except BaseException:
-                self.steps -= U
-                raise
-            self.last_outs = [st["out"] for st in ep["sts"]]
-            return self.last_outs[-1]
+            return self._launch_epoch(buf, rows, key, False)
 
         def per_step(rows):
             o = None
@@ -1275,9 +1202,6 @@ class PolicyUpdater:
                 self._do(kind, item, label)
 
     def _do(self, kind, item, label=None, lane="m"):
-        if kind == "wait_flag":   # (current stream = the critic's) until the actor's lane has signalled THIS step (host count = device count)
-            hip.stream_wait_value32(self.lane_flag, self.steps)
-            return
         if kind in ("run", "run_host"):
             item()
         elif kind == "graph":

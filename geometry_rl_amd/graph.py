@@ -147,8 +147,7 @@ def _mix64(x: int) -> int:
     return x ^ (x >> 31)
 
 
-import os as _os
-BALANCE_NODE_ORDER = _os.environ.get("GRL_BALANCE_NODE_ORDER", "1") == "1"   # module attribute: tests / A/B tools flip it
+BALANCE_NODE_ORDER = True   # module attribute, not environment: tests flip it
 
 
 def balanced_node_order(src: torch.Tensor, n_nodes: int, slots: int, group: int = 8):

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GRL_LIB", os.path.join(_HERE, "libgrl_hip.so"))  # GRL_LIB: debugging builds only
-ABI_VERSION = 208   # include/grl_hip.h GRL_HIP_VERSION
+ABI_VERSION = 209   # include/grl_hip.h GRL_HIP_VERSION
 SOURCES = ["edge_conv.hip", "edge_conv16.hip", "node_ops.hip", "node_mlp.hip", "node_mlp16.hip", "head_ops.hip",
            "critic_ops.hip", "train_ops.hip", "weight_images.hip", "calib.hip", "oneshot.hip"]
 # (source, extra flags, object suffix): the two MFMA files are compiled a second time as the plain-bf16 variant (one MFMA per
@@ -329,20 +329,3 @@ def check_latent(prec: str, *tensors: torch.Tensor):
     for t in tensors:
         if t is not None and (t.dtype != want or not t.is_cuda):
             raise TypeError(f"expected a CUDA {want} latent tensor for the '{prec or 'fp32'}' kernels, got {t.dtype} on {t.device}")
-
-
-_hiprt = None
-
-
-def stream_wait_value32(value_tensor: torch.Tensor, value: int) -> None:
-    """The CURRENT stream waits (in the command processor: no wave, no compute unit is held) until the int32 at ``value_tensor`` is >=
-    ``value`` (hipStreamWaitValue32, flag hipStreamWaitValueGte).  The location must be written by work already enqueued on another
-    stream -- the caller owns that ordering."""
-    global _hiprt
-    if _hiprt is None:
-        _hiprt = ctypes.CDLL("libamdhip64.so")
-        _hiprt.hipStreamWaitValue32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint, ctypes.c_uint32]
-        _hiprt.hipStreamWaitValue32.restype = ctypes.c_int
-    rc = _hiprt.hipStreamWaitValue32(stream_ptr(), ctypes.c_void_p(value_tensor.data_ptr()), ctypes.c_uint32(int(value) & 0xFFFFFFFF), 0, 0xFFFFFFFF)
-    if rc != 0:
-        raise RuntimeError(f"hipStreamWaitValue32 failed with status {rc}")

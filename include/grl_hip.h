@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 /* ABI version (major*10000 + minor*100 + patch); grl_version() returns the value the library was built with. */
-#define GRL_HIP_VERSION 208   /* 208: cfg9[8] = 4 accepted (non-commuting Wasserstein projection), no signature change; 207: grl_ppo_fwd_bwd added (clipped PPO objective); 206: grl_build_features_noise, grl_step_head_noise[_bf16] added (training noise); 205 (round 6): grl_source_hash added; 204 (round 5): grl_head_fused / grl_head_fused_rows removed, grl_calib_mfma / grl_calib_copy added; the exports are exactly this header */
+#define GRL_HIP_VERSION 209   /* 209: three exports removed (the device-cursor variant of grl_gather_rows_many, the hipStreamWaitValue32 capability query, the idle spin kernel of calib.hip); 208: cfg9[8] = 4 accepted (non-commuting Wasserstein projection), no signature change; 207: grl_ppo_fwd_bwd added (clipped PPO objective); 206: grl_build_features_noise, grl_step_head_noise[_bf16] added (training noise); 205 (round 6): grl_source_hash added; 204 (round 5): grl_head_fused / grl_head_fused_rows removed, grl_calib_mfma / grl_calib_copy added; the exports are exactly this header */
 int grl_version(void);
 /* The hash of the sources this binary was built from (16 hex digits + NUL into buf; returns the length).  geometry_rl_amd/hip.py
    source_hash() recomputes it from csrc/, this header and the build's flag tables and refuses a library that disagrees. */
@@ -461,19 +461,12 @@ int grl_fold_record_pairs(int n_seg, const float* const* partial, const int* n_r
 int grl_adam_report_record_pairs(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int n, const float* lr_dev, float beta1,
                                  float beta2, float eps, const int* step_dev, const float* region, int n_records, double* sums,
                                  unsigned int* maxes, float entropy_coef, float* out14, hipStream_t stream);
-/* 1 if the current device supports hipStreamWaitValue32 (hipDeviceAttributeCanUseStreamWaitValue), else 0 (host query, no stream). */
-int grl_can_stream_wait_value(void);
 /* n <= 24 small device-to-device copies in one launch (host arrays of device pointers / byte counts) */
 int grl_copy_many(void* const* dst, const void* const* src, const long long* bytes, int n, hipStream_t stream);
 /* minibatch assembly from a device-resident rollout (train.py:120,128,258-261): dst[k][i,:] = src[k][idx[i],:] for k < n <= 24
  * tensors in one launch; dst / src / row_bytes: HOST arrays; idx: DEVICE int64[n_rows]; row_bytes multiples of 4 */
 int grl_gather_rows_many(void* const* dst, const void* const* src, const long long* row_bytes, int n, const long long* idx, int n_rows,
                          hipStream_t stream);
-/* (ABI 205) the same with the index row chosen ON THE DEVICE: idx = a matrix [n_idx_rows, n_rows] (device int64), the launch gathers line
- * (count[0] - base[0]) mod n_idx_rows (device int32[1] each) -- a recorded step takes "the next minibatch of the epoch"
- * (examples/torchrl/train.py:258-261) without the host touching its arguments.  count = NULL: idx is the row itself. */
-int grl_gather_rows_many_cur(void* const* dst, const void* const* src, const long long* row_bytes, int n, const long long* idx, int n_rows,
-                             const int* count, const int* base, int n_idx_rows, hipStream_t stream);
 /* ---- collector-side observation transform: NDVecNorm / VecNorm running normalisation + ClipTransform,
  * geometry_rl/torchrl/envs/transforms.py:141-163 (on torchrl's VecNorm), configs/rigid_insertion_multi_hepi_trpl_cfg.yaml:47-72.
  * x [rows, K<=64]; state: device float[2K+1] = [sum | ssq | count], updated in place when update != 0;
@@ -501,8 +494,6 @@ int grl_prof_get(int i, char* name, int cap, float* ms);
  * grl_calib_copy: float4 grid-stride copy, bytes a multiple of 16; bytes moved per call = 2 * bytes. */
 int grl_calib_mfma(int iters, float* out, hipStream_t stream);
 int grl_calib_copy(const void* src, void* dst, long long bytes, hipStream_t stream);
-/* one wave that idles for `us` microseconds (s_memrealtime): a delay node for lane-placement experiments (tools/critic_delay_ab.sh) */
-int grl_calib_spin(int us, hipStream_t stream);
 
 #ifdef __cplusplus
 }

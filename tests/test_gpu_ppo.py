@@ -187,7 +187,7 @@ def _make(N, T, seed, **cfg_kw):
 KEYS = ("loss_objective", "loss_critic", "ESS", "entropy", "loss_entropy")
 
 
-@pytest.mark.parametrize("form", ["unrolled", "per_step", "cursor"])
+@pytest.mark.parametrize("form", ["unrolled", "per_step"])
 def test_run_minibatches_equals_the_step_loop(form):
     from geometry_rl_amd import agent
     from geometry_rl_amd.rollout import RolloutBuffer, RolloutDriver
@@ -199,8 +199,6 @@ def test_run_minibatches_equals_the_step_loop(form):
         upd.epoch_unroll = 4 if mode == "launches" else 1
         if form == "per_step":
             upd.form_by_size[N] = "per_step"
-        if form == "cursor":
-            upd.epoch_unroll_max_gated_frames, upd.epoch_gated_from_frames, upd.epoch_cursor = 0, 0, True
         buf = RolloutBuffer(dict(data))
         drv = RolloutDriver(upd, spec, ppo_epochs=2, seed=9)
         drv.compute_advantages(buf, next_last)

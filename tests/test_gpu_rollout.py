@@ -57,39 +57,43 @@ def test_driver_matches_explicit_loop(use_graph):
     assert err <= 1e-7
 
 
-@pytest.mark.parametrize("form", ["unrolled", "cursor"])
+@pytest.mark.parametrize("form", ["unrolled", "unrolled_rollout_per_epoch"])
 def test_several_steps_per_launch_equal_the_step_by_step_loop(form):
     """PolicyUpdater.run_minibatches (round 6): ``unroll`` minibatch steps recorded into ONE graph per lane -- in-graph gathers from a static
     index matrix, private inputs per lane, the critic's gate as a launch of its lane, no join between the steps of a launch.  Ten minibatches
     per epoch with unroll = 4: an eager first step, two 4-step launches, one single step -- the parameters, both Adam moments and every
-    step's loss dict must be those of the step-by-step loop."""
+    step's loss dict must be those of the step-by-step loop.  ``..._rollout_per_epoch``: every epoch is a new rollout pass through the SAME buffer
+    object (RolloutDriver.compute_advantages replaces its state_value / advantage / value_target tensors): the launches must gather from
+    the new tensors, not from the storage the first recording saw."""
     from geometry_rl_amd import agent
     from geometry_rl_amd.rollout import RolloutBuffer, RolloutDriver
     N, T = 8, 10
+    per_epoch = form == "unrolled_rollout_per_epoch"
     res = {}
-    want_form = form
     for form in ("loop", "launches"):
         spec, cfg, loss, data, next_last = _make(N, T, seed=33)
         upd = agent.PolicyUpdater(loss, lr=cfg.lr, use_graph=True)
         upd.epoch_unroll = 4 if form == "launches" else 1
-        if want_form == "cursor":   # the form of the gated sizes (one step per launch, index row by device cursor), forced at this toy size
-            upd.epoch_unroll_max_gated_frames, upd.epoch_gated_from_frames, upd.epoch_cursor = 0, 0, True   # (off by default: measured no better than the per-step program)
         buf = RolloutBuffer(dict(data))
         drv = RolloutDriver(upd, spec, ppo_epochs=2, seed=9)
-        drv.compute_advantages(buf, next_last)
-        kls = []
-        if form == "loop":
-            for idx in drv.minibatches(buf):
-                kls.append(upd.step_from(buf, idx)["kl"].clone())
-            assert upd._epoch is None
-        else:
-            dev = next(iter(buf.data.values())).device
-            for _ in range(2):
-                idxs = drv.epoch_minibatches(buf.N, buf.T, dev)
+        dev = next(iter(buf.data.values())).device
+        kls, keys = [], []
+        for epoch in range(2):
+            if epoch == 0 or per_epoch:
+                drv.compute_advantages(buf, next_last)
+            idxs = drv.epoch_minibatches(buf.N, buf.T, dev)
+            if form == "loop":
+                for idx in idxs:
+                    kls.append(upd.step_from(buf, idx)["kl"].clone())
+                assert upd._epoch is None
+            else:
                 out = upd.run_minibatches(buf, torch.stack(idxs))
-                assert upd._epoch is not None and upd._epoch["key"][2] == (want_form == "cursor")
-                assert len(upd.last_outs) == (1 if want_form == "cursor" else 4)
-            kls = ([o["kl"].clone() for o in upd.last_outs] if want_form == "unrolled" else []) + [out["kl"].clone()]
+                assert upd._epoch is not None and upd._epoch["key"][1] == 4 and upd._epoch["key"][2] is False
+                assert len(upd.last_outs) == 4
+                keys.append(upd._epoch["key"])
+        if form == "launches":
+            assert (keys[0] != keys[1]) == per_epoch   # (a new rollout is recorded again)
+            kls = [o["kl"].clone() for o in upd.last_outs] + [out["kl"].clone()]
         torch.cuda.synchronize()
         assert upd.steps == 2 * T and int(upd.step_dev.item()) == 2 * T and int(upd.step_dev_c.item()) == 2 * T
         res[form] = (upd.flat.detach().clone(), upd.exp_avg.detach().clone(), upd.exp_avg_sq.detach().clone(), kls)
@@ -97,7 +101,7 @@ def test_several_steps_per_launch_equal_the_step_by_step_loop(form):
         assert torch.equal(a, b), (a - b).abs().max().item()
     # epoch 2 of the launch form: steps 11-14, 15-18 by launches (last_outs = steps 15-18), 19-20 singly (out = step 20)
     loop_kls = res["loop"][3]
-    for got, want in zip(res["launches"][3], (loop_kls[14:18] if want_form == "unrolled" else []) + [loop_kls[19]]):
+    for got, want in zip(res["launches"][3], loop_kls[14:18] + [loop_kls[19]]):
         assert torch.equal(got, want)
 
 

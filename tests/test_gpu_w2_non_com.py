@@ -4,7 +4,7 @@
   (c) the whole fused loss (objective, entropy, trust region, critic) and its gradients against the float64 restatement
       (tests/w2nc_ref.py through the oracle's TRPL loss) on random batches at A = 3, 6, 12, 16;
   (d) five updates against the oracle with the restatement registered, rigid HEPi and two-agent EMPN;
-  (e) recorded programs against the step-by-step loop (lanes, one stream, run_minibatches in both forms);
+  (e) recorded programs against the step-by-step loop (lanes, one stream, run_minibatches);
   (f) two data-parallel ranks against one rank; two runs bitwise identical."""
 import os
 
@@ -261,7 +261,7 @@ def _make(N, T, seed):
     return spec, cfg, loss, data, next_last
 
 
-@pytest.mark.parametrize("form", ["unrolled", "cursor"])
+@pytest.mark.parametrize("form", ["unrolled"])
 def test_run_minibatches_equals_the_step_loop(form):
     from geometry_rl_amd import agent
     from geometry_rl_amd.rollout import RolloutBuffer, RolloutDriver
@@ -271,8 +271,6 @@ def test_run_minibatches_equals_the_step_loop(form):
         spec, cfg, loss, data, next_last = _make(N, T, seed=33)
         upd = agent.PolicyUpdater(loss, lr=cfg.lr, use_graph=True)
         upd.epoch_unroll = 4 if mode == "launches" else 1
-        if form == "cursor":
-            upd.epoch_unroll_max_gated_frames, upd.epoch_gated_from_frames, upd.epoch_cursor = 0, 0, True
         buf = RolloutBuffer(dict(data))
         drv = RolloutDriver(upd, spec, ppo_epochs=2, seed=9)
         drv.compute_advantages(buf, next_last)
