@@ -86,82 +86,21 @@ GRL_DEVINL f32x16 bias_frag(const float* bias_s, int n0, int h) {
   return acc;
 }
 
-// One pass of the chain for this lane's row.  BWD keeps the activation derivatives; FENCED selects the two-waves-per-SIMD-safe
-// MFMA grouping (grl_common.h); k_epilogue(nt, acc) receives the two 32-column tiles of the kernel layer K = Wk g2 (pass
-// nullptr_t-like NoK to skip that layer).
-// ---- in-kernel phase timing (diagnostic build only: -DGRL_PHASE_PROF; tools/edge_phase.py reads the totals) ----------------------------
-// s_memtime stamps between the stages of the chain and of the kernels around it, accumulated by ONE wave per workgroup into a
-// __device__ table [kernel][phase].  The stamps cost ~10 % of the wave's cycles and serialise nothing else; shares, not absolutes.
-#ifdef GRL_PHASE_PROF
-__device__ unsigned long long g_ephase[3][24];
-struct PhaseClock {
-  unsigned long long ph[24], last;
-  GRL_DEVINL void start() { for (int i = 0; i < 24; ++i) ph[i] = 0; last = __builtin_amdgcn_s_memtime(); }
-  GRL_DEVINL void stamp(int i) { const unsigned long long t = __builtin_amdgcn_s_memtime(); ph[i] += t - last; last = t; }
-  GRL_DEVINL void flush(int kernel) {
-    if ((threadIdx.x & 63) == 0 && (threadIdx.x >> 6) == 1)
-      for (int i = 0; i < 24; ++i) atomicAdd(&g_ephase[kernel][i], ph[i]);
-  }
-};
-#define PHS(i) pc.stamp(i)
-#else
-struct PhaseClock { GRL_DEVINL void start() {} GRL_DEVINL void stamp(int) {} GRL_DEVINL void flush(int) {} };
-#define PHS(i)
-#endif
+// One pass of the chain for this lane's row.  BWD keeps the activation derivatives; the MFMA groups are fenced for two waves per SIMD
+// (grl_common.h mma_wx_bf_fenced); k_epilogue(nt, acc) receives the two 32-column tiles of the kernel layer K = Wk g2 (pass
+// nullptr_t-like NoK to skip that layer).  The weight fragments of a group are requested in front of it: loading them during the
+// previous group's epilogue measured no faster (round 2: forward 0.52 vs 0.51 ms per step, +14 registers), the SIMD partner already
+// covers their LDS latency.
 struct NoK {};
-// GRL_CHAIN_PIPED (build switch, off): in the fenced (two waves per SIMD) form every MFMA group's weight fragments are requested
-// while the previous group's activation epilogue runs (mma_wx_bf_piped) instead of in front of the group.  Measured round 2: no
-// change (forward 0.52 vs 0.51 ms per step, +14 registers): the LDS latency of the fragments is already covered by the SIMD partner.
-#ifndef GRL_CHAIN_PIPED
-#define GRL_CHAIN_PIPED 0
-#endif
-#ifndef GRL_POS_EARLY
-#define GRL_POS_EARLY 1
-#endif
 struct NoMid { GRL_DEVINL void operator()() const {} };
-template <bool BWD, bool FENCED, class KEpi, class Mid = NoMid>
+template <bool BWD, class KEpi, class Mid = NoMid>
 GRL_DEVINL void edge_chain(const ChainW& w, float a, float b, float4 (&g1)[8], float4 (&gp1)[8], float4 (&g2)[8], float4 (&gp2)[8],
-                           ChainFrags& f, KEpi&& k_epilogue, float* sink_p, PhaseClock& pc, Mid&& mid = NoMid{}) {
+                           ChainFrags& f, KEpi&& k_epilogue, Mid&& mid = NoMid{}) {
   const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
   float4 phi[2];
   poly_frags(a, b, h, phi[0], phi[1]);
   bf16x8 (&ph)[1] = f.ph, (&pl)[1] = f.pl;
   split_frags<16>(phi, ph, pl);
-  PHS(2);   // (a, b) available (positions of this pass arrived) + polynomial features + split
-#if GRL_CHAIN_PIPED
-  if constexpr (FENCED && !BWD && !std::is_same<typename std::decay<KEpi>::type, NoK>::value) {
-    float& sink = *sink_p;
-    auto act1 = [&](int nt) {
-      return [&, nt](const f32x16& acc) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) g1[4 * nt + q] = gelu4(make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]));
-      };
-    };
-    auto act2 = [&](int nt) {
-      return [&, nt](const f32x16& acc) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) g2[4 * nt + q] = gelu4(make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]));
-      };
-    };
-    auto wp = [&](const unsigned short* base, int ld, int nt) { return base + (32 * nt + i) * ld + 8 * h; };
-    WFrags<16> w1a, w1b;
-    WFrags<64> wa, wb;
-    load_wfrags<16>(w1a, wp(w.W1h, LDB1, 0), wp(w.W1l, LDB1, 0));
-    mma_wx_bf_piped<16, 16>(w1a, ph, pl, bias_frag(w.b1s, 0, h), &w1b, wp(w.W1h, LDB1, 1), wp(w.W1l, LDB1, 1), sink, act1(0));
-    mma_wx_bf_piped<16, 64>(w1b, ph, pl, bias_frag(w.b1s, 32, h), &wa, wp(w.W2h, LDB, 0), wp(w.W2l, LDB, 0), sink, act1(1));
-    bf16x8 (&g1h)[4] = f.g1h, (&g1l)[4] = f.g1l;
-    split_frags<64>(g1, g1h, g1l);
-    mma_wx_bf_piped<64, 64>(wa, g1h, g1l, bias_frag(w.b2s, 0, h), &wb, wp(w.W2h, LDB, 1), wp(w.W2l, LDB, 1), sink, act2(0));
-    mma_wx_bf_piped<64, 64>(wb, g1h, g1l, bias_frag(w.b2s, 32, h), &wa, wp(w.Wkh, LDB, 0), wp(w.Wkl, LDB, 0), sink, act2(1));
-    bf16x8 (&g2h)[4] = f.g2h, (&g2l)[4] = f.g2l;
-    split_frags<64>(g2, g2h, g2l);
-    mma_wx_bf_piped<64, 64>(wa, g2h, g2l, zero16(), &wb, wp(w.Wkh, LDB, 1), wp(w.Wkl, LDB, 1), sink,
-                            [&](const f32x16& acc) { k_epilogue(0, acc); });
-    mma_wx_bf_piped<64, 64>(wb, g2h, g2l, zero16(), static_cast<WFrags<64>*>(nullptr), nullptr, nullptr, sink,
-                            [&](const f32x16& acc) { k_epilogue(1, acc); });
-    return;
-  }
-#endif
 #pragma unroll
   for (int nt = 0; nt < 2; ++nt) {
     auto act = [&](const f32x16& acc) {
@@ -173,20 +112,12 @@ GRL_DEVINL void edge_chain(const ChainW& w, float a, float b, float4 (&g1)[8], f
       }
     };
     const unsigned short* wh = w.W1h + (32 * nt + i) * LDB1 + 8 * h, *wl = w.W1l + (32 * nt + i) * LDB1 + 8 * h;
-    if (FENCED) {
-      mma_wx_bf_fenced<16>(wh, wl, ph, pl, bias_frag(w.b1s, 32 * nt, h), act);
-    } else {
-      f32x16 acc = bias_frag(w.b1s, 32 * nt, h);
-      mma_wx_bf<16>(wh, wl, ph, pl, acc);
-      act(acc);
-    }
+    mma_wx_bf_fenced<16>(wh, wl, ph, pl, bias_frag(w.b1s, 32 * nt, h), act);
   }
   mid();    // the caller's early requests for the NEXT pass (positions): their latency hides behind layers 2 and 3
-  PHS(3);   // layer 1: two tiles (fragment loads, 3 MFMAs, GELU each)
   bf16x8 (&g1h)[4] = f.g1h, (&g1l)[4] = f.g1l;
   split_frags<64>(g1, g1h, g1l);
   GRL_SCHED_BARRIER();
-  PHS(4);   // split of g1
 #pragma unroll
   for (int nt = 0; nt < 2; ++nt) {
     auto act = [&](const f32x16& acc) {
@@ -198,33 +129,18 @@ GRL_DEVINL void edge_chain(const ChainW& w, float a, float b, float4 (&g1)[8], f
       }
     };
     const unsigned short* wh = w.W2h + (32 * nt + i) * LDB + 8 * h, *wl = w.W2l + (32 * nt + i) * LDB + 8 * h;
-    if (FENCED) {
-      mma_wx_bf_fenced<64>(wh, wl, g1h, g1l, bias_frag(w.b2s, 32 * nt, h), act);
-    } else {
-      f32x16 acc = bias_frag(w.b2s, 32 * nt, h);
-      mma_wx_bf<64>(wh, wl, g1h, g1l, acc);
-      act(acc);
-    }
+    mma_wx_bf_fenced<64>(wh, wl, g1h, g1l, bias_frag(w.b2s, 32 * nt, h), act);
   }
-  PHS(5);   // layer 2: two tiles (fragment loads, 12 MFMAs, GELU each)
   bf16x8 (&g2h)[4] = f.g2h, (&g2l)[4] = f.g2l;
   split_frags<64>(g2, g2h, g2l);
   GRL_SCHED_BARRIER();
-  PHS(6);   // split of g2
   if constexpr (!std::is_same<typename std::decay<KEpi>::type, NoK>::value) {
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
       const unsigned short* wh = w.Wkh + (32 * nt + i) * LDB + 8 * h, *wl = w.Wkl + (32 * nt + i) * LDB + 8 * h;
-      if (FENCED) {
-        mma_wx_bf_fenced<64>(wh, wl, g2h, g2l, zero16(), [&](const f32x16& acc) { k_epilogue(nt, acc); });
-      } else {
-        f32x16 acc = zero16();
-        mma_wx_bf<64>(wh, wl, g2h, g2l, acc);
-        k_epilogue(nt, acc);
-      }
+      mma_wx_bf_fenced<64>(wh, wl, g2h, g2l, zero16(), [&](const f32x16& acc) { k_epilogue(nt, acc); });
     }
     GRL_SCHED_BARRIER();
-    PHS(7);   // kernel layer: two tiles (fragment loads, 12 MFMAs, message epilogue each)
   }
 }
 
@@ -267,7 +183,7 @@ GRL_DEVINL void meta_indices(const EdgeParams& p, int e, int e_end, PassMeta& m)
 }
 // The positions of a pass are requested as soon as its indices have arrived -- in the MIDDLE of the previous pass's chain (edge_chain's
 // ``mid`` hook, behind layer 1) -- and turned into (a, b) at its end: the dependent index -> position round trip used to sit exposed
-// at the end of every pass (phase timing, tools/edge_phase.py: 12 % of the forward, 14 % of the weights kernel).
+// at the end of every pass (phase timing, docs/history/tools/edge_phase.py: 12 % of the forward, 14 % of the weights kernel).
 GRL_DEVINL void meta_pos_load(const EdgeParams& p, PassMeta& m) {   // loads only: nothing here may wait for them
   m.rx = p.pos_src[3 * m.src]; m.ry = p.pos_src[3 * m.src + 1]; m.rz = p.pos_src[3 * m.src + 2];
   m.qx = p.pos_dst[3 * m.dst]; m.qy = p.pos_dst[3 * m.dst + 1]; m.qz = p.pos_dst[3 * m.dst + 2];
@@ -294,25 +210,14 @@ GRL_DEVINL void meta_invariants(const EdgeParams& p, const float* grid_s, int o,
 // its (edge slot, orientation) row; after the last pass the two edge slots are folded with one cross-lane exchange
 // (lane r <-> r^16) and the rows leave with plain stores.  No LDS traffic besides the weights (LDS float atomics cost
 // ~200 LDS cycles per wave instruction on gfx950 -- measured, profiles/r01_*pmc* -- and made the first version LDS-bound).
-// GRL_FENCED_2W: the forward and the d x_src kernel run two waves per SIMD and therefore use the fenced MFMA groups (DESIGN.md finding 3).
-// -DGRL_FENCED_2W=false builds the hazard's in-situ reproducer (tools/det_check_all.py, tools/run_hazard_check.sh): never ship it.
-#ifndef GRL_FENCED_2W
-#define GRL_FENCED_2W true
-#endif
-#ifndef GRL_FWD_WAVES
-#define GRL_FWD_WAVES 4
-#endif
-constexpr int FWD_WAVES = GRL_FWD_WAVES;
+// The forward runs two waves per SIMD and therefore uses the fenced MFMA groups (DESIGN.md finding 3).
+constexpr int FWD_WAVES = 4;
 static_assert(FWD_WAVES >= 4, "load_chain_weights copies a pre-split image with 256 threads");
-#ifndef GRL_FWD_SPLIT_TILES
-#define GRL_FWD_SPLIT_TILES 512   // at most this many destination tiles: one workgroup per tile (edge_conv_fwd_kernel<true>)
-#endif
-#ifndef GRL_FWD_MAX_BLOCKS
-#define GRL_FWD_MAX_BLOCKS 512   // two 4-wave workgroups per CU = two waves per SIMD (the chain is fenced for that)
-#endif
+constexpr int FWD_SPLIT_TILES = 512;   // at most this many destination tiles: one workgroup per tile (edge_conv_fwd_kernel), else edge_conv16.hip
 // SPLIT: few destination tiles with long edge lists (e.g. the object -> gripper convolution of a small minibatch shard: a few
 // hundred tiles of 16+ passes would occupy a fraction of the SIMDs for the whole launch).  A workgroup then owns ONE tile, its
-// four waves take every fourth pass and the four partial messages are added in wave order through LDS.
+// four waves take every fourth pass and the four partial messages are added in wave order through LDS.  (SPLIT is the only form
+// left; the template argument keeps the kernel's name in traces and profiles.)
 template <bool SPLIT>
 __global__ __launch_bounds__(64 * FWD_WAVES, 2) void edge_conv_fwd_kernel
 (EdgeParams p, st_t* __restrict__ x1 /*[Nd,16,64]*/) {
@@ -323,14 +228,12 @@ __global__ __launch_bounds__(64 * FWD_WAVES, 2) void edge_conv_fwd_kernel
   __syncthreads();
   const int o = r & 15, el = r >> 4;
   const int n_tiles = (p.n_anchor + TD - 1) / TD;
-  constexpr int ESTEP = SPLIT ? 2 * FWD_WAVES : 2;
-  float sink = 0.f;   // keeps the accumulator fences of the pipelined chain alive (never stored, see the end of the kernel)
-  PhaseClock pc;
-  pc.start();
-  for (int tl = SPLIT ? (int)blockIdx.x : (int)blockIdx.x * FWD_WAVES + wave; tl < n_tiles;
-       tl += SPLIT ? (int)gridDim.x : (int)gridDim.x * FWD_WAVES) {
+  static_assert(SPLIT, "one workgroup per tile");
+  constexpr int ESTEP = 2 * FWD_WAVES;
+  float sink = 0.f;   // see the end of the kernel
+  for (int tl = (int)blockIdx.x; tl < n_tiles; tl += (int)gridDim.x) {
     const int d0 = tl * TD, d1 = min(d0 + TD, p.n_anchor);
-    const int e0 = p.rowptr[d0] + (SPLIT ? 2 * wave : 0), e1 = p.rowptr[d1];
+    const int e0 = p.rowptr[d0] + 2 * wave, e1 = p.rowptr[d1];
     float4 accA[8], accB[8];
 #pragma unroll
     for (int t = 0; t < 8; ++t) { accA[t] = make_float4(0.f, 0.f, 0.f, 0.f); accB[t] = accA[t]; }
@@ -338,11 +241,9 @@ __global__ __launch_bounds__(64 * FWD_WAVES, 2) void edge_conv_fwd_kernel
       PassMeta cur;
       meta_indices(p, e0 + el, e1, cur);
       meta_invariants(p, s.grid_s, o, cur);
-      PHS(0);   // tile head: rowptr, first indices + positions (dependent loads, exposed)
 #pragma unroll 1
       for (int e = e0; e < e1; e += ESTEP) {
         PassMeta nxt;
-        const bool more = e + ESTEP < e1;
         // next pass: indices in flight (requested unconditionally -- meta_indices clamps past the end -- so that nothing downstream
         // hangs on a branch: a guarded load's result is merged by register copies that wait for it on the spot)
         meta_indices(p, e + ESTEP + el, e1, nxt);
@@ -350,13 +251,12 @@ __global__ __launch_bounds__(64 * FWD_WAVES, 2) void edge_conv_fwd_kernel
         float4 xv[8];
 #pragma unroll
         for (int t = 0; t < 8; ++t) xv[t] = ld4(xs + 8 * t);                   // this pass: x_src row in flight
-        PHS(1);   // pass top: next indices + this pass's rows requested
         float4 g1[8], gp1[8], g2[8], gp2[8];
         ChainFrags cf;
         const float wa = (cur.valid && cur.dst == d0) ? 1.f : 0.f;
         const float wb = (cur.valid && cur.dst != d0) ? 1.f : 0.f;
         // message = K * x_src, summed into the accumulator of the edge's destination node as each K tile leaves the matrix pipe
-        edge_chain<false, GRL_FENCED_2W>(s, cur.a, cur.b, g1, gp1, g2, gp2, cf, [&](int nt, const f32x16& acc) {
+        edge_chain<false>(s, cur.a, cur.b, g1, gp1, g2, gp2, cf, [&](int nt, const f32x16& acc) {
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const int t = 4 * nt + q;
@@ -364,18 +264,16 @@ __global__ __launch_bounds__(64 * FWD_WAVES, 2) void edge_conv_fwd_kernel
             accA[t] = make_float4(fmaf(m.x, wa, accA[t].x), fmaf(m.y, wa, accA[t].y), fmaf(m.z, wa, accA[t].z), fmaf(m.w, wa, accA[t].w));
             accB[t] = make_float4(fmaf(m.x, wb, accB[t].x), fmaf(m.y, wb, accB[t].y), fmaf(m.z, wb, accB[t].z), fmaf(m.w, wb, accB[t].w));
           }
-        }, &sink, pc, [&]() { if (GRL_POS_EARLY) meta_pos_load(p, nxt); });   // next pass: positions requested mid-chain
-        if (GRL_POS_EARLY) meta_invariants_compute(p, s.grid_s, o, nxt);         // next pass: positions -> (a, b)
-        else if (more) meta_invariants(p, s.grid_s, o, nxt);
+        }, [&]() { meta_pos_load(p, nxt); });          // next pass: positions requested mid-chain
+        meta_invariants_compute(p, s.grid_s, o, nxt);   // next pass: positions -> (a, b)
         cur = nxt;
-        PHS(8);   // (a, b) of the next pass
       }
     }
     // fold the two edge slots; slot 0 lanes store node A's rows, slot 1 lanes node B's
     const int node = d0 + el;
     st_t* dstp = x1 + ((size_t)node * O + o) * C + 4 * h;
-    float4* red = reinterpret_cast<float4*>(smem_raw + sizeof(ChainW) / 4);   // SPLIT only: [FWD_WAVES][8][64]
-    if (SPLIT) __syncthreads();   // the previous tile's sums have been read
+    float4* red = reinterpret_cast<float4*>(smem_raw + sizeof(ChainW) / 4);   // [FWD_WAVES][8][64]
+    __syncthreads();   // the previous tile's sums have been read
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
       float4 a = accA[t], b = accB[t];
@@ -385,24 +283,21 @@ __global__ __launch_bounds__(64 * FWD_WAVES, 2) void edge_conv_fwd_kernel
       // one by index) -- slow, and the store->load ordering proved unreliable with two waves of a block per SIMD
       const bool is_a = el == 0;
       const float4 v = make_float4(is_a ? a.x : b.x, is_a ? a.y : b.y, is_a ? a.z : b.z, is_a ? a.w : b.w);
-      if (SPLIT) red[(wave * 8 + t) * 64 + lane] = v;
-      else if (node < d1) st4(dstp + 8 * t, v);
+      red[(wave * 8 + t) * 64 + lane] = v;
     }
-    PHS(9);   // tile tail: cross-lane fold + stores
-    if (SPLIT) {
-      __syncthreads();
+    __syncthreads();
 #pragma unroll
-      for (int u = 0; u < 8 / FWD_WAVES; ++u) {   // wave w adds up and stores fragments t = w, w + FWD_WAVES, ...
-        const int t = wave + u * FWD_WAVES;
-        float4 v = red[t * 64 + lane];
+    for (int u = 0; u < 8 / FWD_WAVES; ++u) {   // wave w adds up and stores fragments t = w, w + FWD_WAVES, ...
+      const int t = wave + u * FWD_WAVES;
+      float4 v = red[t * 64 + lane];
 #pragma unroll
-        for (int w_ = 1; w_ < FWD_WAVES; ++w_) v = f4_add(v, red[(w_ * 8 + t) * 64 + lane]);
-        if (node < d1) st4(dstp + 8 * t, v);
-      }
+      for (int w_ = 1; w_ < FWD_WAVES; ++w_) v = f4_add(v, red[(w_ * 8 + t) * 64 + lane]);
+      if (node < d1) st4(dstp + 8 * t, v);
     }
   }
-  if (sink == 123456.789f) st1(x1, sink);   // never true
-  pc.flush(0);
+  // never true; without this dead branch hipcc lays out the tile loop's exit differently (inverted compare and branch): it keeps the
+  // instructions of the measured kernel
+  if (sink == 123456.789f) st1(x1, sink);
 }
 
 // (The 32-row message / d x_src / weight-gradient kernels of round 1, superseded by edge_conv16.hip in round 2 and compiled out since, were
@@ -417,11 +312,11 @@ extern "C" {
 // launch shape of the forward for n_dst destination nodes (host-side partitioning, ops.build_edge_set): the image kind its kernel copies
 // (grl_weight_images: 1 = the one-workgroup-per-tile 32-row kernel of small launches, 0 = the 16-row kernel), the wave slots a balanced
 // partition has to cover (0: the launch ignores partitions) and the nodes per round-robin chunk
-int grl_edge_fwd_image_kind(int n_dst) { return (n_dst + TD - 1) / TD <= GRL_FWD_SPLIT_TILES ? 1 : 0; }
+int grl_edge_fwd_image_kind(int n_dst) { return (n_dst + TD - 1) / TD <= FWD_SPLIT_TILES ? 1 : 0; }
 int grl_edge_fwd_chunk_nodes(int n_dst);   // edge_conv16.hip
 int grl_edge_bwd_chunk_nodes(int n_src);
 int grl_edge_fwd_slots(int n_dst) {
-  if ((n_dst + TD - 1) / TD <= GRL_FWD_SPLIT_TILES) return 0;
+  if ((n_dst + TD - 1) / TD <= FWD_SPLIT_TILES) return 0;
   const int npw = grl_edge_fwd_chunk_nodes(n_dst), chunks = (n_dst + npw - 1) / npw;
   int blocks = (chunks + 3) / 4;
   const int cap = grl_edge_fwd_chunk_nodes(-1);   // (-1: the grid cap, workgroups)
@@ -475,7 +370,7 @@ int GRL_ENTRY(grl_edge_conv_fwd_balanced)(const st_t* x_src, const float* pos_sr
   const int n_tiles = (n_dst + TD - 1) / TD;
   const size_t smem = sizeof(ChainW), smem_split = smem + sizeof(float4) * FWD_WAVES * 8 * 64;
   GRL_ONCE(hipFuncSetAttribute((const void*)edge_conv_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_split));
-  if (n_tiles <= GRL_FWD_SPLIT_TILES) {   // fewer tiles than SIMD groups: spread each tile's passes over a workgroup
+  if (n_tiles <= FWD_SPLIT_TILES) {   // fewer tiles than SIMD groups: spread each tile's passes over a workgroup
     grl_prof_begin_replay("edge_conv_fwd_kernel", stream);
     hipLaunchKernelGGL(edge_conv_fwd_kernel<true>, dim3(n_tiles), dim3(64 * FWD_WAVES), smem_split, stream, p, x1);
     grl_prof_end_replay(stream);
@@ -563,12 +458,4 @@ int GRL_ENTRY(grl_edge_messages_bwd)(const st_t* x_src, const float* pos_src, co
                                           W2, b2, Wk, dres, dx_src, partial, blocks, nullptr, nullptr, stream);
 }
 
-#if defined(GRL_PHASE_PROF) && !GRL_PREC
-// diagnostic build only: out [3][24] = accumulated phase ticks of (forward, d x_src, weights) kernels; reset != 0 clears them
-int grl_edge_phase_read(unsigned long long* out72, int reset) {
-  hipMemcpyFromSymbol(out72, HIP_SYMBOL(g_ephase), sizeof(unsigned long long) * 72);
-  if (reset) { unsigned long long z[72] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(g_ephase), z, sizeof(z)); }
-  return 0;
-}
-#endif
 }  // extern "C"

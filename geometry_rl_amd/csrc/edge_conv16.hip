@@ -20,10 +20,6 @@
 // 32-block: position 8 g + j <-> feature 16 (j >> 2) + 4 g + (j & 3); the weight images are staged in that order), so the chain stays
 // in registers exactly as in the 32-row kernels.  Three waves per SIMD: every MFMA group is fenced (all fragment loads, then the
 // MFMAs, then a read of the accumulator: DESIGN.md finding 3).
-#ifndef GRL_B16_BURST
-#define GRL_B16_BURST 1   // fp32 build: MFMA bursts per layer + packed epilogues in the fused backward (see edge_bwd16_kernel; 0 = the grouped form of rounds 2-4)
-#endif
-#define GRL_PK_F4 1   // (plain-bf16 build, or the fp32 burst experiment: packed f32 pairs for the element-wise products, grl_common.h)
 #include "grl_tile16.h"
 #include "grl_wimg.h"
 #include <cstdlib>
@@ -32,13 +28,8 @@ namespace {
 
 constexpr int C = 64, O = 16;
 
-#ifndef GRL_E16_WAVES
-#define GRL_E16_WAVES 4                  // waves per workgroup
-#endif
-#ifndef GRL_E16_WGS
-#define GRL_E16_WGS 3                    // workgroups per CU the register budget is cut for (and the grid is capped at)
-#endif
-constexpr int E16_WAVES = GRL_E16_WAVES, E16_THREADS = 64 * E16_WAVES;
+constexpr int E16_WAVES = 4, E16_THREADS = 64 * E16_WAVES;   // waves per workgroup
+constexpr int E16_WGS = 3;   // workgroups per CU the register budget is cut for (and the grid is capped at)
 constexpr int LD1 = WI_LD1, LD2 = WI_LD2;   // image row lengths, ChainW16 / Edge16Image, stage16: grl_wimg.h (shared with the image producer)
 
 struct Edge16Params {
@@ -59,9 +50,6 @@ struct Edge16Params {
 };
 
 GRL_DEVINL void load_w16(ChainW16& s, const Edge16Params& p) {
-#ifdef GRL_KNOCK_STAGE   // timing knock-out: no weight staging (results are wrong)
-  return;
-#endif
   if (p.wimg) {   // the image of this forward pass (built once per step): a linear copy
     copy_image<E16_THREADS>(&s, p.wimg, (int)sizeof(ChainW16));
     return;
@@ -79,146 +67,20 @@ GRL_DEVINL void group16(const unsigned short* whi, const unsigned short* wlo, co
   bf16x8 wh[KS], wl[KS];
 #pragma unroll
   for (int s = 0; s < KS; ++s) {
-#ifdef GRL_E16_NOLDS
-    wh[s] = xh[s];
-    wl[s] = xl[s];
-#else
     wh[s] = *reinterpret_cast<const bf16x8*>(whi + 32 * s);
     GRL_LO(wl[s] = *reinterpret_cast<const bf16x8*>(wlo + 32 * s);)
-#endif
-#ifdef GRL_E16_LDSONLY
-    asm volatile("" ::"v"(wh[s]), "v"(wl[s]));
-#endif
   }
   if (FENCED) __builtin_amdgcn_sched_barrier(0);
-#if !defined(GRL_E16_NOMFMA) && !defined(GRL_E16_LDSONLY)
 #pragma unroll
   for (int s = 0; s < KS; ++s) {
     acc = mfma16(wh[s], xh[s], acc);
     GRL_LO(acc = mfma16(wl[s], xh[s], acc);)
     GRL_LO(acc = mfma16(wh[s], xl[s], acc);)
   }
-#endif
   epi(acc);
   if (FENCED) __builtin_amdgcn_sched_barrier(0);
 }
 
-
-// timing knock-outs (diagnostic builds only; results are wrong): -DGRL_E16_NOGELU, -DGRL_E16_NOMFMA, -DGRL_E16_NOGATHER
-#ifdef GRL_E16_NOGELU
-#define GELU16(x) (x)
-#elif defined(GRL_E16_SCALAR_GELU)
-GRL_DEVINL float4 gelu4s(float4 x) {
-  float4 g, gp;
-  gelu_both4(x, g, gp);
-  return g;
-}
-#define GELU16(x) gelu4s(x)
-#else
-#define GELU16(x) gelu4(x)
-#endif
-// weight fragments of one chain group (n-tile nt of a 64 x 64 image), requested one group ahead of their MFMAs
-struct WF2 {
-  bf16x8 h[2], l[2];
-  float4 bias;   // the group's accumulator start (requested with the fragments: a read issued inside the group's own region would make
-                 // its wait cover the next group's fragment reads as well -- LDS returns in order)
-};
-GRL_DEVINL void wf_load(WF2& f, const unsigned short* whi, const unsigned short* wlo, const float* bias = nullptr) {
-  f.bias = bias ? *reinterpret_cast<const float4*>(bias) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    f.h[s] = *reinterpret_cast<const bf16x8*>(whi + 32 * s);
-    GRL_LO(f.l[s] = *reinterpret_cast<const bf16x8*>(wlo + 32 * s);)
-  }
-}
-GRL_DEVINL f32x4v wf_mma(const WF2& f, const bf16x8 (&xh)[2], const bf16x8 (&xl)[2], f32x4v acc) {
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    acc = mfma16(f.h[s], xh[s], acc);
-    GRL_LO(acc = mfma16(f.l[s], xh[s], acc);)
-    GRL_LO(acc = mfma16(f.h[s], xl[s], acc);)
-  }
-  return acc;
-}
-
-// The same chain cut into scheduling regions like the fused backward's pass (GRL_E16_REGIONS): the fragments (and bias) of group k + 1
-// are requested before group k's MFMAs, and region k runs the MFMAs of group k + 1 beside the epilogue (GELU) of group k -- matrix and
-// vector work of the SAME wave, the only overlap a SIMD gives (DESIGN.md finding 18).  No LDS read sits between the MFMAs of a chain.
-// Measured (tools/run_variants.sh, one box): 0.46-0.51 ms against 0.48-0.52 for the fenced groups -- inside the noise at three waves per
-// SIMD; the default stays the fenced form (no fragment register is ever re-loaded while an MFMA that reads it may be queued).
-#ifndef GRL_E16_REGIONS
-#define GRL_E16_REGIONS 0
-#endif
-template <class KEpi>
-GRL_DEVINL void chain16_regions(const ChainW16& w, float a, float b, int r, int g, KEpi&& k_epi) {
-#define BAR() __builtin_amdgcn_sched_barrier(0)
-  bf16x8 w1h[4], w1l[4];
-  float4 b1q[4];
-  WF2 wf[2];
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt) {
-    w1h[nt] = *reinterpret_cast<const bf16x8*>(w.W1h + (16 * nt + r) * LD1 + 8 * g);
-    GRL_LO(w1l[nt] = *reinterpret_cast<const bf16x8*>(w.W1l + (16 * nt + r) * LD1 + 8 * g);)
-    b1q[nt] = *reinterpret_cast<const float4*>(w.b1s + 16 * nt + 4 * g);
-  }
-  wf_load(wf[0], w.W2h + r * LD2 + 8 * g, w.W2l + r * LD2 + 8 * g, w.b2s + 4 * g);
-  const float aa = a * a, ab = a * b, bb = b * b;
-  float4 phi;
-  if (g == 0) phi = make_float4(a, b, aa, ab);
-  else if (g == 1) phi = make_float4(ab, bb, aa * a, aa * b);
-  else if (g == 2) phi = make_float4(ab * a, ab * b, ab * a, ab * b);
-  else phi = make_float4(bb * a, bb * b, 0.f, 0.f);
-  bf16x8 ph, pl;
-  split_pair(phi, make_float4(0.f, 0.f, 0.f, 0.f), ph, pl);
-  BAR();
-  bf16x8 xh[2], xl[2], yh[2], yl[2];
-  {
-    float4 g1[4];
-    f32x4v c[4];
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      c[nt] = f32x4v{b1q[nt].x, b1q[nt].y, b1q[nt].z, b1q[nt].w};
-      c[nt] = mfma16(w1h[nt], ph, c[nt]);
-      GRL_LO(c[nt] = mfma16(w1l[nt], ph, c[nt]);)
-      GRL_LO(c[nt] = mfma16(w1h[nt], pl, c[nt]);)
-      if (nt > 0) g1[nt - 1] = GELU16(v4(c[nt - 1]));
-      BAR();
-    }
-    g1[3] = GELU16(v4(c[3]));
-    split_pair(g1[0], g1[1], xh[0], xl[0]);
-    split_pair(g1[2], g1[3], xh[1], xl[1]);
-    BAR();
-  }
-  auto layer64 = [&](int base, const unsigned short* mh, const unsigned short* ml, const unsigned short* nh, const unsigned short* nl,
-                     const float* nbias, const bf16x8 (&ih)[2], const bf16x8 (&il)[2], auto&& epi, auto&& tail) {
-    // groups of image (mh, ml); the group after the last one is tile 0 of (nh, nl) (nullptr: none)
-    f32x4v c[4];
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      if (nt < 3) wf_load(wf[(base + nt + 1) & 1], mh + (16 * (nt + 1) + r) * LD2 + 8 * g, ml + (16 * (nt + 1) + r) * LD2 + 8 * g,
-                          base == 0 ? w.b2s + 16 * (nt + 1) + 4 * g : nullptr);
-      else if (nh) wf_load(wf[(base + nt + 1) & 1], nh + r * LD2 + 8 * g, nl + r * LD2 + 8 * g, nbias);
-      BAR();
-      const float4 bq = wf[(base + nt) & 1].bias;
-      c[nt] = wf_mma(wf[(base + nt) & 1], ih, il, f32x4v{bq.x, bq.y, bq.z, bq.w});
-      if (nt > 0) epi(nt - 1, c[nt - 1]);
-      BAR();
-    }
-    epi(3, c[3]);
-    tail();
-    BAR();
-  };
-  {
-    float4 g2[4];
-    layer64(0, w.W2h, w.W2l, w.Wkh, w.Wkl, nullptr, xh, xl, [&](int nt, const f32x4v& c) { g2[nt] = GELU16(v4(c)); },
-            [&]() {
-              split_pair(g2[0], g2[1], yh[0], yl[0]);
-              split_pair(g2[2], g2[3], yh[1], yl[1]);
-            });
-  }
-  layer64(4, w.Wkh, w.Wkl, nullptr, nullptr, nullptr, yh, yl, [&](int nt, const f32x4v& c) { k_epi(nt, v4(c)); }, [&]() {});
-#undef BAR
-}
 
 // The chain for this lane's row: (a, b) -> K tiles handed to k_epi(nt, float4 of features 16 nt + 4 g + 0..3)
 template <class KEpi>
@@ -237,7 +99,7 @@ GRL_DEVINL void chain16(const ChainW16& w, float a, float b, int r, int g, KEpi&
   for (int nt = 0; nt < 4; ++nt) {
     const float4 bq = *reinterpret_cast<const float4*>(w.b1s + 16 * nt + 4 * g);
     group16<1>(w.W1h + (16 * nt + r) * LD1 + 8 * g, w.W1l + (16 * nt + r) * LD1 + 8 * g, ph, pl, f32x4v{bq.x, bq.y, bq.z, bq.w},
-               [&](const f32x4v& acc) { g1[nt] = GELU16(v4(acc)); });
+               [&](const f32x4v& acc) { g1[nt] = gelu4(v4(acc)); });
   }
   bf16x8 xh[2], xl[2];
   split_pair(g1[0], g1[1], xh[0], xl[0]);
@@ -247,7 +109,7 @@ GRL_DEVINL void chain16(const ChainW16& w, float a, float b, int r, int g, KEpi&
   for (int nt = 0; nt < 4; ++nt) {
     const float4 bq = *reinterpret_cast<const float4*>(w.b2s + 16 * nt + 4 * g);
     group16<2>(w.W2h + (16 * nt + r) * LD2 + 8 * g, w.W2l + (16 * nt + r) * LD2 + 8 * g, xh, xl, f32x4v{bq.x, bq.y, bq.z, bq.w},
-               [&](const f32x4v& acc) { g2[nt] = GELU16(v4(acc)); });
+               [&](const f32x4v& acc) { g2[nt] = gelu4(v4(acc)); });
   }
   bf16x8 yh[2], yl[2];
   split_pair(g2[0], g2[1], yh[0], yl[0]);
@@ -259,14 +121,11 @@ GRL_DEVINL void chain16(const ChainW16& w, float a, float b, int r, int g, KEpi&
                [&](const f32x4v& acc) { k_epi(nt, v4(acc)); });
 }
 
-#ifndef GRL_E16_RESIDENT
-#define GRL_E16_RESIDENT GRL_PREC   // forward: weight fragments resident in registers (bf16 build: always; fp32 build: with GRL_E16_WGS=2, experiment)
-#endif
-#if GRL_E16_RESIDENT
+#if GRL_PREC
 // Resident weight fragments (round 5): a lane's weight fragments depend on (row, k-group, n-tile, K-step) only -- the SAME operand registers
 // for every pass.  Plain-bf16 build: W2 8 + Wk 8 fragments = 64 registers at three waves per SIMD (W1's four would push the kernel over 168
-// registers: they are requested with the biases at the head of the pass).  fp32 build: hi + lo = 128 registers, two waves per SIMD
-// (GRL_E16_WGS=2).  The pass loop then has no fragment read inside the chain at all (the fenced groups exposed one LDS round trip per
+// registers: they are requested with the biases at the head of the pass).  The fp32 build keeps the fenced groups (chain16): its hi + lo
+// fragments would take 128 registers, two waves per SIMD.  The pass loop then has no fragment read inside the chain at all (the fenced groups exposed one LDS round trip per
 // group: 12 per pass, wave cycles wait 0.41 + issue stall 0.23 at three waves per SIMD in the bf16 build, profiles/r05_pmc_table_rope_hepi_bf16_a.txt);
 // the only LDS reads left are W1's fragments and the two layers' biases, requested at the head of the pass behind a scheduling barrier
 // (no MFMA of this wave is in flight there: the previous pass's last accumulators have been consumed).  A layer's MFMAs run as four
@@ -319,7 +178,7 @@ GRL_DEVINL void chain16_resident(const ChainRegs& cr, const ChainW16& w, float a
   for (int nt = 0; nt < 4; ++nt) c[nt] = mfma16(w1[nt], pl, c[nt]);
 #endif
 #pragma unroll
-  for (int nt = 0; nt < 4; ++nt) g1[nt] = GELU16(v4(c[nt]));
+  for (int nt = 0; nt < 4; ++nt) g1[nt] = gelu4(v4(c[nt]));
   bf16x8 xh[2], xl[2];
   split_pair(g1[0], g1[1], xh[0], xl[0]);
   split_pair(g1[2], g1[3], xh[1], xl[1]);
@@ -337,7 +196,7 @@ GRL_DEVINL void chain16_resident(const ChainRegs& cr, const ChainW16& w, float a
 #endif
   }
 #pragma unroll
-  for (int nt = 0; nt < 4; ++nt) g2[nt] = GELU16(v4(c[nt]));
+  for (int nt = 0; nt < 4; ++nt) g2[nt] = gelu4(v4(c[nt]));
   bf16x8 yh[2], yl[2];
   split_pair(g2[0], g2[1], yh[0], yl[0]);
   split_pair(g2[2], g2[3], yh[1], yl[1]);
@@ -359,8 +218,6 @@ GRL_DEVINL void chain16_resident(const ChainRegs& cr, const ChainW16& w, float a
   __builtin_amdgcn_sched_barrier(0);
 }
 #define E16_CHAIN(S, A, B, R, G, EPI) chain16_resident(cregs, S, A, B, R, G, EPI)
-#elif GRL_E16_REGIONS
-#define E16_CHAIN chain16_regions
 #else
 #define E16_CHAIN chain16
 #endif
@@ -370,14 +227,14 @@ constexpr int NPW_MAX = 16;   // anchor nodes per wave chunk (their rowptr entri
 // MODE 1: d x_src       out[anchor] = (dres ? dres[anchor] : 0) + sum of K_e * x_in[other(e) | row]   (anchor = source)
 // MODE 2: messages      msg[edge position] = K_e * x_in[other(e)], no accumulation                    (anchor = destination)
 template <int MODE>
-__global__ __launch_bounds__(E16_THREADS, GRL_E16_WGS) void edge16_kernel(Edge16Params p, st_t* __restrict__ out, const st_t* __restrict__ dres) {
+__global__ __launch_bounds__(E16_THREADS, E16_WGS) void edge16_kernel(Edge16Params p, st_t* __restrict__ out, const st_t* __restrict__ dres) {
   extern __shared__ __attribute__((aligned(16))) float smem_raw[];
   ChainW16& s = *reinterpret_cast<ChainW16*>(smem_raw);
   load_w16(s, p);
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
   const float gx = s.grid_s[3 * r], gy = s.grid_s[3 * r + 1], gz = s.grid_s[3 * r + 2];
-#if GRL_E16_RESIDENT
+#if GRL_PREC
   ChainRegs cregs;
   chain_regs_load(cregs, s, r, g);
 #endif
@@ -418,7 +275,7 @@ __global__ __launch_bounds__(E16_THREADS, GRL_E16_WGS) void edge16_kernel(Edge16
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         float4 v = acc[t];
-        if (MODE == 1 && dres) v = f4_add(v, ld4(dres + ((size_t)(n0 + j) * O + r) * C + 4 * g + 16 * t));
+        if (MODE == 1 && dres) v = f4_add_pk(v, ld4(dres + ((size_t)(n0 + j) * O + r) * C + 4 * g + 16 * t));
         st4(o + 16 * t, v);
         acc[t] = make_float4(0.f, 0.f, 0.f, 0.f);
       }
@@ -443,11 +300,7 @@ __global__ __launch_bounds__(E16_THREADS, GRL_E16_WGS) void edge16_kernel(Edge16
         float4 xv[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t)
-#ifdef GRL_E16_NOGATHER
-          xv[t] = make_float4(1.f, 1.f, 1.f, 1.f);
-#else
           xv[t] = ld4(xs + 16 * t);      // this edge's gathered row, in flight behind the chain
-#endif
         // r = pos_src - pos_dst (hepi.py:109-117), whichever end is the anchor
         float dx = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pox), k)) -
                    __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pax), node));
@@ -462,9 +315,9 @@ __global__ __launch_bounds__(E16_THREADS, GRL_E16_WGS) void edge16_kernel(Edge16
         const float b = sqrtf(dx * dx + dy * dy + dz * dz);
         st_t* mrow = MODE == 2 ? out + ((size_t)e * O + r) * C + 4 * g : nullptr;
         E16_CHAIN(s, a, b, r, g, [&](int nt, const float4& kq) {
-          const float4 m = f4_mul(kq, xv[nt]);
+          const float4 m = f4_mul_pk(kq, xv[nt]);
           if (MODE == 2) st4(mrow + 16 * nt, m);
-          else acc[nt] = f4_add(acc[nt], m);
+          else acc[nt] = f4_add_pk(acc[nt], m);
         });
       }
     }
@@ -503,9 +356,6 @@ struct RFrags {
 // the transposed operand fragments of one weight-gradient product: requested here, consumed by rowred_mma a chain step later
 template <int NTK>
 GRL_DEVINL void rowred_load(const Stage16& st, int lane, RFrags<NTK>& f) {
-#ifdef GRL_B16_NOROWMMA
-  return;
-#endif
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     f.ah[t] = tr_frag(st.Ah, t, lane);
@@ -520,9 +370,6 @@ GRL_DEVINL void rowred_load(const Stage16& st, int lane, RFrags<NTK>& f) {
 // acc[tn][tk] (32 x 32: output feature n on the registers, input feature k on the lane) += A^T B over the 16 staged rows
 template <int NTK>
 GRL_DEVINL void rowred_mma(const RFrags<NTK>& f, f32x16 (&acc)[2][NTK]) {
-#ifdef GRL_B16_NOROWMMA
-  return;
-#endif
 #pragma unroll
   for (int tn = 0; tn < 2; ++tn)
 #pragma unroll
@@ -533,10 +380,8 @@ GRL_DEVINL void rowred_mma(const RFrags<NTK>& f, f32x16 (&acc)[2][NTK]) {
     }
 }
 
-#ifdef GRL_B16_NOGELU
-#define B16_GELU(x, gv, gpv) ((gv) = (x), (gpv) = (x))
-#elif !defined(GRL_B16_SCALAR_GELU) || GRL_PREC || GRL_B16_BURST   // packed pairs: one wave per SIMD issues a v_pk_* in the time of a scalar op; the plain-bf16
-                                                  // build always (its MFMAs come in bursts, not between the epilogue's instructions)
+// GELU value + derivative as packed pairs: one wave per SIMD issues a v_pk_* in the time of a scalar op, and both builds issue the pass's
+// MFMAs in bursts, not between the epilogue's instructions
 GRL_DEVINL void gelu_both4_pk(const float4& x, float4& gv, float4& gpv) {
   v2f g0, g1, d0, d1;
   gelu_pair<true>(v2f{x.x, x.y}, g0, d0);
@@ -544,16 +389,7 @@ GRL_DEVINL void gelu_both4_pk(const float4& x, float4& gv, float4& gpv) {
   gv = make_float4(g0.x, g0.y, g1.x, g1.y);
   gpv = make_float4(d0.x, d0.y, d1.x, d1.y);
 }
-#define B16_GELU(x, gv, gpv) gelu_both4_pk((x), (gv), (gpv))
-#else
-#define B16_GELU(x, gv, gpv) gelu_both4((x), (gv), (gpv))
-#endif
-#ifdef GRL_B16_NOGATHER
-#define B16_LD(p) make_float4(0.5f, 0.25f, -0.5f, 1.f)
-#else
-#define B16_LD(p) ld4(p)
-#endif
-#ifdef GRL_B16_PHASE   // diagnostic build: s_memtime ticks per stage of the pass, wave 0 of every workgroup (tools/edge_phase.py --bwd16)
+#ifdef GRL_B16_PHASE   // diagnostic build: s_memtime ticks per stage of the pass, wave 0 of every workgroup (tools/edge_bwd16_phase.py)
 __device__ unsigned long long g_b16phase[16];
 #define B16_PH(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); ph_[i] += t_ - tl_; tl_ = t_; } while (0)
 #else
@@ -573,7 +409,6 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
   extern __shared__ __attribute__((aligned(16))) float smem_raw[];
   Bwd16Smem& sm = *reinterpret_cast<Bwd16Smem*>(smem_raw);
   const Edge16Params& p = bp.e;
-#ifndef GRL_KNOCK_STAGE
   if (p.wimg) {   // the five images of this step, built once by grl_weight_images: a linear copy (91 KB, 23 16-byte loads per thread)
     copy_image<256>(&sm.img, p.wimg, (int)sizeof(Edge16Image));
   } else {
@@ -584,9 +419,6 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
     stage16<64, 64, 256, true>(sm.img.W2Th, sm.img.W2Tl, p.W2, LD2);
     stage_chain16_small<256>(sm.img.w, p.b1, p.b2, p.grid);
   }
-#else
-  stage_chain16_small<256>(sm.img.w, p.b1, p.b2, p.grid);
-#endif
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
   Stage16& st = sm.st[wave];
   for (int i = lane; i < STG / 2; i += 64) {
@@ -617,15 +449,15 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
   LayerFrags bufA, bufB;
   lf_load(bufA, w.W2h);
   lf_load(bufB, w.Wkh);
-#elif GRL_B16_BURST
-  // fp32 build (round 5; GRL_B16_BURST=0 restores the grouped form): a layer's 24 MFMAs as ONE burst of four independent six-deep chains from a layer-wide fragment
+#else
+  // fp32 build (round 5): a layer's 24 MFMAs as ONE burst of four independent six-deep chains from a layer-wide fragment
   // buffer (hi + lo: 64 registers, ONE buffer: it is refilled for the next layer right behind the burst -- in-order issue, one wave per
   // SIMD: every MFMA of the burst has been issued, i.e. has read its operands, before the first of these reads is issued -- and the
   // reads land during the epilogue), and the epilogues as PACKED f32 pairs behind it (no MFMA between their instructions: a lone wave issues a
   // v_pk_* in the time of a plain instruction, but not inside an MFMA's shadow).  Bitwise the grouped form's results (same products in the
   // same order per accumulator).  A/B on one box, three alternating rounds: 310.4-312.8 -> 312.2-313.7 steps/s (+0.5 %), edge_bwd16 1.19 ->
   // 1.17 ms per step (profiles/r05_ab_burst.txt): the packed epilogues save ~12 % of the pass's vector issue, the burst gives back the
-  // little MFMA / VALU overlap the grouped form had (finding 18: the kernel is additive either way).
+  // little MFMA / VALU overlap the grouped form of rounds 2-4 had (finding 18: the kernel is additive either way).
   struct LayerFrags { bf16x8 h[4][2], l[4][2]; };
   auto lf_load = [&](LayerFrags& f, const unsigned short* imh, const unsigned short* iml) {
 #pragma unroll
@@ -685,39 +517,15 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
     // `dres ? load : 0` written on the load EXPRESSION compiles to a branch around every load with an s_waitcnt vmcnt(0) at its end (the
     // value merges with a constant): four serialised memory round trips per node change -- 22 % of the bf16 build's pass, 7 % of the fp32
     // build's (profiles/r05_edge_bwd16_phases_*.txt).  The loads are therefore unconditional -- from x_src when there is no dres: the rows
-    // the same node loads anyway, so no extra traffic where it matters -- and the SELECT is on the loaded value.
+    // the same node loads anyway, so no extra traffic where it matters -- and the SELECT is on the loaded value.  The fp32 build keeps
+    // round 4's conditional loads: the unconditional form was 1.1 % slower inside its replayed step (DESIGN.md finding 49's A/B,
+    // profiles/r05_ab_fp32_rows_burst.txt).
     const st_t* dres_b = bp.dres ? bp.dres : bp.x_src;
     const unsigned dmask = bp.dres ? 0xFFFFFFFFu : 0u;   // the select as a bit mask (a ?: on a wave-uniform bool becomes branches again)
-    auto keep = [&](const float4& v) {
-      return make_float4(__uint_as_float(__float_as_uint(v.x) & dmask), __uint_as_float(__float_as_uint(v.y) & dmask),
-                         __uint_as_float(__float_as_uint(v.z) & dmask), __uint_as_float(__float_as_uint(v.w) & dmask));
-    };
-#ifndef GRL_B16_ROWS
-#define GRL_B16_ROWS 0   // plain-bf16 build, how the source node's own rows are fetched: 0 = at the node change, widened at the first consumer;
-#endif                   // 1 = "uniform passes" (below).  A/B on one box (tools/r05_ab_rows.sh): 0 wins, see the comment at the #else
-#if GRL_PREC && GRL_B16_ROWS
-    // Plain-bf16 build ("uniform passes", round 5).  The rows arrive as bf16 bits and are widened in registers, a ~2.6 us pass is shorter
-    // than a row gather under load, and s_waitcnt vmcnt counts loads AND stores in issue order: any load or store whose presence depends
-    // on the pass (a node change's row loads) makes the compiler wait for the smallest count over all paths, i.e. for operations that have
-    // only just been issued (phase stamps: 22 % of the pass at the node change, then 41 % at the first consumer when the widening was
-    // merely deferred; knock-out without gathers: -20 % of the launch).  Here EVERY pass issues the same twelve loads at its top -- for the
-    // NEXT edge: its dM row, the x_src row and the dres row of its source node (the node's rows again for each of its edges: L1 / L2 hits)
-    // -- and takes last pass's twelve over right before: one vmcnt(0) per pass, at a point where everything outstanding is a full pass
-    // old.  No row load is tied to a node change; the dres row stays raw (aq) and is added by flush(), the accumulator starts at zero.
-    struct RawRows { uint2 d[4], x[4], a[4]; };
-    RawRows nq;
-    uint2 aq[4];
-    auto widen = [](const uint2& u) {
-      return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xFFFF0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xFFFF0000u));
-    };
-    auto flush = [&](int j) {
-      st_t* o = bp.dx_src + ((size_t)(n0 + j) * O + r) * C + 4 * g;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) st4(o + 16 * t, f4_add(acc[t], widen(make_uint2(aq[t].x & dmask, aq[t].y & dmask))));
-    };
-#elif GRL_PREC
+#if GRL_PREC
     // Plain-bf16 build, rows at the node change (the form that measured best: 2.66 ms per step for the rope workload's three launches
-    // against 2.82-2.9 for the uniform passes above and for rows requested a node ahead -- the extra loads, copies and per-pass widenings
+    // against 2.82-2.9 for "uniform passes" (every pass loading the next edge's rows at its top; docs/history/tools/r05_ab_rows.sh) and
+    // for rows requested a node ahead -- the extra loads, copies and per-pass widenings
     // cost more than the residual wait): the raw rows are kept as loaded (xq, aq) and widened by materialise() in front of the K layer of
     // the node's first pass; a widening right behind the load would be a use that waits for it (node_begin stood a memory round trip at
     // every node change: 22 % of the pass).  dM rows are gathered two edges ahead (dq1, dq2).
@@ -731,12 +539,8 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
       const st_t* ds = dres_b + ((size_t)(n0 + j) * O + r) * C + 4 * g;
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-#ifdef GRL_B16_NOGATHER
-        xq[t] = aq[t] = make_uint2(0x3f003e80u, 0xbf003f80u);
-#else
         xq[t] = *reinterpret_cast<const uint2*>(xs + 16 * t);
         aq[t] = *reinterpret_cast<const uint2*>(ds + 16 * t);
-#endif
       }
       fresh = true;
     };
@@ -757,20 +561,12 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
       for (int t = 0; t < 4; ++t) st4(o + 16 * t, acc[t]);
     };
 #else
-#ifndef GRL_B16_FP32_ROWS
-#define GRL_B16_FP32_ROWS 0   // fp32 build: 0 = round 4's node rows (dres ? load : 0 on the load expression, node change in front of the dM take-over),
-#endif                        // 1 = unconditional loads + bit-mask select + take-over first (what the bf16 build needs).  See the A/B note below.
     auto node_begin = [&](int j) {   // the source node's own row: the same for all of its edges
       const st_t* xs = bp.x_src + ((size_t)(n0 + j) * O + r) * C + 4 * g;
 #pragma unroll
       for (int t = 0; t < 4; ++t) {   // the accumulator starts from the other branch's gradient row (dres), long before it is needed
-        xv[t] = B16_LD(xs + 16 * t);
-#if GRL_B16_FP32_ROWS
-        const float4 dr = B16_LD(dres_b + ((size_t)(n0 + j) * O + r) * C + 4 * g + 16 * t);   // UNCONDITIONAL load, then a select
-        acc[t] = keep(dr);
-#else
-        acc[t] = bp.dres ? B16_LD(bp.dres + ((size_t)(n0 + j) * O + r) * C + 4 * g + 16 * t) : make_float4(0.f, 0.f, 0.f, 0.f);
-#endif
+        xv[t] = ld4(xs + 16 * t);
+        acc[t] = bp.dres ? ld4(bp.dres + ((size_t)(n0 + j) * O + r) * C + 4 * g + 16 * t) : make_float4(0.f, 0.f, 0.f, 0.f);
       }
     };
     auto flush = [&](int j) {
@@ -798,12 +594,7 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
             const uint2 dr = *reinterpret_cast<const uint2*>(dres_b + row + 16 * t);
             v[u][t] = make_uint2(dr.x & dmask, dr.y & dmask);
 #else
-#if GRL_B16_FP32_ROWS
-            const float4 dr = B16_LD(dres_b + row + 16 * t);
-            v[u][t] = keep(dr);
-#else
-            v[u][t] = bp.dres ? B16_LD(bp.dres + row + 16 * t) : make_float4(0.f, 0.f, 0.f, 0.f);
-#endif
+            v[u][t] = bp.dres ? ld4(bp.dres + row + 16 * t) : make_float4(0.f, 0.f, 0.f, 0.f);
 #endif
           }
         }
@@ -820,18 +611,7 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
         }
       }
     };
-#if GRL_PREC && GRL_B16_ROWS
-    if (E0 < E1) {   // the leading nodes without edges are copied; the first node WITH edges becomes the current one
-      while (__builtin_amdgcn_readlane(rp, node + 1) <= E0) ++node;
-      skip_empty_run(0, node);
-      node_end = __builtin_amdgcn_readlane(rp, node + 1);
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-    int pnode = node, pnode_end = node_end;   // the node of the edge whose rows are requested next (runs one edge ahead of `node`)
-#else
     node_begin(0);
-#endif
     for (int eb = E0; eb < E1; eb += 64) {
       const int ee = min(eb + lane, E1 - 1);
       const int oth = p.e_dst[ee];
@@ -844,38 +624,14 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
       // the pass; knock-out without gathers: -20 % of the launch).  The prefetched row is TAKEN OVER BEFORE the node change below: vmcnt
       // counts in issue order, and with the node change's stores and loads issued in front of the take-over the wait for the old gather
       // would also wait for the row loads that have only just been requested.
-#if GRL_PREC && GRL_B16_ROWS
-      auto rows_issue = [&](int kk) {   // the twelve loads of edge eb + kk (pnode: its source node)
-        const int en = eb + kk;
-        while (en >= pnode_end) { ++pnode; pnode_end = __builtin_amdgcn_readlane(rp, pnode + 1); }
-        const int row_in = __builtin_amdgcn_readlane(xrow, kk);
-        const st_t* dm = p.x_in + ((size_t)row_in * O + r) * C + 4 * g;
-        const st_t* xs = bp.x_src + ((size_t)(n0 + pnode) * O + r) * C + 4 * g;
-        const st_t* ds = dres_b + ((size_t)(n0 + pnode) * O + r) * C + 4 * g;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-#ifdef GRL_B16_NOGATHER
-          nq.d[t] = nq.x[t] = nq.a[t] = make_uint2(0x3f003e80u, 0xbf003f80u);
-#else
-          nq.d[t] = *reinterpret_cast<const uint2*>(dm + 16 * t);
-          nq.x[t] = *reinterpret_cast<const uint2*>(xs + 16 * t);
-          nq.a[t] = *reinterpret_cast<const uint2*>(ds + 16 * t);
-#endif
-        }
-      };
-      rows_issue(0);
-#elif GRL_PREC
+#if GRL_PREC
       uint2 dq1[4], dq2[4];   // raw bf16 dM rows of the next two edges (widened when taken over)
       auto dq_issue = [&](uint2 (&q)[4], int kk) {
         const int row_in = __builtin_amdgcn_readlane(xrow, kk);
         const st_t* dm = p.x_in + ((size_t)row_in * O + r) * C + 4 * g;
 #pragma unroll
         for (int t = 0; t < 4; ++t)
-#ifdef GRL_B16_NOGATHER
-          q[t] = make_uint2(0x3f003e80u, 0xbf003f80u);
-#else
           q[t] = *reinterpret_cast<const uint2*>(dm + 16 * t);
-#endif
       };
       dq_issue(dq1, 0);
       dq_issue(dq2, min(1, nb - 1));
@@ -885,7 +641,7 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
         const int row_in = __builtin_amdgcn_readlane(xrow, kk);
         const st_t* dm = p.x_in + ((size_t)row_in * O + r) * C + 4 * g;
 #pragma unroll
-        for (int t = 0; t < 4; ++t) dvn[t] = B16_LD(dm + 16 * t);
+        for (int t = 0; t < 4; ++t) dvn[t] = ld4(dm + 16 * t);
       };
       dv_issue(0);
 #endif
@@ -894,24 +650,12 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
         const int e = eb + k;
         B16_PH(7);   // (diagnostic build) loop tail of the previous pass
         float4 dv[4];
-#if GRL_PREC && GRL_B16_ROWS
-        // take-over of the twelve rows requested by the previous pass, PINNED here (the empty asm statements are uses the compiler
-        // cannot sink): the one vmcnt wait of the pass, with nothing younger than a pass in flight
-        uint2 dq[4], xq[4], an[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          dq[t] = nq.d[t]; xq[t] = nq.x[t]; an[t] = nq.a[t];
-          asm volatile("" : "+v"(dq[t].x), "+v"(dq[t].y), "+v"(xq[t].x), "+v"(xq[t].y), "+v"(an[t].x), "+v"(an[t].y));
-        }
-#elif GRL_PREC
+#if GRL_PREC
 #pragma unroll
         for (int t = 0; t < 4; ++t) {   // taken over BEFORE the node change below (vmcnt counts in issue order)
           dv[t] = widen(dq1[t]);
           dq1[t] = dq2[t];
         }
-#elif GRL_B16_FP32_ROWS
-#pragma unroll
-        for (int t = 0; t < 4; ++t) dv[t] = dvn[t];
 #endif
         B16_PH(8);   // this edge's prefetched rows taken over (vmcnt wait)
         if (e >= node_end) {            // the edge belongs to a later node of the chunk
@@ -921,48 +665,28 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
           skip_empty_run(node + 1, m);
           node = m;
           node_end = __builtin_amdgcn_readlane(rp, m + 1);
-#if GRL_PREC && GRL_B16_ROWS
-#pragma unroll
-          for (int t = 0; t < 4; ++t) acc[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-#else
           node_begin(m);
-#endif
         }
-#if GRL_PREC && GRL_B16_ROWS
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {   // (behind the flush, which adds the OLD node's dres row)
-          aq[t] = an[t];
-          dv[t] = widen(dq[t]);
-          xv[t] = widen(xq[t]);
-        }
-        rows_issue(min(k + 1, nb - 1));
-#elif GRL_PREC
+#if GRL_PREC
         dq_issue(dq2, min(k + 2, nb - 1));
 #else
-#if !GRL_B16_FP32_ROWS
 #pragma unroll
         for (int t = 0; t < 4; ++t) dv[t] = dvn[t];
-#endif
         dv_issue(min(k + 1, nb - 1));
 #endif
         B16_PH(10);  // node change (flush, skip of empty nodes, node_begin), next gather issued
         // layer 1's weight fragments and biases, and the first 64-deep group: requested before the invariants are computed
         bf16x8 w1h[4], w1l[4];
         float4 b1q[4];
-        WF2 wf[2];
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
           w1h[nt] = *reinterpret_cast<const bf16x8*>(w.W1h + (16 * nt + r) * LD1 + 8 * g);
           GRL_LO(w1l[nt] = *reinterpret_cast<const bf16x8*>(w.W1l + (16 * nt + r) * LD1 + 8 * g);)
           b1q[nt] = *reinterpret_cast<const float4*>(w.b1s + 16 * nt + 4 * g);
         }
-#if GRL_PREC || GRL_B16_BURST
         float4 b2q[4];   // layer 2's biases (its fragments are resident in bufA)
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) b2q[nt] = *reinterpret_cast<const float4*>(w.b2s + 16 * nt + 4 * g);
-#else
-        wf_load(wf[0], w.W2h + r * LD2 + 8 * g, w.W2l + r * LD2 + 8 * g, w.b2s + 4 * g);
-#endif
         // dW1 (| db1) of the PREVIOUS pass: its operands were staged at that pass's end (zero tiles before a wave's first pass); the six
         // MFMAs run beside this pass's first GELU instead of standing alone behind an exposed LDS round trip
         RFrags<1> rf1;
@@ -1021,7 +745,7 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
           tail();
           BAR();
         };
-#elif GRL_B16_BURST
+#else
         auto layer64 = [&](int base, const bf16x8 (&ih)[2], const bf16x8 (&il)[2], auto&& epi, auto&& tail) {
           f32x4v c[4];
 #pragma unroll
@@ -1046,26 +770,8 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
           tail();
           BAR();
         };
-#else
-        // a 64-deep layer: groups base .. base + 3 (wf[base & 1] already requested); epi(nt, c) consumes tile nt one region later
-        auto layer64 = [&](int base, const bf16x8 (&ih)[2], const bf16x8 (&il)[2], auto&& epi, auto&& tail) {
-          f32x4v c[4];
-#pragma unroll
-          for (int nt = 0; nt < 4; ++nt) {
-            if (base + nt + 1 < 16)
-              wf_load(wf[(nt + 1) & 1], wptr_h(base + nt + 1), wptr_l(base + nt + 1), base + nt + 1 < 4 ? w.b2s + 16 * (nt + 1) + 4 * g : nullptr);
-            BAR();
-            const float4 bq = wf[nt & 1].bias;
-            c[nt] = wf_mma(wf[nt & 1], ih, il, f32x4v{bq.x, bq.y, bq.z, bq.w});
-            if (nt > 0) epi(nt - 1, c[nt - 1]);
-            BAR();
-          }
-          epi(3, c[3]);
-          tail();
-          BAR();
-        };
 #endif
-#if GRL_B16_BURST && !GRL_PREC
+#if !GRL_PREC
         {
           float4 g1[4];
           BAR();
@@ -1081,7 +787,7 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
           rowred_mma<1>(rf1, accB);
           BAR();
 #pragma unroll
-          for (int nt = 0; nt < 4; ++nt) B16_GELU(v4(c[nt]), g1[nt], gp1[nt]);
+          for (int nt = 0; nt < 4; ++nt) gelu_both4_pk(v4(c[nt]), g1[nt], gp1[nt]);
           split_pair(g1[0], g1[1], xh[0], xl[0]);
           split_pair(g1[2], g1[3], xh[1], xl[1]);
           BAR();
@@ -1097,10 +803,10 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
             c[nt] = mfma16(w1h[nt], ph[0], c[nt]);
             GRL_LO(c[nt] = mfma16(w1l[nt], ph[0], c[nt]);)
             GRL_LO(c[nt] = mfma16(w1h[nt], pl[0], c[nt]);)
-            if (nt > 0) B16_GELU(v4(c[nt - 1]), g1[nt - 1], gp1[nt - 1]);
+            if (nt > 0) gelu_both4_pk(v4(c[nt - 1]), g1[nt - 1], gp1[nt - 1]);
             BAR();
           }
-          B16_GELU(v4(c[3]), g1[3], gp1[3]);
+          gelu_both4_pk(v4(c[3]), g1[3], gp1[3]);
           rowred_mma<1>(rf1, accB);
           split_pair(g1[0], g1[1], xh[0], xl[0]);
           split_pair(g1[2], g1[3], xh[1], xl[1]);
@@ -1110,23 +816,23 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
         B16_PH(1);   // layer 1 (12 MFMA, GELU + derivative, split)
         {
           float4 g2[4];
-          layer64(0, xh, xl, [&](int nt, const f32x4v& c) { B16_GELU(v4(c), g2[nt], gp2[nt]); },
+          layer64(0, xh, xl, [&](int nt, const f32x4v& c) { gelu_both4_pk(v4(c), g2[nt], gp2[nt]); },
                   [&]() {
                     split_pair(g2[0], g2[1], yh[0], yl[0]);
                     split_pair(g2[2], g2[3], yh[1], yl[1]);
                   });
         }
         B16_PH(2);   // layer 2 (24 MFMA, GELU + derivative, split)
-#if GRL_PREC && !GRL_B16_ROWS
+#if GRL_PREC
         materialise();   // the node's own rows, requested at the node change, are widened here -- first use below
 #endif
         // ---- K = Wk g2: d x_src row += K * dM;  dK = dM * x_src, staged with g2 for dWk += dK^T g2 (consumed after the dZ2 groups)
         bf16x8 kh[2], kl[2];
         RFrags<2> rf;
-        layer64(4, yh, yl, [&](int nt, const f32x4v& c) { acc[nt] = f4_add(acc[nt], f4_mul(v4(c), dv[nt])); },
+        layer64(4, yh, yl, [&](int nt, const f32x4v& c) { acc[nt] = f4_add_pk(acc[nt], f4_mul_pk(v4(c), dv[nt])); },
                 [&]() {
-                  split_pair(f4_mul(dv[0], xv[0]), f4_mul(dv[1], xv[1]), kh[0], kl[0]);
-                  split_pair(f4_mul(dv[2], xv[2]), f4_mul(dv[3], xv[3]), kh[1], kl[1]);
+                  split_pair(f4_mul_pk(dv[0], xv[0]), f4_mul_pk(dv[1], xv[1]), kh[0], kl[0]);
+                  split_pair(f4_mul_pk(dv[2], xv[2]), f4_mul_pk(dv[3], xv[3]), kh[1], kl[1]);
                   stage_put<2>(st.Ah, st.Al, kh, kl, r, g);
                   stage_put<2>(st.Bh, st.Bl, yh, yl, r, g);
                   rowred_load<2>(st, lane, rf);
@@ -1138,8 +844,8 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
           float4 dz2[4];
           layer64(8, kh, kl,
                   [&](int nt, const f32x4v& c) {
-                    dz2[nt] = f4_mul(v4(c), gp2[nt]);
-                    db2[nt] = f4_add(db2[nt], dz2[nt]);
+                    dz2[nt] = f4_mul_pk(v4(c), gp2[nt]);
+                    db2[nt] = f4_add_pk(db2[nt], dz2[nt]);
                   },
                   [&]() {
                     rowred_mma<2>(rf, accK);
@@ -1156,7 +862,7 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
         bf16x8 uh[2], ul[2];
         {
           float4 dz1[4];
-          layer64(12, zh, zl, [&](int nt, const f32x4v& c) { dz1[nt] = f4_mul(v4(c), gp1[nt]); },
+          layer64(12, zh, zl, [&](int nt, const f32x4v& c) { dz1[nt] = f4_mul_pk(v4(c), gp1[nt]); },
                   [&]() {
                     rowred_mma<2>(rf, accA);
                     split_pair(dz1[0], dz1[1], uh[0], ul[0]);
@@ -1180,13 +886,8 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
 #undef BAR
       }
     }
-#if GRL_PREC && GRL_B16_ROWS
-    if (E0 < E1) { flush(node); skip_empty_run(node + 1, nn); }   // the last node with edges, then the trailing nodes without
-    else skip_empty_run(0, nn);
-#else
     flush(node);                  // the last node with edges (or node 0 of a chunk without any), then the trailing nodes without
     skip_empty_run(node + 1, nn);
-#endif
   }
 
   {   // dW1 of the wave's last pass
@@ -1265,8 +966,8 @@ extern "C" {
 #if !GRL_PREC   // launch-shape queries (host-side partitioning): the constants live here, ops.build_edge_set asks instead of copying them
 static_assert(E16_WAVES == 4, "grl_edge_fwd_slots (edge_conv.hip) counts four wave slots per workgroup");
 int grl_edge_fwd_chunk_nodes(int n_dst) {   // nodes per round-robin chunk of the forward; n_dst < 0: the grid cap in workgroups
-  if (n_dst < 0) return 256 * GRL_E16_WGS;
-  const int npw = n_dst / (4 * 256 * E16_WAVES * GRL_E16_WGS);
+  if (n_dst < 0) return 256 * E16_WGS;
+  const int npw = n_dst / (4 * 256 * E16_WAVES * E16_WGS);
   return npw < 1 ? 1 : (npw > NPW_MAX ? NPW_MAX : npw);
 }
 int grl_edge_bwd_chunk_nodes(int n_src) {
@@ -1287,19 +988,11 @@ int GRL_ENTRY(grl_edge16_launch)(int mode, const st_t* x_in, const float* pos_sr
   if (n_anchor <= 0) return 0;
   // chunks: at least ~4 per wave slot of the chip (256 CUs x 12 waves) while the graph allows it
   int npw = grl_edge_fwd_chunk_nodes(n_anchor);
-#ifdef GRL_E16_TUNE
-  static const int env_npw = getenv("GRL_E16_NPW") ? atoi(getenv("GRL_E16_NPW")) : 0;
-  if (env_npw > 0) npw = env_npw;
-#endif
   Edge16Params p{x_in, pos_src, pos_dst, rowptr, e_src, e_dst, erow, grid, W1, b1, W2, b2, Wk, n_anchor, n_edges, dim, anchor_is_dst,
                  per_edge, npw, (mode == 0 && split && n_slots >= E16_WAVES && n_slots % E16_WAVES == 0) ? split : nullptr, wimg};
   const int n_chunks = (n_anchor + npw - 1) / npw;
   int blocks = p.split ? n_slots / E16_WAVES : (n_chunks + E16_WAVES - 1) / E16_WAVES;
-  int cap = 256 * GRL_E16_WGS;
-#ifdef GRL_E16_TUNE                        // diagnostic builds: grid cap and chunk size from the environment
-  static const int env_cap = getenv("GRL_E16_BLOCKS") ? atoi(getenv("GRL_E16_BLOCKS")) : 0;
-  if (env_cap > 0) cap = env_cap;
-#endif
+  int cap = 256 * E16_WGS;
   if (blocks > cap && !p.split) blocks = cap;
   if (blocks < 1) blocks = 1;
   const size_t smem = sizeof(ChainW16);

@@ -12,22 +12,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// ---- diagnostic switches that produce WRONG RESULTS (timing knock-outs: a part of a kernel removed to see what it costs) ------------
-// They compile only together with -DGRL_DIAG, and a GRL_DIAG object exports `grl_diag_build`: geometry_rl_amd/hip.py refuses to build
-// such flags into libgrl_hip.so and refuses to load a library that exports the symbol as the product library (tools/build_variants.sh
-// builds them under _variants/, bench.py loads those only with GRL_ALLOW_DIAG_LIB=1).  One mis-set flag can no longer ship a wrong kernel.
-#if defined(GRL_KNOCK_MFMA) || defined(GRL_KNOCK_STAGE) || defined(GRL_E16_NOLDS) || defined(GRL_E16_NOGELU) || defined(GRL_E16_NOGATHER) || \
-    defined(GRL_E16_LDSONLY) || defined(GRL_E16_NOMFMA) || defined(GRL_B16_NOROWMMA) || defined(GRL_B16_NOGELU) || defined(GRL_B16_NOGATHER) || \
-    defined(GRL_MLPB_NOMFMA) || defined(GRL_MLPB_NOGELU) || defined(GRL_MLPB_NOBARRIER) || defined(GRL_M16_KNOCK) || \
-    (defined(GRL_FENCED_2W) && !(GRL_FENCED_2W))   /* only a command-line definition is visible here */
-#ifndef GRL_DIAG
-#error "timing knock-out switches produce wrong results: they need -DGRL_DIAG (and can then not be linked into the product library)"
-#endif
-#endif
-#ifdef GRL_DIAG
-extern "C" __attribute__((weak, visibility("default"))) int grl_diag_build() { return 1; }
-#endif
-
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define GRL_DEVINL __device__ __forceinline__
@@ -104,13 +88,10 @@ GRL_DEVINL void acc_to_frag(const f32x16& a, float4& f0, float4& f1, float4& f2,
 #ifndef GRL_PREC
 #define GRL_PREC 0   // (documented below, at the split-bf16 section: 1 = the plain-bf16 build of BASELINE config 5)
 #endif
-// GRL_PREC = 1 only: GELU through the logistic approximation of the normal CDF, Phi(x) ~ sigma(1.5976 x + 0.07056 x^3) (|error| <= 1.4e-4,
+// GRL_PREC = 1 only (the #if GRL_PREC branches below): GELU through the logistic approximation of the normal CDF, Phi(x) ~ sigma(1.5976 x + 0.07056 x^3) (|error| <= 1.4e-4,
 // far below the 4e-3 of a bf16 operand; the build's tolerance is 2e-2): value 5 plain + 2 transcendental
 // instructions per element instead of 12 + 2, value + derivative 10 + 2 instead of 14 + 2 -- GELU is two thirds of the vector instructions of
 // the bf16 kernels (profiles/r03_pmc_table_rope_hepi_bf16.txt).  The derivative is the exact derivative of the approximant.
-#ifndef GRL_GELU_LOGISTIC
-#define GRL_GELU_LOGISTIC GRL_PREC
-#endif
 GRL_DEVINL float gelu_logistic(float x) {
   const float w = x * fmaf(x * x, -0.07056f * 1.44269504088896f, -1.5976f * 1.44269504088896f);   // -(u log2 e)
   return x * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(w));
@@ -125,7 +106,7 @@ GRL_DEVINL void gelu_logistic_both(float x, float& g, float& gp) {
 typedef float v2f __attribute__((ext_vector_type(2)));
 GRL_DEVINL v2f fma2(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
 GRL_DEVINL v2f splat2(float a) { return v2f{a, a}; }
-// GRL_GELU_V2 (round 3, default): the same A&S 7.1.26 evaluation with fewer issue slots -- what the MFMA kernels are short of
+// The A&S 7.1.26 evaluation in the form with the fewest issue slots (round 3) -- what the MFMA kernels are short of
 // (DESIGN.md finding 22).  Per PAIR of elements, value + derivative: 4 transcendental + 4 plain + 12 packed instructions (was 4 + 6 + 15):
 //   e2 = exp2(-x^2/2 log2 e + log2(1/sqrt(2 pi))) = pdf(x)            (the 1/sqrt(2 pi) rides in the exponent: an FMA instead of a multiply)
 //   hq = (b1 t + .. + b5 t^5) e2 = erfc(|x|/sqrt 2)/2 = Phi(-|x|)      (b_i = a_i sqrt(2 pi)/2)
@@ -134,9 +115,6 @@ GRL_DEVINL v2f splat2(float a) { return v2f{a, a}; }
 // modifiers of v_fma_f32) + 8 packed (was 4 + 4 + 11).  Max |error| against erf-GELU in fp32: 4.7e-7 / 3.3e-7 (old form: 3.3e-7), derivative 3.0e-7.
 // A transcendental-free odd polynomial x P(x^2) for Phi - 1/2 was priced and dropped: 13 coefficients for 6e-7 on |x| <= 5 (26 packed-FMA
 // issue slots per pair against 17 for the rcp + exp it replaces) and a degree-25 Horner form cancels catastrophically in fp32.
-#ifndef GRL_GELU_V2
-#define GRL_GELU_V2 1
-#endif
 // Packed form of the logistic GELU (round 5, plain-bf16 build): the same operations as gelu_logistic / gelu_logistic_both on TWO elements per
 // instruction.  A lone wave issues a v_pk_mul_f32 / v_pk_fma_f32 in ~5.2 cycles (profiles/r02_valu_rates.txt) -- the cost of ONE plain
 // instruction -- so the ten plain operations per element become ten per PAIR (66 -> 43 cycles per element with the two transcendentals).
@@ -170,14 +148,14 @@ GRL_DEVINL void gelu_logistic_both_pair(v2f x, v2f& g, v2f& gp) {
 template <bool WITH_GRAD> GRL_DEVINL void gelu_pair_as(v2f x, v2f& g, v2f& gp);
 template <bool WITH_GRAD>
 GRL_DEVINL void gelu_pair(v2f x, v2f& g, v2f& gp) {
-#if GRL_GELU_LOGISTIC
+#if GRL_PREC
   if (WITH_GRAD) gelu_logistic_both_pair(x, g, gp);
   else gelu_logistic_pair(x, g);
   return;
 #endif
   gelu_pair_as<WITH_GRAD>(x, g, gp);
 }
-// the A&S 7.1.26 form in EVERY build (gelu_pair's form where GRL_GELU_LOGISTIC is off): parameter-only code such as the fiber basis must
+// the A&S 7.1.26 form in EVERY build (gelu_pair's form in the fp32 build): parameter-only code such as the fiber basis must
 // not change its numbers with the precision of the build it happens to be compiled into (gelu_exact_f / gelu_exact_grad_f below)
 template <bool WITH_GRAD>
 GRL_DEVINL void gelu_pair_as(v2f x, v2f& g, v2f& gp) {
@@ -185,7 +163,6 @@ GRL_DEVINL void gelu_pair_as(v2f x, v2f& g, v2f& gp) {
   v2f t, e;
   t.x = __builtin_amdgcn_rcpf(fmaf(fabsf(x.x), kp, 1.0f));
   t.y = __builtin_amdgcn_rcpf(fmaf(fabsf(x.y), kp, 1.0f));
-#if GRL_GELU_V2
   if (WITH_GRAD) {
     const v2f arg = fma2(x * x, splat2(-0.72134752044448170368f), splat2(-1.32574806473615910f));   // log2 pdf(x)
     e.x = __builtin_amdgcn_exp2f(arg.x);
@@ -214,32 +191,10 @@ GRL_DEVINL void gelu_pair_as(v2f x, v2f& g, v2f& gp) {
     g.x = fmaf(-fabsf(x.x), hq.x, fmaxf(x.x, 0.f));
     g.y = fmaf(-fabsf(x.y), hq.y, fmaxf(x.y, 0.f));
   }
-#else
-  const v2f arg = (x * x) * splat2(-0.72134752044448170368f);   // -x^2/2 * log2(e)
-  e.x = __builtin_amdgcn_exp2f(arg.x);
-  e.y = __builtin_amdgcn_exp2f(arg.y);
-  v2f poly = fma2(t, splat2(1.061405429f), splat2(-1.453152027f));
-  poly = fma2(poly, t, splat2(1.421413741f));
-  poly = fma2(poly, t, splat2(-0.284496736f));
-  poly = fma2(poly, t, splat2(0.254829592f));
-  const v2f q = (poly * t) * e;
-  const v2f hx = x * splat2(0.5f);
-  v2f s;
-  s.x = fabsf(hx.x);
-  s.y = fabsf(hx.y);
-  g = fma2(-s, q, s + hx);
-  if (WITH_GRAD) {
-    v2f cs;
-    cs.x = copysignf(0.5f, x.x);
-    cs.y = copysignf(0.5f, x.y);
-    const v2f cdf = fma2(-cs, q, cs + splat2(0.5f));
-    gp = fma2(x * e, splat2(0.39894228040143267794f), cdf);
-  }
-#endif
 }
 // value only, scalar form (plain f32 instructions; 12 + 2 transcendental per element): for forward kernels built without packed math
 GRL_DEVINL float gelu_val(float x) {
-#if GRL_GELU_LOGISTIC
+#if GRL_PREC
   return gelu_logistic(x);
 #endif
   const float t = __builtin_amdgcn_rcpf(fmaf(fabsf(x), 0.3275911f * 0.70710678118654752440f, 1.0f));
@@ -266,7 +221,7 @@ GRL_DEVINL float4 gelu4(float4 x) {
 // wave (packed f32 operations do not overlap with the matrix pipe: MI355X_MICROARCH.md cycle constants; DESIGN.md finding 23)
 GRL_DEVINL void gelu_both_as(float x, float& g, float& gp);
 GRL_DEVINL void gelu_both(float x, float& g, float& gp) {
-#if GRL_GELU_LOGISTIC
+#if GRL_PREC
   gelu_logistic_both(x, g, gp);
   return;
 #endif
@@ -274,7 +229,6 @@ GRL_DEVINL void gelu_both(float x, float& g, float& gp) {
 }
 GRL_DEVINL void gelu_both_as(float x, float& g, float& gp) {   // (the A&S form in every build: see gelu_pair_as)
   const float t = __builtin_amdgcn_rcpf(fmaf(fabsf(x), 0.3275911f * 0.70710678118654752440f, 1.0f));
-#if GRL_GELU_V2
   const float e = __builtin_amdgcn_exp2f(fmaf(x * x, -0.72134752044448170368f, -1.32574806473615910f));   // pdf(x)
   float poly = fmaf(t, 1.33027442959f, -1.82125597911f);
   poly = fmaf(poly, t, 1.78147793657f);
@@ -284,18 +238,6 @@ GRL_DEVINL void gelu_both_as(float x, float& g, float& gp) {   // (the A&S form 
   const float cdf = copysignf(0.5f - hq, x) + 0.5f;
   g = x * cdf;
   gp = fmaf(x, e, cdf);
-#else
-  const float e = __builtin_amdgcn_exp2f((x * -0.72134752044448170368f) * x);   // exp(-x^2/2)
-  float poly = fmaf(t, 1.061405429f, -1.453152027f);
-  poly = fmaf(poly, t, 1.421413741f);
-  poly = fmaf(poly, t, -0.284496736f);
-  poly = fmaf(poly, t, 0.254829592f);
-  const float q = (poly * t) * e;                       // erfc(|x| / sqrt 2)
-  const float cs = copysignf(0.5f, x);
-  const float cdf = fmaf(-cs, q, cs + 0.5f);            // 1/2 + sign(x)/2 (1 - q)
-  g = x * cdf;
-  gp = fmaf(x * e, 0.39894228040143267794f, cdf);
-#endif
 }
 GRL_DEVINL void gelu_both4(float4 x, float4& g, float4& gp) {
   gelu_both(x.x, g.x, gp.x);
@@ -339,19 +281,18 @@ GRL_DEVINL float4 load_nt4(const float* p) {
 GRL_DEVINL void store_nt4(float* p, const float4& v) {
   __builtin_nontemporal_store(f32x4n{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4n*>(p));
 }
-#if (GRL_PREC || (defined(GRL_B16_BURST) && GRL_B16_BURST)) && defined(GRL_PK_F4)   // plain-bf16 build of a file that asks for it: element-wise products and sums as packed pairs (see gelu_logistic_pair)
-GRL_DEVINL float4 f4_mul(float4 a, float4 b) {
+GRL_DEVINL float4 f4_mul(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
+GRL_DEVINL float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+// the same as packed pairs (v_pk_mul_f32 / v_pk_add_f32; see gelu_logistic_pair): for kernels whose element-wise work does not run
+// beside their own MFMAs (edge_conv16.hip)
+GRL_DEVINL float4 f4_mul_pk(float4 a, float4 b) {
   const v2f lo = v2f{a.x, a.y} * v2f{b.x, b.y}, hi = v2f{a.z, a.w} * v2f{b.z, b.w};
   return make_float4(lo.x, lo.y, hi.x, hi.y);
 }
-GRL_DEVINL float4 f4_add(float4 a, float4 b) {
+GRL_DEVINL float4 f4_add_pk(float4 a, float4 b) {
   const v2f lo = v2f{a.x, a.y} + v2f{b.x, b.y}, hi = v2f{a.z, a.w} + v2f{b.z, b.w};
   return make_float4(lo.x, lo.y, hi.x, hi.y);
 }
-#else
-GRL_DEVINL float4 f4_mul(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-GRL_DEVINL float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-#endif
 GRL_DEVINL float4 f4_scale(float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
 
 // copy a row-major [rows][K] fp32 matrix from global into an LDS image with leading dim ld (pads untouched)
@@ -396,9 +337,6 @@ void grl_prof_end_replay(hipStream_t stream);
 // 1 = plain bf16 products (ONE MFMA per product, operands rounded to nearest bf16, fp32 accumulation) -- the reduced-precision
 // variant of BASELINE config 5 (rope_shaping_hepi_trpl, bf16): the same kernels compiled a second time with -DGRL_PREC=1 and the
 // entry points suffixed _bf16.  In that build the "lo" halves below are never formed and every lo product is dropped.
-#ifndef GRL_PREC
-#define GRL_PREC 0
-#endif
 #if GRL_PREC
 #define GRL_LO(...)
 #define GRL_ENTRY(name) name##_bf16
@@ -410,11 +348,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 GRL_DEVINL f32x16 mfma_bf(bf16x8 a, bf16x8 b, f32x16 c) {
-#ifdef GRL_KNOCK_MFMA   // timing knock-out (diagnostic builds of one file; results are wrong)
-  return c;
-#else
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-#endif
 }
 
 GRL_DEVINL unsigned pack_hi(float a, float b) {  // upper halves of a (low word) and b (high word)
@@ -565,39 +499,14 @@ GRL_DEVINL void stage_split_T(unsigned short* hi, unsigned short* lo, const floa
 
 // acc(32 n x 32 r) += W[n0+i][0..K) . X[r][0..K)   with split operands.
 //   whi/wlo = &image[(n0 + (lane&31)) * ld + 8*(lane>>5)]
-template <int K>
-GRL_DEVINL void mma_wx_bf(const unsigned short* whi, const unsigned short* wlo, const bf16x8 (&xh)[K / 16], const bf16x8 (&xl)[K / 16],
-                          f32x16& acc) {
-#pragma unroll
-  for (int s = 0; s < K / 16; ++s) {
-    const bf16x8 wh = *reinterpret_cast<const bf16x8*>(whi + 16 * s);
-    GRL_LO(const bf16x8 wl = *reinterpret_cast<const bf16x8*>(wlo + 16 * s);)
-    acc = mfma_bf(wh, xh[s], acc);
-    GRL_LO(acc = mfma_bf(wl, xh[s], acc);)
-    GRL_LO(acc = mfma_bf(wh, xl[s], acc);)
-  }
-}
-
-// Fenced form for kernels that run two waves per SIMD.  Measured on gfx950 (tools/det_check_all.py, tools/variant_check.sh):
-// when LDS operand loads are interleaved with the MFMAs of a dependent chain (the form above) and a second wave shares the SIMD,
+// Fenced form for kernels that run two waves per SIMD.  Measured on gfx950 (tools/det_check_all.py, docs/history/tools/variant_check.sh):
+// when LDS operand loads are interleaved with the MFMAs of a dependent chain and a second wave shares the SIMD,
 // a few 1e-4 of the tiles come out wrong, different ones on every run -- a later load lands in a register that an earlier,
 // still queued MFMA has not read yet (the register allocator reuses dead operand registers; with one wave per SIMD the queue
 // never gets deep enough).  The cure is structural: load EVERY operand fragment of the group first, then issue the MFMAs, then
 // run an epilogue that reads the accumulator (it cannot start before the group has finished), and only then let the next loads go.
-// GRL_MFMA_PRIO (build switch, off): the wave raises its issue priority for the duration of an MFMA group, so that a SIMD
-// partner's VALU stream cannot delay the issue of this wave's dependent MFMAs (MI355X_MICROARCH.md "Two waves per SIMD", items 2
-// and 4).  Measured round 2 (tools/run_variants.sh, one box, two alternating rounds): 237-245 steps/s against 239-240 without --
-// inside the box-internal noise for every kernel; left off.
-#ifndef GRL_MFMA_PRIO
-#define GRL_MFMA_PRIO 0
-#endif
-#if GRL_MFMA_PRIO
-#define GRL_PRIO_HI() __builtin_amdgcn_s_setprio(1)
-#define GRL_PRIO_LO() __builtin_amdgcn_s_setprio(0)
-#else
-#define GRL_PRIO_HI()
-#define GRL_PRIO_LO()
-#endif
+// The group runs at normal issue priority: s_setprio(1) around it measured inside the box-internal noise (round 2: 237-245 steps/s
+// against 239-240 without).
 template <int K>
 struct WFrags { bf16x8 h[K / 16], l[K / 16]; };
 template <int K>
@@ -608,149 +517,20 @@ GRL_DEVINL void load_wfrags(WFrags<K>& w, const unsigned short* whi, const unsig
     GRL_LO(w.l[s] = *reinterpret_cast<const bf16x8*>(wlo + 16 * s);)
   }
 }
-// a real VALU read of the accumulator: everything after it is ordered behind the completion of the MFMA group that produced acc
-GRL_DEVINL void acc_fence(const f32x16& acc, float& sink) {
-  sink += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, acc[0]), 0xE4, 0xF, 0xF, false));
-}
+// acc(32 n x 32 r) += W[n0+i][0..K) . X[r][0..K) with split operands, then epilogue(acc);
+//   whi/wlo = &image[(n0 + (lane&31)) * ld + 8*(lane>>5)]
 template <int K, class Epi>
 GRL_DEVINL void mma_wx_bf_fenced(const unsigned short* whi, const unsigned short* wlo, const bf16x8 (&xh)[K / 16],
                                  const bf16x8 (&xl)[K / 16], f32x16 acc, Epi&& epilogue) {
   WFrags<K> w;
   load_wfrags<K>(w, whi, wlo);
   __builtin_amdgcn_sched_barrier(0);
-  GRL_PRIO_HI();
 #pragma unroll
   for (int s = 0; s < K / 16; ++s) {
     acc = mfma_bf(w.h[s], xh[s], acc);
     GRL_LO(acc = mfma_bf(w.l[s], xh[s], acc);)
     GRL_LO(acc = mfma_bf(w.h[s], xl[s], acc);)
   }
-  GRL_PRIO_LO();
   epilogue(acc);
   __builtin_amdgcn_sched_barrier(0);
-}
-// Pipelined form of the fenced group: the weight fragments of THIS group were loaded by the previous call (``cur``); the fragments
-// of the NEXT group (``nhi`` / ``nlo``, K_NEXT deep) are requested right after a real read of the finished accumulator -- no MFMA
-// is in flight any more (the hazard the fence exists for) -- and land while the epilogue (activation, splits) runs, instead of
-// exposing their LDS latency in front of the next group.
-template <int K, int K_NEXT, class Epi>
-GRL_DEVINL void mma_wx_bf_piped(const WFrags<K>& cur, const bf16x8 (&xh)[K / 16], const bf16x8 (&xl)[K / 16], f32x16 acc,
-                                WFrags<K_NEXT>* next, const unsigned short* nhi, const unsigned short* nlo, float& sink,
-                                Epi&& epilogue) {
-  __builtin_amdgcn_sched_barrier(0);
-  GRL_PRIO_HI();
-#pragma unroll
-  for (int s = 0; s < K / 16; ++s) {
-    acc = mfma_bf(cur.h[s], xh[s], acc);
-    GRL_LO(acc = mfma_bf(cur.l[s], xh[s], acc);)
-    GRL_LO(acc = mfma_bf(cur.h[s], xl[s], acc);)
-  }
-  GRL_PRIO_LO();
-  acc_fence(acc, sink);
-  __builtin_amdgcn_sched_barrier(0);
-  if (next) load_wfrags<K_NEXT>(*next, nhi, nlo);
-  epilogue(acc);
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// ---- register-level transposes on the matrix pipe -------------------------------------------------------------------------
-// X (32 rows x 32 columns) given as split-bf16 A operands (lane = row) times a 0/1 selection matrix gives X back in the
-// ACCUMULATOR layout, i.e. with the column on the lane and the rows in the registers (acc row order == bf16 k-order): exactly the
-// operand layout a product that sums over X's rows needs.  Two MFMAs per 32x32 tile and per hi/lo part, no LDS, exact (x * 1.0).
-//   sel0 / sel1: lane (j = l&31, h = l>>5), element jj = 1.0 iff 8*(jj>>2) + 4h + (jj&3) == j (for j < 16) resp. j - 16 (j >= 16)
-GRL_DEVINL void make_selectors(bf16x8& sel0, bf16x8& sel1) {
-  const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
-  u32x4 s0, s1;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    unsigned v0 = 0, v1 = 0;
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int jj = 2 * w + e;
-      const int kappa = 8 * (jj >> 2) + 4 * h + (jj & 3);
-      if (j < 16 && kappa == j) v0 |= 0x3F80u << (16 * e);
-      if (j >= 16 && kappa == j - 16) v1 |= 0x3F80u << (16 * e);
-    }
-    s0[w] = v0;
-    s1[w] = v1;
-  }
-  sel0 = __builtin_bit_cast(bf16x8, s0);
-  sel1 = __builtin_bit_cast(bf16x8, s1);
-}
-// columns 0..15 come from operand c0, columns 16..31 from operand c1 (two consecutive K-step fragments of the row-major tile)
-GRL_DEVINL f32x16 transpose32(const bf16x8& c0, const bf16x8& c1, const bf16x8& sel0, const bf16x8& sel1) {
-  f32x16 t = zero16();
-  t = mfma_bf(c0, sel0, t);
-  t = mfma_bf(c1, sel1, t);
-  return t;
-}
-// accumulator tile holding bf16-exact values -> the two K-step operand fragments (rows 0..15 / 16..31 of the reduction)
-GRL_DEVINL void acc_to_bf(const f32x16& t, bf16x8& k0, bf16x8& k1) {
-  u32x4 a, b;
-  a[0] = pack_hi(t[0], t[1]); a[1] = pack_hi(t[2], t[3]); a[2] = pack_hi(t[4], t[5]); a[3] = pack_hi(t[6], t[7]);
-  b[0] = pack_hi(t[8], t[9]); b[1] = pack_hi(t[10], t[11]); b[2] = pack_hi(t[12], t[13]); b[3] = pack_hi(t[14], t[15]);
-  k0 = __builtin_bit_cast(bf16x8, a);
-  k1 = __builtin_bit_cast(bf16x8, b);
-}
-
-// A 32-column tile of a row-major activation block (rows on the lanes), transposed and split: lane = column, K-steps 0/1 =
-// rows 0..15 / 16..31 (accumulator row order), hi and lo bf16 parts.  Built from the tile's two 16-column fragment pairs.
-struct TTile { bf16x8 h0, h1, l0, l1; };
-GRL_DEVINL TTile transpose_split(const bf16x8& ch0, const bf16x8& ch1, const bf16x8& cl0, const bf16x8& cl1, const bf16x8& sel0,
-                                 const bf16x8& sel1, float* colsum = nullptr) {
-  TTile t;
-  const f32x16 th = transpose32(ch0, ch1, sel0, sel1);
-#if GRL_PREC
-  if (colsum) {
-    float sacc = 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) sacc += th[q];
-    *colsum += sacc;
-  }
-  acc_to_bf(th, t.h0, t.h1);
-  t.l0 = t.h0; t.l1 = t.h1;   // placeholders, never used
-#else
-  const f32x16 tl = transpose32(cl0, cl1, sel0, sel1);
-  if (colsum) {  // sum over this lane's 16 rows of (hi + lo) = the column sum restricted to them; the other 16 rows: lane ^ 32
-    float sacc = 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) sacc += th[q] + tl[q];
-    *colsum += sacc;
-  }
-  acc_to_bf(th, t.h0, t.h1);
-  acc_to_bf(tl, t.l0, t.l1);
-#endif
-  return t;
-}
-// acc[m][n] += sum over the 32 rows r of P[r][m] Q[r][n]  (both operands transposed-split; split-bf16, 6 MFMAs)
-GRL_DEVINL void mma_tn_bf(const TTile& p, const TTile& q, f32x16& acc) {
-  acc = mfma_bf(p.h0, q.h0, acc); GRL_LO(acc = mfma_bf(p.l0, q.h0, acc); acc = mfma_bf(p.h0, q.l0, acc);)
-  acc = mfma_bf(p.h1, q.h1, acc); GRL_LO(acc = mfma_bf(p.l1, q.h1, acc); acc = mfma_bf(p.h1, q.l1, acc);)
-}
-// The same for accumulators that live for a whole launch (weight gradients).  hipcc (ROCm 7.2) splits the live ranges of such
-// loop-carried 16-register tuples and pays for it with AGPR-to-AGPR copies in front of the MFMA groups and at the loop header
-// (256 v_accvgpr_mov per pass of edge_conv_bwd_w: 13 % of its vector issue slots).  With the accumulator tied as a read-write AGPR
-// operand of an asm MFMA there is nothing to copy at the instruction: it is updated in place.  Measured round 2: the register
-// allocator then places the same number of copies elsewhere (288 instead of 256 v_accvgpr_mov per pass) and the launch time does
-// not move (1.20 vs 1.19 ms per step): GRL_ASM_ACC stays 0 (builtin form); the switch is kept for compiler upgrades.
-// The asm is opaque to the compiler's hazard recognizer: the s_nop covers a VALU-written operand, and whoever reads such an
-// accumulator with VALU code later must let the last MFMA drain first (asm_acc_drain()).
-#ifndef GRL_ASM_ACC
-#define GRL_ASM_ACC 0
-#endif
-GRL_DEVINL void mfma_acc(const bf16x8& a, const bf16x8& b, f32x16& c) {
-#if GRL_ASM_ACC
-  asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-#else
-  c = mfma_bf(a, b, c);
-#endif
-}
-GRL_DEVINL void asm_acc_drain() {
-#if GRL_ASM_ACC
-  asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // 32 wait states > the 18 an MFMA result needs before a VALU read
-#endif
-}
-GRL_DEVINL void mma_tn_bf_acc(const TTile& p, const TTile& q, f32x16& acc) {
-  mfma_acc(p.h0, q.h0, acc); GRL_LO(mfma_acc(p.l0, q.h0, acc); mfma_acc(p.h0, q.l0, acc);)
-  mfma_acc(p.h1, q.h1, acc); GRL_LO(mfma_acc(p.l1, q.h1, acc); mfma_acc(p.h1, q.l1, acc);)
 }

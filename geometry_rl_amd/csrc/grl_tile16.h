@@ -68,16 +68,9 @@ GRL_DEVINL void stage_put(unsigned short* ih, unsigned short* il, const bf16x8 (
 // the node-MLP backward's 828 per chunk: a lone wave pays ~5 cycles for each).  What it covered -- an operand register written by a VALU
 // instruction less than two wait states before the MFMA reads it (the compiler inserts those wait states for builtin MFMAs; asm is opaque
 // to its hazard recognizer) -- is now CHECKED on the generated ISA at build time instead: tools/isa_acc_lint.py (tests/test_isa_lint.py)
-// fails on any vector write to a source register of an asm MFMA inside that window.  -DGRL_MFMA_ASM_NOP=1 restores the nop.
-#ifndef GRL_MFMA_ASM_NOP
-#define GRL_MFMA_ASM_NOP 0
-#endif
+// fails on any vector write to a source register of an asm MFMA inside that window.
 GRL_DEVINL void mfma32_acc(const bf16x8& a, const bf16x8& b, f32x16& c) {
-#if GRL_MFMA_ASM_NOP
-  asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-#else
   asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
-#endif
 }
 // Before the accumulators are read with vector instructions at the end of a launch the last asm MFMA must have drained (an MFMA result
 // needs 18 wait states before a VALU read, invisible to the compiler for asm MFMAs).  Every tile is re-defined by an (empty, volatile) asm statement behind the drain, so no v_accvgpr_read of a tile can be scheduled above it (with a bare memory clobber the compiler hoisted reads

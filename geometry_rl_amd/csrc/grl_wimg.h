@@ -11,11 +11,9 @@
 #include "grl_common.h"
 
 // ---- 16-row edge chain (edge_conv16.hip): k-order inside a 32-block: position 8 g + j <-> feature 16 (j >> 2) + 4 g + (j & 3)
-#ifndef GRL_LD1
-#define GRL_LD1 40
-#endif
-constexpr int WI_LD1 = GRL_LD1;  // bf16 elements per image row, layer 1 (K = 14 padded to one 32-deep step): 40 (80-B rows) is 2-way conflicted for
-                                 // the ds_read_b128 lane groups, 48 (96-B rows) conflict-free (tools: the bank model of MI355X_MICROARCH.md)
+constexpr int WI_LD1 = 40;       // bf16 elements per image row, layer 1 (K = 14 padded to one 32-deep step): 40 (80-B rows) is 2-way conflicted for
+                                 // the ds_read_b128 lane groups, 48 (96-B rows) conflict-free (the bank model of MI355X_MICROARCH.md) but
+                                 // no faster: the forward is bound by issue slots (docs/history/profiles/r03_edge16_fwd_lds_conflicts.txt)
 constexpr int WI_LD2 = 64 + 16;  // layers 2 and 3: 160-B rows put the 16 lanes of every ds_read_b128 group on disjoint banks (72: 2-way)
 struct ChainW16 {
   unsigned short W1h[64 * WI_LD1], W1l[64 * WI_LD1];

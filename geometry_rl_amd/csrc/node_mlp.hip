@@ -3,27 +3,13 @@
 // Rows are (node, orientation) pairs; each wave owns 32 rows (2 nodes) per step and keeps the whole chain in registers
 // (see grl_common.h): LayerNorm by lane-pair shuffles, W3/W4 staged once per workgroup in LDS as MFMA A operands.
 //
-// Backward: ONE fused launch (node_mlp_bwd_fused_kernel below): dx2 and all six parameter gradients, nothing handed over through HBM.
-#ifdef GRL_MLPB_NOMFMA
-#define GRL_KNOCK_MFMA
-#endif
+// Backward: ONE fused launch on 16-row chunks (node_mlp16.hip): dx2 and all six parameter gradients, nothing handed over through HBM.
 #include "grl_common.h"
 #include "grl_wimg.h"
 #include <stdlib.h>
-#ifdef GRL_MLPB_NOBARRIER   // timing knock-out: the chunk loop of the fused backward without its barriers (results are wrong)
-#define MLPB_SYNC()
-#else
-#define MLPB_SYNC() __syncthreads()
-#endif
 
 namespace {
 
-#ifndef GRL_MLP_NT
-#define GRL_MLP_NT 1
-#endif
-#ifndef GRL_MLPF_PIPE
-#define GRL_MLPF_PIPE 1
-#endif
 constexpr int C = 64, O = 16, W = 256;
 constexpr float LN_EPS = 1e-5f;
 // split-bf16 weight images for the forward kernel: struct MlpSmemBf (grl_wimg.h, shared with the image producer)
@@ -72,10 +58,8 @@ __global__ __launch_bounds__(512) void node_mlp_fwd_kernel(const st_t* __restric
   if (wimg) {   // the whole struct, built once per forward pass by grl_weight_images (kind 2): a linear copy
     copy_image<512>(&s, wimg, (int)sizeof(MlpSmemBf));
   } else {
-#ifndef GRL_KNOCK_STAGE   // (timing knock-out: no weight staging; results are wrong)
     stage_split<W, C, C, 512>(s.W3h, s.W3l, W3, LB3);
     stage_split<C, W, W, 512>(s.W4h, s.W4l, W4, LB4);
-#endif
     for (int i = threadIdx.x; i < W; i += blockDim.x) s.b3s[i] = b3[i];
     for (int i = threadIdx.x; i < C; i += blockDim.x) { s.b4s[i] = b4[i]; s.gam[i] = gam[i]; s.bet[i] = bet[i]; }
   }
@@ -138,7 +122,6 @@ __global__ __launch_bounds__(512) void node_mlp_fwd_kernel(const st_t* __restric
     bf16x8 ah[4], al[4];
     split_frags<64>(a, ah, al);
     f32x16 o0 = bias_acc(s.b4s, 0, h), o1 = bias_acc(s.b4s, 32, h);
-#if GRL_MLPF_PIPE
     // Software pipeline over the eight 32-unit hidden tiles (round 2, DESIGN.md findings 18 / 20): one scheduling region holds the
     // GELU + split of tile nt (vector work), the z chain of tile nt + 1 and the two output chains of tile nt - 1 (24 MFMAs) -- three
     // independent streams of the SAME wave; every weight fragment is requested one region before its MFMAs, none between the MFMAs
@@ -221,21 +204,6 @@ __global__ __launch_bounds__(512) void node_mlp_fwd_kernel(const st_t* __restric
       GRL_LO(o0 = mfma_bf(f4.h[0][u], pl[u], o0);)
       GRL_LO(o1 = mfma_bf(f4.h[1][u], pl[u], o1);)
     }
-#else
-#pragma unroll 1
-    for (int nt = 0; nt < 8; ++nt) {
-      f32x16 acc = bias_acc(s.b3s, 32 * nt, h);
-      mma_wx_bf<64>(s.W3h + (32 * nt + r) * LB3 + 8 * h, s.W3l + (32 * nt + r) * LB3 + 8 * h, ah, al, acc);
-      float4 hq[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        hq[q] = gelu4(make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]));
-      bf16x8 hh[2], hl[2];
-      split_frags<32>(hq, hh, hl);
-      mma_wx_bf<32>(s.W4h + r * LB4 + 32 * nt + 8 * h, s.W4l + r * LB4 + 32 * nt + 8 * h, hh, hl, o0);
-      mma_wx_bf<32>(s.W4h + (32 + r) * LB4 + 32 * nt + 8 * h, s.W4l + (32 + r) * LB4 + 32 * nt + 8 * h, hh, hl, o1);
-    }
-#endif
     float4 res[8], y[8];
 #if GRL_PREC
 #pragma unroll
@@ -257,420 +225,9 @@ __global__ __launch_bounds__(512) void node_mlp_fwd_kernel(const st_t* __restric
   if (sink == 123456.789f) st1(out, sink);   // keeps the fences alive; never true
 }
 
-#ifdef GRL_MLP_PHASE_PROF
-__device__ unsigned long long g_phase[2][16];
-#define PH(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (lane == 0 && (wave == 0 || wave == 5)) ph[i] += t_ - tlast; tlast = t_; } while (0)
-#else
-#define PH(i)
-#endif
 // partial slab per workgroup: [dW3 256x64 | db3 256 | dW4 64x256 | db4 64 | dgamma 64 | dbeta 64]
 constexpr int MLP_PARTIAL = W * C + W + C * W + C + C + C;
 
-// ------------------------------------------------------------------------------------------------ backward, fused
-// ONE launch, nothing handed over through HBM.  A workgroup of 8 waves (two per SIMD, <= 256 registers, no spills) walks 32-row
-// chunks; wave w owns hidden tile w (32 of the 256 hidden units):
-//   1. all 512 threads: load x2 / dOut (one float4 per thread, prefetched a chunk ahead), LayerNorm by 16-lane reductions, write
-//      a = LN(x2) and dOut as split-bf16 fragment images to LDS; per-thread column sums for db4
-//   2. the four shared 32-column tiles (a | dOut) are transposed in registers (transpose32; hi parts by waves 0-3, lo parts by
-//      waves 4-7) -> LDS
-//   3. every wave, its hidden tile: z^T, dH^T with the hidden unit on the lane (activation on the A side: the layout the row
-//      reductions need, no transpose); dZ = dH * gelu'(z); dW3 += dZ^T a, dW4 += dOut^T h (split-bf16, accumulators in registers
-//      for the whole launch); dZ back to row layout (one register transpose) and dA^T += W3^T dZ with the W3 tile transposed in
-//      registers; partial dA rows to LDS in two rounds (waves 0-3 write, waves 4-7 add)
-//   4. all threads: sum the four partial dA rows, LayerNorm backward (16-lane reductions), store dx2; per-thread column sums for
-//      dgamma / dbeta.
-// W4^T fragments live in LDS, W3 fragments in the workgroup's own (still unused) partial slab, i.e. L2-resident global memory.
-// Two waves share every SIMD, so each MFMA group is fenced (grl_common.h, mma_wx_bf_fenced): all operand loads first, then the
-// MFMAs, then a VALU read of the accumulator before the next loads may go; the two K-halves of z and dH are separate groups to
-// halve the operand registers live at a time.
-// partial slab per workgroup: [dW3 256x64 | db3 256 | dW4 64x256 | db4 64 | dgamma 64 | dbeta 64]  (MLP_PARTIAL)
-constexpr int LDF = GRL_LDB(64);  // 72 bf16: activation fragment images (same layout as the weight images)
-constexpr int LDD = C + 4;        // 68 fp32: partial dA rows
-
-// sum over the 16 consecutive lanes that share a row.  GRL_ROW_DPP (round 3, default): four DPP adds on the vector pipe (quad_perm xor 1,
-// xor 2, row_half_mirror, row_mirror) instead of four dependent ds_bpermute round trips through the LDS (~4 x 100 cycles of latency
-// in front of every LayerNorm statistic, twice per stage, with all eight waves phase-locked in that stage).
-#ifndef GRL_ROW_DPP
-#define GRL_ROW_DPP 1
-#endif
-template <int CTRL>
-GRL_DEVINL float dpp_read(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-GRL_DEVINL float row16_sum(float v) {
-#if GRL_ROW_DPP
-  v += dpp_read<0xB1>(v);    // quad_perm [1,0,3,2]
-  v += dpp_read<0x4E>(v);    // quad_perm [2,3,0,1]
-  v += dpp_read<0x141>(v);   // row_half_mirror: the other quad of the 8-lane half
-  v += dpp_read<0x140>(v);   // row_mirror: the other half of the 16-lane row
-#else
-  v += __shfl_xor(v, 1, 64);
-  v += __shfl_xor(v, 2, 64);
-  v += __shfl_xor(v, 4, 64);
-  v += __shfl_xor(v, 8, 64);
-#endif
-  return v;
-}
-GRL_DEVINL void put_split4(unsigned short* hi, unsigned short* lo, const float4& v) {  // 4 consecutive image positions
-  uint2 hv, lv;
-  hv.x = pack_hi(v.x, v.y); hv.y = pack_hi(v.z, v.w);
-  lv.x = pack_rn(v.x - trunc_bf16(v.x), v.y - trunc_bf16(v.y));
-  lv.y = pack_rn(v.z - trunc_bf16(v.z), v.w - trunc_bf16(v.w));
-  *reinterpret_cast<uint2*>(hi) = hv;
-  *reinterpret_cast<uint2*>(lo) = lv;
-}
-GRL_DEVINL TTile load_ttile(const u32x4 (*tt)[64], int lane) {
-  TTile t;
-  t.h0 = __builtin_bit_cast(bf16x8, tt[0][lane]);
-  t.h1 = __builtin_bit_cast(bf16x8, tt[1][lane]);
-  t.l0 = __builtin_bit_cast(bf16x8, tt[2][lane]);
-  t.l1 = __builtin_bit_cast(bf16x8, tt[3][lane]);
-  return t;
-}
-
-struct MlpBwdSmem {
-  unsigned short Ah[32 * LDF], Al[32 * LDF];
-  unsigned short Dh[32 * LDF], Dl[32 * LDF];
-  u32x4 TT[4][4][64];
-  float DA[4][32 * LDD];      // dA partial rows: waves 0-3 write, waves 4-7 add (second round); reused for the final column sums
-  u32x4 W4F[8][4][2][64];
-};
-// W3 as split-bf16 B-operand fragments of the eight hidden tiles: slab[(tile * 8 + 2 * sidx + part) * 64 + lane], part 0 = hi, 1 = lo
-__global__ __launch_bounds__(512) void mlp_w3_frags_kernel(const float* __restrict__ W3, u32x4* __restrict__ slab) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
-  const float* wrow = W3 + (size_t)(32 * wave + r) * C;
-  u32x4* w3f = slab + (size_t)wave * 4 * 2 * 64;
-#pragma unroll
-  for (int sidx = 0; sidx < 4; ++sidx) {
-    bf16x8 gh, gl;
-    split_pair(*reinterpret_cast<const float4*>(wrow + 16 * sidx + 4 * h), *reinterpret_cast<const float4*>(wrow + 16 * sidx + 8 + 4 * h), gh, gl);
-    w3f[(sidx * 2 + 0) * 64 + lane] = __builtin_bit_cast(u32x4, gh);
-    w3f[(sidx * 2 + 1) * 64 + lane] = __builtin_bit_cast(u32x4, gl);
-  }
-}
-
-__global__ __launch_bounds__(512) void node_mlp_bwd_fused_kernel(const st_t* __restrict__ x2, const st_t* __restrict__ dout,
-                                                                  const float* __restrict__ W3, const float* __restrict__ b3,
-                                                                  const float* __restrict__ W4, const float* __restrict__ gam,
-                                                                  const float* __restrict__ bet, st_t* __restrict__ dx2,
-                                                                  float* __restrict__ partial, const u32x4* __restrict__ w3_shared,
-                                                                  int n_rows) {
-  extern __shared__ __attribute__((aligned(16))) float smem_raw[];
-  MlpBwdSmem& s = *reinterpret_cast<MlpBwdSmem*>(smem_raw);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-  const int cq = tid & 15, lrow = tid >> 4;   // cooperative stages: thread = (row of the chunk, column quad)
-  const int kq = cq & 3, pq = (kq == 1) ? 2 : (kq == 2) ? 1 : kq;
-  const int ppos = 16 * (cq >> 2) + 4 * pq;
-  const float4 gq = *reinterpret_cast<const float4*>(gam + 4 * cq), bq = *reinterpret_cast<const float4*>(bet + 4 * cq);
-  bf16x8 sel0, sel1;
-  make_selectors(sel0, sel1);
-  float sink = 0.f;
-
-  // this wave's hidden tile (lane = hidden unit j): W4^T fragments -> LDS; the W3 fragments come from ONE image shared by all
-  // workgroups (mlp_w3_frags_kernel, 64 KB: resident in every XCD's L2 -- a private 64 KB slab per workgroup, 16 MB in all, missed
-  // L2 on ~20 % of its re-reads and tripled the launch's fabric traffic: VERDICT r1 item 5, profiles/r02_pmc_table_v3 vs _v4)
-  const u32x4* w3f = w3_shared + (size_t)wave * 4 * 2 * 64;
-  const int j = 32 * wave + r;
-  const float b3v = b3[j];
-  {
-#pragma unroll
-    for (int sidx = 0; sidx < 4; ++sidx) {
-      const float* c0 = W4 + (size_t)(16 * sidx + 4 * h) * W + j, *c1 = c0 + (size_t)8 * W;
-      bf16x8 fh, fl;
-      split_pair(make_float4(c0[0], c0[W], c0[2 * W], c0[3 * W]), make_float4(c1[0], c1[W], c1[2 * W], c1[3 * W]), fh, fl);
-      s.W4F[wave][sidx][0][lane] = __builtin_bit_cast(u32x4, fh);
-      s.W4F[wave][sidx][1][lane] = __builtin_bit_cast(u32x4, fl);
-    }
-  }
-  f32x16 aW3[2], aW4[2];
-  aW3[0] = zero16(); aW3[1] = zero16(); aW4[0] = zero16(); aW4[1] = zero16();
-  float adb3 = 0.f;
-  float4 dgam = make_float4(0.f, 0.f, 0.f, 0.f), dbet = dgam, db4 = dgam;
-
-  const int n_chunks = (n_rows + 31) >> 5;
-  float4 px, pd;
-  auto fetch = [&](int c) {
-    const int row = c * 32 + lrow;
-    const bool ok = row < n_rows;
-    const size_t g = (size_t)(ok ? row : 0) * C + 4 * cq;
-#if GRL_MLP_NT   // streamed once: keep these lines from displacing the workgroup's W3 fragment slab in L2 (profiles/r01_pmc_table_v12:
-                 // the launch fetched 2.9x its algorithmic bytes from the fabric; with nt loads 2.4x: profiles/r02_node_mlp_bwd_nt_fetch.txt)
-    px = ld4_nt(x2 + g);
-    pd = ld4_nt(dout + g);
-#else
-    px = ld4(x2 + g);
-    pd = ld4(dout + g);
-#endif
-    if (!ok) pd = make_float4(0.f, 0.f, 0.f, 0.f);
-  };
-  int ch = blockIdx.x;
-  if (ch < n_chunks) fetch(ch);
-#ifdef GRL_MLP_PHASE_PROF
-  unsigned long long ph[16] = {0}, tlast = __builtin_amdgcn_s_memtime();
-#endif
-#pragma unroll 1
-  for (; ch < n_chunks; ch += gridDim.x) {
-    PH(0);
-    // W3 fragments of this wave's hidden tile (its slab in L2): requested here, a whole LayerNorm stage and a barrier before
-    // their first use -- loaded inside the product groups their L2 latency was exposed four times per chunk (phase timing:
-    // 35-44 % of a chunk in the z / dH group)
-    u32x4 w3pre[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) w3pre[q] = w3f[q * 64 + lane];
-    // ------------------------------------------------------------ 1: LayerNorm + fragment images
-    float4 xh;
-    float rstd;
-    {
-      const float4 x = px, d = pd;
-      const float mean = row16_sum((x.x + x.y) + (x.z + x.w)) * (1.f / C);
-      const float4 xc = make_float4(x.x - mean, x.y - mean, x.z - mean, x.w - mean);
-      rstd = rsqrtf(row16_sum((xc.x * xc.x + xc.y * xc.y) + (xc.z * xc.z + xc.w * xc.w)) * (1.f / C) + LN_EPS);
-      xh = f4_scale(xc, rstd);
-      const float4 a = make_float4(xh.x * gq.x + bq.x, xh.y * gq.y + bq.y, xh.z * gq.z + bq.z, xh.w * gq.w + bq.w);
-      const int off = lrow * LDF + ppos;
-      put_split4(s.Ah + off, s.Al + off, a);
-      put_split4(s.Dh + off, s.Dl + off, d);
-      db4 = f4_add(db4, d);
-    }
-    const int ch_next = ch + gridDim.x;
-    if (ch_next < n_chunks) fetch(ch_next);
-    PH(1);
-    MLPB_SYNC();
-    PH(2);
-    // ------------------------------------------------------------ 2: the four shared transposed tiles (all eight waves)
-    {  // tile = wave & 3 (a | a | dOut | dOut column halves); waves 0-3 transpose the hi parts, waves 4-7 the lo parts
-      const int tile = wave & 3;
-      const bool lo_part = wave >= 4;
-      const unsigned short* img = (tile < 2 ? (lo_part ? s.Al : s.Ah) : (lo_part ? s.Dl : s.Dh)) + r * LDF + 32 * (tile & 1) + 8 * h;
-      const bf16x8 c0 = *reinterpret_cast<const bf16x8*>(img), c1 = *reinterpret_cast<const bf16x8*>(img + 16);
-      __builtin_amdgcn_sched_barrier(0);
-      if (!(GRL_PREC && lo_part)) {   // plain-bf16 build: there are no lo parts (waves 4-7 idle here)
-        bf16x8 t0, t1;
-        acc_to_bf(transpose32(c0, c1, sel0, sel1), t0, t1);   // reads its accumulator (packs): fenced by construction
-        s.TT[tile][lo_part ? 2 : 0][lane] = __builtin_bit_cast(u32x4, t0);
-        s.TT[tile][lo_part ? 3 : 1][lane] = __builtin_bit_cast(u32x4, t1);
-      }
-    }
-    PH(3);
-    // (no barrier yet: z, dH and the activation below only read the fragment images; the transposed tiles are first needed by dW3)
-    // ------------------------------------------------------------ 3: this wave's hidden tile
-    f32x16 z, dh = zero16();
-#pragma unroll
-    for (int q = 0; q < 16; ++q) z[q] = b3v;
-    // two K-halves per product, each its own fenced group: half the operand registers live at a time
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      bf16x8 ah[2], al[2], w3h[2], w3l[2];   // W3 fragments of this wave's tile: from its slab in L2 (re-read in the dA phase)
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int sidx = 2 * half + u;
-        w3h[u] = __builtin_bit_cast(bf16x8, w3pre[sidx * 2 + 0]);
-        w3l[u] = __builtin_bit_cast(bf16x8, w3pre[sidx * 2 + 1]);
-        ah[u] = *reinterpret_cast<const bf16x8*>(s.Ah + r * LDF + 16 * sidx + 8 * h);
-        al[u] = *reinterpret_cast<const bf16x8*>(s.Al + r * LDF + 16 * sidx + 8 * h);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      GRL_PRIO_HI();
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        z = mfma_bf(ah[u], w3h[u], z);
-        GRL_LO(z = mfma_bf(al[u], w3h[u], z);)
-        GRL_LO(z = mfma_bf(ah[u], w3l[u], z);)
-      }
-      GRL_PRIO_LO();
-      mfma_fence(z, sink);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      bf16x8 dyh[2], dyl[2], w4h[2], w4l[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int sidx = 2 * half + u;
-        dyh[u] = *reinterpret_cast<const bf16x8*>(s.Dh + r * LDF + 16 * sidx + 8 * h);
-        dyl[u] = *reinterpret_cast<const bf16x8*>(s.Dl + r * LDF + 16 * sidx + 8 * h);
-        w4h[u] = __builtin_bit_cast(bf16x8, s.W4F[wave][sidx][0][lane]);
-        w4l[u] = __builtin_bit_cast(bf16x8, s.W4F[wave][sidx][1][lane]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      GRL_PRIO_HI();
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        dh = mfma_bf(dyh[u], w4h[u], dh);
-        GRL_LO(dh = mfma_bf(dyl[u], w4h[u], dh);)
-        GRL_LO(dh = mfma_bf(dyh[u], w4l[u], dh);)
-      }
-      GRL_PRIO_LO();
-      if (half == 0) {
-        mfma_fence(dh, sink);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    PH(4);
-    float4 hv[4], dz[4];
-    float csum = 0.f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {   // reads z and dh: fences both groups
-      float4 gp;
-#ifdef GRL_MLPB_NOGELU
-      hv[q] = make_float4(z[4 * q], z[4 * q + 1], z[4 * q + 2], z[4 * q + 3]); gp = hv[q];
-#else
-      gelu_both4(make_float4(z[4 * q], z[4 * q + 1], z[4 * q + 2], z[4 * q + 3]), hv[q], gp);
-#endif
-      dz[q] = f4_mul(make_float4(dh[4 * q], dh[4 * q + 1], dh[4 * q + 2], dh[4 * q + 3]), gp);
-      csum += (dz[q].x + dz[q].y) + (dz[q].z + dz[q].w);
-    }
-    adb3 += csum;
-    TTile hT, zT;
-    split_pair(hv[0], hv[1], hT.h0, hT.l0);
-    split_pair(hv[2], hv[3], hT.h1, hT.l1);
-    split_pair(dz[0], dz[1], zT.h0, zT.l0);
-    split_pair(dz[2], dz[3], zT.h1, zT.l1);
-    __builtin_amdgcn_sched_barrier(0);
-    PH(5);
-    MLPB_SYNC();   // transposed shared tiles (stage 2) complete
-    PH(6);
-
-    {
-      const TTile ta0 = load_ttile(s.TT[0], lane), ta1 = load_ttile(s.TT[1], lane);
-      __builtin_amdgcn_sched_barrier(0);
-      GRL_PRIO_HI();
-      mma_tn_bf(zT, ta0, aW3[0]);
-      mma_tn_bf(zT, ta1, aW3[1]);
-      GRL_PRIO_LO();
-      mfma_fence(aW3[1], sink);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-
-    {
-      const TTile td0 = load_ttile(s.TT[2], lane), td1 = load_ttile(s.TT[3], lane);
-      __builtin_amdgcn_sched_barrier(0);
-      GRL_PRIO_HI();
-      mma_tn_bf(td0, hT, aW4[0]);
-      mma_tn_bf(td1, hT, aW4[1]);
-      GRL_PRIO_LO();
-      mfma_fence(aW4[1], sink);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    PH(7);
-    // dZ back to row layout, then dA^T per 32-column tile: partial rows to LDS (waves 0-3 write, waves 4-7 add)
-    u32x4 w3d[8];      // the same W3 fragments again, for dA: the first column tile's in flight behind the dZ transposes
-#pragma unroll
-    for (int q = 0; q < 4; ++q) w3d[q] = w3f[q * 64 + lane];
-    bf16x8 zrh0, zrh1, zrl0, zrl1;
-    acc_to_bf(transpose32(zT.h0, zT.h1, sel0, sel1), zrh0, zrh1);
-    GRL_LO(acc_to_bf(transpose32(zT.l0, zT.l1, sel0, sel1), zrl0, zrl1);)
-    __builtin_amdgcn_sched_barrier(0);
-    float4 daf[8];
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct) {
-      bf16x8 th0, th1, tl0, tl1;
-      if (ct == 1) {
-#pragma unroll
-        for (int q = 4; q < 8; ++q) w3d[q] = w3f[q * 64 + lane];
-      }
-      {
-        const bf16x8 ch0 = __builtin_bit_cast(bf16x8, w3d[(2 * ct) * 2 + 0]);
-        const bf16x8 ch1 = __builtin_bit_cast(bf16x8, w3d[(2 * ct + 1) * 2 + 0]);
-        const bf16x8 cl0 = __builtin_bit_cast(bf16x8, w3d[(2 * ct) * 2 + 1]);
-        const bf16x8 cl1 = __builtin_bit_cast(bf16x8, w3d[(2 * ct + 1) * 2 + 1]);
-        __builtin_amdgcn_sched_barrier(0);
-        acc_to_bf(transpose32(ch0, ch1, sel0, sel1), th0, th1);
-        GRL_LO(acc_to_bf(transpose32(cl0, cl1, sel0, sel1), tl0, tl1);)
-      }
-      f32x16 da = zero16();
-      da = mfma_bf(th0, zrh0, da); GRL_LO(da = mfma_bf(tl0, zrh0, da); da = mfma_bf(th0, zrl0, da);)
-      da = mfma_bf(th1, zrh1, da); GRL_LO(da = mfma_bf(tl1, zrh1, da); da = mfma_bf(th1, zrl1, da);)
-      acc_to_frag(da, daf[4 * ct], daf[4 * ct + 1], daf[4 * ct + 2], daf[4 * ct + 3]);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    PH(8);
-    // waves w and w + 4 share buffer DA[w]: each writes one column half in the first round and adds its other half onto the
-    // partner's in the second, so all eight waves move data in both rounds (fixed order per element: first writer, then adder)
-    float* drow = s.DA[wave & 3] + r * LDD + 4 * h;
-    if (wave < 4) {   // (static register indices: a run-time fragment offset would push daf into scratch)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) *reinterpret_cast<float4*>(drow + 8 * t) = daf[t];
-    } else {
-#pragma unroll
-      for (int t = 4; t < 8; ++t) *reinterpret_cast<float4*>(drow + 8 * t) = daf[t];
-    }
-    MLPB_SYNC();
-    PH(9);
-    if (wave < 4) {
-#pragma unroll
-      for (int t = 4; t < 8; ++t) {
-        float4* p = reinterpret_cast<float4*>(drow + 8 * t);
-        *p = f4_add(*p, daf[t]);
-      }
-    } else {
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        float4* p = reinterpret_cast<float4*>(drow + 8 * t);
-        *p = f4_add(*p, daf[t]);
-      }
-    }
-    MLPB_SYNC();
-    PH(10);
-    // ------------------------------------------------------------ 4: LayerNorm backward
-    {
-      const int row = ch * 32 + lrow;
-      float4 da = *reinterpret_cast<const float4*>(s.DA[0] + lrow * LDD + 4 * cq);
-#pragma unroll
-      for (int w_ = 1; w_ < 4; ++w_) da = f4_add(da, *reinterpret_cast<const float4*>(s.DA[w_] + lrow * LDD + 4 * cq));
-      const float4 g = f4_mul(da, gq);
-      const float mg = row16_sum((g.x + g.y) + (g.z + g.w)) * (1.f / C);
-      const float mgx = row16_sum((g.x * xh.x + g.y * xh.y) + (g.z * xh.z + g.w * xh.w)) * (1.f / C);
-      const float4 dx = make_float4(rstd * (g.x - mg - xh.x * mgx), rstd * (g.y - mg - xh.y * mgx), rstd * (g.z - mg - xh.z * mgx),
-                                    rstd * (g.w - mg - xh.w * mgx));
-#if GRL_MLP_NT
-      if (row < n_rows) st4_nt(dx2 + (size_t)row * C + 4 * cq, dx);
-#else
-      if (row < n_rows) st4(dx2 + (size_t)row * C + 4 * cq, dx);
-#endif
-      dgam = make_float4(fmaf(da.x, xh.x, dgam.x), fmaf(da.y, xh.y, dgam.y), fmaf(da.z, xh.z, dgam.z), fmaf(da.w, xh.w, dgam.w));
-      dbet = f4_add(dbet, da);
-    }
-    // (stage 1 of the next chunk only writes the A / D images, last read before the two barriers above)
-    PH(11);
-  }
-#ifdef GRL_MLP_PHASE_PROF
-  if (lane == 0 && (wave == 0 || wave == 5))
-    for (int i = 0; i < 12; ++i) atomicAdd(&g_phase[wave == 5][i], ph[i]);
-#endif
-
-  // ---- partial slab.  accumulator element i of lane (n = r, h) holds row m = 8(i>>2) + 4h + (i&3) of the 32x32 tile
-  __syncthreads();   // every wave is done with its W3 fragments (same slab)
-  float* out = partial + (size_t)blockIdx.x * MLP_PARTIAL;
-  float* oW3 = out, *ob3 = oW3 + W * C, *oW4 = ob3 + W, *ob4 = oW4 + C * W, *og = ob4 + C, *obt = og + C;
-  const int j0 = 32 * wave;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int m = 8 * (i >> 2) + 4 * h + (i & 3);
-#pragma unroll
-    for (int t2 = 0; t2 < 2; ++t2) {
-      oW3[(size_t)(j0 + m) * C + 32 * t2 + r] = aW3[t2][i];
-      oW4[(size_t)(32 * t2 + m) * W + j0 + r] = aW4[t2][i];
-    }
-  }
-  {
-    const float v = adb3 + __shfl_xor(adb3, 32, 64);
-    if (h == 0) ob3[j0 + r] = v;
-  }
-  float* red = &s.DA[0][0];   // [32 rows][3][64]
-  *reinterpret_cast<float4*>(red + (lrow * 3 + 0) * C + 4 * cq) = db4;
-  *reinterpret_cast<float4*>(red + (lrow * 3 + 1) * C + 4 * cq) = dgam;
-  *reinterpret_cast<float4*>(red + (lrow * 3 + 2) * C + 4 * cq) = dbet;
-  __syncthreads();
-  if (tid < 3 * C) {
-    const int which = tid >> 6, c = tid & 63;
-    float t = 0.f;
-#pragma unroll
-    for (int g_ = 0; g_ < 32; ++g_) t += red[(g_ * 3 + which) * C + c];
-    (which == 0 ? ob4 : which == 1 ? og : obt)[c] = t;
-  }
-  if (sink == 123456.789f) out[0] = sink;   // keeps the fences alive; never true
-}
 
 int blocks_for(int n_rows, int rows_per_block, int cap) {
   const int b = (n_rows + rows_per_block - 1) / rows_per_block;
@@ -707,10 +264,7 @@ int GRL_ENTRY(grl_node_mlp_fwd)(const st_t* x2, const st_t* x_dst, const float* 
 }
 
 // partial [grl_node_mlp_bwd_blocks(n_rows) + 1][grl_node_mlp_partial_size()]: one gradient row per workgroup, and the LAST row is scratch
-// (the shared W3 fragment image, 64 KB) -- sum rows 0 .. blocks-1 only.  d x_dst is simply dout (residual), not produced here.
-#ifndef GRL_MLP_BWD16
-#define GRL_MLP_BWD16 1   // round 3: the 16-row, one-barrier-per-chunk kernel of node_mlp16.hip; 0 = the 32-row kernel above
-#endif
+// (node_mlp16.hip) -- sum rows 0 .. blocks-1 only.  d x_dst is simply dout (residual), not produced here.
 int GRL_ENTRY(grl_node_mlp_bwd16_launch)(const st_t* x2, const st_t* dout, const float* W3, const float* b3, const float* W4,
                                          const float* gamma, const float* beta, st_t* dx2, float* partial, int n_rows, int blocks,
                                          const void* wimg, hipStream_t stream);
@@ -720,7 +274,8 @@ int GRL_ENTRY(grl_node_mlp_bwd)(const st_t* x2, const st_t* dout, const float* W
                      const float* gamma, const float* beta, st_t* dx2, float* partial, int n_rows, hipStream_t stream) {
   return GRL_ENTRY(grl_node_mlp_bwd_img)(x2, dout, W3, b3, W4, b4, gamma, beta, dx2, partial, n_rows, nullptr, stream);
 }
-// the same with an optional pre-split fragment image of this step's weights (grl_weight_images kind 3; used by the 16-row kernel)
+// the same with an optional pre-split fragment image of this step's weights (grl_weight_images kind 3).  n_rows must be a multiple of 16
+// (it is n_nodes * 16): the 16-row kernel returns -3 for any other count and launches nothing.
 int GRL_ENTRY(grl_node_mlp_bwd_img)(const st_t* x2, const st_t* dout, const float* W3, const float* b3, const float* W4, const float* b4,
                      const float* gamma, const float* beta, st_t* dx2, float* partial, int n_rows, const void* wimg, hipStream_t stream) {
   (void)b4;
@@ -728,27 +283,10 @@ int GRL_ENTRY(grl_node_mlp_bwd_img)(const st_t* x2, const st_t* dout, const floa
     hipMemsetAsync(partial, 0, sizeof(float) * MLP_PARTIAL, stream);
     return 0;
   }
-  if (GRL_MLP_BWD16 && n_rows % 16 == 0) {
-    grl_prof_begin_replay("node_mlp_bwd16_kernel", stream);
-    const int rc = GRL_ENTRY(grl_node_mlp_bwd16_launch)(x2, dout, W3, b3, W4, gamma, beta, dx2, partial, n_rows, grl_node_mlp_bwd_blocks(n_rows), wimg, stream);
-    grl_prof_end_replay(stream);
-    return rc;
-  }
-  GRL_ONCE(hipFuncSetAttribute((const void*)node_mlp_bwd_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MlpBwdSmem)));
-  const int blocks = grl_node_mlp_bwd_blocks(n_rows);
-  u32x4* slab = reinterpret_cast<u32x4*>(partial + (size_t)blocks * MLP_PARTIAL);
-  hipLaunchKernelGGL(mlp_w3_frags_kernel, dim3(1), dim3(512), 0, stream, W3, slab);
-  hipLaunchKernelGGL(node_mlp_bwd_fused_kernel, dim3(blocks), dim3(512), sizeof(MlpBwdSmem), stream, x2, dout, W3, b3, W4, gamma, beta, dx2,
-                     partial, slab, n_rows);
-  GRL_CHECK_LAUNCH();
-  return 0;
+  grl_prof_begin_replay("node_mlp_bwd16_kernel", stream);
+  const int rc = GRL_ENTRY(grl_node_mlp_bwd16_launch)(x2, dout, W3, b3, W4, gamma, beta, dx2, partial, n_rows, grl_node_mlp_bwd_blocks(n_rows), wimg, stream);
+  grl_prof_end_replay(stream);
+  return rc;
 }
 
-#ifdef GRL_MLP_PHASE_PROF
-int grl_mlp_phase_read(unsigned long long* out32, int reset) {
-  hipMemcpyFromSymbol(out32, HIP_SYMBOL(g_phase), sizeof(unsigned long long) * 32);
-  if (reset) { unsigned long long z[32] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(g_phase), z, sizeof(z)); }
-  return 0;
-}
-#endif
 }  // extern "C"

@@ -52,7 +52,9 @@ template <int CTRL>
 GRL_DEVINL float dpp_read(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
 }
-GRL_DEVINL float row16_sum(float v) {   // sum over the 16 lanes of a DPP row (quad_perm xor 1, xor 2, row_half_mirror, row_mirror)
+// sum over the 16 lanes of a DPP row (quad_perm xor 1, xor 2, row_half_mirror, row_mirror): four DPP adds on the vector pipe instead of
+// four dependent ds_bpermute round trips through the LDS (round 3)
+GRL_DEVINL float row16_sum(float v) {
   v += dpp_read<0xB1>(v);
   v += dpp_read<0x4E>(v);
   v += dpp_read<0x141>(v);
@@ -69,12 +71,11 @@ GRL_DEVINL void split4(const float4& v, uint2& hi, uint2& lo) {
   lo.y = pack_rn(v.z - trunc_bf16(v.z), v.w - trunc_bf16(v.w));
 #endif
 }
-// GRL_M16_SCALAR (default): plain f32 vector instructions only in this kernel (scalar GELU, file compiled with -fno-slp-vectorize)
-#ifndef GRL_M16_SCALAR
-#define GRL_M16_SCALAR (!GRL_PREC)   // the plain-bf16 build takes the packed logistic GELU (grl_common.h gelu_logistic_both_pair): +1.3 % on the
-#endif                               // rope workload's step, A/B profiles/r05_ab_mlp_pk.txt; the fp32 build stays scalar (finding 23)
+// fp32 build: plain f32 vector instructions only in this kernel (scalar GELU, file compiled with -fno-slp-vectorize; finding 23).  The
+// plain-bf16 build takes the packed logistic GELU (grl_common.h gelu_logistic_both_pair): +1.3 % on the rope workload's step, A/B
+// profiles/r05_ab_mlp_pk.txt
 GRL_DEVINL void gelu_both4_pk(const float4& x, float4& gv, float4& gpv) {
-#if GRL_M16_SCALAR
+#if !GRL_PREC
   gelu_both4(x, gv, gpv);
   return;
 #endif
@@ -113,18 +114,6 @@ __global__ __launch_bounds__(256, 1) void node_mlp_bwd16_kernel(const st_t* __re
   const int j0 = 64 * wave;
   WFrag16 w3f, w3t;
   float4 b3q[4];
-#ifdef GRL_KNOCK_STAGE   // timing knock-out: constant fragments instead of the strided weight loads (results are wrong)
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt) {
-    b3q[nt] = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const u32x4 c = {0x3c003c00u + lane, 0x3c003c00u, 0x3c003c00u, 0x3c003c00u};
-      w3f.h[nt][s] = w3f.l[nt][s] = w3t.h[nt][s] = w3t.l[nt][s] = __builtin_bit_cast(bf16x8, c);
-      sm.W4F[wave][nt][s][0][lane] = c; sm.W4F[wave][nt][s][1][lane] = c;
-    }
-  }
-#else
   if (wimg) {   // the fragments of this step's weights, pre-split once by grl_weight_images (kind 3): 48 coalesced 16-byte loads per lane
                 // instead of 16 vector + 128 strided dword loads and 48 splits
 #pragma unroll
@@ -170,11 +159,6 @@ __global__ __launch_bounds__(256, 1) void node_mlp_bwd16_kernel(const st_t* __re
     }
   }
   }
-#endif
-#ifndef GRL_M16_PIN_STATIC
-#define GRL_M16_PIN_STATIC 1
-#endif
-#if GRL_M16_PIN_STATIC
   // the 32 static fragments are defined in the accumulator half of the register file (MFMA A operands may be AGPRs): without this the
   // allocator keeps them as AGPR spill slots of ordinary registers and reads them back with 128 v_accvgpr_read per chunk
 #pragma unroll
@@ -184,7 +168,6 @@ __global__ __launch_bounds__(256, 1) void node_mlp_bwd16_kernel(const st_t* __re
       asm volatile("" : "+a"(w3f.h[nt][s]));  asm volatile("" : "+a"(w3t.h[nt][s]));
       GRL_LO(asm volatile("" : "+a"(w3f.l[nt][s]));  asm volatile("" : "+a"(w3t.l[nt][s]));)
     }
-#endif
   f32x16 aW3[2][2], aW4[2][2];   // dW3[hidden tile][channel tile], dW4[channel tile][hidden tile]
 #pragma unroll
   for (int a_ = 0; a_ < 2; ++a_)
@@ -203,9 +186,6 @@ __global__ __launch_bounds__(256, 1) void node_mlp_bwd16_kernel(const st_t* __re
   raw4_t px = raw4_t{}, pd = px, pxn = px, pdn = px;
   float4 pxw = make_float4(0.f, 0.f, 0.f, 0.f), pdw = pxw;
   auto fetch = [&](int i, raw4_t& fx, raw4_t& fd) {   // this thread's quad of chunk i (clamped: the loads of a non-existent chunk are never used)
-#if defined(GRL_M16_KNOCK) && (GRL_M16_KNOCK & 1)   // timing knock-out (GRL_DIAG builds only): no row loads behind the first two chunks
-    if (i >= 2) return;
-#endif
     const size_t gofs = ((size_t)chunk_of(i < n_mine ? i : n_mine - 1) * 16 + srow) * C + 4 * cq;
     fx = ld4_raw(x2 + gofs);
     fd = ld4_raw(dout + gofs);
@@ -333,10 +313,7 @@ __global__ __launch_bounds__(256, 1) void node_mlp_bwd16_kernel(const st_t* __re
   }
   __syncthreads();
 
-#ifndef GRL_M16_BURST
-#define GRL_M16_BURST GRL_PREC   // plain-bf16 build: z and dH of a chunk as ONE burst of sixteen MFMAs (the W4^T fragments resident in registers:
-#endif                           // no lo halves, they fit), the GELUs and dZ as packed f32 pairs behind it -- the edge backward's recipe (round 5)
-#if GRL_M16_BURST
+#if GRL_PREC
   bf16x8 w4r[4][2];
 #pragma unroll
   for (int nt = 0; nt < 4; ++nt)
@@ -371,12 +348,8 @@ __global__ __launch_bounds__(256, 1) void node_mlp_bwd16_kernel(const st_t* __re
     fetch(it + 2, pxn, pdn);
     BAR();
     M16_PH(1);   // fragment reads issued
-    // ---- z = W3 a + b3 (hidden on the registers, row on the lane), then dH = W4^T dOut.  GRL_M16_PAIRS (build switch, off: measured equal, profiles/r03_mlp16_log.txt): the n-tiles go in PAIRS --
-    // a region holds the twelve MFMAs of two tiles and the GELU (value + derivative) of the two tiles before: four independent packed
-    // chains for the vector pipe instead of two (a lone wave pays ~8 cycles per DEPENDENT instruction, 4 per independent one)
-#ifndef GRL_M16_PAIRS
-#define GRL_M16_PAIRS 0
-#endif
+    // ---- z = W3 a + b3 (hidden on the registers, row on the lane), then dH = W4^T dOut.  (fp32 build: n-tiles in pairs per region --
+    // four independent packed chains for the vector pipe instead of two -- measured equal, profiles/r03_mlp16_log.txt)
     float4 hv[4], gp[4];
     bf16x8 zh[2], zl[2], hh[2], hl[2];
     {
@@ -404,7 +377,7 @@ __global__ __launch_bounds__(256, 1) void node_mlp_bwd16_kernel(const st_t* __re
         dz[nt] = f4_mul(v4(e[nt]), gp[nt]);
         db3[nt] = f4_add(db3[nt], dz[nt]);
       };
-#if GRL_M16_BURST
+#if GRL_PREC
       static_assert(GRL_PREC, "the burst form keeps W4^T resident: plain-bf16 build only");
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) { c[nt] = f32x4v{b3q[nt].x, b3q[nt].y, b3q[nt].z, b3q[nt].w}; e[nt] = f32x4v{0.f, 0.f, 0.f, 0.f}; }
@@ -422,23 +395,6 @@ __global__ __launch_bounds__(256, 1) void node_mlp_bwd16_kernel(const st_t* __re
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) dz_tile(nt);
       split_pair(dz[0], dz[1], zh[0], zl[0]);
-#elif GRL_M16_PAIRS
-      z_tile(0); z_tile(1); w4_load(0); w4_load(1);
-      BAR();
-      z_tile(2); z_tile(3);
-      gelu_both4_pk(v4(c[0]), hv[0], gp[0]); gelu_both4_pk(v4(c[1]), hv[1], gp[1]);
-      BAR();
-      M16_PH(2);   // z: 24 MFMA, two GELU tiles
-      dh_tile(0); dh_tile(1);
-      gelu_both4_pk(v4(c[2]), hv[2], gp[2]); gelu_both4_pk(v4(c[3]), hv[3], gp[3]);
-      BAR();
-      w4_load(2); w4_load(3);
-      BAR();
-      dh_tile(2); dh_tile(3);
-      dz_tile(0); dz_tile(1);
-      split_pair(dz[0], dz[1], zh[0], zl[0]);
-      BAR();
-      dz_tile(2); dz_tile(3);
 #else
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) {
@@ -598,8 +554,7 @@ __global__ __launch_bounds__(256, 1) void node_mlp_bwd16_kernel(const st_t* __re
 
 extern "C" {
 
-// Internal entry point (called by grl_node_mlp_bwd of node_mlp.hip when GRL_MLP_BWD16 is on): n_rows must be a multiple of 16 (it is
-// n_nodes * 16), `blocks` workgroups are launched and each writes its partial row.
+// Internal entry point (called by grl_node_mlp_bwd of node_mlp.hip): n_rows must be a multiple of 16 (it is n_nodes * 16), `blocks` workgroups are launched and each writes its partial row.
 int GRL_ENTRY(grl_node_mlp_bwd16_launch)(const st_t* x2, const st_t* dout, const float* W3, const float* b3, const float* W4,
                                          const float* gamma, const float* beta, st_t* dx2, float* partial, int n_rows, int blocks,
                                          const void* wimg, hipStream_t stream) {

@@ -171,10 +171,7 @@ GRL_DEVINL void lift_encode_bwd_body(const float* __restrict__ scal, const float
   // registers at the loop end -- did not survive the compiler: the loads were sunk behind the back-edge to their first use, and in the
   // bf16 build each of the four waited for the one before it (270 us for the rope minibatch's 180 MB, round 5).
   // Slots past N re-read the iteration's first node with their input zeroed (no branch around a load).
-#ifndef GRL_LIFT_LB
-#define GRL_LIFT_LB (GRL_PREC ? 4 : 2)
-#endif
-  constexpr int LB = GRL_LIFT_LB;
+  constexpr int LB = GRL_PREC ? 4 : 2;
   for (long long n0 = wave; n0 < N; n0 += (long long)n_waves * LB) {
     raw4_t dq[LB][4];
     float in[LB];
@@ -250,13 +247,7 @@ __global__ __launch_bounds__(256) void lift_encode_bwd_multi_kernel(LiftMulti m,
 // from LDS), then thread (c, q) -- channel c, orientation quad q -- reads the 16 orientation values of its channel from LDS (bank = c:
 // conflict-free) against its register slice of fk.  Round 2's kernels had each of the four waves load the node's 16 rows itself, one
 // dword per lane and one node at a time: ~20 KB of distinct bytes in flight per CU, 3.1 / 2.4 TB/s.
-#ifndef GRL_FIBER_FB
-#define GRL_FIBER_FB 4
-#endif
-#ifndef GRL_FIBER_NT
-#define GRL_FIBER_NT 0   // bit 0: non-temporal loads, bit 1: non-temporal stores
-#endif
-constexpr int FB = GRL_FIBER_FB;                  // nodes per batch
+constexpr int FB = 4;                             // nodes per batch
 constexpr int FB_E = FB * O * C;                  // elements per batch
 template <int NT> struct FiberRegs { raw4_t r[FB_E / 4 / NT]; };   // four-element pieces per thread and batch (NT threads per workgroup), RAW:
 // widened where they go to LDS -- widened at the load (bf16 build) every prefetch was waited for before the batch in LDS was computed (round 5)
@@ -269,7 +260,7 @@ template <int NT> GRL_DEVINL void fiber_load(FiberRegs<NT>& R, const st_t* __res
 #if GRL_PREC
     R.r[i] = ld4_raw(p);
 #else
-    R.r[i] = (GRL_FIBER_NT & 1) ? ld4_nt(p) : ld4(p);
+    R.r[i] = ld4(p);
 #endif
   }
 }
@@ -281,8 +272,7 @@ template <int NT> GRL_DEVINL void fiber_store(st_t* __restrict__ dst, long long 
 #pragma unroll
   for (int i = 0; i < FB_E / 4 / NT; ++i) {
     const int e = 4 * (threadIdx.x + NT * i);
-    if (GRL_FIBER_NT & 2) st4_nt(dst + batch * FB_E + e, *reinterpret_cast<const float4*>(tile + e));
-    else st4(dst + batch * FB_E + e, *reinterpret_cast<const float4*>(tile + e));
+    st4(dst + batch * FB_E + e, *reinterpret_cast<const float4*>(tile + e));
   }
 }
 // the last, partial batch of a launch (N % FB nodes; one workgroup, once): guarded element-wise copies, rows past N are zero in LDS
@@ -361,14 +351,11 @@ constexpr int FIBER_PARTIAL = O * O * C + C;
 // its own and cost 1-2 % of the step on every workload: sixteen resident waves per CU starve the critic's backward next to it.)
 constexpr int FBW = 4;                       // waves per workgroup
 constexpr int FBR = O / FBW;                 // orientations per thread
-// Two forms of the backward batch.  GRL_FIBER_BWD_PK = 1 (the plain-bf16 build, where the kernel is instruction-bound: 656 -> 404 us on the
-// rope minibatch's large layer): packed pairs, the own quad re-read from LDS.  0 (the fp32 build, HBM-bound either way: 154 us for 728 MB):
+// Two forms of the backward batch.  The plain-bf16 build (where the kernel is instruction-bound: 656 -> 404 us on the
+// rope minibatch's large layer): packed pairs, the own quad re-read from LDS.  The fp32 build (HBM-bound either way: 154 us for 728 MB):
 // round 4's form -- with the packed form the kernel itself is 10 % faster and the REPLAYED step 1.7 % slower on two boxes
 // (profiles/r05_ab_nodeops.txt: 324.8 / 325.1 with this form, 319.1 / 319.4 with the packed one), so it stays.
-#ifndef GRL_FIBER_BWD_PK
-#define GRL_FIBER_BWD_PK GRL_PREC
-#endif
-#if !GRL_FIBER_BWD_PK
+#if !GRL_PREC
 GRL_DEVINL void fiber_bwd_batch(const float* tx, const float* td, float* to, const float (&kq)[FBR][O], float (&dk)[O][FBR], float& db,
                                 int c, int q) {
 #pragma unroll 1
@@ -395,7 +382,7 @@ GRL_DEVINL void fiber_bwd_batch(const float* tx, const float* td, float* to, con
   }
 }
 #endif
-#if GRL_FIBER_BWD_PK
+#if GRL_PREC
 // The thread's own quad of dx2 (orientations FBR q .. FBR q + 3) is read from LDS a second time: picked out of the register array dv[] by
 // the (wave-uniform, but not to the compiler) index q it cost 120 v_cmp / v_cndmask per node beside 128 FMAs (round 5: the bf16 build of
 // this kernel is instruction-bound).  Both products run as packed pairs over the quad (v_pk_fma_f32: 64 per node).
@@ -439,7 +426,7 @@ __global__ __launch_bounds__(64 * FBW, 2) void fiber_conv_bwd_kernel(const st_t*
   __shared__ __attribute__((aligned(16))) float to[FB_E];   // dx1 of the batch: leaves as 16-byte stores
   __shared__ float red[FBW * C];
   const int c = threadIdx.x & 63, q = threadIdx.x >> 6;
-#if GRL_FIBER_BWD_PK
+#if GRL_PREC
   v2f kq[O][FBR / 2];   // [p][j]: fk[o = FBR q + j][p][c] / 16   (rows this thread back-propagates to), pairs over j
   v2f dk[O][FBR / 2];   // d fk[o][p = FBR q + j][c], pairs over j
 #pragma unroll
@@ -764,10 +751,9 @@ __global__ __launch_bounds__(256) void lift_fiber_basis_bwd_kernel(LiftMulti m, 
 // out[j] += sum_w partial[w][j], bitwise reproducible: a workgroup owns 64 columns; its 8 waves sum interleaved row groups
 // (wave g: rows g, g+8, ..., four independent running sums each, combined in a fixed order) and the 8 wave sums are folded
 // through LDS in wave order.  No atomics, so the result does not depend on scheduling.
-#ifndef GRL_RED_WAVES
-#define GRL_RED_WAVES 2   // waves per fold workgroup.  Round 6 A/B (profiles/r06_ab_fold_waves.txt): 8 -> 4 -> 2 waves: 0.320 -> 0.304 -> 0.299 ms at 32 frames, 0.638 -> 0.618 -> 0.614 at 512, 3.113 -> 3.08 at 4096 -- short-lived 512-thread workgroups were the fold's cost, not its bytes
-#endif
-constexpr int RED_WAVES = GRL_RED_WAVES;
+// waves per fold workgroup.  Round 6 A/B (profiles/r06_ab_fold_waves.txt): 8 -> 4 -> 2 waves: 0.320 -> 0.304 -> 0.299 ms at 32 frames,
+// 0.638 -> 0.618 -> 0.614 at 512, 3.113 -> 3.08 at 4096 -- short-lived 512-thread workgroups were the fold's cost, not its bytes
+constexpr int RED_WAVES = 2;
 // RED_DEPTH independent loads in flight per wave: the slabs are row-strided, so a wave's walk down its rows is a chain of
 // memory latencies -- with 4 in flight the longest columns (2048 rows: gradients fed by two convolutions) took 64 round trips.
 constexpr int RED_DEPTH = 16;

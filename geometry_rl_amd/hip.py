@@ -22,12 +22,11 @@ SOURCES = ["edge_conv.hip", "edge_conv16.hip", "node_ops.hip", "node_mlp.hip", "
 # per-source compiler flags.  edge_conv16.hip: its 512-register backward kernel keeps the chain's MFMA results in VGPRs (the default
 # selection would put every MFMA result of such a kernel into AGPRs) and pins the weight-gradient tiles to AGPRs itself (asm)
 # node_mlp16.hip additionally without SLP vectorisation: beside the MFMAs of its one wave per SIMD plain f32 instructions overlap with the matrix
-# pipe, packed ones (v_pk_*) do not (DESIGN.md finding 23)
-# (edge_conv16.hip the same, with the scalar GELU in its one-wave backward: +1 % on the step, profiles/r03_ab_edge16_noslp.txt)
-FILE_FLAGS = {"edge_conv16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize", "-DGRL_B16_SCALAR_GELU"],
+# pipe, packed ones (v_pk_*) do not (DESIGN.md finding 23); edge_conv16.hip the same (+1 % on the step, docs/history/profiles/r03_ab_edge16_noslp.txt)
+FILE_FLAGS = {"edge_conv16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
               "node_mlp16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"],
               # the ConvNeXt forward: plain-f32 GELU as well (0.313 vs 0.330 ms per step; the 16-row edge forward, three waves per SIMD, is
-              # FASTER with its packed GELU: 0.48 vs 0.52 ms -- profiles/r03_ab_forward_gelu_ld1.txt)
+              # FASTER with its packed GELU: 0.48 vs 0.52 ms -- docs/history/profiles/r03_ab_forward_gelu_ld1.txt)
               "node_mlp.hip": ["-fno-slp-vectorize", "-DGRL_GELU4_SCALAR=1"]}
 VARIANTS = [("edge_conv.hip", ["-DGRL_PREC=1"], ".bf16"), ("edge_conv16.hip", ["-DGRL_PREC=1"], ".bf16"),
             ("node_mlp.hip", ["-DGRL_PREC=1"], ".bf16"), ("node_mlp16.hip", ["-DGRL_PREC=1"], ".bf16"),
@@ -101,9 +100,6 @@ def build(verbose: bool = True, force: bool = False, root=None) -> str:
     ("prebuilt" = nothing compiled).  ``root``: build another checkout of this repository (tests)."""
     import json
     import time
-    all_flags = [f for fl in FILE_FLAGS.values() for f in fl] + [f for _, fl, _ in VARIANTS for f in fl]
-    if any(f.startswith("-DGRL_DIAG") for f in all_flags):
-        raise RuntimeError("GRL_DIAG (timing knock-outs: wrong results) must never be built into libgrl_hip.so -- use tools/build_variants.sh")
     csrc, header, lint_py = _pkg_paths(root)
     lib_path = os.path.join(os.path.dirname(csrc), "libgrl_hip.so") if root else LIB_PATH
     info_path = os.path.join(root, "BUILD_INFO.json") if root else BUILD_INFO
@@ -224,9 +220,6 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} is missing: the HIP extension must be built (python -c 'import __graft_entry__ as g; g.build()'). "
                 "geometry_rl_amd has no CPU or PyTorch fallback path.")
         _lib = ctypes.CDLL(LIB_PATH)
-        if hasattr(_lib, "grl_diag_build") and not os.environ.get("GRL_ALLOW_DIAG_LIB"):
-            raise RuntimeError(f"{LIB_PATH} is a GRL_DIAG build (timing knock-outs: its results are wrong).  Diagnostic libraries are loaded "
-                               "only with GRL_ALLOW_DIAG_LIB=1 (tools/run_variants.sh); rebuild the product library with __graft_entry__.build()")
         # the binary must be the one THESE sources build (an explicitly named debugging library -- GRL_LIB, tools/r0*_ab_libs.sh -- is the
         # caller's business; GRL_ALLOW_STALE_LIB=1 switches the check off for bisecting)
         if "GRL_LIB" not in os.environ and os.environ.get("GRL_ALLOW_STALE_LIB", "0") == "0":

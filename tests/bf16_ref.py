@@ -8,7 +8,7 @@ Rounding points, as the GRL_PREC branches of csrc/edge_conv16.hip, csrc/node_mlp
 * every MFMA product takes both operands rounded to nearest bf16 (``split_pair`` / ``pack_rn``: no lo halves), accumulates in fp32 --
   here in float64 -- and adds the fp32 bias in the accumulator (``mm``, forward and backward: the backward rounds the incoming gradient
   and reuses the rounded forward operands; the first basis layer's bias gradient is an MFMA column of that rounded gradient too);
-* GELU is the build's logistic approximant x sigma(1.5976 x + 0.07056 x^3) with its exact derivative (GRL_GELU_LOGISTIC);
+* GELU is the build's logistic approximant x sigma(1.5976 x + 0.07056 x^3) with its exact derivative (the GRL_PREC branches of csrc/grl_common.h);
 * polynomial features, LayerNorm, the per-edge product K_e * x_src and the softmax stay in fp32 arithmetic (float64 here).
 
 ``rounding=False, logistic=False`` turns every rounding off and restores the erf GELU: the functions then reproduce the oracle

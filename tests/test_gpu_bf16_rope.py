@@ -7,7 +7,7 @@
   rounded to nearest bf16, bf16 latents, fp32 accumulation: entry points ``*_bf16``) against BOTH the fp32 oracle and the fp32 HIP
   path; every actor gradient tensor against the fp32 HIP path (relative L2 error <= 2e-2, worst element <= 3e-2 of the tensor's
   largest) and the parameters after one Adam step (mean distance <= 0.02 lr).  The build's GELU is the logistic approximation of the
-  normal CDF (csrc/grl_common.h GRL_GELU_LOGISTIC; |error| 4e-4 on the value, 8e-4 on the derivative).  Tolerance as BASELINE.md section 3 states it for this config: every loss-dict entry within 2e-2 relative
+  normal CDF (csrc/grl_common.h gelu_logistic, the GRL_PREC build; |error| 4e-4 on the value, 8e-4 on the derivative).  Tolerance as BASELINE.md section 3 states it for this config: every loss-dict entry within 2e-2 relative
   (|got - ref| <= 2e-2 * max(|ref|, floor)), loc / var / state_value within 2e-2 * max(1, max|ref|); 1e-4 is unattainable with
   8-bit mantissas.  Measured margins are printed.
 """

@@ -299,6 +299,20 @@ def test_deepsets_critic_shapes(B, n, d):
         assert err <= 1e-4 * max(1.0, float(gr.abs().max())), (k, err, float(gr.abs().max()))
 
 
+def test_node_mlp_bwd_rejects_a_row_count_that_is_not_a_multiple_of_16():
+    """The node-MLP backward runs on 16-row chunks (rows = n_nodes * 16): any other row count is an error, not a launch."""
+    from geometry_rl_amd import hip
+    dv = dev()
+    rows = 2 * 16 - 1
+    x2, dout, dx2 = (torch.zeros(2 * 16, 64, device=dv) for _ in range(3))
+    w3, b3, w4, b4 = (torch.zeros(s, device=dv) for s in [(256, 64), (256,), (64, 256), (64,)])
+    gam, bet = torch.ones(64, device=dv), torch.zeros(64, device=dv)
+    partial = torch.zeros(hip.query("grl_node_mlp_bwd_blocks", rows) + 1, hip.query("grl_node_mlp_partial_size"), device=dv)
+    with pytest.raises(RuntimeError, match="grl_node_mlp_bwd failed"):
+        hip.call("grl_node_mlp_bwd", x2, dout, w3, b3, w4, b4, gam, bet, dx2, partial, rows)
+    torch.cuda.synchronize()
+
+
 def test_kernel_prof_stamp_mode_times_a_replayed_launch():
     """grl_prof_enable(2): wall-clock stamp kernels around a launch are ordinary graph nodes, so the duration of a REPLAYED launch can
     be read back (bench.py's `roofline.replayed_launches`).  Here: the node-MLP backward recorded into a hipGraph, replayed three

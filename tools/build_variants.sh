@@ -2,7 +2,7 @@
 # Run HERE (hipcc cross-compiles): build one libgrl_hip variant per set of flags under _variants/ (git-ignored, shipped by gpurun);
 # `gpurun -- 'bash tools/run_variants.sh'` then times them on ONE box.   usage: bash tools/build_variants.sh name1 "-DA=0 -DB=1" name2 "..." ...
 # A flag written @file.hip:-flag applies to that source file only (e.g. "@edge_conv16.hip:-fno-slp-vectorize"); it reaches BOTH builds of
-# that file (fp32 and the -DGRL_PREC=1 twin).  Timing knock-outs (-DGRL_E16_NOGELU, ...: wrong results) compile only with -DGRL_DIAG.
+# that file (fp32 and the -DGRL_PREC=1 twin).  The phase-tick builds: -DGRL_B16_PHASE (edge_bwd16_kernel), -DGRL_M16_PHASE (node_mlp_bwd16_kernel).
 # The jobs are geometry_rl_amd/hip.py's own (SOURCES + VARIANTS with FILE_FLAGS); a variant's flags come later on the command line and win.
 # Variant libraries are linked WITHOUT the export map (diagnostic entry points such as grl_edge_bwd16_phase_read stay visible).
 set -e
