@@ -534,3 +534,18 @@ GRL_DEVINL void mma_wx_bf_fenced(const unsigned short* whi, const unsigned short
   epilogue(acc);
   __builtin_amdgcn_sched_barrier(0);
 }
+
+// One element of torch.optim.Adam (no amsgrad, no weight decay): m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2;
+// p -= lr/bc1 * m / (sqrt(v) / sqrt(bc2) + eps).  The arithmetic of EVERY device form (adam_kernel, adam_dev_kernel and
+// adam_dev_report_pairs_kernel in train_ops.hip, the fused fold tail in node_ops.hip), with its multiply-adds written out and the
+// compiler's own contraction off: left to the compiler, the fold tail's copy was contracted and the others were not, and the forms
+// differed in the last bit of a few elements in a thousand (tests/test_gpu_train_ops.py::test_adam_forms_bitwise).
+GRL_DEVINL void adam_element(float g, float& p, float& m, float& v, float b1, float b2, float eps, float lr_bc1, float bc2_sqrt) {
+#pragma clang fp contract(off)
+  const float mi = fmaf(1.f - b1, g, b1 * m);
+  const float vi = fmaf(g, (1.f - b2) * g, b2 * v);
+  m = mi;
+  v = vi;
+  const float denom = sqrtf(vi) / bc2_sqrt + eps;
+  p = fmaf(-lr_bc1, mi / denom, p);
+}

@@ -845,7 +845,7 @@ struct ReduceMulti {
 // applies Adam to the parameters they belong to (the optimizer launch and its read of the gradient disappear; the gradient is stored as
 // well: .grad stays inspectable), and one EXTRA workgroup folds the fused loss kernel's slots, evaluates the reported values and advances
 // the optimizer's step count for the next step -- three more launches of the lane's tail gone (fold + Adam + report + count were
-// 32 + 6 + 6 + 6 us at 512 frames).  Arithmetic of the update: adam_dev_kernel's (train_ops.hip), bit for bit.
+// 32 + 6 + 6 + 6 us at 512 frames).  Arithmetic of the update: adam_dev_kernel's (train_ops.hip), bit for bit (grl_common.h adam_element).
 struct FoldTail {
   long long d_param, d_m, d_v;     // element offsets from a gradient entry to its parameter / first moment / second moment
   const float* lr_dev;
@@ -866,15 +866,7 @@ struct FoldTail {
   int pairs_rank, pairs_world;     // float pairs (grl_report.h trpl_write_record_pairs) instead of evaluating the reported values
 };
 GRL_DEVINL void adam_apply(float g, float* __restrict__ gp, const FoldTail& t, float lr, float bc1, float bc2_sqrt) {
-  float* p = gp + t.d_param;
-  float* m = gp + t.d_m;
-  float* v = gp + t.d_v;
-  const float mi = t.b1 * *m + (1.f - t.b1) * g;
-  const float vi = t.b2 * *v + (1.f - t.b2) * g * g;
-  *m = mi;
-  *v = vi;
-  const float denom = sqrtf(vi) / bc2_sqrt + t.eps;
-  *p -= (lr / bc1) * (mi / denom);
+  adam_element(g, gp[t.d_param], gp[t.d_m], gp[t.d_v], t.b1, t.b2, t.eps, lr / bc1, bc2_sqrt);
 }
 // float4 variant: a wave covers 4 rows x 64 columns per load (16 lanes x float4 per row, lane >> 4 picks the row), so a
 // workgroup still owns only 64 columns -- tall thin slabs (1024-2048 rows x 4096 columns) need that many workgroups: with 256

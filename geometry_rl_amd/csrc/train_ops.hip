@@ -8,21 +8,15 @@
 
 namespace {
 
-// torch.optim.Adam (no amsgrad, no weight decay): m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2;
-// p -= lr / (1-b1^t) * m / (sqrt(v) / sqrt(1-b2^t) + eps).   scale = optional gradient pre-scale (1/world, clip coefficient)
+// torch.optim.Adam (no amsgrad, no weight decay), one element at a time by grl_common.h adam_element (the arithmetic all forms share):
+// bc1 = 1-b1^t, bc2_sqrt = sqrt(1-b2^t).   scale = optional gradient pre-scale (1/world, clip coefficient)
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                   float* __restrict__ v, int n, float lr, float b1, float b2, float eps,
                                                   float bc1, float bc2_sqrt, const float* __restrict__ scale_dev,
                                                   float scale_host) {
-  const float scale = scale_host * (scale_dev ? scale_dev[0] : 1.f);
+  const float scale = scale_host * (scale_dev ? scale_dev[0] : 1.f), lr_bc1 = lr / bc1;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const float gi = g[i] * scale;
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] -= (lr / bc1) * (mi / denom);
+    adam_element(g[i] * scale, p[i], m[i], v[i], b1, b2, eps, lr_bc1, bc2_sqrt);
   }
 }
 
@@ -35,15 +29,9 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, co
   const float t = (float)step_dev[0];
   const float lr = lr_dev[0];   // learning rate in device memory: an annealed rate (train.py:264-271) reaches a replayed graph
   const float bc1 = 1.f - powf(b1, t), bc2_sqrt = sqrtf(1.f - powf(b2, t));
-  const float scale = scale_host * (scale_dev ? scale_dev[0] : 1.f);
+  const float scale = scale_host * (scale_dev ? scale_dev[0] : 1.f), lr_bc1 = lr / bc1;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const float gi = g[i] * scale;
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] -= (lr / bc1) * (mi / denom);
+    adam_element(g[i] * scale, p[i], m[i], v[i], b1, b2, eps, lr_bc1, bc2_sqrt);
   }
 }
 
@@ -62,15 +50,9 @@ __global__ __launch_bounds__(256) void adam_dev_report_pairs_kernel(float* __res
   }
   const float t = (float)step_dev[0];
   const float lr = lr_dev[0];
-  const float bc1 = 1.f - powf(b1, t), bc2_sqrt = sqrtf(1.f - powf(b2, t));
+  const float bc1 = 1.f - powf(b1, t), bc2_sqrt = sqrtf(1.f - powf(b2, t)), lr_bc1 = lr / bc1;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += n_adam_blocks * blockDim.x) {
-    const float gi = g[i] * 1.f;            // (the same arithmetic as adam_dev_kernel with scale 1: bitwise its update)
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] -= (lr / bc1) * (mi / denom);
+    adam_element(g[i], p[i], m[i], v[i], b1, b2, eps, lr_bc1, bc2_sqrt);   // (adam_dev_kernel with scale 1: bitwise its update)
   }
 }
 
