@@ -50,6 +50,15 @@ class AgentConfig:
     # configs/algorithm/{trpl,ppo}.yaml: "trpl" (TRPLLoss + projection) or "ppo" (ClipPPOLoss2, no projection; objective/default.yaml)
     algorithm: str = "trpl"
     clip_epsilon: float = 0.2
+    # entropy control of the projection (configs/algorithm/projection/*.yaml: entropy_schedule, target_entropy, temperature, entropy_eq,
+    # entropy_first; utils_algo_graph.py:246-253 adds total_train_steps): None / False = off, "linear" | "exp" = the scheduled entropy
+    # projection runs inside the fused loss launch (TRPLLoss(entropy_control=True))
+    entropy_schedule: Optional[str] = None
+    target_entropy: float = 0.0
+    temperature: float = 0.5
+    entropy_eq: bool = False
+    entropy_first: bool = False
+    total_train_steps: Optional[int] = None
 
 
 def build_agent(spec: TaskSpec, cfg: AgentConfig, device="cuda", group=None):
@@ -99,10 +108,12 @@ def build_agent(spec: TaskSpec, cfg: AgentConfig, device="cuda", group=None):
                             critic_in_features=spec.in_features, group=group)
         return actor, critic, None, loss
     projection = KLProjectionLayer(proj_type=cfg.proj_type, mean_bound=cfg.mean_bound, cov_bound=cfg.cov_bound,
-                                   trust_region_coeff=cfg.trust_region_coeff, scale_prec=True, entropy_schedule=False, action_dim=A)
+                                   trust_region_coeff=cfg.trust_region_coeff, scale_prec=True, entropy_schedule=cfg.entropy_schedule or False,
+                                   action_dim=A, total_train_steps=cfg.total_train_steps, target_entropy=cfg.target_entropy,
+                                   temperature=cfg.temperature, entropy_eq=cfg.entropy_eq, entropy_first=cfg.entropy_first)
     loss = TRPLLoss(actor, critic, projection=projection, entropy_coef=cfg.entropy_coef, critic_coef=cfg.critic_coef,
                     clip_value=cfg.clip_value, loss_critic_type="l2", normalize_advantage=True, in_features=a_in,
-                    critic_in_features=spec.in_features, group=group)
+                    critic_in_features=spec.in_features, group=group, entropy_control=bool(cfg.entropy_schedule))
     return actor, critic, projection, loss
 
 
@@ -203,6 +214,11 @@ class PolicyUpdater:
         # learning rate, device side: the recorded Adam launches read it, so an annealed rate (train.py:264-271 writes
         # ``group["lr"] = lr * alpha`` before every iteration; configs/algorithm/optim/default.yaml:5) takes effect under replay
         self.lr_dev = torch.full((1,), float(lr), device=dev, dtype=torch.float32)
+        # entropy bounds, device side (TRPL with entropy control): one entry per step of a launch.  The fused loss launch of step j of a
+        # launch reads entry j; the host fills the entries stream-ordered in front of the launch (_entropy_prepare), so recorded programs
+        # replay a moving bound unchanged -- the bound is data, like lr_dev
+        self.BETA_SLOTS = 64
+        self.beta_table = torch.zeros(self.BETA_SLOTS, device=dev, dtype=torch.float64)
         self._lr = float(lr)
         self.use_graph = use_graph
         if use_graph and getattr(loss_module.actor_network, "post_fc", False):
@@ -287,6 +303,23 @@ class PolicyUpdater:
             self._program, self._epoch = None, None
         self._loss_ptr = ptr
 
+    def _entropy_prepare(self, batch, n_steps: int = 1):
+        """TRPL with entropy control: latch the layer's initial entropy at the first update (from ``batch``; data parallel: the global
+        mean, one all-reduce, outside every recorded program) and write the bounds of updates ``steps .. steps + n_steps - 1`` into the
+        table's first entries on the current stream.  No synchronisation once the initial entropy is known."""
+        from .trpl import entropy_active, latch_initial_entropy
+        m = self.loss_module
+        if not entropy_active(m):
+            return
+        if m.projection.initial_entropy is None:
+            b = batch
+            if b is None or ("var" not in b and "covariance_matrix" not in b):
+                raise ValueError("the first update with entropy control needs the old distribution (loc, var) in the minibatch")
+            latch_initial_entropy(m, b)
+        if n_steps > self.BETA_SLOTS:
+            raise ValueError(f"{n_steps} steps per launch with entropy control: the bound table has {self.BETA_SLOTS} entries")
+        ops.write_doubles(self.beta_table, m.projection.entropy_bounds(range(self.steps, self.steps + n_steps)))
+
     def anneal_lr(self, base_lr: float, iteration: int, total_iterations: int) -> float:
         """train.py:264-271: ``alpha = 1 - i / total; lr = base_lr * alpha`` for both optimisers."""
         self.lr = base_lr * (1.0 - iteration / float(total_iterations))
@@ -359,6 +392,7 @@ class PolicyUpdater:
         st["obs"] = [b[k] for k in m.in_features]
         st["cobs"] = [b[k] for k in m.critic_in_features]
         st["zw"] = torch.empty(26, device=self.flat.device, dtype=torch.float64)
+        st.setdefault("beta", self.beta_table[0:1])   # (entropy control: the bound this step's loss launch reads; _compile_epoch sets entry j)
 
     def _actor_head(self, st, adv, adv_local):
         """Actor forward + fused loss kernel (actor terms only) + actor backward; -> the loss kernel's fold handle."""
@@ -370,7 +404,7 @@ class PolicyUpdater:
         loc, sigma = actor.forward_diag(*st["obs"], train=True)
         with torch.no_grad():
             fold_, _mx, dloc, dsigma, _ = trpl_launch(m, loc, sigma, None, st["b"], adv, sums=sums, maxes=maxes, defer_fold=True,
-                                                      adv_local=adv_local)
+                                                      adv_local=adv_local, beta=st["beta"])
         st.update(loc=loc.detach(), sigma=sigma.detach())
         # the lift's and the fiber basis' backward launches only feed the tail's fold: the first of the two waits for the other and they
         # share ONE launch (ops._tail_pre_offer)
@@ -424,7 +458,7 @@ class PolicyUpdater:
             with torch.no_grad():
                 zw = st["zw"]
                 sums, maxes, dloc, dsigma, dvalue = trpl_launch(m, loc, sigma, value, st["b"], st["adv"], sums=zw[10:22],
-                                                                maxes=zw[22:23].view(torch.int32))
+                                                                maxes=zw[22:23].view(torch.int32), beta=st["beta"])
             torch.autograd.backward([loc, sigma], [dloc, dsigma])
             with torch.no_grad():
                 pipe.bwd3(dvalue)
@@ -934,7 +968,7 @@ class PolicyUpdater:
             return lambda: hip.call("grl_gather_rows_many", *args, row, B)
         sts, mains, critics = [], [], []
         for j in range(U):
-            st = {}
+            st = {"beta": self.beta_table[j:j + 1]}   # (entropy control: step j of a launch reads ITS bound)
             self._plan_lanes(sa, st, cbatch=sc, gate_override=gate)
             main_all, critic_all = st.pop("lanes")
             mains.append((gather(ga, j), main_all))
@@ -962,6 +996,7 @@ class PolicyUpdater:
         """``rows`` [U, B] (device int64): U steps as ONE recorded launch per lane, recorded first when ``key`` (_epoch_key) is not the
         recording's.  Returns the loss dict of the last step; ``self.last_outs`` holds those of all U."""
         U = int(rows.shape[0])
+        self._entropy_prepare(None, U)   # (the first update of a size has run eagerly: nothing is latched here)
         if self._epoch is None or self._epoch["key"] != key:
             self.loss_module._global_steps = self.steps
             self._compile_epoch(buf, rows[0], U, gate=gate)
@@ -1120,6 +1155,7 @@ class PolicyUpdater:
             with torch.no_grad():
                 actor.forward_diag(*[batch[k] for k in m.in_features], train=True)   # calibrates on this rank's shard
             self.sync_replicas()                                                       # ... and rank 0's factors win everywhere
+        self._entropy_prepare(batch)
         self.steps += 1
         try:
             return self._step(batch)

@@ -274,10 +274,12 @@ struct TrplPtrs {
   const float *tgt_mean, *tgt_S;
   int ms_row0;
   const float* clip_eps;   // PROJ 3 only: device float[1]
+  const double* ent_beta;  // ENT only: device double[1], the entropy bound of THIS launch (read when the kernel runs)
+  int ent_mode;            // ENT only: bit 0 = equality form (every frame is scaled), bit 1 = entropy stage in FRONT of the trust region
 };
 // The body for workgroup `blk` of a launch whose workgroups have NT threads: the first TRPL_FPB * L of them carry the frames (whole waves:
 // 64 / 128 / 256 threads), the others only take part in the advantage sums and in the barriers.
-template <int L, int PROJ, int NT>
+template <int L, int PROJ, int NT, bool ENT = false>
 GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, int blk, int tid) {
   const float* __restrict__ mean = q_.mean; const float* __restrict__ sigma = q_.sigma; const float* __restrict__ action = q_.action;
   const float* __restrict__ old_mean = q_.old_mean; const float* __restrict__ old_var = q_.old_var;
@@ -325,7 +327,24 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
   const double mu = mean[kms], sg = sigma[kms], ac = action[k];
   const double mo = PROJ == 3 ? 0.0 : (double)old_mean[k], So = PROJ == 3 ? 1.0 : (double)old_var[k];   // (PPO: no old distribution)
   const double S = sg * sg;                  // policy covariance diagonal == "std" seen by the projection (trpl.py:241)
-  const double t = S * S, o = So * So;       // kl_projection_layer.py:60-63: covariance(std) = std**2
+  // ---- (ENT) scheduled entropy projection in FRONT of the trust region: the projection below runs on (mu, Sx = alpha S)
+  bool e_act = false, e_first = false;
+  double e_alpha = 1.0, e_beta = 0.0, e_c = 0.0, inv_k = 0.0, Sx = S;
+  if (ENT) {
+    e_beta = q_.ent_beta[0];
+    e_first = (q_.ent_mode & 2) != 0;
+    // k/2 log(2 pi e): entropy = e_c + sum log x (gnn_gaussian_policy_diag.py:104-126).  Written as ONE product, unlike c_ent below: a
+    // common subexpression with it would change how c_ent + sum log S is contracted, and the inactive stage would no longer be bitwise free
+    e_c = (double)A * 1.4189385332046727418;
+    inv_k = 1.0 / (double)A;
+    if (e_first) {
+      const double ent = e_c + gsum<L>(M(log(S)));
+      e_act = (q_.ent_mode & 1) != 0 || ent < e_beta;
+      e_alpha = exp((e_beta - ent) * inv_k);
+      Sx = e_act ? e_alpha * S : S;
+    }
+  }
+  const double t = Sx * Sx, o = So * So;     // kl_projection_layer.py:60-63: covariance(std) = std**2
   // ---- mean projection (base_projection_layer.py:71-100)
   double mp = 0.0;
   if (PROJ != 3) { const double d = (mu - mo) / So; mp = gsum<L>(M(d * d)); }
@@ -380,14 +399,14 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
     v = t;
     pS = S;
   } else if (PROJ == 4) {
-    const double r = 1.0 - S / So;
+    const double r = 1.0 - Sx / So;
     w_tot = mp + gsum<L>(M(r * r));
     c_act = w_tot > cfg.mean_bound + cfg.cov_bound;
-    pS = S;
+    pS = Sx;
     if (c_act) {
       w_t = sqrt((cfg.mean_bound + cfg.cov_bound) / (w_tot + 1e-16));
       pm = (1.0 - w_t) * mo + w_t * mu;
-      w_d = (1.0 - w_t) + w_t * S * So;
+      w_d = (1.0 - w_t) + w_t * Sx * So;
       w_x = w_d * w_d * (So * So);
       w_n = sqrt(gsum<L>(M(w_x * w_x)));
       double y = w_x / w_n, z = 1.0;
@@ -403,18 +422,27 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
     }
     v = pS * pS;
   } else {
-    const double d = PROJ == 1 ? o - t : 1.0 - S / So;
+    const double d = PROJ == 1 ? o - t : 1.0 - Sx / So;
     const double part = gsum<L>(M(d * d));
     c_act = part > cfg.cov_bound;
     if (c_act) eta = fabs(sqrt(part / cfg.cov_bound) - 1.0);
     const double den = 1.0 + eta + 1e-16;
-    if (PROJ == 1) { v = c_act ? (t + eta * o) / den : t; pS = c_act ? sqrt(v) : S; }
-    else { pS = c_act ? (S + eta * So) / den : S; v = pS * pS; }
+    if (PROJ == 1) { v = c_act ? (t + eta * o) / den : t; pS = c_act ? sqrt(v) : Sx; }
+    else { pS = c_act ? (Sx + eta * So) / den : Sx; v = pS * pS; }
   }
   if (ext) {
     pm = tgt_mean[k];
     pS = tgt_S[k];
     v = pS * pS;
+  }
+  // ---- (ENT) scheduled entropy projection BEHIND the trust region: pS <- alpha pS; everything below (log-prob, entropy bonus, regression
+  //      target, metrics) sees the scaled pS, the projection's backward its own output pS0 (and v = pS0^2)
+  const double pS0 = pS;
+  if (ENT && !e_first) {
+    const double ent = e_c + gsum<L>(M(log(pS0)));
+    e_act = (q_.ent_mode & 1) != 0 || ent < e_beta;
+    e_alpha = exp((e_beta - ent) * inv_k);
+    pS = e_act ? e_alpha * pS0 : pS0;
   }
   // ---- log-prob under the projected distribution, importance weight, objective
   const double LOG2PI = 1.8378770664093454836;
@@ -480,6 +508,10 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
     g_pm -= ctr * 2.0 * (mu - pm) / (S * S);
     g_pS -= ctr * 2.0 * (S - pS);
   }
+  if (ENT && !e_first && e_act) {   // y = alpha(x) x, x = pS0:  g_x_i = alpha (g_y_i - (sum_j g_y_j x_j) / (k x_i))
+    const double dot = gsum<L>(M(g_pS * pS0));
+    g_pS = e_alpha * (g_pS - dot * inv_k / pS0);
+  }
   double gmu, gS;
   if (m_act && !ext) {
     const double dot = gsum<L>(M(g_pm * (mo - pm) / D));
@@ -488,19 +520,19 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
   } else gmu = g_pm;
   if (ext) gS = 0.0;
   else if (PROJ == 0) {
-    const double gv = g_pS / (2.0 * pS);
+    const double gv = g_pS / (2.0 * pS0);
     if (c_act) {
       const double dvt = v * v / (t * t * (eta + 1.0));
       const double dve = -v * v * (1.0 / o - 1.0 / t) / ((eta + 1.0) * (eta + 1.0));
       const double gk = 0.5 * (1.0 / o - 1.0 / v);
       const double denom = gsum<L>(M(gk * dve)), num = gsum<L>(M(gv * dve));
-      gS = (gv * dvt - num * gk * dvt / denom) * 2.0 * S;
-    } else gS = gv * 2.0 * S;
+      gS = (gv * dvt - num * gk * dvt / denom) * 2.0 * Sx;
+    } else gS = gv * 2.0 * Sx;
   } else if (PROJ == 4) {
     gS = g_pS;   // (inside the bound: pass-through)
     if (c_act) {   // reverse of: pS = Y10 sqrt(n); the ten steps; Y0 = x / n, n = |x|; x = d^2 So^2; d, pm <- t <- mp + cp
       const double sn = sqrt(w_n);
-      double gy = g_pS * sn, gz = 0.0, gn = g_pS * pS * 0.5 / w_n;   // (pS * 0.5 / n = Y10 * 0.5 / sqrt(n))
+      double gy = g_pS * sn, gz = 0.0, gn = g_pS * pS0 * 0.5 / w_n;   // (pS0 * 0.5 / n = Y10 * 0.5 / sqrt(n))
 #pragma unroll
       for (int it = 9; it >= 0; --it) {
         const double y = ys[it], z = zs[it], T = 0.5 * (3.0 - z * y);
@@ -510,17 +542,21 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
       }
       gn = gsum<L>(M(gn - gy * w_x / (w_n * w_n)));
       const double gd = (gy / w_n + gn * w_x / w_n) * 2.0 * w_d * (So * So);
-      const double g_t = gsum<L>(M(g_pm * (mu - mo) + gd * (S * So - 1.0)));
+      const double g_t = gsum<L>(M(g_pm * (mu - mo) + gd * (Sx * So - 1.0)));
       const double g_tot = -0.5 * g_t * w_t / (w_tot + 1e-16);
       gmu = g_pm * w_t + g_tot * 2.0 * (mu - mo) / (So * So);
-      gS = gd * w_t * So - g_tot * 2.0 * (1.0 - S / So) / So;
+      gS = gd * w_t * So - g_tot * 2.0 * (1.0 - Sx / So) / So;
     }
   } else if (c_act) {
     const double den = 1.0 + eta + 1e-16, deta = 1.0 / (2.0 * (eta + 1.0) * cfg.cov_bound);
-    const double st_ = gsum<L>(M(PROJ == 1 ? g_pS / (2.0 * pS) * (o - v) / den : g_pS * (So - pS) / den));
-    if (PROJ == 1) gS = g_pS / (2.0 * pS) * 2.0 * S / den + st_ * deta * (-4.0 * (o - t) * S);
-    else gS = g_pS / den + st_ * deta * (-2.0 * (1.0 - S / So) / So);
+    const double st_ = gsum<L>(M(PROJ == 1 ? g_pS / (2.0 * pS0) * (o - v) / den : g_pS * (So - pS0) / den));
+    if (PROJ == 1) gS = g_pS / (2.0 * pS0) * 2.0 * Sx / den + st_ * deta * (-4.0 * (o - t) * Sx);
+    else gS = g_pS / den + st_ * deta * (-2.0 * (1.0 - Sx / So) / So);
   } else gS = g_pS;
+  if (ENT && e_first && e_act) {   // y = alpha(x) x, x = S: between the projection's backward and the regression term's direct gradient
+    const double dot = gsum<L>(M(gS * S));
+    gS = e_alpha * (gS - dot * inv_k / S);
+  }
   if (PROJ == 0) {
     gmu += ctr * (mu - pm) / (pS * pS);
     gS += ctr * (S / (pS * pS) - 1.0 / S);
@@ -593,6 +629,11 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
 template <int L, int PROJ>
 __global__ __launch_bounds__(TRPL_FPB * L) void trpl_lanes_kernel(TrplCfg cfg, TrplPtrs q_, int B) {
   trpl_lanes_body<L, PROJ, TRPL_FPB * L>(cfg, q_, B, (int)blockIdx.x, (int)threadIdx.x);
+}
+// the same with the scheduled entropy projection (ENT): instances of their own, the ones above are untouched
+template <int L, int PROJ>
+__global__ __launch_bounds__(TRPL_FPB * L) void trpl_lanes_ent_kernel(TrplCfg cfg, TrplPtrs q_, int B) {
+  trpl_lanes_body<L, PROJ, TRPL_FPB * L, true>(cfg, q_, B, (int)blockIdx.x, (int)threadIdx.x);
 }
 
 // slots [n_blocks][14] -> sums[12] (written, not accumulated) and maxes[2] (float bits); fixed order (grl_report.h trpl_fold_columns)
@@ -775,15 +816,22 @@ static int trpl_launch(const double* cfg9, int action_dim, const float* mean, co
                        const float* old_mean, const float* old_var, const float* old_logp, const float* advantage,
                        const float* value, const float* old_value, const float* value_target, float* dmean, float* dsigma,
                        float* dvalue, float* proj_mean, float* proj_var, const double* adv_stats, double* sums,
-                       unsigned int* maxes, double* slots, const float* tgt_mean, const float* tgt_S, int batch, hipStream_t stream) {
+                       unsigned int* maxes, double* slots, const float* tgt_mean, const float* tgt_S, int batch, hipStream_t stream,
+                       int ent_mode = -1, const double* ent_beta = nullptr) {
   if (action_dim > 16 || action_dim < 1 || batch < 1 || !slots) return -2;
+  if (ent_mode >= 0 && (ent_mode > 3 || !ent_beta || tgt_mean)) return -2;
   TrplCfg c{cfg9[0], cfg9[1], cfg9[2], cfg9[3], cfg9[4], cfg9[5], cfg9[6], cfg9[7], action_dim, (int)cfg9[9]};
   const int proj = (int)cfg9[8];
   if (proj < 0 || proj > 4 || proj == 3) return -3;   // (3, the PPO mode, has its own entry point: grl_ppo_fwd_bwd)
   const TrplPtrs tp{mean, sigma, action, old_mean, old_var, old_logp, advantage, value, old_value, value_target, dmean, dsigma, dvalue,
-                    proj_mean, proj_var, adv_stats, slots, tgt_mean, tgt_S, 0, nullptr};
-#define GRL_TRPL_LAUNCH(LL, PJ)                                                                                                       \
-  hipLaunchKernelGGL((trpl_lanes_kernel<LL, PJ>), dim3(trpl_blocks(batch)), dim3(TRPL_FPB * LL), 0, stream, c, tp, batch)
+                    proj_mean, proj_var, adv_stats, slots, tgt_mean, tgt_S, 0, nullptr, ent_beta, ent_mode < 0 ? 0 : ent_mode};
+#define GRL_TRPL_LAUNCH(LL, PJ)                                                                                                           \
+  do {                                                                                                                                    \
+    if (ent_mode < 0)                                                                                                                     \
+      hipLaunchKernelGGL((trpl_lanes_kernel<LL, PJ>), dim3(trpl_blocks(batch)), dim3(TRPL_FPB * LL), 0, stream, c, tp, batch);            \
+    else                                                                                                                                  \
+      hipLaunchKernelGGL((trpl_lanes_ent_kernel<LL, PJ>), dim3(trpl_blocks(batch)), dim3(TRPL_FPB * LL), 0, stream, c, tp, batch);        \
+  } while (0)
 #define GRL_TRPL_WIDTH(PJ)                                        \
   do {                                                            \
     if (action_dim <= 4) GRL_TRPL_LAUNCH(4, PJ);                  \
@@ -815,7 +863,7 @@ int grl_ppo_fwd_bwd(const double* cfg6, const float* clip_eps, int action_dim, c
   if (value && (!old_value || !value_target || !dvalue)) return -2;
   const TrplCfg c{0.0, 0.0, 0.0, cfg6[0], cfg6[1], cfg6[2], cfg6[3], cfg6[4], action_dim, (int)cfg6[5]};
   const TrplPtrs tp{mean, sigma, action, nullptr, nullptr, old_logp, advantage, value, old_value, value_target, dmean, dsigma, dvalue,
-                    nullptr, nullptr, adv_stats, slots, nullptr, nullptr, 0, clip_eps};
+                    nullptr, nullptr, adv_stats, slots, nullptr, nullptr, 0, clip_eps, nullptr, 0};
   if (action_dim <= 4) hipLaunchKernelGGL((trpl_lanes_kernel<4, 3>), dim3(trpl_blocks(batch)), dim3(TRPL_FPB * 4), 0, stream, c, tp, batch);
   else if (action_dim <= 8) hipLaunchKernelGGL((trpl_lanes_kernel<8, 3>), dim3(trpl_blocks(batch)), dim3(TRPL_FPB * 8), 0, stream, c, tp, batch);
   else hipLaunchKernelGGL((trpl_lanes_kernel<16, 3>), dim3(trpl_blocks(batch)), dim3(TRPL_FPB * 16), 0, stream, c, tp, batch);
@@ -841,6 +889,41 @@ int grl_trpl_fwd_bwd(const double* cfg9, int action_dim, const float* mean, cons
                      unsigned int* maxes, double* slots, int batch, hipStream_t stream) {
   return trpl_launch(cfg9, action_dim, mean, sigma, action, old_mean, old_var, old_logp, advantage, value, old_value, value_target,
                      dmean, dsigma, dvalue, proj_mean, proj_var, adv_stats, sums, maxes, slots, nullptr, nullptr, batch, stream);
+}
+
+// The same launch with the scheduled entropy projection (base_projection_layer.py:14-68, 232-273) inside it.  ent_mode: bit 0 = equality
+// form, bit 1 = entropy stage in front of the trust region (entropy_first); ent_beta: DEVICE double[1], the bound of this step, read when
+// the kernel runs (a recorded launch sees every write to it).  Derivation: include/grl_hip.h.
+int grl_trpl_fwd_bwd_ent(const double* cfg9, int action_dim, const float* mean, const float* sigma, const float* action,
+                         const float* old_mean, const float* old_var, const float* old_logp, const float* advantage,
+                         const float* value, const float* old_value, const float* value_target, float* dmean, float* dsigma,
+                         float* dvalue, float* proj_mean, float* proj_var, const double* adv_stats, double* sums,
+                         unsigned int* maxes, double* slots, int batch, int ent_mode, const double* ent_beta, hipStream_t stream) {
+  if (ent_mode < 0 || ent_mode > 3 || !ent_beta) return -2;
+  return trpl_launch(cfg9, action_dim, mean, sigma, action, old_mean, old_var, old_logp, advantage, value, old_value, value_target,
+                     dmean, dsigma, dvalue, proj_mean, proj_var, adv_stats, sums, maxes, slots, nullptr, nullptr, batch, stream, ent_mode,
+                     ent_beta);
+}
+
+// n <= 16 doubles handed over BY VALUE (kernel arguments) and written to device memory by one small launch, stream-ordered: how the host
+// fills the entropy bounds that recorded launches read (no staging buffer whose reuse would have to be fenced, no synchronisation)
+struct WriteDoubles { double v[16]; };
+__global__ __launch_bounds__(64) void write_doubles_kernel(WriteDoubles w, double* __restrict__ dst, int n) {
+  const int i = (int)threadIdx.x;
+  if (i < n) {
+    double x = w.v[0];
+#pragma unroll
+    for (int j = 1; j < 16; ++j) x = i == j ? w.v[j] : x;
+    dst[i] = x;
+  }
+}
+int grl_write_doubles(double* dst, const double* host_values, int n, hipStream_t stream) {
+  if (!dst || !host_values || n < 1 || n > 16) return -2;
+  WriteDoubles w;
+  for (int j = 0; j < 16; ++j) w.v[j] = j < n ? host_values[j] : 0.0;
+  hipLaunchKernelGGL(write_doubles_kernel, dim3(1), dim3(64), 0, stream, w, dst, n);
+  GRL_CHECK_LAUNCH();
+  return 0;
 }
 
 // Boundary methods of the projection layer (base_projection_layer.py:292-327 get_trust_region_loss, :332-384 compute_metrics) for

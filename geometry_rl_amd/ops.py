@@ -927,14 +927,20 @@ TRPL_SUM_KEYS = ("loss_objective", "loss_trust_region", "entropy_dist", "loss_cr
 
 def trpl_fwd_bwd(loc, sigma, batch, value, *, mean_bound, cov_bound, trust_region_coeff, entropy_coef, critic_coef, clip_value,
                  global_batch: int, adv_stats: Optional[torch.Tensor], want_projection: bool = False, sums=None, maxes=None,
-                 proj_type: int = 0, defer_fold: bool = False, adv_local: bool = False):
+                 proj_type: int = 0, defer_fold: bool = False, adv_local: bool = False, ent_mode: Optional[int] = None,
+                 ent_beta: Optional[torch.Tensor] = None):
     """Launches the fused TRPL kernel (proj_type 0 KL | 1 Frobenius | 2 Wasserstein | 4 non-commuting Wasserstein).  Returns (sums fp64[12], maxes u32[2], dloc,
     dsigma, dvalue, proj_mean, proj_var).  ``defer_fold``: the per-workgroup slots are not folded into ``sums`` / ``maxes`` by this call;
-    the returned ``sums`` is then a callable that does it (on whatever stream is current when it is called) and returns (sums, maxes)."""
+    the returned ``sums`` is then a callable that does it (on whatever stream is current when it is called) and returns (sums, maxes).
+    ``ent_mode`` (not None): the scheduled entropy projection runs inside the launch (grl_trpl_fwd_bwd_ent) -- bit 0 equality form, bit 1
+    entropy in front of the trust region; ``ent_beta``: a device float64 tensor of one element, the bound, read by the kernel when it
+    runs (a recorded launch sees every write to it)."""
     import ctypes
     hip.check_f32(loc, sigma)
     B, A = loc.shape
     dev = loc.device
+    if ent_mode is not None and (ent_beta is None or ent_beta.dtype != torch.float64 or ent_beta.numel() != 1 or ent_beta.device != dev):
+        raise ValueError("ent_beta must be a one-element float64 tensor on the policy's device")
     cfg = (ctypes.c_double * 10)(mean_bound, cov_bound, trust_region_coeff, entropy_coef, critic_coef,
                                  clip_value if clip_value else 0.0, 1.0 / global_batch, float(global_batch), float(proj_type),
                                  1.0 if adv_local else 0.0)   # adv_local: the batch's advantage statistics are summed inside the kernel
@@ -947,12 +953,14 @@ def trpl_fwd_bwd(loc, sigma, batch, value, *, mean_bound, cov_bound, trust_regio
     pm = torch.empty_like(loc) if want_projection else None
     pv = torch.empty_like(loc) if want_projection else None
     f = lambda t: t.reshape(B, -1).contiguous() if t.dim() > 1 else t.contiguous()
-    hip.call("grl_trpl_fwd_bwd", cfg, A, loc.contiguous(), sigma.contiguous(), f(batch["action"]), f(batch["loc"]), f(batch["var"]),
+    hip.call("grl_trpl_fwd_bwd" if ent_mode is None else "grl_trpl_fwd_bwd_ent", cfg, A, loc.contiguous(), sigma.contiguous(),
+             f(batch["action"]), f(batch["loc"]), f(batch["var"]),
              batch["sample_log_prob"].reshape(B).contiguous(), batch["advantage"].reshape(B).contiguous(),
              value.reshape(B).contiguous() if value is not None else None,
              batch["state_value"].reshape(B).contiguous() if value is not None else None,
              batch["value_target"].reshape(B).contiguous() if value is not None else None,
-             dloc, dsigma, dvalue, pm, pv, adv_stats, None if defer_fold else sums, maxes, slots, B)
+             dloc, dsigma, dvalue, pm, pv, adv_stats, None if defer_fold else sums, maxes, slots, B,
+             *(() if ent_mode is None else (int(ent_mode), ent_beta)))
     if defer_fold:
         def fold(sums=sums, maxes=maxes, slots=slots):
             hip.call("grl_trpl_fold", slots, B, sums, maxes)
@@ -960,6 +968,18 @@ def trpl_fwd_bwd(loc, sigma, batch, value, *, mean_bound, cov_bound, trust_regio
         fold.slots, fold.batch, fold.sums, fold.maxes = slots, B, sums, maxes   # (for a caller that folds and reports in one launch)
         return fold, maxes, dloc, dsigma, dvalue, pm, pv
     return sums, maxes, dloc, dsigma, dvalue, pm, pv
+
+
+def write_doubles(dst: torch.Tensor, values) -> None:
+    """dst[:len(values)] = values (a device float64 tensor, host floats): the values travel as kernel arguments of small launches on the
+    current stream (grl_write_doubles, 16 per launch) -- stream-ordered, no staging buffer, no synchronisation."""
+    import ctypes
+    vals = [float(v) for v in values]
+    if dst.dtype != torch.float64 or not dst.is_cuda or dst.numel() < len(vals):
+        raise ValueError("write_doubles: a device float64 tensor with room for the values")
+    for i in range(0, len(vals), 16):
+        part = vals[i:i + 16]
+        hip.call("grl_write_doubles", dst[i:i + len(part)], (ctypes.c_double * len(part))(*part), len(part))
 
 
 def ppo_fwd_bwd(loc, sigma, batch, value, *, clip_epsilon: torch.Tensor, entropy_coef, critic_coef, clip_value, global_batch: int,

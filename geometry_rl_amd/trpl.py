@@ -113,8 +113,9 @@ class KLProjectionLayer:
                  entropy_schedule=None, action_dim=None, total_train_steps=None, target_entropy=0.0, temperature=0.0,
                  entropy_eq=False, entropy_first=False, cpu=False, dtype=torch.float32, **ignored):
         # entropy control (base_projection_layer.py:176-185): the schedule, the bound and the two projections are here (pinned by the
-        # tier-2e fixture); the FUSED update kernel does not apply them -- TRPLLoss refuses a layer with an active schedule instead of
-        # silently skipping the entropy projection (no reference TRPL config turns it on: configs/algorithm/projection/kl.yaml:9)
+        # tier-2e fixture) as plain tensor arithmetic; the FUSED update kernel applies them inside its one launch when the loss module is
+        # built with ``entropy_control=True`` (opt-in: without it TRPLLoss refuses a layer with an active schedule instead of silently
+        # skipping the entropy projection; no reference TRPL config turns the schedule on: configs/algorithm/projection/kl.yaml:9)
         if entropy_schedule and not (action_dim and total_train_steps):
             raise AssertionError("entropy_schedule needs action_dim and total_train_steps (base_projection_layer.py:177)")
         self.entropy_schedule_type = entropy_schedule or None
@@ -135,6 +136,28 @@ class KLProjectionLayer:
         """base_projection_layer.py:329-330."""
         init = self.initial_entropy if self.initial_entropy is not None else torch.as_tensor(0.0)
         return self._entropy_schedule(init, torch.as_tensor(self.target_entropy, dtype=init.dtype, device=init.device), self.temperature, step)
+
+    @property
+    def has_entropy_control(self):
+        """base_projection_layer.py:386-388."""
+        return bool(self.entropy_schedule_type)
+
+    @property
+    def entropy_mode(self):
+        """The fused kernel's mode word (include/grl_hip.h grl_trpl_fwd_bwd_ent): bit 0 equality form, bit 1 entropy first."""
+        return (1 if self.entropy_eq else 0) | (2 if self.entropy_first else 0)
+
+    def entropy_bounds(self, steps):
+        """[float(get_entropy_bound(s)) for s in steps] without touching the device: the schedule's arithmetic (the reference's, in the
+        dtype of ``initial_entropy``) on a host copy of the latched initial entropy, fetched once."""
+        init = self.initial_entropy
+        if init is None:
+            raise RuntimeError("the initial entropy has not been latched yet (first update: trpl.latch_initial_entropy)")
+        if getattr(self, "_init_host_src", None) is not init:
+            self._init_host_src, self._init_host = init, torch.as_tensor(init).detach().cpu()
+        h = self._init_host
+        tgt = torch.as_tensor(self.target_entropy, dtype=h.dtype)
+        return [float(self._entropy_schedule(h, tgt, self.temperature, int(s))) for s in steps]
 
     def entropy_projection(self, policy, p, q, step):
         """The entropy half of base_projection_layer.py:200-205,266-283 on its own: latches the initial entropy (mean entropy of the OLD
@@ -197,9 +220,13 @@ class KLProjectionLayer:
             n = sums[10]
             mx = maxes.view(torch.float32)
             mc, cc = (sums[6] / n).float(), (sums[7] / n).float()
-            return OrderedDict(kl=(sums[11] / n).float(), constraint=mc + cc, mean_constraint=mc, cov_constraint=cc,
-                               entropy=(sums[8] / n).float(), entropy_diff=(sums[9] / n).float(), mean_constraint_max=mx[0],
-                               cov_constraint_max=mx[1])
+            out = OrderedDict(kl=(sums[11] / n).float(), constraint=mc + cc, mean_constraint=mc, cov_constraint=cc,
+                              entropy=(sums[8] / n).float(), entropy_diff=(sums[9] / n).float(), mean_constraint_max=mx[0],
+                              cov_constraint_max=mx[1])
+            if self.has_entropy_control:   # base_projection_layer.py:380-382: mean(entropy - bound(step)); one bound for the batch
+                assert step is not None, "compute_metrics of a layer with an entropy schedule needs the step"
+                out["entropy_constraint"] = out["entropy"] - torch.as_tensor(self.get_entropy_bound(step)).to(out["entropy"])
+            return out
 
 
 class FrobeniusProjectionLayer(KLProjectionLayer):
@@ -278,12 +305,37 @@ def adv_stats_local(m, batch, out):
     hip.call("grl_adv_stats", adv, out, adv.numel())
 
 
-def trpl_launch(m, loc, sigma, value, batch, adv_stats, sums=None, maxes=None, defer_fold=False, adv_local=False):
+def entropy_active(m) -> bool:
+    """Does this loss module's launch carry the scheduled entropy projection?  (opt-in AND a layer with a schedule)"""
+    return bool(getattr(m, "entropy_control", False) and getattr(getattr(m, "projection", None), "entropy_schedule_type", None))
+
+
+def latch_initial_entropy(m, batch) -> None:
+    """base_projection_layer.py:202-203: at the first update, ``initial_entropy`` = mean of policy.entropy(q) over the minibatch, q = the
+    OLD distribution (batch "loc", "var").  Data parallel: the mean over the GLOBAL minibatch (one all-reduce of sum and count, here,
+    outside every recorded program).  A value the caller set beforehand (resume) is kept."""
+    layer = m.projection
+    if layer.initial_entropy is not None:
+        return
+    var = batch["var"] if "var" in batch else batch["covariance_matrix"].diagonal(dim1=-2, dim2=-1)
+    with torch.no_grad():
+        ent = _entropy_of((None, var.reshape(var.shape[0], -1).float()))
+        if m.group is None:
+            layer.initial_entropy = ent.mean().detach()
+        else:
+            import torch.distributed as dist
+            t = torch.stack([ent.double().sum(), torch.as_tensor(float(ent.numel()), dtype=torch.float64, device=ent.device)])
+            dist.all_reduce(t, group=m.group)
+            layer.initial_entropy = (t[0] / t[1]).to(ent.dtype)
+
+
+def trpl_launch(m, loc, sigma, value, batch, adv_stats, sums=None, maxes=None, defer_fold=False, adv_local=False, beta=None):
     """One launch of the fused kernel on detached inputs: rank-local (sums, maxes) and the gradients of the (1/B_global-scaled)
     losses with respect to loc, sigma and value.  ``defer_fold``: see ops.trpl_fwd_bwd (``sums`` comes back as the folding callable).
     ``adv_local`` (one rank): the advantage statistics are summed inside the kernel; ``value=None``: actor-only (the critic's share of
     the loss comes from ``value_loss`` on the critic's lane).  A PPO loss module (``m.algorithm == "ppo"``) takes the same launch in
-    its PPO mode (ppo.ppo_launch): same slots, same returns."""
+    its PPO mode (ppo.ppo_launch): same slots, same returns.  With entropy control (``entropy_active(m)``) the launch is the one with
+    the entropy stage and reads its bound from ``beta`` (device float64[1]; default: the loss module's own buffer)."""
     if getattr(m, "algorithm", "trpl") == "ppo":
         from .ppo import ppo_launch
         return ppo_launch(m, loc, sigma, value, batch, adv_stats, sums=sums, maxes=maxes, defer_fold=defer_fold, adv_local=adv_local)
@@ -294,7 +346,8 @@ def trpl_launch(m, loc, sigma, value, batch, adv_stats, sums=None, maxes=None, d
         cov_bound=p.cov_bound, trust_region_coeff=p.trust_region_coeff,
         entropy_coef=m.entropy_coef if m.entropy_bonus else 0.0, critic_coef=m.critic_coef,
         clip_value=float(m.clip_value) if m.clip_value is not None else 0.0, global_batch=B * m.world_size, adv_stats=adv_stats,
-        sums=sums, maxes=maxes, proj_type=getattr(p, "proj_code", 0), defer_fold=defer_fold, adv_local=adv_local)
+        sums=sums, maxes=maxes, proj_type=getattr(p, "proj_code", 0), defer_fold=defer_fold, adv_local=adv_local,
+        **(dict(ent_mode=p.entropy_mode, ent_beta=beta if beta is not None else m.entropy_beta(loc.device)) if entropy_active(m) else {}))
     return sums, maxes, dloc, dsigma, dvalue
 
 
@@ -410,15 +463,20 @@ class TRPLLoss(_LossBase):
     def __init__(self, actor_network, critic_network, *, projection: KLProjectionLayer, clip_epsilon=0.2, entropy_bonus=True,
                  samples_mc_entropy=1, entropy_coef=0.01, critic_coef=1.0, trust_region_coef=1.0, loss_critic_type="l2",
                  normalize_advantage=True, gamma=None, separate_losses=False, clip_value=None, in_features=None, group=None,
-                 critic_in_features=None, **kwargs):
+                 critic_in_features=None, entropy_control=False, **kwargs):
         super().__init__()
         if loss_critic_type != "l2":
             raise NotImplementedError("loss_critic_type is l2 in configs/algorithm/objective/trpl.yaml:12")
         actor_network = _unwrap(actor_network, "forward_diag")
         critic_network = _unwrap(critic_network, "_network1")
-        if getattr(projection, "entropy_schedule_type", None):
+        # ``entropy_control=True`` (opt-in): a layer with an entropy schedule is accepted and its entropy projection runs inside the fused
+        # launch, the bound of update ``_global_steps`` read from device memory; without a schedule the flag changes nothing
+        self.entropy_control = bool(entropy_control)
+        self._entropy_beta = None
+        if getattr(projection, "entropy_schedule_type", None) and not self.entropy_control:
             raise NotImplementedError("an entropy schedule (base_projection_layer.py:266-283) is not applied by the fused update kernel; the "
-                                      "projection layer offers it on its own (KLProjectionLayer.entropy_projection / __call__)")
+                                      "projection layer offers it on its own (KLProjectionLayer.entropy_projection / __call__); pass "
+                                      "entropy_control=True to run it inside the fused launch")
         self.actor_network, self.critic_network, self.projection = actor_network, critic_network, projection
         self.trust_region_coef = trust_region_coef
         self.entropy_bonus, self.entropy_coef, self.critic_coef = entropy_bonus, float(entropy_coef), float(critic_coef)
@@ -438,6 +496,13 @@ class TRPLLoss(_LossBase):
         import torch.distributed as dist
         return dist.get_world_size(self.group)
 
+    def entropy_beta(self, device):
+        """The loss module's own one-element device buffer (float64) of the entropy bound: what the eager ``forward`` writes and its launch
+        reads (PolicyUpdater hands its recorded launches entries of a table of its own instead)."""
+        if self._entropy_beta is None or self._entropy_beta.device != device:
+            self._entropy_beta = torch.zeros(1, device=device, dtype=torch.float64)
+        return self._entropy_beta
+
     @property
     def out_keys(self):   # trpl.py:155-170 (+ the TRPL entries forward() sets, :302-321)
         keys = ["loss_objective", "loss_trust_region"]
@@ -455,6 +520,9 @@ class TRPLLoss(_LossBase):
         obs = [b[k] for k in self.in_features]
         loc, sigma = self.actor_network.forward_diag(*obs, train=True)
         value = self.critic_network(*[b[k] for k in self.critic_in_features]) if self.critic_coef else None
+        if entropy_active(self):   # the bound of update ``_global_steps`` (train.py:275: the count before the update), stream-ordered
+            latch_initial_entropy(self, b)
+            ops.write_doubles(self.entropy_beta(loc.device), self.projection.entropy_bounds([self._global_steps]))
         actor, critic, mt = _run_trpl(self, loc, sigma, value, b)
         out = {
             "loss_objective": actor - (mt["loss_trust_region"] + mt["loss_entropy"]),  # value = objective; gradient = d(actor loss)

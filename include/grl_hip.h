@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 /* ABI version (major*10000 + minor*100 + patch); grl_version() returns the value the library was built with. */
-#define GRL_HIP_VERSION 209   /* 209: three exports removed (the device-cursor variant of grl_gather_rows_many, the hipStreamWaitValue32 capability query, the idle spin kernel of calib.hip); 208: cfg9[8] = 4 accepted (non-commuting Wasserstein projection), no signature change; 207: grl_ppo_fwd_bwd added (clipped PPO objective); 206: grl_build_features_noise, grl_step_head_noise[_bf16] added (training noise); 205 (round 6): grl_source_hash added; 204 (round 5): grl_head_fused / grl_head_fused_rows removed, grl_calib_mfma / grl_calib_copy added; the exports are exactly this header */
+#define GRL_HIP_VERSION 210   /* 210: grl_trpl_fwd_bwd_ent (scheduled entropy projection inside the fused TRPL launch) and grl_write_doubles added, no existing signature changed; 209: three exports removed (the device-cursor variant of grl_gather_rows_many, the hipStreamWaitValue32 capability query, the idle spin kernel of calib.hip); 208: cfg9[8] = 4 accepted (non-commuting Wasserstein projection), no signature change; 207: grl_ppo_fwd_bwd added (clipped PPO objective); 206: grl_build_features_noise, grl_step_head_noise[_bf16] added (training noise); 205 (round 6): grl_source_hash added; 204 (round 5): grl_head_fused / grl_head_fused_rows removed, grl_calib_mfma / grl_calib_copy added; the exports are exactly this header */
 int grl_version(void);
 /* The hash of the sources this binary was built from (16 hex digits + NUL into buf; returns the length).  geometry_rl_amd/hip.py
    source_hash() recomputes it from csrc/, this header and the build's flag tables and refuses a library that disagrees. */
@@ -284,6 +284,30 @@ int grl_ppo_fwd_bwd(const double* cfg6, const float* clip_eps, int action_dim, c
                     const float* old_logp, const float* advantage, const float* value, const float* old_value, const float* value_target,
                     float* dmean, float* dsigma, float* dvalue, const double* adv_stats, double* sums, unsigned int* maxes, double* slots,
                     int batch, hipStream_t stream);
+/* (ABI 210) grl_trpl_fwd_bwd with the projection layer's second half inside the launch: the scheduled ENTROPY projection
+ * (base_projection_layer.py:14-68 entropy_inequality_projection / entropy_equality_projection, :232-273 their place around the trust-region
+ * projection; utils/projection_utils.py:252-280 the schedule that yields the bound).  Notation of the kernel: x = the "std" diagonal the
+ * stage scales, k = action_dim, ent(x) = k/2 log(2 pi e) + sum_i log x_i (what policy.entropy returns for the diagonal policy),
+ *   alpha = exp((beta - ent(x)) / k),   y_i = alpha x_i   =>   ent(y) = ent(x) + k log alpha = beta.
+ * ent_mode bit 0 (entropy_eq): 1 = every frame is scaled (equality), 0 = only frames with ent(x) < beta (inequality; the others pass).
+ * ent_mode bit 1 (entropy_first): 0 = x is the trust-region projection's output pS; log-prob, entropy bonus, regression target and metrics
+ *   see y.  1 = x is the policy's own S and the trust-region projection runs on (mean, y); regression loss and metrics still compare the
+ *   ORIGINAL (mean, S) with the result (objectives/trpl.py:244, 306, 318).
+ * Backward: d alpha / d x_j = -alpha / (k x_j), so for an upstream gradient g_y
+ *   g_x_i = alpha (g_y_i - (sum_j g_y_j x_j) / (k x_i))   on scaled frames, g_x = g_y elsewhere (the frame's mask has no gradient):
+ * one more sum over the frame's lanes.  Position 0: between d loss / d pS and the projection's backward (which keeps its own output as
+ * linearisation point); position 1: between the projection's backward and the regression term's direct gradient at the original S.
+ * ent_beta: DEVICE double[1], the bound of this step, read when the kernel runs -- a recorded launch sees every write to it (like clip_eps
+ * of grl_ppo_fwd_bwd and lr_dev of the Adam launches).  Everything else (cfg9, slots, sums, maxes, folds, records) as grl_trpl_fwd_bwd;
+ * with beta = -inf in the inequality form the outputs are bitwise those of grl_trpl_fwd_bwd. */
+int grl_trpl_fwd_bwd_ent(const double* cfg9, int action_dim, const float* mean, const float* sigma, const float* action,
+                         const float* old_mean, const float* old_var, const float* old_logp, const float* advantage,
+                         const float* value, const float* old_value, const float* value_target, float* dmean, float* dsigma,
+                         float* dvalue, float* proj_mean, float* proj_var, const double* adv_stats, double* sums,
+                         unsigned int* maxes, double* slots, int batch, int ent_mode, const double* ent_beta, hipStream_t stream);
+/* (ABI 210) dst[0..n) = host_values[0..n), n <= 16: the values travel as kernel arguments of one small launch, stream-ordered (how the
+ * host fills the entropy bounds that recorded launches read; nothing is synchronised) */
+int grl_write_doubles(double* dst, const double* host_values, int n, hipStream_t stream);
 /* projection-layer boundary methods for an arbitrary DETACHED target (base_projection_layer.py:292-327 get_trust_region_loss,
  * :332-384 compute_metrics): the same kernel with its projection step skipped.  tgt_S = the target's "std" diagonal as the layer
  * sees it (= covariance diagonal of the policy).  sums[1] = trust_region_coeff * sum measure(p, target), sums[6..9,11] / maxes = the
