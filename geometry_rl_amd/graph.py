@@ -81,7 +81,8 @@ def rope_spec(n_links=80, G=2, variable_length=False) -> TaskSpec:
     ``variable_length`` (BASELINE config 5; not in the reference, which requires equal rope sizes within a batch,
     rope_tasks_data.py:127): an extra ``infos`` group carries ``links_num_points`` [B,1]; links / target points beyond that count are
     zero padding, treated exactly like the rigid tasks' padded object points -- no edges, dropped from the actor graph, still summed by
-    the DeepSets critic."""
+    the DeepSets critic.  No reference fixture can pin this form (tests/golden/tier3_*: the reference's rope builder connects all links);
+    it is held to its oracle tests alone."""
     spec = _rope_spec(n_links, G)
     if variable_length:
         spec.obs_names["infos"], spec.obs_dims["infos"] = ["links_num_points"], [1]

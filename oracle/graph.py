@@ -7,7 +7,9 @@ rope.py = pyg_data/rope_tasks_data.py, tf.py = pyg_data/transforms.py, deepsets.
 vf.py = ../algorithms/trust_region_projections/models/value/gnn_vf_net.py.
 
 PyG pieces (HeteroData/Batch.from_data_list/coalesce/node_type_subgraph, torch_cluster.knn_graph, nn.MLP,
-LayerNorm(mode="graph")) are not importable here: restated from the call sites [upstream; PARITY UNPINNED].
+LayerNorm(mode="graph")) are not importable here: restated from the call sites [upstream].  Everything around them -- split, topology,
+features, critic input, value -- is pinned against the reference's own data classes and GNNVFNet run under stubs of those pieces
+(tools/make_golden.py tier3, tests/test_oracle_golden.py); variable-length ropes and rigid knn_to_actuators_k > 0 have no fixture.
 """
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
@@ -32,6 +34,7 @@ class TaskSpec:
     angular_velocity: bool = True  # rigid only (rigid.py:65)
     n_vec: int = 4  # vectors per node: rigid 4 (rigid.py:219), cloth/rope 3
     in_features: List[str] = field(default_factory=list)
+    knn_to_actuators_k: int = -1  # > 0: task edges only from the k points nearest to each actuator (cloth.py:267-274, rope.py:263-268)
 
 
 def rigid_spec(P=32, G=1, E_mesh=180, angular_velocity=True, object_velocity=True) -> TaskSpec:
@@ -150,6 +153,18 @@ def knn_edges(points: torch.Tensor, k: int) -> torch.Tensor:
     return torch.stack([nbr.reshape(-1), centre.reshape(-1)])
 
 
+def knn_to_actuator_edges(points: torch.Tensor, actuators: torch.Tensor, k: int) -> torch.Tensor:
+    """cloth.py:267-274 / rope.py:263-268: per actuator g, torch_cluster.knn(points, actuator[None], k) [upstream: rows (query, point)]
+    flipped and its query row set to g: edges [point, g] from the min(k, n) points nearest to the actuator.  Ties unpinned."""
+    n, G = points.shape[0], actuators.shape[0]
+    kk = min(k, n)
+    if kk == 0:
+        return torch.zeros(2, 0, dtype=torch.long)
+    d = torch.cdist(actuators.double(), points.double())
+    nbr = d.topk(kk, dim=1, largest=False).indices  # [G, kk]
+    return torch.stack([nbr.reshape(-1), torch.arange(G)[:, None].expand(G, kk).reshape(-1)])
+
+
 def full_edges(n_src: int, n_dst: int, exclude_self: bool) -> torch.Tensor:
     """rigid.py:289-300,313-319 (and the cloth/rope equivalents): j -> k double loops."""
     j, k = torch.meshgrid(torch.arange(n_src), torch.arange(n_dst), indexing="ij")
@@ -170,23 +185,27 @@ def build_topology(spec: TaskSpec, split: dict, full_graph_obs: bool) -> dict:
     n_per = {t: posv[t].shape[1] for t in spec.node_types}
     edges: Dict[EdgeType, List[torch.Tensor]] = {et: [] for et in spec.edge_types}
     G = n_per["grippers"]
+    kta = spec.knn_to_actuators_k
+    # kta > 0: the rigid builder upstream computes the same kNN but never assigns it (rigid.py:302-319); like geometry_rl_amd/graph.py
+    # every family follows the cloth / rope semantics here
+    task = lambda pts: knn_to_actuator_edges(pts, posv["grippers"][i], kta) if kta > 0 else full_edges(pts.shape[0], G, False)
     for i in range(B):
         if spec.family == "rigid":
             p = int(split["infos"]["object_num_points"][i].long().item())
             pts = posv["object_geometry"][i][:p]
             loc = {spec.edge_types[0]: knn_edges(pts, spec.knn_k),  # rigid.py:285-287
                    spec.edge_types[1]: full_edges(G, G, True) if G > 1 else torch.zeros(2, 0, dtype=torch.long),
-                   spec.edge_types[2]: full_edges(p, G, False)}  # rigid.py:313-319
+                   spec.edge_types[2]: task(pts)}  # rigid.py:313-319
         elif spec.family == "cloth":
             H = n_per["hole_boundary"]
             loc = {spec.edge_types[0]: full_edges(H, H, True), spec.edge_types[1]: full_edges(G, G, True),
-                   spec.edge_types[2]: full_edges(H, G, False)}
+                   spec.edge_types[2]: task(posv["hole_boundary"][i])}
         else:
             L = n_per["links"]
             if "infos" in split and "links_num_points" in split["infos"]:   # variable-length ropes: only the valid links have edges
                 L = min(L, int(split["infos"]["links_num_points"][i].long().item()))
             loc = {spec.edge_types[0]: knn_edges(posv["links"][i][:L], spec.knn_k),  # rope.py:251
-                   spec.edge_types[1]: full_edges(G, G, True), spec.edge_types[2]: full_edges(L, G, False)}
+                   spec.edge_types[1]: full_edges(G, G, True), spec.edge_types[2]: task(posv["links"][i][:L])}
         for et, ei in loc.items():
             src, _, dst = et
             off = torch.tensor([[i * n_per[src]], [i * n_per[dst]]])

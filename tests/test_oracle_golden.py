@@ -232,3 +232,131 @@ def test_frobenius_and_wasserstein_projections(golden_dir, name):
     close(mk.mean(), z["metric.mean_constraint"], 1e-5, 1e-4)
     close(ck.max(), z["metric.cov_constraint_max"], 1e-5, 1e-4)
     close((km + kc).mean(), z["metric.kl"], 1e-5, 1e-4)
+
+
+# ------------------------------------------------------------------------------------------------ tier3: data classes, critic wrapper
+# The reference's RigidTasksData / ClothTasksData / RopeTasksData and GNNVFNet -> DeepSets.one_step, run as reference code under stubs of
+# the PyG containers (tools/make_golden.py tier3; tests/data_fixtures.py says what no fixture covers).  Node features, positions and
+# one-hot columns are gathers, zeros and ONE float32 subtraction of two observation values, rounded the same way on both sides: they
+# must be exactly equal.
+import data_fixtures as dfx
+
+
+def oracle_spec(fx):
+    """The oracle's TaskSpec with the recorded observation layout and constructor keywords."""
+    spec = {"rigid": gr.rigid_spec, "cloth": gr.cloth_spec, "rope": gr.rope_spec}[fx.family]()
+    spec.obs_names = {g: list(n) for g, n in fx.observation_names.items()}
+    spec.obs_dims = {g: [d[0] for d in ds] for g, ds in fx.observation_dim.items()}
+    spec.num_actuators = fx.n_per("grippers")
+    spec.knn_k = fx.kwargs.get("knn_k", 3)
+    spec.angular_velocity = fx.kwargs.get("angular_velocity", True)
+    spec.knn_to_actuators_k = fx.kwargs.get("knn_to_actuators_k", -1)
+    return spec
+
+
+def oracle_layout(fx, tag):
+    spec = oracle_spec(fx)
+    lay = dfx.layouts(fx.case)[tag]
+    split = gr.split_obs(spec, fx.obs)
+    topo = gr.build_topology(spec, split, full_graph_obs=lay["full_graph_obs"])
+    graph, s, v = gr.build_features(spec, topo, split, dist_as_pos=lay["dist_as_pos"])
+    return spec, lay, topo, graph, s, v
+
+
+LAYOUT_IDS = [(c, t) for c in dfx.CASES for t in dfx.layouts(c)]
+
+
+@pytest.mark.parametrize("case,tag", LAYOUT_IDS)
+def test_data_class_features_equal_the_reference(golden_dir, case, tag):
+    fx = dfx.Fixture(golden_dir, case)
+    spec, lay, topo, graph, s, v = oracle_layout(fx, tag)
+    assert topo["node_types"] == fx.node_types(tag)                     # which types full_graph_obs keeps, in the reference's order
+    for t in fx.node_types(tag):
+        assert torch.equal(graph["pos"][t], fx.node(tag, "pos", t)), t
+        assert torch.equal(s[t], fx.node(tag, "properties", t)), t      # the one-hot column: index among ALL node types
+        assert torch.equal(v[t][:, :3], fx.node(tag, "norm_pos", t)), t
+        if lay["concat_input_vector"]:
+            assert torch.equal(torch.cat([s[t], v[t]], dim=1), fx.node(tag, "input_vector", t)), t
+        else:
+            assert torch.equal(s[t], fx.node(tag, "scalar", t)), t
+            assert torch.equal(v[t], fx.node(tag, "vector", t)), t
+    if lay["concat_input_vector"]:
+        assert torch.equal(gr.critic_input(topo, s, v), fx.critic_dense(tag))
+    # the read-out rows of one sample: the actuators' offset among the kept types (base_data.py:37-43)
+    m = fx.z[f"{tag}.output_mask"].tolist()
+    if lay["output_mask_key"] is None:
+        assert m == [-1, -1]
+    else:
+        start = sum(topo["n_per"][t] for t in topo["node_types"][:topo["node_types"].index("grippers")])
+        assert m == [start, start + topo["n_per"]["grippers"]]
+
+
+@pytest.mark.parametrize("case,tag", LAYOUT_IDS)
+def test_data_class_edges_equal_the_reference(golden_dir, case, tag):
+    """Edge sets per edge type in the reference's numbering (b * P + j: it keeps padded points as nodes); padded nodes have no edges."""
+    fx = dfx.Fixture(golden_dir, case)
+    spec, lay, topo, graph, s, v = oracle_layout(fx, tag)
+    assert sorted(topo["edge_index"].keys()) == sorted(fx.edge_types(tag))
+    n_edges = 0
+    for et in fx.edge_types(tag):
+        ei = topo["edge_index"][et]
+        ours = sorted(zip(ei[0].tolist(), ei[1].tolist()))
+        assert ours == fx.edge_set(tag, et), et
+        assert len(set(ours)) == len(ours)
+        fx.compact_edge_set(tag, et)                                    # asserts that no reference edge touches a padded point
+        n_edges += len(ours)
+    assert n_edges > 0
+
+
+@pytest.mark.parametrize("case", list(dfx.CASES))
+def test_data_fixture_has_no_neighbour_ties(golden_dir, case):
+    """The generator's condition, restated on the stored positions: every neighbour query has a relative gap of at least 1e-3 between
+    its k-th and (k+1)-th distance, so the neighbour SETS are defined (the order among equidistant points is not, upstream)."""
+    fx = dfx.Fixture(golden_dir, case)
+    spec = oracle_spec(fx)
+    posv = gr.split_obs(spec, fx.obs)["position_vectors"]
+    nv = fx.n_valid()
+    gap = float("inf")
+    for b in range(fx.B):
+        pts = posv[fx.main][b][:int(nv[b])]
+        if fx.family != "cloth":
+            gap = min(gap, dfx.tie_gap(pts, pts, spec.knn_k, True))
+        if spec.knn_to_actuators_k > 0:
+            gap = min(gap, dfx.tie_gap(pts, posv["grippers"][b], spec.knn_to_actuators_k, False))
+    assert gap >= dfx.TIE_GAP, gap
+    assert min(gap, 1e30) == pytest.approx(float(fx.z["tie_gap_min"]), rel=1e-9)
+    if case == "rigid_g1":   # the case's point counts: full, fewer than knn_k + 1, in between
+        P = fx.n_per(fx.main)
+        assert int(nv.max()) == P and int(nv.min()) < spec.knn_k + 1 and any(spec.knn_k + 1 <= int(n) < P for n in nv)
+
+
+@pytest.mark.parametrize("case", dfx.CRITIC_CASES)
+@pytest.mark.parametrize("rank", ["2d", "3d"])
+def test_critic_value_and_gradients_equal_the_reference(golden_dir, case, rank):
+    """gnn_vf_net.py / deepsets.py as reference code (float64, PyG's MLP restated in the stub) against oracle.graph.critic_input ->
+    value_forward: type concatenation order, padded points in the sum, reshape by batch, statistics per time step.  Bars of the tier2b test."""
+    fx = dfx.Fixture(golden_dir, case)
+    z = dfx.load_critic(golden_dir)
+    spec = oracle_spec(fx)
+    P = {k[len(case) + 7:]: v.double().requires_grad_(True) for k, v in z.items() if k.startswith(case + ".param.")}
+    obs3 = {k: z[f"{case}.obs3.{k}"] for k in dfx.IN_FEATURES if f"{case}.obs3.{k}" in z}
+    assert all(torch.equal(obs3[k][:, 0], fx.obs[k]) for k in obs3)     # the 2-D batch is the case's own observations
+
+    def value(obs):
+        split = gr.split_obs(spec, {k: v.double() for k, v in obs.items()})
+        topo = gr.build_topology(spec, split, full_graph_obs=True)
+        _, s, v = gr.build_features(spec, topo, split, dist_as_pos=False)
+        return gr.value_forward(P, gr.critic_input(topo, s, v).double())
+
+    if rank == "2d":
+        val = value({k: v[:, 0] for k, v in obs3.items()})
+    else:
+        T = obs3["scalars"].shape[1]
+        val = torch.stack([value({k: v[:, t] for k, v in obs3.items()}) for t in range(T)], dim=1)   # gnn_vf_net.py:72-80
+    close(val, z[f"{case}.{rank}.state_value"], 2e-6)
+    (val * z[f"{case}.{rank}.cotangent"]).sum().backward()
+    n = 0
+    for k, p in P.items():
+        close(p.grad, z[f"{case}.{rank}.grad.{k}"], 1e-5, 1e-4)
+        n += 1
+    assert n == 14

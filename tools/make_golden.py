@@ -16,6 +16,11 @@ section 8c), so three tiers are used:
           tier are flagged ``tier2b`` and pin everything else in those files (invariants, bases, message, einsum,
           calibration order, node MLP, readout).
 
+  tier 3  the graph / feature builders (pyg_data/rigid_tasks_data.py, cloth_tasks_data.py, rope_tasks_data.py, transforms.py) and the
+          critic wrapper (gnn_vf_net.py -> deepsets.py) run as reference code under stubs of the PyG data containers, the two neighbour
+          searches and PyG's MLP (install_data_stubs): fixtures tier3_data_<case>.npz and tier3_critic.npz, flagged
+          ``generated_under_semantic_stubs``.
+
 Only inputs/outputs (arrays) are written; no reference source text is stored.
 """
 import os
@@ -620,9 +625,426 @@ def tier2f():
     print("tier2f:", len(rec), "arrays,", os.path.getsize(os.path.join(OUT, "tier2f_projection_w2_non_com.npz")), "bytes")
 
 
+# ----------------------------------------------------------------------------------------------- tier 3: data classes + critic wrapper
+def _plain(key):
+    """A str / tuple-of-str key from the reference's str- and tuple-valued enum members."""
+    import enum
+    if isinstance(key, enum.Enum):
+        key = key.value
+    if isinstance(key, tuple):
+        return tuple(_plain(k) for k in key)
+    return str(key)
+
+
+def _sq_dist(a, b):
+    """[len(a), len(b)] squared distances in float64."""
+    a, b = a.detach().double(), b.detach().double()
+    return ((a[:, None, :] - b[None, :, :]) ** 2).sum(-1)
+
+
+def install_data_stubs():
+    """PyG 2.5.2 / torch_cluster container and neighbour semantics the reference's data classes rely on, restated from the upstream
+    documentation.  None of it is the reference's own arithmetic; fixtures made under it carry ``generated_under_semantic_stubs``.
+
+    HeteroData   attribute stores keyed by node type (str) or edge type (3-tuple), created on first access; ``node_types`` /
+                 ``edge_types`` in insertion order; a node store's ``num_nodes`` is the length of its ``pos``; a store answers ``keys()`` and
+                 ``hasattr``; ``coalesce()`` sorts every ``edge_index`` by (row, col) and drops duplicates; ``clone()`` copies the tensors;
+                 ``to()`` is the identity (CPU only); anything else set on the object (``output_mask_key`` ...) is a plain attribute;
+                 ``node_offsets``: the start of each node type when the types are laid out one after another in ``node_types`` order
+                 (base_data.py:39 reads it -- one semantic beyond the issue's list); ``node_type_subgraph(types)`` drops the other node
+                 types and every edge type that touches one of them, the kept ones stay in their order.
+    Batch        ``from_data_list``: node attributes concatenated type by type, every ``edge_index`` shifted by the node counts of the
+                 samples before it (source row by the source type's, destination row by the destination type's); ``len()`` = number of
+                 graphs; ``batch[0]``: the first sample's stores, restricted to the node types the batch still has.
+    transforms   BaseTransform (``__call__`` -> ``forward``), Compose, Cartesian (pos[row] - pos[col]), Distance (their norm), both with
+                 ``norm=False`` only, appended to an existing ``edge_attr``.  Nothing downstream reads that ``edge_attr``.
+    functional_transform   a decorator that returns the class unchanged.
+    knn_graph(x, k)   for every point its min(k, n - 1) nearest OTHER points, edges [neighbour, centre]; knn(x, y, k): for every point
+                 of y its min(k, len(x)) nearest points of x, rows [index into y, index into x].  Brute force in float64; the order among
+                 equidistant points is undefined upstream, so tier3 asserts that its inputs have none (tie_gap).
+    nn.MLP       the one form deepsets.py builds, ``MLP([a, b, c], norm="layer_norm")``: Linear -> LayerNorm(mode="graph") -> ReLU -> Linear
+                 (plain last layer); the norm takes mean and biased std over ALL elements of its input, adds eps = 1e-5 to the std, then
+                 applies the per-channel weight and bias; parameter names ``lins.N`` / ``norms.N``."""
+    import copy
+
+    def mod(name, **attrs):
+        m = sys.modules.get(name) or types.ModuleType(name)
+        m.__dict__.update(attrs)
+        sys.modules[name] = m
+        return m
+
+    class Store:
+        def __init__(self):
+            object.__setattr__(self, "_d", {})
+
+        def __getattr__(self, k):
+            try:
+                return object.__getattribute__(self, "_d")[k]
+            except KeyError:
+                raise AttributeError(k) from None
+
+        def __setattr__(self, k, v):
+            self._d[k] = v
+
+        def keys(self):
+            return list(self._d.keys())
+
+        @property
+        def num_nodes(self):
+            return self._d["pos"].shape[0]
+
+        def copy(self, deep):
+            s = Store()
+            s._d.update({k: (v.clone() if deep and torch.is_tensor(v) else v) for k, v in self._d.items()})
+            return s
+
+    class Data:
+        def __init__(self, **kw):
+            self.__dict__.update(kw)
+
+    class HeteroData:
+        def __init__(self):
+            self.__dict__["_nodes"], self.__dict__["_edges"] = {}, {}
+
+        def __getitem__(self, key):
+            if isinstance(key, int):
+                return self._example(key)
+            key = _plain(key)
+            table = self._edges if isinstance(key, tuple) else self._nodes
+            if key not in table:
+                table[key] = Store()
+            return table[key]
+
+        node_types = property(lambda self: list(self._nodes.keys()))
+        edge_types = property(lambda self: list(self._edges.keys()))
+
+        @property
+        def node_offsets(self):
+            out, o = {}, 0
+            for t, s in self._nodes.items():
+                out[t] = o
+                o += s.num_nodes
+            return out
+
+        def _copy(self, deep):
+            new = copy.copy(self)
+            new.__dict__["_nodes"] = {k: s.copy(deep) for k, s in self._nodes.items()}
+            new.__dict__["_edges"] = {k: s.copy(deep) for k, s in self._edges.items()}
+            return new
+
+        def clone(self):
+            return self._copy(True)
+
+        def to(self, device, *a, **k):
+            return self
+
+        def coalesce(self):
+            for s in self._edges.values():
+                s.edge_index = torch.unique(s.edge_index, dim=1)   # (sorted by row, then column; duplicates dropped)
+            return self
+
+        def node_type_subgraph(self, node_types):
+            keep = [_plain(t) for t in node_types]
+            new = self._copy(False)
+            new.__dict__["_nodes"] = {t: s for t, s in new._nodes.items() if t in keep}
+            new.__dict__["_edges"] = {e: s for e, s in new._edges.items() if e[0] in keep and e[2] in keep}
+            return new
+
+    class Batch(HeteroData):
+        @classmethod
+        def from_data_list(cls, data_list):
+            b = cls()
+            b.__dict__["_num_graphs"], b.__dict__["_first"] = len(data_list), data_list[0]
+            for t in data_list[0].node_types:
+                for k in data_list[0][t].keys():
+                    setattr(b[t], k, torch.cat([getattr(d[t], k) for d in data_list], dim=0))
+            start = {t: [0] for t in data_list[0].node_types}
+            for d in data_list:
+                for t in start:
+                    start[t].append(start[t][-1] + d[t].num_nodes)
+            for e in data_list[0].edge_types:
+                b[e].edge_index = torch.cat([d[e].edge_index + torch.tensor([[start[e[0]][i]], [start[e[2]][i]]])
+                                             for i, d in enumerate(data_list)], dim=1)
+            return b
+
+        def __len__(self):
+            return self._num_graphs
+
+        def _example(self, i):
+            assert i == 0
+            return self._first.node_type_subgraph(self.node_types)
+
+    class BaseTransform:
+        def __call__(self, data):
+            return self.forward(data)
+
+    class Compose(BaseTransform):
+        def __init__(self, transforms):
+            self.transforms = transforms
+
+        def forward(self, data):
+            for t in self.transforms:
+                data = t(data)
+            return data
+
+    class _EdgePseudo(BaseTransform):
+        def __init__(self, norm=True, max_value=None, cat=True):
+            assert not norm
+            self.cat = cat
+
+        def forward(self, data):
+            (row, col), pos, pseudo = data.edge_index, data.pos, data.edge_attr
+            new = self.value(pos, row, col)
+            if pseudo is not None and self.cat:
+                pseudo = pseudo.view(-1, 1) if pseudo.dim() == 1 else pseudo
+                new = torch.cat([pseudo, new.type_as(pseudo)], dim=-1)
+            data.edge_attr = new
+            return data
+
+    class Cartesian(_EdgePseudo):
+        def value(self, pos, row, col):
+            return pos[row] - pos[col]
+
+    class Distance(_EdgePseudo):
+        def value(self, pos, row, col):
+            return torch.norm(pos[col] - pos[row], p=2, dim=-1).view(-1, 1)
+
+    def knn(x, y, k, *a, **kw):
+        if x.shape[0] == 0 or y.shape[0] == 0:
+            return torch.zeros(2, 0, dtype=torch.long)
+        kk = min(k, x.shape[0])
+        nbr = _sq_dist(y, x).topk(kk, dim=1, largest=False).indices                     # [len(y), kk]
+        return torch.stack([torch.arange(y.shape[0])[:, None].expand(-1, kk).reshape(-1), nbr.reshape(-1)])
+
+    def knn_graph(x, k, *a, **kw):
+        n = x.shape[0]
+        if n <= 1:
+            return torch.zeros(2, 0, dtype=torch.long)
+        d = _sq_dist(x, x)
+        d.fill_diagonal_(float("inf"))
+        kk = min(k, n - 1)
+        nbr = d.topk(kk, dim=1, largest=False).indices
+        return torch.stack([nbr.reshape(-1), torch.arange(n)[:, None].expand(-1, kk).reshape(-1)])
+
+    class GraphLayerNorm(nn.Module):
+        def __init__(self, channels, eps=1e-5):
+            super().__init__()
+            self.eps = eps
+            self.weight, self.bias = nn.Parameter(torch.ones(channels)), nn.Parameter(torch.zeros(channels))
+
+        def forward(self, x):
+            x = x - x.mean()
+            return x / (x.std(unbiased=False) + self.eps) * self.weight + self.bias
+
+    class MLP(nn.Module):
+        def __init__(self, channel_list, norm=None, **kw):
+            super().__init__()
+            assert len(channel_list) == 3 and norm == "layer_norm" and not kw
+            self.lins = nn.ModuleList([nn.Linear(a, b) for a, b in zip(channel_list[:-1], channel_list[1:])])
+            self.norms = nn.ModuleList([GraphLayerNorm(channel_list[1])])
+
+        def forward(self, x):
+            return self.lins[1](torch.relu(self.norms[0](self.lins[0](x))))
+
+    tg = mod("torch_geometric")
+    tg.nn = mod("torch_geometric.nn", knn=knn, knn_graph=knn_graph, MLP=MLP)
+    tg.data = mod("torch_geometric.data", Data=Data, HeteroData=HeteroData, Batch=Batch)
+    tg.data.datapipes = mod("torch_geometric.data.datapipes", functional_transform=lambda name: (lambda cls: cls))
+    tg.transforms = mod("torch_geometric.transforms", BaseTransform=BaseTransform, Compose=Compose, Cartesian=Cartesian, Distance=Distance)
+    for name in list(sys.modules):   # (an earlier tier may have imported these under the name-only containers)
+        if name.startswith("geometry_rl.modules.pyg_data") or name.endswith((".deepsets", ".gnn_vf_net", ".base_gnn", ".mpnn")):
+            del sys.modules[name]
+
+
+TIE_GAP = 1e-3   # (d_{k+1} - d_k) / d_k of every neighbour query of a tier3 fixture is at least this (Euclidean distances, float64)
+
+
+def tie_gap(x, y, k, exclude_self):
+    """The smallest relative gap between the k-th and the (k+1)-th nearest point of ``x`` over the queries ``y`` (inf: nothing to choose)."""
+    d = _sq_dist(y, x).sqrt()
+    if exclude_self:
+        d.fill_diagonal_(float("inf"))
+    n = x.shape[0] - int(exclude_self)
+    if n <= k:
+        return float("inf")
+    d = d.sort(dim=1).values
+    return float(((d[:, k] - d[:, k - 1]) / d[:, k - 1]).min())
+
+
+def tier3():
+    """The reference's RigidTasksData / ClothTasksData / RopeTasksData (imported unmodified, under install_data_stubs) on synthetic
+    observations, each case in the two layouts examples/torchrl/builders/utils_algo_graph.py builds -- actor: full_graph_obs=False,
+    dist_as_pos=True, output_mask_key="grippers", concat_input_vector=False; critic: full_graph_obs=True, dist_as_pos=False,
+    output_mask_key=None, concat_input_vector=True; cloth also ``actor_full`` = the actor layout with full_graph_obs=True (the flag changes
+    its node_type_list) -- and GNNVFNet -> DeepSets.one_step on the critic layout of rigid_g1 and cloth (tier3_critic.npz).
+
+    Not pinned here, by construction: (a) variable-length ropes -- the reference's rope builder reads no point count and connects all
+    links, the extension has only its oracle tests; (b) the rigid builder with knn_to_actuators_k > 0, which never assigns its task edges
+    upstream (rigid_tasks_data.py:302-319; the deviation is documented in geometry_rl_amd/graph.py); (c) training noise.
+
+    Every neighbour query of a case (kNN among the valid points of the main node type; with knn_to_actuators_k every actuator's query)
+    must have a relative gap of at least TIE_GAP between its k-th and (k+1)-th distance: a seed that fails is skipped for the next."""
+    install_data_stubs()
+    from geometry_rl.modules.pyg_data.rigid_tasks_data import RigidTasksData
+    from geometry_rl.modules.pyg_data.cloth_tasks_data import ClothTasksData
+    from geometry_rl.modules.pyg_data.rope_tasks_data import RopeTasksData
+    from geometry_rl.modules.pyg_models.deepsets import DeepSets
+    from geometry_rl.algorithms.trust_region_projections.models.value.gnn_vf_net import GNNVFNet
+    from oracle import graph as gr
+    from geometry_rl_amd import synthetic as syn
+
+    def rigid_obs(B, P, G, counts, seed, **kw):
+        """make_rigid_obs with the per-sample point counts of the case (padded raw positions zero, as the environment leaves them)."""
+        obs = syn.make_rigid_obs(B, P=P, G=G, E_mesh=4, seed=seed, **kw)
+        n = torch.tensor(counts)
+        g = torch.Generator().manual_seed(1000 + seed)
+        obj = torch.rand(B, P, 3, generator=g) * 2 - 1
+        tgt = obj + 0.3 * (torch.rand(B, 1, 3, generator=g) * 2 - 1)
+        valid = (torch.arange(P)[None, :] < n[:, None]).float()[..., None]
+        pos = obs["position_vectors"].clone()
+        pos[:, 3 * G:3 * (G + P)] = (obj * valid).reshape(B, -1)
+        pos[:, 3 * (G + P):] = (tgt * valid).reshape(B, -1)
+        obs["position_vectors"] = pos
+        obs["infos"][:, 0] = n.float()
+        return obs
+
+    cases = {
+        "rigid_g1": dict(cls=RigidTasksData, spec=gr.rigid_spec(P=12, G=1, E_mesh=4), main="object_geometry", counts=[12, 3, 7],
+                         obs=lambda s: rigid_obs(3, 12, 1, [12, 3, 7], s), kw=dict(angular_velocity=True, knn_k=3)),
+        "rigid_g2": dict(cls=RigidTasksData, spec=gr.rigid_spec(P=10, G=2, E_mesh=4, angular_velocity=False, object_velocity=False),
+                         main="object_geometry", counts=[10, 6],
+                         obs=lambda s: rigid_obs(2, 10, 2, [10, 6], s, angular_velocity=False, object_velocity=False),
+                         kw=dict(angular_velocity=False, knn_k=3)),
+        "cloth": dict(cls=ClothTasksData, spec=gr.cloth_spec(n_particles=12, n_hole=6, G=4, E_cloth=4), main="hole_boundary",
+                      obs=lambda s: syn.make_cloth_obs(2, n_particles=12, n_hole=6, G=4, E_cloth=4, seed=s), kw=dict()),
+        "rope": dict(cls=RopeTasksData, spec=gr.rope_spec(n_links=9, G=2), main="links",
+                     obs=lambda s: syn.make_rope_obs(3, n_links=9, G=2, seed=s), kw=dict(knn_k=3)),
+        "rope_kta": dict(cls=RopeTasksData, spec=gr.rope_spec(n_links=9, G=2), main="links",
+                         obs=lambda s: syn.make_rope_obs(3, n_links=9, G=2, seed=s), kw=dict(knn_k=3, knn_to_actuators_k=2)),
+        "cloth_kta": dict(cls=ClothTasksData, spec=gr.cloth_spec(n_particles=12, n_hole=6, G=4, E_cloth=4), main="hole_boundary",
+                          obs=lambda s: syn.make_cloth_obs(2, n_particles=12, n_hole=6, G=4, E_cloth=4, seed=s),
+                          kw=dict(knn_to_actuators_k=2)),
+    }
+    layouts = {"actor": dict(full_graph_obs=False, dist_as_pos=True, output_mask_key="grippers", concat_input_vector=False),
+               "critic": dict(full_graph_obs=True, dist_as_pos=False, output_mask_key=None, concat_input_vector=True)}
+
+    def case_gap(c, obs):
+        spec = c["spec"]
+        posv = gr.split_obs(spec, obs)["position_vectors"]
+        B = posv["grippers"].shape[0]
+        counts = c.get("counts", [posv[c["main"]].shape[1]] * B)
+        gap = float("inf")
+        for i in range(B):
+            pts = posv[c["main"]][i][:counts[i]]
+            if spec.family != "cloth":
+                gap = min(gap, tie_gap(pts, pts, c["kw"]["knn_k"], True))
+            if c["kw"].get("knn_to_actuators_k", -1) > 0:
+                gap = min(gap, tie_gap(pts, posv["grippers"][i], c["kw"]["knn_to_actuators_k"], False))
+        return gap
+
+    def ref_kwargs(c):
+        spec = c["spec"]
+        return dict(observation_dim={g: [(d,) for d in ds] for g, ds in spec.obs_dims.items()},
+                    observation_names={g: list(ns) for g, ns in spec.obs_names.items()}, training_noise=False, **c["kw"])
+
+    def record(rec, tag, data, iv, concat):
+        rec[f"{tag}.node_types"] = np.array(data.node_types)
+        rec[f"{tag}.edge_types"] = np.array(["|".join(e) for e in data.edge_types])
+        for t in data.node_types:
+            for k in ("pos", "norm_pos", "properties"):
+                rec[f"{tag}.{k}.{t}"] = getattr(data[t], k)
+        for e in data.edge_types:
+            rec[f"{tag}.edge_index." + "|".join(e)] = data[e].edge_index
+        if concat:
+            assert [_plain(t) for t in iv] == data.node_types
+            for t, v in iv.items():
+                rec[f"{tag}.input_vector.{_plain(t)}"] = v
+        else:
+            for t, v in iv[0].items():
+                rec[f"{tag}.scalar.{_plain(t)}"] = v
+            for t, v in iv[1].items():
+                rec[f"{tag}.vector.{_plain(t)}"] = v
+        m = data.output_mask
+        rec[f"{tag}.output_mask"] = np.array([-1, -1] if m == slice(None) else [m.start, m.stop], dtype=np.int64)
+
+    seeds = {}
+    for name, c in cases.items():
+        seed = 31
+        while case_gap(c, c["obs"](seed)) < TIE_GAP:
+            seed += 1
+        obs = c["obs"](seed)
+        gap = case_gap(c, obs)
+        assert gap >= TIE_GAP, (name, gap)
+        seeds[name] = seed
+        spec = c["spec"]
+        rec = {"obs." + k: v for k, v in obs.items()}
+        for g in spec.obs_names:
+            rec["observation_names." + g] = np.array(spec.obs_names[g])
+            rec["observation_dim." + g] = np.array(spec.obs_dims[g], dtype=np.int64)
+        for k in ("knn_k", "knn_to_actuators_k", "angular_velocity"):
+            if k in c["kw"]:
+                rec["kwarg." + k] = np.int64(c["kw"][k])
+        rec["generated_under_semantic_stubs"] = np.int64(1)
+        rec["tie_gap_min"] = np.float64(min(gap, 1e30))
+        lay = dict(layouts)
+        if spec.family == "cloth":
+            lay["actor_full"] = dict(layouts["actor"], full_graph_obs=True)
+        for tag, lk in lay.items():
+            hd = c["cls"](**ref_kwargs(c), **lk)
+            data, iv = hd.build_data(*[obs[k] for k in spec.in_features], train=True)
+            record(rec, tag, data, iv, lk["concat_input_vector"])
+        path = os.path.join(OUT, f"tier3_data_{name}.npz")
+        np.savez(path, **npd(rec))
+        print(f"tier3 {name}: seed {seed}, tie gap {gap:.3g}, {len(rec)} arrays, {os.path.getsize(path)} bytes")
+
+    # ---- critic: GNNVFNet -> DeepSets.one_step, float64 on float32-representable inputs (the critic layout has no arithmetic before
+    # the network: its features are copies of the observations), 2-D batch and 3-D [N, T, .] input
+    T = 3
+    rec = {"generated_under_semantic_stubs": np.int64(1)}
+    for name in ("rigid_g1", "cloth"):
+        c = cases[name]
+        spec = c["spec"]
+        frames = [c["obs"](seeds[name])] + [c["obs"](seeds[name] + 100 + t) for t in range(1, T)]
+        obs3 = {k: torch.stack([f[k] for f in frames], dim=1) for k in spec.in_features}       # [N, T, .]
+        if "infos" in obs3:
+            assert bool((obs3["infos"][:, :, 0] == obs3["infos"][:, :1, 0]).all())
+        d_in = len(spec.node_types) + 3 * spec.n_vec
+        torch.manual_seed(41)
+        hd = c["cls"](**ref_kwargs(c), **layouts["critic"])
+        net = GNNVFNet(gnn=DeepSets(input_dim_node=d_in, output_dim=64, hidden_dim=64, norm=["layer_norm", "layer_norm"]), hyper_data=hd)
+        with torch.no_grad():   # the norms start at weight 1 / bias 0, the final layer small: make every parameter's role visible
+            for k, p in net.named_parameters():
+                if "norms" in k:
+                    p.add_(0.2 * torch.randn(p.shape))
+            net.final.weight.mul_(3.0)
+            net.final.bias.add_(0.1)
+        for k, v in net.state_dict().items():
+            rec[f"{name}.param.{k}"] = v.clone()
+        net.double()
+        g = torch.Generator().manual_seed(43)
+        for tag, args in (("2d", [obs3[k][:, 0].double() for k in spec.in_features]), ("3d", [obs3[k].double() for k in spec.in_features])):
+            net.zero_grad()
+            v = net(*args, train=True)
+            w = torch.randn(v.shape, generator=g).double()
+            (v * w).sum().backward()
+            assert tuple(v.shape) == ((len(frames[0]["scalars"]), 1) if tag == "2d" else (len(frames[0]["scalars"]), T, 1))
+            rec[f"{name}.{tag}.state_value"], rec[f"{name}.{tag}.cotangent"] = v, w
+            for k, p in net.named_parameters():
+                rec[f"{name}.{tag}.grad.{k}"] = p.grad.float()   # (stored rounded to float32, 6e-8 relative: four 64 x 64 sets stay small)
+        for k, v in obs3.items():
+            rec[f"{name}.obs3.{k}"] = v
+    path = os.path.join(OUT, "tier3_critic.npz")
+    np.savez(path, **npd(rec))
+    print("tier3 critic:", len(rec), "arrays,", os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(4)
+    if len(sys.argv) > 1 and sys.argv[1] == "tier3":   # only the tier3 fixtures
+        install_stubs()
+        tier3()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "tier2f":
         install_stubs()
         tier2f()
@@ -648,5 +1070,6 @@ if __name__ == "__main__":
     tier2b(attention=True)
     tier2e()
     tier2f()
+    tier3()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
