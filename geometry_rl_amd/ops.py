@@ -4,6 +4,7 @@ Only plumbing lives here: argument checks, workspace allocation with torch's cac
 forward/backward kernel pair into autograd so the modules in ``geometry_rl_amd.modules`` behave like ordinary
 ``nn.Module``s.  No arithmetic of the hot path is done in Python/PyTorch.
 """
+import contextlib
 from dataclasses import dataclass
 from typing import Optional
 
@@ -101,11 +102,24 @@ def _reduce(partial: torch.Tensor, out: torch.Tensor):
     hip.call("grl_reduce_partials", partial, out, partial.shape[0], out.numel())
 
 
-# Deferred folding: while a list is installed here (PolicyUpdater does, around the backward), folds whose destinations are all
-# existing leaf ``.grad`` buffers are queued and executed by ONE launch (flush_deferred_grads) instead of one launch each.
+# Deferred folding: while a list is installed here (``deferred_folds``: PolicyUpdater does, around the backward), folds whose destinations
+# are all existing leaf ``.grad`` buffers are queued and executed by ONE launch (flush_deferred_grads) instead of one launch each.
 SPLIT_BACKWARD = True   # edge-balanced wave partition in the fused edge backward (EdgeSet.split_s); module attributes, not environment
 SPLIT_FORWARD = True    # ... and in the forward (EdgeSet.split_d): tools flip them in-process for A/B runs
 DEFERRED = None
+
+
+@contextlib.contextmanager
+def deferred_folds():
+    """Arm the fold queue for the block and put back what was installed before, whatever the block raises (a queue left armed would collect
+    the leaf gradients of every later backward in the process, and nobody would flush them).  Flushing stays the block's business:
+    ``flush_deferred_grads`` or one of the fused tails, which consume the queue."""
+    global DEFERRED
+    keep, DEFERRED = DEFERRED, []
+    try:
+        yield
+    finally:
+        DEFERRED = keep
 
 
 def _launch_folds(jobs, overwrite=False):
@@ -508,7 +522,7 @@ class EdgeConv(torch.autograd.Function):
                  dim, *args, x1, sd, (sd.numel() - 1) if sd is not None else 0, wimg.e16 if wimg else None, wimg.e32 if wimg else None,
                  rows=edges.n_edges * 16)
         global AFTER_EDGE_HOOK
-        if AFTER_EDGE_HOOK is not None:   # behind the launch (PolicyUpdater: the signal the critic's lane starts on -- agent.py); the hook
+        if AFTER_EDGE_HOOK is not None:   # behind the launch (PolicyUpdater: the signal the critic's lane starts on -- updater.py); the hook
             if AFTER_EDGE_HOOK():         # returns True once it has fired (it declines during the calibrating pass in front of the step's own)
                 AFTER_EDGE_HOOK = None
         ctx.save_for_backward(x_src, pos_src, pos_dst, grid3, *args)

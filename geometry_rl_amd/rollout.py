@@ -25,7 +25,7 @@ from typing import Dict, Iterator, Optional
 
 import torch
 
-from . import agent as _agent
+from . import agent as _agent, updater as _updater
 
 PPO_KEYS = ("action", "loc", "var", "sample_log_prob", "state_value", "advantage", "value_target")
 
@@ -51,7 +51,7 @@ class RolloutBuffer:
 
 
 class RolloutDriver:
-    def __init__(self, updater: "_agent.PolicyUpdater", spec, gamma: float = 0.99, lmbda: float = 0.95, ppo_epochs: int = 5,
+    def __init__(self, updater: "_updater.PolicyUpdater", spec, gamma: float = 0.99, lmbda: float = 0.95, ppo_epochs: int = 5,
                  seed: int = 0, mini_batch_size: Optional[int] = None, sampling: str = "env_aligned",
                  allow_stale_topology: bool = False):
         self.updater, self.spec = updater, spec
@@ -199,15 +199,10 @@ class PolicyActor:
             return self._pass(obs)
         if self._graph is None:
             self._static = {k: obs[k].clone() for k in self.spec.in_features}
-            g = torch.cuda.CUDAGraph()
-            if self.gen is not None and hasattr(g, "register_generator_state"):
-                g.register_generator_state(self.gen)
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with _agent._no_gc_while_capturing(), torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
+
+            def record():
                 self._out = self._pass(self._static)
-            torch.cuda.current_stream().wait_stream(side)
-            self._graph = g
+            self._graph = _updater.capture([record], generator=self.gen)
         for k in self.spec.in_features:
             self._static[k].copy_(obs[k])
         self._graph.replay()

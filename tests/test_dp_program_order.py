@@ -1,4 +1,4 @@
-"""The data-parallel step drives TWO communicators concurrently from two streams (agent.PolicyUpdater._plan_dp: the actor's lane on
+"""The data-parallel step drives TWO communicators concurrently from two streams (updater.PolicyUpdater._plan_dp: the actor's lane on
 ``group``, the critic's lane on ``group_c``).  On RCCL that is deadlock-free if (a) every rank enqueues the SAME sequence of collectives on
 each communicator and (b) the program has no dependency cycle once the k-th collective of a communicator is one rendezvous of all ranks.
 Neither needs a GPU to check: the program is data (``PolicyUpdater.program_outline``).  Four gloo ranks on CPU."""
@@ -112,6 +112,23 @@ def _worker(rank, world, port, one_comm, ret):
     dist.destroy_process_group()
 
 
+# the data-parallel program's (kind, lane, label) sequence in host order, with the epoch's advantage statistics published; the same for both
+# values of GRL_DP_ONE_COMM (only the communicator of the critic's collectives differs)
+_OUTLINE_PUBLISHED = [
+    ("fork", "m", None),
+    ("run", "s", None), ("sum", "s", "critic_ln1_fwd_stats"),
+    ("run", "s", None), ("sum", "s", "critic_ln2_fwd_stats"),
+    ("run", "m", None), ("sum", "m", "flat_gradient_actor+loss_records"),
+    ("run", "s", None), ("sum", "s", "critic_ln2_bwd_stats"),
+    ("run", "s", None), ("sum", "s", "critic_ln1_bwd_stats"),
+    ("run", "m", None),
+    ("run", "s", None), ("sum", "s", "flat_gradient_critic"), ("sum", "s", "loss_critic_sum"),
+    ("run", "s", None),
+    ("join", "m", "join_critic_lane"), ("run_host", "m", None)]
+# ... and without them: one more graph and collective at the head of the actor's lane
+_OUTLINE_UNPUBLISHED = _OUTLINE_PUBLISHED[:1] + [("run", "m", None), ("sum", "m", "advantage_stats")] + _OUTLINE_PUBLISHED[1:]
+
+
 @pytest.mark.parametrize("one_comm", [False, True])
 def test_four_ranks_enqueue_one_sequence_per_communicator_and_no_cycle(one_comm):
     world = 4
@@ -123,6 +140,7 @@ def test_four_ranks_enqueue_one_sequence_per_communicator_and_no_cycle(one_comm)
         progs = [r[pub] for r in per_rank]
         assert all(p == progs[0] for p in progs), "ranks built different programs"
         prog = progs[0]
+        assert [e[:3] for e in prog] == (_OUTLINE_PUBLISHED if pub else _OUTLINE_UNPUBLISHED)
         colls = [(label, comm) for kind, lane, label, comm in prog if kind == "sum"]
         # 7 collectives per update with published advantage statistics, 8 without; the actor's lane carries exactly one (two)
         assert len(colls) == (7 if pub else 8)

@@ -54,24 +54,20 @@ def _worker(rank, world, port, args, ret):
 
     orig_do = upd._do
 
-    def timed_do(kind, item):
+    def timed_do(entry):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         t0 = time.perf_counter()
         payload = None
-        if kind not in ("run", "graph") and item is not None and kind != "wait":
-            t = item()
+        if entry.kind == "sum":   # evaluate the tensor getter here, for the payload size
+            t = entry.item()
             payload = None if t is None else t.numel() * t.element_size()
-            item_ = (lambda t=t: t)
-            orig_do(kind, item_)
-        else:
-            orig_do(kind, item)
+            entry = entry._replace(item=lambda: t)
+        orig_do(entry)
         host = time.perf_counter() - t0
         e1.record()
-        lane = "s" if torch.cuda.current_stream() != main_stream else "m"
-        records.append((kind, payload, lane, e0, e1, host))
+        records.append((entry.kind, payload, entry.lane, e0, e1, host))
 
-    main_stream = torch.cuda.current_stream()
     upd._do = timed_do
     torch.cuda.synchronize()
     t0 = time.perf_counter()

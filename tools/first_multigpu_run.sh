@@ -1,7 +1,7 @@
 #!/bin/bash
 # First contact with a multi-GPU node: nothing of the N > 1 path has ever run on more than one GPU.  One call does
 #   (1) bench.py --gpus 2 / 4 / 8 for rigid HEPi and two-agent EMPN, each under a timeout; a hang or a non-zero exit starts a FRESH child
-#       with GRL_DP_ONE_COMM=1 (both lanes on one communicator: the documented fallback of agent.PolicyUpdater._plan_dp);
+#       with GRL_DP_ONE_COMM=1 (both lanes on one communicator: the documented fallback of updater.PolicyUpdater._plan_dp);
 #   (2) at the largest N: a sweep of NCCL_ALGO x NCCL_PROTO for the step's one bandwidth-relevant collective (0.54 MB actor gradient);
 #   (3) one table of every line's `data_parallel` block: gpurun_out/multigpu/table.txt  (tools/dp_table.py).
 # Usage (from the repo root, on the node):  bash tools/first_multigpu_run.sh [max_gpus]

@@ -1,6 +1,6 @@
 import os, sys, time, socket
 import torch, torch.distributed as dist
-sys.path.insert(0, "/root/repo" if os.path.exists("/root/repo/bench.py") else os.environ["GRAFT_REPO_ROOT"])
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench as B
 from geometry_rl_amd import agent, synthetic as syn
 from geometry_rl_amd.rollout import RolloutBuffer, RolloutDriver
@@ -28,10 +28,10 @@ for i in range(8):
 torch.cuda.synchronize()
 orig = upd._do
 log = []
-def traced(kind, item, label=None, lane="m"):
+def traced(entry):
     t0 = time.perf_counter()
-    orig(kind, item, label, lane)
-    log.append((kind, label, lane, 1e6 * (time.perf_counter() - t0)))
+    orig(entry)
+    log.append((entry.kind, entry.label, entry.lane, 1e6 * (time.perf_counter() - t0)))
 upd._do = traced
 for i in range(3):
     log.clear()
