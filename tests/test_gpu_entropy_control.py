@@ -8,14 +8,12 @@ path around it, on the GPU:
   * TRPLLoss.forward (opt-in) against the oracle actor + entropy_ref; compute_metrics' entropy_constraint;
   * PolicyUpdater: every program bitwise the eager step-by-step loop while the bound moves, nothing recorded again;
   * data parallel: the latched initial entropy is the global mean, the update the one-rank update."""
+import contextlib
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 import entropy_cases as ec
 import entropy_ref
@@ -23,10 +21,9 @@ import test_gpu_trpl_kernel as tk
 import trpl_cases as tc
 from geometry_rl_amd import ops
 from oracle import trpl as otr
-from spawn_util import spawn_ranks
+from updater_cases import DEV, assert_ranks_match, dp_ref, make_rollout, run_single, spawn_dp
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 
 
 def _beta_dev(beta):
@@ -117,14 +114,6 @@ def test_kl_bound_holds_behind_an_entropy_stage_in_front(eq):
 
 
 # ---------------------------------------------------------------------------------------------------- the loss module and the updater
-def _agent(dev, group=None, **cfg_kw):
-    from geometry_rl_amd import agent, graph
-    spec = graph.rigid_spec()
-    cfg = agent.AgentConfig(only_upper_hemisphere=True, output_dim=2, output_dim_vec=2, **cfg_kw)
-    torch.manual_seed(0)
-    return (spec, cfg) + tuple(agent.build_agent(spec, cfg, device=dev, group=group))
-
-
 def _initial_of(batch):
     """mean of policy.entropy(q) in the layer's float32 arithmetic (base_projection_layer.py:202-203)."""
     var = batch["var"].float()
@@ -189,41 +178,23 @@ def test_loss_forward_matches_the_oracle_with_entropy_ref(proj_type, eq, first):
     assert "entropy_constraint" not in out.keys()
 
 
-def _rollout(schedule, total, seed=33, N=8, T=12, **cfg_kw):
-    """Updater inputs in the manner of tests/test_gpu_rollout.py, with a schedule steep enough to move the active set."""
-    from geometry_rl_amd import synthetic as syn
-    spec, cfg, actor, critic, proj, loss = _agent(DEV, entropy_schedule=schedule, total_train_steps=total, entropy_first=True,
-                                                  temperature=0.5, **cfg_kw)
-    frames = []
-    for t in range(T + 1):
-        b = dict(syn.make_rigid_obs(N, seed=seed + t))
-        b.update(syn.make_ppo_fields(N, 6, seed=seed + t))
-        frames.append(b)
-    data = {k: torch.stack([f[k] for f in frames[:T]], dim=1).to(DEV) for k in frames[0]}
-    g = syn.make_gae_inputs(N, T, seed=seed)
-    data.update(reward=g["reward"].reshape(N, T, 1).to(DEV), done=g["done"].reshape(N, T, 1).to(DEV),
-                terminated=g["terminated"].reshape(N, T, 1).to(DEV))
-    next_last = {k: frames[T][k].unsqueeze(1).to(DEV) for k in spec.in_features}
-    with torch.no_grad():
-        actor.forward_diag(*[data[k][:, 0].contiguous() for k in spec.in_features], train=True)
-    return spec, cfg, proj, loss, data, next_last
-
-
 def _run_form(form, schedule, n_updates, total):
     from geometry_rl_amd import agent
     from geometry_rl_amd.rollout import RolloutBuffer, RolloutDriver
-    spec, cfg, proj, loss, data, next_last = _rollout(schedule, total)
+    # updater inputs in the manner of tests/test_gpu_rollout.py, with a schedule steep enough to move the active set
+    r = make_rollout(8, 12, seed=33, entropy_schedule=schedule, total_train_steps=total, entropy_first=True, temperature=0.5)
+    spec, proj, loss = r.spec, r.proj, r.loss
     kw = dict(eager=dict(use_graph=False), lanes=dict(use_graph=True), one_stream=dict(use_graph=True, overlap_critic=False),
               step_from=dict(use_graph=True), unrolled=dict(use_graph=True), per_step=dict(use_graph=True))[form]
-    upd = agent.PolicyUpdater(loss, lr=cfg.lr, **kw)
+    upd = agent.PolicyUpdater(loss, lr=r.cfg.lr, **kw)
     upd.autotune_form = False
     if form == "unrolled":
         upd.epoch_unroll = 4
     if form == "per_step":
         upd.epoch_unroll, upd.form_by_size = 4, {8: "per_step"}
-    buf = RolloutBuffer(dict(data))
+    buf = RolloutBuffer(dict(r.data))
     drv = RolloutDriver(upd, spec, ppo_epochs=1, seed=9)
-    drv.compute_advantages(buf, next_last)
+    drv.compute_advantages(buf, r.next_last)
     idxs = drv.epoch_minibatches(buf.N, buf.T, DEV)[:n_updates]
     assert len(idxs) == n_updates
     keys = list(spec.in_features) + ["action", "loc", "var", "sample_log_prob", "state_value", "advantage", "value_target"]
@@ -289,57 +260,30 @@ def test_updater_programs_are_bitwise_the_eager_loop_while_the_bound_moves(sched
 
 
 # ---------------------------------------------------------------------------------------------------- data parallel
-def _dp_setup(B, group):
-    from geometry_rl_amd import agent, graph, synthetic as syn
-    spec = graph.rigid_spec(G=2, angular_velocity=False, object_velocity=False)
-    batch = dict(syn.make_rigid_obs(B, G=2, angular_velocity=False, object_velocity=False, seed=4))
-    batch.update(syn.make_ppo_fields(B, 6, seed=4))
-    batch["var"] = batch["var"] * torch.linspace(0.5, 2.0, B)[:, None]     # the shards' mean entropies differ
-    cfg = agent.AgentConfig(entropy_schedule="linear", total_train_steps=10, target_entropy=float(_initial_of(batch)) + 3.0, entropy_first=False)
-    torch.manual_seed(0)
-    actor, critic, proj, loss = agent.build_agent(spec, cfg, device=DEV, group=group)
-    return spec, cfg, actor, proj, loss, {k: v.to(DEV) for k, v in batch.items()}
+def _spread_entropies(batch):
+    batch["var"] = batch["var"] * torch.linspace(0.5, 2.0, batch["var"].shape[0])[:, None]     # the shards' mean entropies differ
+    return dict(target_entropy=float(_initial_of(batch)) + 3.0)
 
 
-def _dp_worker(rank, world, port, B, ret):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    from geometry_rl_amd import agent
-    spec, cfg, actor, proj, loss, batch = _dp_setup(B, dist.group.WORLD)
-    with torch.no_grad():
-        actor.forward_diag(*[batch[k] for k in spec.in_features], train=True)
-    lo, hi = rank * B // world, (rank + 1) * B // world
-    shard = {k: v[lo:hi].contiguous() for k, v in batch.items()}
-    upd = agent.PolicyUpdater(loss, lr=cfg.lr, group=dist.group.WORLD)
+@contextlib.contextmanager
+def _outline_is_stable(case, upd, shard, rank, ret):
     outline = upd.program_outline()
-    for _ in range(2):
-        out = upd.step(shard)
+    yield
     assert upd.program_outline() == outline
-    ret[rank] = (float(proj.initial_entropy), {k: float(out[k].detach()) for k in ("loss_objective", "loss_trust_region", "loss_entropy", "kl",
-                                                                                   "entropy_diff")}, upd.flat.detach().cpu())
-    dist.destroy_process_group()
+    ret[f"initial_entropy{rank}"] = float(case.proj.initial_entropy)
 
 
 def test_two_ranks_latch_the_global_mean_and_match_one_rank():
-    from geometry_rl_amd import agent
-    B, world = 16, 2
-    spec, cfg, actor, proj, loss, batch = _dp_setup(B, None)
-    with torch.no_grad():
-        actor.forward_diag(*[batch[k] for k in spec.in_features], train=True)
-    upd = agent.PolicyUpdater(loss, lr=cfg.lr)
-    for _ in range(2):
-        out = upd.step(batch)
-    want_init = float(_initial_of(batch))
-    assert abs(float(proj.initial_entropy) - want_init) <= 1e-6 * abs(want_init)
-    ref = {k: float(out[k].detach()) for k in ("loss_objective", "loss_trust_region", "loss_entropy", "kl", "entropy_diff")}
-    ref_flat = upd.flat.detach().cpu()
-    ret = mp.Manager().dict()
-    spawn_ranks(_dp_worker, world, (world,), (B, ret,))
+    world = 2
+    case_ref = dp_ref(16, cfg_kw=dict(entropy_schedule="linear", total_train_steps=10, entropy_first=False),
+                      batch_hook=(__name__, "_spread_entropies"))
+    kw = dict(use_graph=False, n_steps=2, keys=("loss_objective", "loss_trust_region", "loss_entropy", "kl", "entropy_diff"), updater_kw={})
+    ref, ref_flat, case = run_single(case_ref, **kw)
+    want_init = float(_initial_of(case.batch))
+    assert abs(float(case.proj.initial_entropy) - want_init) <= 1e-6 * abs(want_init)
+    ret = spawn_dp(case_ref, world, extra=(__name__, "_outline_is_stable"), **kw)
     for r in range(world):
-        init, losses, flat = ret[r]
+        init = ret[f"initial_entropy{r}"]
+        print(f"rank {r}: initial entropy {init:.6f}")
         assert abs(init - want_init) <= 1e-6 * abs(want_init), (r, init, want_init)    # the GLOBAL mean, not the shard's
-        for k, v in ref.items():
-            assert abs(losses[k] - v) <= 1e-5 * max(1.0, abs(v)), (r, k, losses[k], v)
-        err = (flat - ref_flat).abs().max().item()
-        print(f"rank {r}: initial entropy {init:.6f}, max |param - single-rank param| = {err:.3e}")
-        assert err <= 2e-6
+    assert_ranks_match(ref, ref_flat, ret, world, 1e-5, 2e-6)

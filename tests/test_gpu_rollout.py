@@ -3,29 +3,9 @@
 import pytest
 import torch
 
+from updater_cases import make_rollout, snapshot
+
 pytestmark = pytest.mark.gpu
-
-
-def _make(N, T, seed):
-    from geometry_rl_amd import agent, graph, synthetic as syn
-    dev = torch.device("cuda:0")
-    spec = graph.rigid_spec()
-    cfg = agent.AgentConfig(only_upper_hemisphere=True, output_dim=2, output_dim_vec=2)
-    torch.manual_seed(0)
-    actor, critic, proj, loss = agent.build_agent(spec, cfg, device=dev)
-    frames = []
-    for t in range(T + 1):  # one synthetic frame set per time step (same env -> same point count: env_offset 0)
-        b = dict(syn.make_rigid_obs(N, seed=seed + t))
-        b.update(syn.make_ppo_fields(N, 6, seed=seed + t))
-        frames.append(b)
-    data = {k: torch.stack([f[k] for f in frames[:T]], dim=1).to(dev) for k in frames[0]}
-    g = syn.make_gae_inputs(N, T, seed=seed)
-    data.update(reward=g["reward"].reshape(N, T, 1).to(dev), done=g["done"].reshape(N, T, 1).to(dev),
-                terminated=g["terminated"].reshape(N, T, 1).to(dev))
-    next_last = {k: frames[T][k].unsqueeze(1).to(dev) for k in spec.in_features}
-    with torch.no_grad():
-        actor.forward_diag(*[data[k][:, 0].contiguous() for k in spec.in_features], train=True)   # calibration
-    return spec, cfg, loss, data, next_last
 
 
 @pytest.mark.parametrize("use_graph", [False, True])
@@ -34,22 +14,22 @@ def test_driver_matches_explicit_loop(use_graph):
     from geometry_rl_amd.rollout import RolloutBuffer, RolloutDriver
     N, T = 8, 4
     # reference: same sampler, batches built with index_select, eager updates
-    spec, cfg, loss, data, next_last = _make(N, T, seed=21)
-    upd = agent.PolicyUpdater(loss, lr=cfg.lr)
-    buf = RolloutBuffer(dict(data))
-    drv = RolloutDriver(upd, spec, ppo_epochs=2, seed=5)
-    drv.compute_advantages(buf, next_last)
+    r = make_rollout(N, T, seed=21)
+    upd = agent.PolicyUpdater(r.loss, lr=r.cfg.lr)
+    buf = RolloutBuffer(dict(r.data))
+    drv = RolloutDriver(upd, r.spec, ppo_epochs=2, seed=5)
+    drv.compute_advantages(buf, r.next_last)
     adv_ref = buf.data["advantage"].clone()
-    keys = list(spec.in_features) + ["action", "loc", "var", "sample_log_prob", "state_value", "advantage", "value_target"]
+    keys = list(r.spec.in_features) + ["action", "loc", "var", "sample_log_prob", "state_value", "advantage", "value_target"]
     for idx in drv.minibatches(buf):
         upd.step(buf.rows(idx, keys))
     ref_flat = upd.flat.detach().cpu()
 
-    spec, cfg, loss, data, next_last = _make(N, T, seed=21)
-    upd2 = agent.PolicyUpdater(loss, lr=cfg.lr, use_graph=use_graph)
-    buf2 = RolloutBuffer(dict(data))
-    drv2 = RolloutDriver(upd2, spec, ppo_epochs=2, seed=5)
-    out = drv2.run(buf2, next_last)
+    r = make_rollout(N, T, seed=21)
+    upd2 = agent.PolicyUpdater(r.loss, lr=r.cfg.lr, use_graph=use_graph)
+    buf2 = RolloutBuffer(dict(r.data))
+    drv2 = RolloutDriver(upd2, r.spec, ppo_epochs=2, seed=5)
+    out = drv2.run(buf2, r.next_last)
     assert torch.equal(buf2.data["advantage"], adv_ref)
     assert upd2.steps == 2 * T and out is not None
     err = (upd2.flat.detach().cpu() - ref_flat).abs().max().item()
@@ -71,16 +51,16 @@ def test_several_steps_per_launch_equal_the_step_by_step_loop(form):
     per_epoch = form == "unrolled_rollout_per_epoch"
     res = {}
     for form in ("loop", "launches"):
-        spec, cfg, loss, data, next_last = _make(N, T, seed=33)
-        upd = agent.PolicyUpdater(loss, lr=cfg.lr, use_graph=True)
+        r = make_rollout(N, T, seed=33)
+        upd = agent.PolicyUpdater(r.loss, lr=r.cfg.lr, use_graph=True)
         upd.epoch_unroll = 4 if form == "launches" else 1
-        buf = RolloutBuffer(dict(data))
-        drv = RolloutDriver(upd, spec, ppo_epochs=2, seed=9)
+        buf = RolloutBuffer(dict(r.data))
+        drv = RolloutDriver(upd, r.spec, ppo_epochs=2, seed=9)
         dev = next(iter(buf.data.values())).device
         kls, keys = [], []
         for epoch in range(2):
             if epoch == 0 or per_epoch:
-                drv.compute_advantages(buf, next_last)
+                drv.compute_advantages(buf, r.next_last)
             idxs = drv.epoch_minibatches(buf.N, buf.T, dev)
             if form == "loop":
                 for idx in idxs:
@@ -96,7 +76,7 @@ def test_several_steps_per_launch_equal_the_step_by_step_loop(form):
             kls = [o["kl"].clone() for o in upd.last_outs] + [out["kl"].clone()]
         torch.cuda.synchronize()
         assert upd.steps == 2 * T and int(upd.step_dev.item()) == 2 * T and int(upd.step_dev_c.item()) == 2 * T
-        res[form] = (upd.flat.detach().clone(), upd.exp_avg.detach().clone(), upd.exp_avg_sq.detach().clone(), kls)
+        res[form] = snapshot(upd, kls)
     for a, b in zip(res["loop"][:3], res["launches"][:3]):
         assert torch.equal(a, b), (a - b).abs().max().item()
     # epoch 2 of the launch form: steps 11-14, 15-18 by launches (last_outs = steps 15-18), 19-20 singly (out = step 20)
@@ -115,12 +95,12 @@ def test_measured_choice_of_the_recorded_form_changes_nothing_but_the_time():
     N, T = 96, 30
     res = {}
     for form in ("loop", "measured"):
-        spec, cfg, loss, data, next_last = _make(N, T, seed=57)
-        upd = agent.PolicyUpdater(loss, lr=cfg.lr, use_graph=True)
+        r = make_rollout(N, T, seed=57)
+        upd = agent.PolicyUpdater(r.loss, lr=r.cfg.lr, use_graph=True)
         upd.epoch_unroll = 4
-        buf = RolloutBuffer(dict(data))
-        drv = RolloutDriver(upd, spec, ppo_epochs=1, seed=5)
-        drv.compute_advantages(buf, next_last)
+        buf = RolloutBuffer(dict(r.data))
+        drv = RolloutDriver(upd, r.spec, ppo_epochs=1, seed=5)
+        drv.compute_advantages(buf, r.next_last)
         dev = next(iter(buf.data.values())).device
         idx = torch.stack(drv.epoch_minibatches(buf.N, buf.T, dev))     # [30, 96]
         if form == "loop":
@@ -137,7 +117,7 @@ def test_measured_choice_of_the_recorded_form_changes_nothing_but_the_time():
             assert upd.form_times[N] == times            # (not measured again)
         torch.cuda.synchronize()
         assert upd.steps == T and int(upd.step_dev.item()) == T and int(upd.step_dev_c.item()) == T
-        res[form] = (upd.flat.detach().clone(), upd.exp_avg.detach().clone(), upd.exp_avg_sq.detach().clone())
+        res[form] = snapshot(upd, None)[:3]
     for a, b in zip(res["loop"], res["measured"]):
         assert torch.equal(a, b), (a - b).abs().max().item()
 
@@ -151,12 +131,12 @@ def test_launch_forms_can_be_mixed_and_follow_a_changed_hyper_parameter():
     N, T = 8, 12
     res = {}
     for form in ("loop", "mixed"):
-        spec, cfg, loss, data, next_last = _make(N, T, seed=41)
-        upd = agent.PolicyUpdater(loss, lr=cfg.lr, use_graph=True)
+        r = make_rollout(N, T, seed=41)
+        upd = agent.PolicyUpdater(r.loss, lr=r.cfg.lr, use_graph=True)
         upd.epoch_unroll = 4
-        buf = RolloutBuffer(dict(data))
-        drv = RolloutDriver(upd, spec, ppo_epochs=1, seed=3)
-        drv.compute_advantages(buf, next_last)
+        buf = RolloutBuffer(dict(r.data))
+        drv = RolloutDriver(upd, r.spec, ppo_epochs=1, seed=3)
+        drv.compute_advantages(buf, r.next_last)
         dev = next(iter(buf.data.values())).device
         idx = torch.stack(drv.epoch_minibatches(buf.N, buf.T, dev))     # [12, 8]
         if form == "loop":
@@ -222,10 +202,10 @@ def test_time_batched_critic_pass_is_the_loop_bitwise(N, T, budget):
     """The once-per-rollout critic pass (train.py:249-251): all time steps as groups of ONE launch set (per-step LayerNorm statistic
     slots) must give bitwise the values of the reference's loop over T (gnn_vf_net.py:72-80) -- also when the byte budget cuts the
     time axis into chunks (third case: three steps per chunk)."""
-    spec, cfg, loss, data, next_last = _make(N, T, seed=33)
-    critic = loss.critic_network
+    r = make_rollout(N, T, seed=33)
+    critic = r.loss.critic_network
     vf = critic._network1
-    obs = [data[k] for k in spec.in_features]
+    obs = [r.data[k] for k in r.spec.in_features]
     with torch.no_grad():
         looped = torch.stack([vf._values([a[:, i].contiguous() for a in obs], False) for i in range(T)], dim=1)
         if budget is not None:

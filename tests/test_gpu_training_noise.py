@@ -3,21 +3,18 @@ counter-based Gaussian noise (Philox4x32-10 + Box-Muller, include/grl_hip.h grl_
 memory.  Checked against the host restatement (tests/noise_ref.py): exact features per family / layout / numbering, the cloth no-op, the
 statistics of the stream, a whole update against the oracle fed the same noise, every recorded form against the step-by-step loop,
 reproducibility, the collector and two data-parallel ranks."""
-import os
+import contextlib
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 from oracle import graph as ogr, step as ost
 from noise_ref import add_noise
 from parity_util import G_TOL, adam_first_step_bound, adam_first_step_bound_elem, grad_error, grad_scales, param_excess
-from spawn_util import spawn_ranks
+from updater_cases import DEV, dp_ref, make_rollout, run_loop_and_launches, run_step_modes, spawn_dp
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 
 
 def _obs(name, B):
@@ -245,76 +242,45 @@ def test_update_matches_the_oracle_with_the_same_noise(name, B, monkeypatch):
 
 
 # ---------------------------------------------------------------------------------------------------------- recorded forms = the loop
-def _make(N, T, seed, noise_seed=None, **cfg_kw):
-    from geometry_rl_amd import agent, graph, synthetic as syn
-    spec = graph.rigid_spec()
-    cfg = agent.AgentConfig(only_upper_hemisphere=True, output_dim=2, output_dim_vec=2, training_noise=True, **cfg_kw)
-    torch.manual_seed(0)
-    actor, critic, proj, loss = agent.build_agent(spec, cfg, device=DEV)
-    if noise_seed is not None:
-        actor.hyper_data.set_noise_state(noise_seed, 0)
-    frames = []
-    for t in range(T + 1):
-        b = dict(syn.make_rigid_obs(N, seed=seed + t))
-        b.update(syn.make_ppo_fields(N, 6, seed=seed + t))
-        frames.append(b)
-    data = {k: torch.stack([f[k] for f in frames[:T]], dim=1).to(DEV) for k in frames[0]}
-    g = syn.make_gae_inputs(N, T, seed=seed)
-    data.update(reward=g["reward"].reshape(N, T, 1).to(DEV), done=g["done"].reshape(N, T, 1).to(DEV),
-                terminated=g["terminated"].reshape(N, T, 1).to(DEV))
-    next_last = {k: frames[T][k].unsqueeze(1).to(DEV) for k in spec.in_features}
-    with torch.no_grad():
-        actor.forward_diag(*[data[k][:, 0].contiguous() for k in spec.in_features], train=True)   # calibration (+ draw 0)
-    return spec, cfg, actor, loss, data, next_last
+def _noisy_rollout(N, T, seed, noise_seed=None):
+    """(the calibrating forward consumes draw 0)"""
+    seeded = None if noise_seed is None else (lambda actor, *_: actor.hyper_data.set_noise_state(noise_seed, 0))
+    return make_rollout(N, T, seed, after_build=seeded, training_noise=True)
+
+
+@contextlib.contextmanager
+def _draws(r, n):
+    d0 = r.actor.hyper_data.noise_state()
+    yield d0
+    assert r.actor.hyper_data.noise_state() == (d0[0], d0[1] + n)
 
 
 @pytest.mark.parametrize("form", ["unrolled", "per_step"])
 def test_run_minibatches_equals_the_step_loop(form):
-    from geometry_rl_amd import agent
-    from geometry_rl_amd.rollout import RolloutBuffer, RolloutDriver
     N, T = 8, 10
-    res = {}
-    for mode in ("loop", "launches"):
-        spec, cfg, actor, loss, data, next_last = _make(N, T, seed=33)
-        upd = agent.PolicyUpdater(loss, lr=cfg.lr, use_graph=True)
-        upd.epoch_unroll = 4 if mode == "launches" else 1
-        if form == "per_step":
-            upd.form_by_size[N] = "per_step"   # the gated per-step program (the critic's lane waits for the first edge convolution)
-        buf = RolloutBuffer(dict(data))
-        drv = RolloutDriver(upd, spec, ppo_epochs=2, seed=9)
-        drv.compute_advantages(buf, next_last)
-        d0 = actor.hyper_data.noise_state()
-        if mode == "loop":
-            for idx in drv.minibatches(buf):
-                upd.step_from(buf, idx)
-        else:
-            for _ in range(2):
-                upd.run_minibatches(buf, torch.stack(drv.epoch_minibatches(buf.N, buf.T, DEV)))
-            assert (upd._epoch is not None) == (form == "unrolled")
-        torch.cuda.synchronize()
-        assert actor.hyper_data.noise_state() == (d0[0], d0[1] + 2 * T)   # one draw per update
-        res[mode] = (upd.flat.detach().clone(), upd.exp_avg.detach().clone(), upd.exp_avg_sq.detach().clone())
-    for a, b in zip(res["loop"], res["launches"]):
+    res = run_loop_and_launches(lambda: _noisy_rollout(N, T, seed=33), form, N=N, T=T, ppo_epochs=2, driver_seed=9, unroll=4, keys=(),
+                                per_mode=lambda mode, r, upd: _draws(r, 2 * T))   # one draw per update
+    for a, b in zip(res["loop"][:3], res["launches"][:3]):
         assert torch.equal(a, b), (a - b).abs().max().item()
 
 
 def test_replays_draw_fresh_noise_like_eager_steps_and_lanes_equal_one_stream():
-    from geometry_rl_amd import agent
-    N, T, k = 8, 2, 4
-    res = {}
-    for mode in ("eager", "graph", "one_stream", "frozen"):
-        spec, cfg, actor, loss, data, next_last = _make(N, T, seed=41)
-        batch = {kk: v[:, 0].contiguous() for kk, v in data.items()}
-        upd = agent.PolicyUpdater(loss, lr=cfg.lr, use_graph=mode != "eager", overlap_critic=mode != "one_stream")
-        d0 = actor.hyper_data.noise_state()
-        for _ in range(k):
-            if mode == "frozen":   # the same draw every step: another update
-                actor.hyper_data.set_noise_state(*d0)
-            upd.step(batch)
-        torch.cuda.synchronize()
-        if mode != "frozen":
-            assert actor.hyper_data.noise_state() == (d0[0], d0[1] + k)
-        res[mode] = upd.flat.detach().clone()
+    k = 4
+    d0 = {}
+
+    @contextlib.contextmanager
+    def draws(mode, r, upd):
+        d0[mode] = r.actor.hyper_data.noise_state()
+        with contextlib.nullcontext() if mode == "frozen" else _draws(r, k):
+            yield
+
+    def freeze(mode, r):
+        if mode == "frozen":   # the same draw every step: another update
+            r.actor.hyper_data.set_noise_state(*d0[mode])
+
+    res = run_step_modes(lambda: _noisy_rollout(8, 2, seed=41), ("eager", "graph", "one_stream", "frozen"), k, (),
+                         lambda mode: dict(use_graph=mode != "eager", overlap_critic=mode != "one_stream"), before_step=freeze, per_mode=draws)
+    res = {mode: snap[0] for mode, snap in res.items()}
     e_graph = (res["graph"] - res["eager"]).abs().max().item()
     e_lanes = (res["graph"] - res["one_stream"]).abs().max().item()
     e_frozen = (res["graph"] - res["frozen"]).abs().max().item()
@@ -327,10 +293,10 @@ def test_reproducible_with_the_same_seed():
     N, T = 8, 3
     res = []
     for noise_seed in (None, None, 77):
-        spec, cfg, actor, loss, data, next_last = _make(N, T, seed=51, noise_seed=noise_seed)
-        upd = agent.PolicyUpdater(loss, lr=cfg.lr, use_graph=True)
+        r = _noisy_rollout(N, T, seed=51, noise_seed=noise_seed)
+        upd = agent.PolicyUpdater(r.loss, lr=r.cfg.lr, use_graph=True)
         for t in range(T):
-            b = {kk: v[:, t].contiguous() for kk, v in data.items()}
+            b = {kk: v[:, t].contiguous() for kk, v in r.data.items()}
             upd.step(b)
         res.append(upd.flat.detach().clone())
     assert torch.equal(res[0], res[1])
@@ -342,15 +308,14 @@ def test_collector_draws_fresh_noise_per_replay():
     N, T = 8, 3
     outs = {}
     for use_graph in (False, True):
-        spec, cfg, actor, loss, data, next_last = _make(N, T, seed=61)
-        pa = PolicyActor(actor, spec, use_graph=use_graph, deterministic=True)
-        obs = {k: data[k][:, 0].contiguous() for k in spec.in_features}
-        d0 = actor.hyper_data.noise_state()
-        outs[use_graph] = [pa(obs)["loc"].clone() for _ in range(4)]
-        assert actor.hyper_data.noise_state() == (d0[0], d0[1] + 4)
-        ev = PolicyActor(actor, spec, use_graph=use_graph, deterministic=True, train=False)
-        quiet = [ev(obs)["loc"].clone() for _ in range(3)]
-        assert actor.hyper_data.noise_state() == (d0[0], d0[1] + 4)   # evaluation draws nothing
+        r = _noisy_rollout(N, T, seed=61)
+        pa = PolicyActor(r.actor, r.spec, use_graph=use_graph, deterministic=True)
+        obs = {k: r.data[k][:, 0].contiguous() for k in r.spec.in_features}
+        with _draws(r, 4):
+            outs[use_graph] = [pa(obs)["loc"].clone() for _ in range(4)]
+        ev = PolicyActor(r.actor, r.spec, use_graph=use_graph, deterministic=True, train=False)
+        with _draws(r, 0):   # evaluation draws nothing
+            quiet = [ev(obs)["loc"].clone() for _ in range(3)]
         assert torch.equal(quiet[0], quiet[1]) and torch.equal(quiet[0], quiet[2])
     for a, b in zip(outs[False], outs[True]):
         assert (a - b).abs().max().item() <= 1e-6
@@ -358,33 +323,18 @@ def test_collector_draws_fresh_noise_per_replay():
 
 
 # ---------------------------------------------------------------------------------------------------------- data parallel
-def _dp_worker(rank, world, port, ret):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    from geometry_rl_amd import agent, graph, synthetic as syn
-    B = 16
-    spec = graph.rigid_spec(G=2, angular_velocity=False, object_velocity=False)
-    cfg = agent.AgentConfig(training_noise=True)
-    torch.manual_seed(0)
-    actor, critic, proj, loss = agent.build_agent(spec, cfg, device=DEV, group=dist.group.WORLD)
-    batch = dict(syn.make_rigid_obs(B, G=2, angular_velocity=False, object_velocity=False, seed=4))
-    batch.update(syn.make_ppo_fields(B, 6, seed=4))
-    batch = {k: v.to(DEV) for k, v in batch.items()}
-    lo, hi = rank * B // world, (rank + 1) * B // world
-    shard = {k: v[lo:hi].contiguous() for k, v in batch.items()}
-    upd = agent.PolicyUpdater(loss, lr=cfg.lr, group=dist.group.WORLD)
-    for _ in range(2):
-        upd.step(shard)
+@contextlib.contextmanager
+def _report_noise_state(case, upd, shard, rank, ret):
+    yield
     torch.cuda.synchronize()
-    ret[rank] = (actor.hyper_data.noise_state(), upd.flat.detach().cpu())
-    dist.destroy_process_group()
+    ret[f"noise{rank}"] = case.actor.hyper_data.noise_state()
 
 
 def test_data_parallel_ranks_draw_their_own_noise():
-    world = 2
-    ret = mp.Manager().dict()
-    spawn_ranks(_dp_worker, world, (world,), (ret,))
-    (s0, f0), (s1, f1) = ret[0], ret[1]
+    """The natural order: no calibrating forward in front of the first update."""
+    ret = spawn_dp(dp_ref(16, cfg_kw=dict(training_noise=True), calibrate_first=False), 2, use_graph=False, n_steps=2, keys=(), updater_kw={},
+                   extra=(__name__, "_report_noise_state"))
+    (s0, f0), (s1, f1) = ((ret[f"noise{r}"], ret[r][1]) for r in range(2))
     print("rank noise states", s0, s1)
     assert s0[0] != s1[0] and s0[1] == s1[1]
     assert torch.equal(f0, f1)

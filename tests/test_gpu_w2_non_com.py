@@ -6,6 +6,7 @@
   (d) five updates against the oracle with the restatement registered, rigid HEPi and two-agent EMPN;
   (e) recorded programs against the step-by-step loop (lanes, one stream, run_minibatches);
   (f) two data-parallel ranks against one rank; two runs bitwise identical."""
+import contextlib
 import os
 
 import numpy as np
@@ -16,9 +17,9 @@ import w2nc_ref
 from oracle import step as ost, trpl as otr
 from geometry_rl_amd import synthetic as syn
 from parity_util import adam_first_step_bound, grad_scales
+from updater_cases import DEV, assert_ranks_match, dp_ref, make_rollout, run_loop_and_launches, run_step_modes, run_two_ranks
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 EPS, EPS_COV = 0.05, 0.0025
 
 
@@ -240,72 +241,28 @@ def test_five_updates_match_the_oracle(registered, name, B, K):
 KEYS = ("loss_objective", "loss_trust_region", "loss_critic", "kl", "constraint", "entropy", "ESS")
 
 
-def _make(N, T, seed):
-    from geometry_rl_amd import agent, graph
-    spec = graph.rigid_spec()
-    cfg = agent.AgentConfig(only_upper_hemisphere=True, output_dim=2, output_dim_vec=2, proj_type="w2_non_com")
-    torch.manual_seed(0)
-    actor, critic, proj, loss = agent.build_agent(spec, cfg, device=DEV)
-    frames = []
-    for t in range(T + 1):
-        b = dict(syn.make_rigid_obs(N, seed=seed + t))
-        b.update(syn.make_ppo_fields(N, 6, seed=seed + t))
-        frames.append(b)
-    data = {k: torch.stack([f[k] for f in frames[:T]], dim=1).to(DEV) for k in frames[0]}
-    g = syn.make_gae_inputs(N, T, seed=seed)
-    data.update(reward=g["reward"].reshape(N, T, 1).to(DEV), done=g["done"].reshape(N, T, 1).to(DEV),
-                terminated=g["terminated"].reshape(N, T, 1).to(DEV))
-    next_last = {k: frames[T][k].unsqueeze(1).to(DEV) for k in spec.in_features}
-    with torch.no_grad():
-        actor.forward_diag(*[data[k][:, 0].contiguous() for k in spec.in_features], train=True)   # calibration
-    return spec, cfg, loss, data, next_last
-
-
 @pytest.mark.parametrize("form", ["unrolled"])
 def test_run_minibatches_equals_the_step_loop(form):
-    from geometry_rl_amd import agent
-    from geometry_rl_amd.rollout import RolloutBuffer, RolloutDriver
     N, T = 8, 10
-    res = {}
-    for mode in ("loop", "launches"):
-        spec, cfg, loss, data, next_last = _make(N, T, seed=33)
-        upd = agent.PolicyUpdater(loss, lr=cfg.lr, use_graph=True)
-        upd.epoch_unroll = 4 if mode == "launches" else 1
-        buf = RolloutBuffer(dict(data))
-        drv = RolloutDriver(upd, spec, ppo_epochs=2, seed=9)
-        drv.compute_advantages(buf, next_last)
-        outs = []
-        if mode == "loop":
-            for idx in drv.minibatches(buf):
-                o = upd.step_from(buf, idx)
-                outs.append({k: o[k].clone() for k in KEYS})
-        else:
-            for _ in range(2):
-                o = upd.run_minibatches(buf, torch.stack(drv.epoch_minibatches(buf.N, buf.T, DEV)))
-            assert upd._epoch is not None
-            outs.append({k: o[k].clone() for k in KEYS})
-        torch.cuda.synchronize()
-        assert upd.steps == 2 * T
-        res[mode] = (upd.flat.detach().clone(), upd.exp_avg.detach().clone(), upd.exp_avg_sq.detach().clone(), outs)
+    res = run_loop_and_launches(lambda: make_rollout(N, T, seed=33, proj_type="w2_non_com"), form, N=N, T=T, ppo_epochs=2, driver_seed=9,
+                                unroll=4, keys=KEYS)
     for a, b in zip(res["loop"][:3], res["launches"][:3]):
         assert torch.equal(a, b), (a - b).abs().max().item()
     for k in KEYS:
         assert torch.equal(res["loop"][3][-1][k], res["launches"][3][-1][k]), k
 
 
+@contextlib.contextmanager
+def _graph_modes_are_recorded(mode, r, upd):
+    yield
+    if mode in ("graph", "one_stream"):
+        assert upd.mode.startswith("graph") and upd._program is not None
+
+
 def test_recorded_programs_equal_the_eager_loop():
-    from geometry_rl_amd import agent
-    N, T, k = 8, 2, 4
-    res = {}
-    for mode in ("eager", "graph", "one_stream", "one_stream_eager"):
-        spec, cfg, loss, data, next_last = _make(N, T, seed=41)
-        batch = {kk: v[:, 0].contiguous() for kk, v in data.items()}
-        upd = agent.PolicyUpdater(loss, lr=cfg.lr, use_graph=mode in ("graph", "one_stream"), overlap_critic=not mode.startswith("one_stream"))
-        outs = [{kk: v.clone() for kk, v in upd.step(batch).items() if kk in KEYS} for _ in range(k)]
-        torch.cuda.synchronize()
-        if mode in ("graph", "one_stream"):
-            assert upd.mode.startswith("graph") and upd._program is not None
-        res[mode] = (upd.flat.detach().clone(), upd.exp_avg.detach().clone(), upd.exp_avg_sq.detach().clone(), outs)
+    res = run_step_modes(lambda: make_rollout(8, 2, seed=41, proj_type="w2_non_com"), ("eager", "graph", "one_stream", "one_stream_eager"), 4,
+                         KEYS, lambda mode: dict(use_graph=mode in ("graph", "one_stream"), overlap_critic=not mode.startswith("one_stream")),
+                         per_mode=_graph_modes_are_recorded)
     for a, b in (("eager", "graph"), ("one_stream_eager", "one_stream")):
         for x, y in zip(res[a][:3], res[b][:3]):
             assert torch.equal(x, y), (a, b, (x - y).abs().max().item())
@@ -319,9 +276,9 @@ def test_two_runs_are_bitwise_identical():
     from geometry_rl_amd import agent
     res = []
     for _ in range(2):
-        spec, cfg, loss, data, next_last = _make(16, 3, seed=45)
-        upd = agent.PolicyUpdater(loss, lr=cfg.lr, use_graph=True)
-        outs = [{kk: v.clone() for kk, v in upd.step({k: v[:, t].contiguous() for k, v in data.items()}).items() if kk in KEYS}
+        r = make_rollout(16, 3, seed=45, proj_type="w2_non_com")
+        upd = agent.PolicyUpdater(r.loss, lr=r.cfg.lr, use_graph=True)
+        outs = [{kk: v.clone() for kk, v in upd.step({k: v[:, t].contiguous() for k, v in r.data.items()}).items() if kk in KEYS}
                 for t in range(3)]
         torch.cuda.synchronize()
         res.append((upd.flat.detach().clone(), outs))
@@ -332,54 +289,8 @@ def test_two_runs_are_bitwise_identical():
 
 
 # ------------------------------------------------------------------------------------------------------------- (f) data parallel
-def _dp_setup(B, group):
-    from geometry_rl_amd import agent, graph
-    spec = graph.rigid_spec(G=2, angular_velocity=False, object_velocity=False)
-    cfg = agent.AgentConfig(proj_type="w2_non_com")
-    torch.manual_seed(0)
-    actor, critic, proj, loss = agent.build_agent(spec, cfg, device=DEV, group=group)
-    batch = dict(syn.make_rigid_obs(B, G=2, angular_velocity=False, object_velocity=False, seed=4))
-    batch.update(syn.make_ppo_fields(B, 6, seed=4))
-    return spec, cfg, actor, loss, {k: v.to(DEV) for k, v in batch.items()}
-
-
-def _dp_worker(rank, world, port, B, ret):
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    from geometry_rl_amd import agent
-    spec, cfg, actor, loss, batch = _dp_setup(B, dist.group.WORLD)
-    with torch.no_grad():
-        actor.forward_diag(*[batch[k] for k in spec.in_features], train=True)
-    lo, hi = rank * B // world, (rank + 1) * B // world
-    shard = {k: v[lo:hi].contiguous() for k, v in batch.items()}
-    upd = agent.PolicyUpdater(loss, lr=cfg.lr, clip_grad_norm=cfg.clip_grad_norm, group=dist.group.WORLD, use_graph=True)
-    for _ in range(3):
-        out = upd.step(shard)
-    ret[rank] = ({k: float(out[k].detach()) for k in KEYS}, upd.flat.detach().cpu())
-    dist.destroy_process_group()
-
-
 def test_two_ranks_match_single_rank():
-    import torch.multiprocessing as mp
-    from geometry_rl_amd import agent
-    from spawn_util import spawn_ranks
-    B, world = 16, 2
-    spec, cfg, actor, loss, batch = _dp_setup(B, None)
-    with torch.no_grad():
-        actor.forward_diag(*[batch[k] for k in spec.in_features], train=True)
-    upd = agent.PolicyUpdater(loss, lr=cfg.lr, clip_grad_norm=cfg.clip_grad_norm, use_graph=True)
-    for _ in range(3):
-        out = upd.step(batch)
-    ref_losses = {k: float(out[k].detach()) for k in KEYS}
-    ref_flat = upd.flat.detach().cpu()
-    ret = mp.Manager().dict()
-    spawn_ranks(_dp_worker, world, (world,), (B, ret))
-    assert all(r in ret for r in range(world))
-    for r in range(world):
-        losses, flat = ret[r]
-        for k, v in ref_losses.items():
-            assert abs(losses[k] - v) <= 1e-5 * max(1.0, abs(v)), (r, k, losses[k], v)
-        err = (flat - ref_flat).abs().max().item()
-        print(f"rank {r}: max |param - single-rank param| = {err:.3e}")
-        assert err <= 2e-6
+    world = 2
+    ref_losses, ref_flat, ret = run_two_ranks(dp_ref(16, cfg_kw=dict(proj_type="w2_non_com")), world, use_graph=True, dp_use_graph=True,
+                                              n_steps=3, keys=KEYS, updater_kw=dict(clip_grad_norm=False))
+    assert_ranks_match(ref_losses, ref_flat, ret, world, 1e-5, 2e-6)

@@ -1,0 +1,217 @@
+"""Shared scaffolding of the GPU tests that drive ``PolicyUpdater``: the rollout-shaped inputs, the bodies that run one case through several
+program forms, and the data-parallel pair (one rank on the whole batch, ``world`` ranks on its shards).  TEST INFRASTRUCTURE ONLY, a plain
+module like tests/trpl_cases.py.  The runners return what each form left behind and compare NOTHING: every comparison, with its operator
+and tolerance, stays in the test that owns it.
+
+Pieces that a spawned rank needs from a test file are named ``(module, function, ...)`` and looked up in the child: closures do not
+survive ``mp.spawn``, the test directory is importable there."""
+import contextlib
+import importlib
+import os
+from collections import namedtuple
+from functools import partial
+
+import torch
+
+from spawn_util import spawn_ranks
+
+DEV = torch.device("cuda:0")
+RIGID2 = dict(G=2, angular_velocity=False, object_velocity=False)    # the data-parallel tests' spec: two grippers, positions only
+
+Rollout = namedtuple("Rollout", "spec cfg actor critic proj loss data next_last")
+DPCase = namedtuple("DPCase", "spec cfg actor critic proj loss batch")
+
+
+def _named(ref):
+    return getattr(importlib.import_module(ref[0]), ref[1])
+
+
+def calibrate(actor, spec, batch):
+    """The first training forward: the data-dependent re-initialisation of the convolutions."""
+    with torch.no_grad():
+        actor.forward_diag(*[batch[k] for k in spec.in_features], train=True)
+
+
+# ------------------------------------------------------------------------------------------------------------- rollout-shaped inputs
+def make_rollout(N, T, seed, *, spec=None, after_build=None, **cfg_kw):
+    """The small rigid HEPi agent (or ``spec``, a rigid one) with T + 1 synthetic frame sets of N environments: [N, T] data with GAE inputs,
+    the frame behind the last as ``next_last``, calibrated on time step 0.  ``after_build(actor, critic, proj, loss)`` runs before the
+    calibrating forward."""
+    from geometry_rl_amd import agent, graph, synthetic as syn
+    spec = graph.rigid_spec() if spec is None else spec
+    cfg = agent.AgentConfig(**dict(dict(only_upper_hemisphere=True, output_dim=2, output_dim_vec=2), **cfg_kw))
+    torch.manual_seed(0)
+    actor, critic, proj, loss = agent.build_agent(spec, cfg, device=DEV)
+    if after_build is not None:
+        after_build(actor, critic, proj, loss)
+    frames = []
+    for t in range(T + 1):  # one synthetic frame set per time step (same env -> same point count: env_offset 0)
+        b = dict(syn.make_rigid_obs(N, seed=seed + t))
+        b.update(syn.make_ppo_fields(N, 6, seed=seed + t))
+        frames.append(b)
+    data = {k: torch.stack([f[k] for f in frames[:T]], dim=1).to(DEV) for k in frames[0]}
+    g = syn.make_gae_inputs(N, T, seed=seed)
+    data.update(reward=g["reward"].reshape(N, T, 1).to(DEV), done=g["done"].reshape(N, T, 1).to(DEV),
+                terminated=g["terminated"].reshape(N, T, 1).to(DEV))
+    next_last = {k: frames[T][k].unsqueeze(1).to(DEV) for k in spec.in_features}
+    calibrate(actor, spec, {k: data[k][:, 0].contiguous() for k in spec.in_features})
+    return Rollout(spec, cfg, actor, critic, proj, loss, data, next_last)
+
+
+# ------------------------------------------------------------------------------------------------------------- program forms
+def snapshot(upd, outs):
+    return upd.flat.detach().clone(), upd.exp_avg.detach().clone(), upd.exp_avg_sq.detach().clone(), outs
+
+
+def _around(per_mode, mode, r, upd):
+    """``per_mode(mode, rollout, updater)``: a context manager around a mode's updates and the synchronisation behind them."""
+    return contextlib.nullcontext() if per_mode is None else per_mode(mode, r, upd)
+
+
+def run_loop_and_launches(make, form, *, N, T, ppo_epochs, driver_seed, unroll, keys, per_mode=None):
+    """``ppo_epochs`` epochs of T minibatches, "loop": step_from one by one, "launches": run_minibatches with ``unroll`` steps per launch
+    (``form`` "per_step": the size pinned to the per-step program).  -> {mode: snapshot}, outs = every step's loss dict ("loop") or the
+    last one ("launches"), restricted to ``keys``."""
+    from geometry_rl_amd import agent
+    from geometry_rl_amd.rollout import RolloutBuffer, RolloutDriver
+    res = {}
+    for mode in ("loop", "launches"):
+        r = make()
+        upd = agent.PolicyUpdater(r.loss, lr=r.cfg.lr, use_graph=True)
+        upd.epoch_unroll = unroll if mode == "launches" else 1
+        if form == "per_step":
+            upd.form_by_size[N] = "per_step"   # the gated per-step program (the critic's lane waits for the first edge convolution)
+        buf = RolloutBuffer(dict(r.data))
+        drv = RolloutDriver(upd, r.spec, ppo_epochs=ppo_epochs, seed=driver_seed)
+        drv.compute_advantages(buf, r.next_last)
+        outs = []
+        with _around(per_mode, mode, r, upd):
+            if mode == "loop":
+                for idx in drv.minibatches(buf):
+                    o = upd.step_from(buf, idx)
+                    outs.append({k: o[k].clone() for k in keys})
+            else:
+                for _ in range(ppo_epochs):
+                    o = upd.run_minibatches(buf, torch.stack(drv.epoch_minibatches(buf.N, buf.T, DEV)))
+                assert (upd._epoch is not None) == (form != "per_step")
+                outs.append({k: o[k].clone() for k in keys})
+            torch.cuda.synchronize()
+        assert upd.steps == ppo_epochs * T
+        res[mode] = snapshot(upd, outs)
+    return res
+
+
+def run_step_modes(make, modes, k, keys, updater_kw_of_mode, before_step=None, per_mode=None):
+    """Per mode a fresh ``make()`` and ``k`` updates of its time step 0 by ``PolicyUpdater(**updater_kw_of_mode(mode))``;
+    ``before_step(mode, rollout)`` runs in front of every update.  -> {mode: snapshot}, outs = every step's loss dict restricted to ``keys``."""
+    from geometry_rl_amd import agent
+    res = {}
+    for mode in modes:
+        r = make()
+        batch = {kk: v[:, 0].contiguous() for kk, v in r.data.items()}
+        upd = agent.PolicyUpdater(r.loss, lr=r.cfg.lr, **updater_kw_of_mode(mode))
+        outs = []
+        with _around(per_mode, mode, r, upd):
+            for _ in range(k):
+                if before_step is not None:
+                    before_step(mode, r)
+                outs.append({kk: v.clone() for kk, v in upd.step(batch).items() if kk in keys})
+            torch.cuda.synchronize()
+        res[mode] = snapshot(upd, outs)
+    return res
+
+
+# ------------------------------------------------------------------------------------------------------------- data parallel
+def dp_case(B, group, *, cfg_kw, batch_hook=None, calibrate_first=True):
+    """The data-parallel tests' agent and minibatch: two-gripper rigid spec, ``seed=4`` fields, replicas from one seed, calibrated on the
+    WHOLE batch so that every rank starts from identical weights.  ``batch_hook`` names a function that may edit the (host) batch and
+    returns further AgentConfig keywords derived from it."""
+    from geometry_rl_amd import agent, graph, synthetic as syn
+    spec = graph.rigid_spec(**RIGID2)
+    batch = dict(syn.make_rigid_obs(B, seed=4, **RIGID2))
+    batch.update(syn.make_ppo_fields(B, 6, seed=4))
+    if batch_hook is not None:
+        cfg_kw = dict(cfg_kw, **_named(batch_hook)(batch))
+    cfg = agent.AgentConfig(**cfg_kw)
+    torch.manual_seed(0)
+    actor, critic, proj, loss = agent.build_agent(spec, cfg, device=DEV, group=group)
+    batch = {k: v.to(DEV) for k, v in batch.items()}
+    if calibrate_first:
+        calibrate(actor, spec, batch)
+    return DPCase(spec, cfg, actor, critic, proj, loss, batch)
+
+
+def dp_ref(B, **case_kw):
+    """What ``dp_worker`` and ``run_single`` take as ``case_ref``: (module, function, keywords) of a builder called with ``group=``."""
+    return (__name__, "dp_case", dict(B=B, **case_kw))
+
+
+@contextlib.contextmanager
+def rendezvous(rank, world, port, backend="gloo", **init_kw):
+    """The one place a rank joins its process group (and leaves it, when nothing raised)."""
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group(backend, rank=rank, world_size=world, **init_kw)
+    yield dist.group.WORLD
+    dist.destroy_process_group()
+
+
+def shard_of(batch, rank, world):
+    B = next(iter(batch.values())).shape[0]
+    lo, hi = rank * B // world, (rank + 1) * B // world
+    return {k: v[lo:hi].contiguous() for k, v in batch.items()}
+
+
+def dp_worker(rank, world, port, case_ref, ret, *, use_graph, n_steps, keys, updater_kw, extra=None):
+    """One rank: rendezvous, the case built on the group, its shard, ``n_steps`` updates -> ret[rank] = (last loss dict restricted to
+    ``keys``, parameters).  ``extra`` = (module, function, *args) names a context manager ``f(case, upd, shard, rank, ret, *args)`` around the
+    updates; what it yields, if anything, is called with the step number in front of every update."""
+    from geometry_rl_amd import agent
+    with rendezvous(rank, world, port) as group:
+        case = _named(case_ref)(group=group, **case_ref[2])
+        shard = shard_of(case.batch, rank, world)
+        upd = agent.PolicyUpdater(case.loss, lr=case.cfg.lr, group=group, use_graph=use_graph, **updater_kw)
+        hook = contextlib.nullcontext() if extra is None else _named(extra)(case, upd, shard, rank, ret, *extra[2:])
+        with hook as before_step:
+            for i in range(n_steps):
+                if before_step is not None:
+                    before_step(i)
+                out = upd.step(shard)
+        ret[rank] = ({k: float(out[k].detach()) for k in keys}, upd.flat.detach().cpu())
+
+
+def spawn_dp(case_ref, world, **worker_kw):
+    """``world`` ranks of ``dp_worker`` -> what they left in ``ret``, as a plain dict."""
+    import torch.multiprocessing as mp
+    ret = mp.Manager().dict()
+    spawn_ranks(partial(dp_worker, **worker_kw), world, (world,), (case_ref, ret))
+    assert all(r in ret for r in range(world))
+    return dict(ret)
+
+
+def run_single(case_ref, *, use_graph, n_steps, keys, updater_kw):
+    """The one-rank side: the same case on the whole batch -> (last loss dict restricted to ``keys``, parameters, the case)."""
+    from geometry_rl_amd import agent
+    case = _named(case_ref)(group=None, **case_ref[2])
+    upd = agent.PolicyUpdater(case.loss, lr=case.cfg.lr, use_graph=use_graph, **updater_kw)
+    for _ in range(n_steps):
+        out = upd.step(case.batch)
+    return {k: float(out[k].detach()) for k in keys}, upd.flat.detach().cpu(), case
+
+
+def run_two_ranks(case_ref, world=2, *, use_graph, dp_use_graph, n_steps, keys, updater_kw, extra=None):
+    """-> (one rank's losses, one rank's parameters, the ranks' ``ret``); ``use_graph`` is the one-rank updater's, ``dp_use_graph`` the ranks'."""
+    ref_losses, ref_flat, _ = run_single(case_ref, use_graph=use_graph, n_steps=n_steps, keys=keys, updater_kw=updater_kw)
+    ret = spawn_dp(case_ref, world, use_graph=dp_use_graph, n_steps=n_steps, keys=keys, updater_kw=updater_kw, extra=extra)
+    return ref_losses, ref_flat, ret
+
+
+def assert_ranks_match(ref_losses, ref_flat, ret, world, loss_rtol, flat_atol):
+    """Every rank's (losses, parameters) against the one-rank side: losses to ``loss_rtol * max(1, |v|)``, parameters to ``flat_atol``."""
+    for r in range(world):
+        losses, flat = ret[r]
+        for k, v in ref_losses.items():
+            assert abs(losses[k] - v) <= loss_rtol * max(1.0, abs(v)), (r, k, losses[k], v)
+        err = (flat - ref_flat).abs().max().item()
+        print(f"rank {r}: max |param - single-rank param| = {err:.3e}")
+        assert err <= flat_atol, (r, err)
