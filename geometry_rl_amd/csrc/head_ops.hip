@@ -583,7 +583,9 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
       const bool inside = dlt >= -cfg.clip_value && dlt <= cfg.clip_value;
       const double Vc = Vo + fmin(fmax(dlt, -cfg.clip_value), cfg.clip_value);
       const double l2 = (Vc - R) * (Vc - R);
-      if (l2 > l1) { l = l2; g = inside ? 2.0 * (Vc - R) : 0.0; }
+      const double g2 = inside ? 2.0 * (Vc - R) : 0.0;
+      if (l2 > l1) { l = l2; g = g2; }
+      else if (l2 == l1) g = 0.5 * (g + g2);   // a tie: torch.max hands each side half (Vc == V inside the range: g itself, bit for bit)
     }
     acc[3] = l * cfg.critic_coef;
     if (fr && i == 0) dvalue[b] = (float)(g * cfg.critic_coef * cfg.inv_batch);
@@ -690,7 +692,9 @@ __global__ __launch_bounds__(1024) void value_loss_kernel(const float* __restric
       const bool inside = dlt >= -clip_value && dlt <= clip_value;
       const double Vc = Vo + fmin(fmax(dlt, -clip_value), clip_value);
       const double l2 = (Vc - R) * (Vc - R);
-      if (l2 > l1) { l = l2; g = inside ? 2.0 * (Vc - R) : 0.0; }
+      const double g2 = inside ? 2.0 * (Vc - R) : 0.0;
+      if (l2 > l1) { l = l2; g = g2; }
+      else if (l2 == l1) g = 0.5 * (g + g2);   // a tie: torch.max hands each side half (see the fused loss kernel's value branch)
     }
     s += l * critic_coef;
     dvalue[b] = (float)(g * critic_coef * inv_batch);

@@ -244,7 +244,9 @@ int grl_readout_bwd(const float* lat, const float* grid, const float* Wd, const 
  *               cov_constraint, entropy(p), entropy_diff, count, kl  (per-frame sums; divide by count);  maxes u32[2] (float bits) */
 /* (ABI 203) the critic's share of the loss on its own: clipped l2 value loss (trpl.py:213-228, objectives/utils.py:5-28) and d loss / d V per
  * frame (already scaled by critic_coef / B_global) -- elementwise, so the critic's lane needs nothing from the fused actor kernel (which is
- * then called with value = NULL).  out2 fp64[2] = {sum over the frames of critic_coef * loss, that sum * inv_batch}; one workgroup */
+ * then called with value = NULL).  out2 fp64[2] = {sum over the frames of critic_coef * loss, that sum * inv_batch}; one workgroup.
+ * Where the clipped and the unclipped loss are EQUAL the gradient is the mean of the two sides' (torch.max's autograd; outside the clip
+ * range that is half the plain gradient -- the fused loss kernel's value branch does the same). */
 int grl_value_loss(const float* value, const float* old_value, const float* value_target, double clip_value, double critic_coef,
                    double inv_batch, float* dvalue, double* out2, float* mean_out /* float[1] or NULL */, int batch, hipStream_t stream);
 /* (ABI 203) data parallel: a rank's slots -> ONE record of 14 doubles (12 sums, 2 maxes); all-gather the records (one collective instead of
@@ -361,15 +363,22 @@ int grl_deepsets_bwd1(const float* x, const float* h1, const double* stats1, dou
                       const double* bstats1, float* partial, int batch, int n_nodes, int d, hipStream_t stream);
 
 /* ---- training loop: examples/torchrl/train.py:134-146,249-251,308-316; pyg_data/rigid_tasks_data.py:285-287 ------------- */
+/* out[j] += sum_rows partial[row*n + j].  Zero rows (n_rows <= 0), here and in grl_reduce_partials_seg: NOTHING is launched, so a destination
+ * keeps its contents even where an overwrite bit is set -- a caller that hands over an uninitialised destination must have at least one
+ * row (every *_blocks query returns >= 1, and ops._emit_grads is only reached with such a slab: tests/test_gpu_fold_ops.py pins both halves).
+ * The entry points of the multi kernel below treat a zero-row slab as a sum of nothing instead: among other slabs of its destination it
+ * contributes nothing, and a destination fed by nothing else is written with zeros under overwrite. */
 int grl_reduce_partials(const float* partial, float* out, int n_rows, int n, hipStream_t stream);
-/* dst[i][0..len[i]) += sum_rows partial[row*ld + start[i] + j], i < n_seg <= 8; dst/start/len are HOST arrays */
+/* dst[i][0..len[i]) += sum_rows partial[row*ld + start[i] + j], i < n_seg <= 8 (more: -2); dst/start/len are HOST arrays */
 int grl_reduce_partials_seg(const float* partial, int n_rows, int ld, int n_seg, float* const* dst, const int* start, const int* len,
                             int overwrite_mask /* bit i: dst[i] = sum instead of += */, hipStream_t stream);
 /* n_seg <= 64 independent folds in ONE launch (all arrays HOST arrays of length n_seg): every leaf gradient of a backward pass */
 int grl_reduce_partials_multi(int n_seg, const float* const* partial, const int* n_rows, const int* ld, const int* start,
                               const int* len, float* const* dst, hipStream_t stream);
 /* (ABI 203) overwrite != 0: every destination is WRITTEN with the sum of its slabs instead of accumulated into (no zeroed gradient buffer
- * needed), provided all slabs of a destination are in this call; the launch is a flat grid of one workgroup per 64 columns */
+ * needed), provided all slabs of a destination are in this call; the launch is a flat grid of one workgroup per 64 columns.  Bitwise
+ * reproducible, and a destination's bits depend neither on the other destinations of the launch nor on its place among them.  More than
+ * 64 segments: -2; two segments with one destination and different lengths: -3 (nothing is launched). */
 int grl_reduce_partials_multi_ow(int n_seg, const float* const* partial, const int* n_rows, const int* ld, const int* start,
                                  const int* len, float* const* dst, int overwrite, hipStream_t stream);
 /* (ABI 203) the step's tail in ONE launch (one rank, no gradient clipping; train.py:308-316): the fold above, plus -- adam != 0 -- the Adam
