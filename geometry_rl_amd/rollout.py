@@ -25,7 +25,7 @@ from typing import Dict, Iterator, Optional
 
 import torch
 
-from . import agent as _agent, updater as _updater
+from . import agent as _agent, hip as _hip, updater as _updater
 
 PPO_KEYS = ("action", "loc", "var", "sample_log_prob", "state_value", "advantage", "value_target")
 
@@ -48,6 +48,54 @@ class RolloutBuffer:
     def rows(self, idx: torch.Tensor, keys) -> Dict[str, torch.Tensor]:
         """Plain (allocating) minibatch: rows ``idx`` of the given keys."""
         return {k: self.flat(k).index_select(0, idx) for k in keys}
+
+
+def explained_variance(value: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """``train/explained_variance`` (train.py:142,325: torchmetrics ``ExplainedVariance()`` on ``state_value`` against ``value_target``)
+    of a rollout's [N, T(, 1)] float32 tensors -> device float32[2]: [0] what the metric returns for [N, T, 1] inputs -- it reduces over
+    dimension 0, one score 1 - Var(target - value) / Var(target) per time step, and averages the scores uniformly; a zero denominator
+    scores 1 where the numerator is 0 too and 0 otherwise -- and [1] the same score over all N*T frames at once.  torchmetrics is not a
+    dependency of this package: the semantics is RESTATED and UNPINNED (no fixture from the reference checks it; tests/stats_ref.py is the
+    float64 restatement the kernel is tested against).  Two launches, no synchronisation."""
+    _hip.check_f32(value, target)
+    N, T = int(value.shape[0]), int(value.shape[1])
+    if value.numel() != N * T or target.numel() != N * T:
+        raise ValueError(f"expected [N, T] or [N, T, 1] tensors, got {tuple(value.shape)} and {tuple(target.shape)}")
+    nbytes = _hip.query("grl_explained_variance_scratch_bytes", N, T)
+    if nbytes < 0:
+        raise ValueError(f"grl_explained_variance does not take a rollout of {N} x {T} frames")
+    scratch = torch.empty(nbytes, device=value.device, dtype=torch.uint8)
+    out = torch.empty(2, device=value.device, dtype=torch.float32)
+    _hip.call("grl_explained_variance", value.contiguous(), target.contiguous(), N, T, scratch, out)
+    return out
+
+
+class EpisodeStats:
+    """torchrl's collector-side ``RewardSum`` and ``StepCounter`` transforms, which every reference config lists
+    (configs/rigid_insertion_multi_hepi_trpl_cfg.yaml:74-76), for N environments on the device.  ``scan(reward, done)`` takes a rollout's
+    [N, T(, 1)] reward (float32) and done (bool) and returns ``episode_reward`` (the running return: a float32 sum, one add per step) and
+    ``step_count`` (the running length) per frame; the frame behind a ``done`` frame starts from 0, and the running values are carried in
+    ``ret_state`` / ``len_state`` from one call to the next (episodes continue across rollouts).  ``sums`` (device fp64[3]) holds the last
+    scan's (sum of episode_reward, sum of step_count, number) over its done frames: what train.py:238-246 logs as ``train/reward`` and
+    ``train/episode_length``.  RESTATED and UNPINNED: torchrl is not a dependency and no fixture from the reference checks it
+    (tests/stats_ref.py is the restatement the kernel is tested against)."""
+
+    def __init__(self, N: int, device="cuda"):
+        self.N = int(N)
+        self.ret_state = torch.zeros(self.N, device=device, dtype=torch.float32)
+        self.len_state = torch.zeros(self.N, device=device, dtype=torch.int32)
+        self.sums = torch.zeros(3, device=device, dtype=torch.float64)
+
+    def scan(self, reward: torch.Tensor, done: torch.Tensor):
+        _hip.check_f32(reward)
+        N, T = int(reward.shape[0]), int(reward.shape[1])
+        if N != self.N or reward.numel() != N * T or done.numel() != N * T:
+            raise ValueError(f"expected [{self.N}, T] or [{self.N}, T, 1] tensors, got {tuple(reward.shape)} and {tuple(done.shape)}")
+        episode_reward = torch.empty(reward.shape, device=reward.device, dtype=torch.float32)
+        step_count = torch.empty(reward.shape, device=reward.device, dtype=torch.int32)
+        _hip.call("grl_episode_scan", reward.contiguous(), done.to(torch.uint8).contiguous(), self.ret_state, self.len_state,
+                  episode_reward, step_count, self.sums, N, T)
+        return episode_reward, step_count
 
 
 class RolloutDriver:
@@ -144,6 +192,8 @@ class RolloutDriver:
         """One rollout pass: [GAE] + ppo_epochs * T policy updates.  Returns the loss dict of the last update."""
         if next_last is not None:
             self.compute_advantages(buf, next_last)
+        if getattr(self.updater, "track_stats", False):
+            self.updater.stats_reset()   # (the means iteration_log reports are those of THIS pass)
         out = None
         dev = next(iter(buf.data.values())).device
         for _ in range(self.ppo_epochs):
@@ -156,6 +206,29 @@ class RolloutDriver:
                 for idx in idxs:
                     out = self.updater.step_from(buf, idx)
         return out
+
+
+    def iteration_log(self, buf: RolloutBuffer, episode_stats: Optional["EpisodeStats"] = None) -> Dict[str, float]:
+        """The ``log_info`` of one training iteration (train.py:237-246, 318-333) after ``run``, as Python floats: ``train/<key>`` = the mean
+        of every reported loss term over the pass's ppo_epochs x minibatches updates (``PolicyUpdater(track_stats=True).stats_read()``),
+        ``train/explained_variance`` (+ ``_flat``: over all frames at once) of the buffer's state_value against value_target, ``train/lr``,
+        ``train/clip_epsilon`` (PPO), and ``train/reward`` / ``train/episode_length`` when ``episode_stats`` (the one ``collect`` scanned this
+        rollout with) saw at least one finished episode -- omitted otherwise, as in train.py:239.  The host-side timing keys are the
+        caller's.  Everything is enqueued first; the host then waits ONCE per call, not once per step."""
+        upd = self.updater
+        ev = explained_variance(buf.data["state_value"], buf.data["value_target"])
+        eps = getattr(upd.loss_module, "clip_epsilon", None)
+        means = upd.stats_read()                                   # (the synchronisation)
+        log = {f"train/{k}": v for k, v in means.items() if k != "updates"}
+        ev = ev.tolist()
+        log.update({"train/explained_variance": ev[0], "train/explained_variance_flat": ev[1], "train/lr": upd.lr})
+        if torch.is_tensor(eps):
+            log["train/clip_epsilon"] = float(eps)
+        if episode_stats is not None:
+            ret, length, n = episode_stats.sums.tolist()
+            if n > 0:
+                log.update({"train/reward": ret / n, "train/episode_length": length / n})
+        return log
 
 
 class PolicyActor:
@@ -209,11 +282,13 @@ class PolicyActor:
         return self._out
 
 
-def collect(env_step, first_obs: Dict[str, torch.Tensor], actor: PolicyActor, T: int, normalizer=None):
+def collect(env_step, first_obs: Dict[str, torch.Tensor], actor: PolicyActor, T: int, normalizer=None, episode_stats=None):
     """The data-collection half of one training iteration (train.py:114-123, 232-247) with everything on the device: for T steps the
     (optionally normalised) observation goes through the collector-side actor, the action into ``env_step(action) -> (next raw
     observation groups, reward [N], done [N] bool, terminated [N] bool)``; the frames are stacked into a ``RolloutBuffer`` [N, T, ...].
-    Returns ``(buffer, next_last)`` as ``RolloutDriver.run`` takes them (``next_last``: the observation after the last step, [N, 1, width])."""
+    Returns ``(buffer, next_last)`` as ``RolloutDriver.run`` takes them (``next_last``: the observation after the last step, [N, 1, width]).
+    ``episode_stats``: an ``EpisodeStats`` -- its scan runs once over the stacked rollout and the buffer gains ``episode_reward`` and
+    ``step_count`` [N, T, 1] (the collector-side RewardSum / StepCounter transforms)."""
     raw = first_obs
     frames = []
     for _ in range(T):
@@ -226,4 +301,6 @@ def collect(env_step, first_obs: Dict[str, torch.Tensor], actor: PolicyActor, T:
         frames.append(rec)
     last = normalizer(raw, update=False) if normalizer is not None else raw
     data = {k: torch.stack([f[k] for f in frames], dim=1) for k in frames[0]}
+    if episode_stats is not None:
+        data["episode_reward"], data["step_count"] = episode_stats.scan(data["reward"], data["done"])
     return RolloutBuffer(data), {k: v.unsqueeze(1) for k, v in last.items()}

@@ -377,22 +377,27 @@ def report_dict(o, m=None):
                   "entropy_diff": o[11], "loss_objective_value": o[12]}
 
 
-def report_values(m, slots, B, sums, maxes):
+def report_critic(o):
+    """The critic loss of the 14-float report (filled where the fused loss kernel ran WITH the value terms: one stream)."""
+    return o[1]
+
+
+def report_values(m, slots, B, sums, maxes, out=None):
     """Fold of the fused kernel's per-workgroup slots and the reported values in ONE launch (one rank): -> (actor loss, critic loss,
-    metrics dict) like ``loss_values``."""
+    metrics dict) like ``loss_values``.  ``out``: the float32[14] buffer to report into."""
     ent_coef = m.entropy_coef if m.entropy_bonus else 0.0
-    o = torch.empty(14, device=sums.device, dtype=torch.float32)
+    o = out if out is not None else torch.empty(14, device=sums.device, dtype=torch.float32)
     hip.call("grl_trpl_report", slots, B, sums, maxes, float(ent_coef), o)
-    return o[0], o[1], report_dict(o, m)[1]
+    return o[0], report_critic(o), report_dict(o, m)[1]
 
 
-def loss_values(m, sums, maxes):
+def loss_values(m, sums, maxes, out=None):
     """(actor loss, critic loss, metrics dict) from the globally reduced sums / maxes (trpl.py:280-321): one launch, the entries
-    are views of its 14-float output."""
+    are views of its 14-float output (``out``: the float32[14] buffer to report into)."""
     ent_coef = m.entropy_coef if m.entropy_bonus else 0.0
-    o = torch.empty(14, device=sums.device, dtype=torch.float32)
+    o = out if out is not None else torch.empty(14, device=sums.device, dtype=torch.float32)
     hip.call("grl_trpl_loss_values", sums, maxes, float(ent_coef), o)
-    return o[0], o[1], report_dict(o, m)[1]
+    return o[0], report_critic(o), report_dict(o, m)[1]
 
 
 def _run_trpl(m, loc, sigma, value, batch):

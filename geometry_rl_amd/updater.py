@@ -79,11 +79,16 @@ class PolicyUpdater:
     ``loss_module`` is a TRPLLoss or a ClipPPOLoss2: every program runs either (the fused loss kernel is the only launch that differs).
     PPO's ``clip_epsilon`` buffer is read from device memory by that launch, so an in-place write (``loss.clip_epsilon.copy_(eps)``)
     takes effect at the next step or replay without recording again; within one ``run_minibatches`` launch of several steps it is
-    constant, like ``lr``.  Replacing the buffer by another tensor drops the recorded program (it is recorded again)."""
+    constant, like ``lr``.  Replacing the buffer by another tensor drops the recorded program (it is recorded again).
+
+    ``track_stats=True``: every program ends each lane with one more small launch (``grl_stats_accumulate``) that adds the values the
+    update reports to running fp64 sums in device memory -- ``stats_read()`` returns their means over all updates since ``stats_reset()``
+    (what train.py:294,320 logs as ``train/<key>``) without a host synchronisation per step; the updates themselves are unchanged.  False
+    (default): nothing is allocated and every program is what it is without the argument."""
 
     def __init__(self, loss_module, lr=3e-4, eps=1e-5, betas=(0.9, 0.999), clip_grad_norm=False, max_grad_norm=1.0,
                  group=None, use_graph=False, overlap_critic=True, allow_eager_fallback=False, force_dp_plan=False,
-                 critic_after_first_conv=True):
+                 critic_after_first_conv=True, track_stats=False):
         self.loss_module, self.group = loss_module, group
         self.overlap_critic = overlap_critic   # one rank: False = everything on the caller's stream (_plan_one_stream)
         self.force_dp_plan = force_dp_plan     # a process group of ONE rank runs the data-parallel program (bench.py --dp-plan)
@@ -148,6 +153,12 @@ class PolicyUpdater:
         self.BETA_SLOTS = 64
         self.beta_table = torch.zeros(self.BETA_SLOTS, device=dev, dtype=torch.float64)
         self._lr = float(lr)
+        # running sums of the reported values (track_stats): the actor lane's 14 report values + the number of updates, the critic lane's
+        # loss + its count; each lane adds to its own, so the lanes still share nothing
+        self.track_stats = bool(track_stats)
+        self.stats_actor = torch.zeros(15, device=dev, dtype=torch.float64) if self.track_stats else None
+        self.stats_critic = torch.zeros(2, device=dev, dtype=torch.float64) if self.track_stats else None
+        self._stats_one_stream = False   # the running program is _plan_one_stream: its report carries the critic loss
         self.use_graph = use_graph
         if use_graph and getattr(loss_module.actor_network, "post_fc", False):
             # config 1's baseline actor is a stock torch.nn.TransformerEncoder: its launches are torch's own (rocBLAS / hipBLASLt
@@ -251,6 +262,44 @@ class PolicyUpdater:
         if n_steps > self.BETA_SLOTS:
             raise ValueError(f"{n_steps} steps per launch with entropy control: the bound table has {self.BETA_SLOTS} entries")
         ops.write_doubles(self.beta_table, m.projection.entropy_bounds(range(self.steps, self.steps + n_steps)))
+
+    # ---- the means of the reported values over many updates (track_stats=True)
+    def _stats_add(self, src, acc):
+        """``acc[:n] += src``, ``acc[n] += 1`` on the current stream: the last launch of a lane (no-op without track_stats)."""
+        if self.track_stats:
+            hip.call("grl_stats_accumulate", src, int(src.numel()), acc)
+
+    def stats_reset(self):
+        """Zero the running sums (on the caller's stream: every program joins the critic's lane at its end)."""
+        if not self.track_stats:
+            raise RuntimeError("PolicyUpdater(track_stats=True) keeps the running sums; this updater was built without them")
+        self.stats_actor.zero_()
+        self.stats_critic.zero_()
+
+    def stats_read(self) -> Dict[str, float]:
+        """The fp64 means of every reported value over the updates since ``stats_reset()`` as Python floats, under the loss module's own
+        key names (``loss_objective``, ``loss_critic``, then the keys of ``trpl.report_dict`` / ``ppo.report_dict``), and ``"updates"``,
+        their number.  Joins the critic's lane and synchronises ONCE (two small device-to-host copies)."""
+        from .trpl import report_critic, report_dict
+        if not self.track_stats:
+            raise RuntimeError("PolicyUpdater(track_stats=True) keeps the running sums; this updater was built without them")
+        if self._cstream is not None:
+            torch.cuda.current_stream().wait_stream(self._cstream)
+        a, c = self.stats_actor.cpu(), self.stats_critic.cpu()
+        n, n_c = int(a[14]), int(c[1])
+        if self._stats_one_stream and n_c == 0:
+            n_c = n   # (one stream: the critic loss rides in the actor lane's report)
+            critic_sum = report_critic(a)
+        else:
+            critic_sum = c[0]
+        if n != n_c:
+            raise RuntimeError(f"the actor's lane counted {n} updates, the critic's {n_c}: the running sums do not belong to one sequence")
+        out = {"updates": n}
+        if n:
+            _, mt = report_dict(a[:14] / n, self.loss_module)
+            mt = {k: float(v) for k, v in mt.items()}
+            out.update(loss_objective=mt.pop("loss_objective_value"), loss_critic=float(critic_sum / n), **mt)
+        return out
 
     def anneal_lr(self, base_lr: float, iteration: int, total_iterations: int) -> float:
         """train.py:264-271: ``alpha = 1 - i / total; lr = base_lr * alpha`` for both optimisers."""
@@ -364,6 +413,7 @@ class PolicyUpdater:
         actor, vf = m.actor_network, m.critic_network._network1
         leaves = self._critic_leaves()
         ow = self._fold_overwrite
+        self._stats_one_stream = True
 
         def s0():  # critic features, first critic stage, advantage statistics
             self._prep(batch, st, zero=self.gflat)
@@ -406,8 +456,10 @@ class PolicyUpdater:
                 # clipping their two Adam steps are ONE launch over the flat buffer (element-wise: the same numbers)
                 for i_, (lo, hi) in enumerate(((0, na), (na, n)) if self.clip else ((0, n),)):
                     self._adam(st, lo, hi, i_)
-                a_loss, c_loss, mt = loss_values(m, st["sums"], st["maxes"])
+                o14 = torch.empty(14, device=self.flat.device, dtype=torch.float32) if self.track_stats else None
+                a_loss, c_loss, mt = loss_values(m, st["sums"], st["maxes"], out=o14)
                 st["lv_main"], st["c_loss"] = (a_loss, mt), c_loss
+                self._stats_add(o14, self.stats_actor)   # (one call: the report carries the critic loss)
 
         return [Entry("run", s0), Entry("run", s1), Entry("run", s2), Entry("run", s3), Entry("run_host", lambda: self._finish(st))]
 
@@ -512,6 +564,7 @@ class PolicyUpdater:
         # the one-launch tail needs every leaf gradient of the lane in the fold queue (overwrite mode) and no clipping (which needs the
         # finished gradient norm before Adam)
         fuse_tail = not self.clip and ow
+        self._stats_one_stream = False
         # Gate the critic's lane behind the actor's first edge convolution?  It pays where the critic then finishes inside the actor's FORWARD
         # (its kernels cost the one-wave-per-SIMD backward launches far more than the forward ones: gated at the forward's END the step is 6 %
         # slower): measured on rigid HEPi +1.1 % at 4096 frames, +3 % at 512, +1 % at 32, 0 at 2048, -1.5 % at 1024, where a forward of
@@ -525,7 +578,7 @@ class PolicyUpdater:
                 with self._actor_lane_head(gate):
                     fold_ = self._actor_head(st, None, bool(m.normalize_advantage and st["obs"][0].shape[0] > 1))
                 with torch.no_grad():
-                    done = False
+                    done, o14 = False, None
                     if fuse_tail:   # fold + Adam + reported values: ONE launch at the lane's end (ops.fold_adam_report)
                         o14 = torch.empty(14, device=self.flat.device, dtype=torch.float32)
                         ent = m.entropy_coef if m.entropy_bonus else 0.0
@@ -538,9 +591,12 @@ class PolicyUpdater:
                     if not done:
                         ops.flush_deferred_grads(overwrite=ow)
                         self._adam(st, 0, na, 0)
-                        a_loss, _c, mt = report_values(m, fold_.slots, fold_.batch, fold_.sums, fold_.maxes)
+                        if self.track_stats and o14 is None:
+                            o14 = torch.empty(14, device=self.flat.device, dtype=torch.float32)
+                        a_loss, _c, mt = report_values(m, fold_.slots, fold_.batch, fold_.sums, fold_.maxes, out=o14 if self.track_stats else None)
             if gate and not (done and ops.SIGNAL_IN_KERNEL):   # ... and once more at the lane's end, whatever happened above (an actor without an edge convolution; a
                 self._signal_lane()                            # signal that carried a stale count): the critic's lane can be late, it can never be stuck
+            self._stats_add(o14, self.stats_actor)             # (track_stats: the lane's last launch, whichever tail wrote the report)
             st.update(sums=fold_.sums, maxes=fold_.maxes, lv_main=(a_loss, mt))
 
         # (the critic lane's inputs: the epoch program gives each lane a private copy)
@@ -553,6 +609,7 @@ class PolicyUpdater:
                 if not (fuse_tail and ops.fold_adam_report(ow, self._tail_args(na, n_all, self.step_dev_c))):
                     ops.flush_deferred_grads(overwrite=ow)
                     self._adam(st, na, n_all, 1, self.step_dev_c)
+                self._stats_add(st["c_loss"], self.stats_critic)
 
         st["lanes"] = (main_all, critic_all)
         return [Entry("fork", None), Entry("run", main_all), Entry("run", critic_all, "s"), Entry("join", None),
@@ -580,6 +637,7 @@ class PolicyUpdater:
         # rollout.RolloutDriver.publish_advantage_stats): the statistics kernel, its all-reduce and the graph boundary behind it leave
         # the actor's lane -- two graphs and one collective on its path.
         published = m.normalize_advantage and "adv_stats" in batch
+        self._stats_one_stream = False
 
         def p_stats():
             self._prep(batch, st, zero=self.gflat[:na])
@@ -628,6 +686,7 @@ class PolicyUpdater:
                     hip.call("grl_adam_report_record_pairs", self.flat[:na], self.gflat[:na], self.exp_avg[:na], self.exp_avg_sq[:na], na,
                              self.lr_dev, float(self.betas[0]), float(self.betas[1]), float(self.eps), self.step_dev,
                              self.gbuf[:self._rec], world, st["sums"], st["maxes"], float(ent), o14)
+                self._stats_add(o14, self.stats_actor)   # (the GLOBAL values: every rank adds the same numbers, no collective)
 
         q_fwd1, q_fwd2, q_fwd3, q_bwd2, bwd1 = self._critic_stages(batch, st, world, gate_dp)
 
@@ -640,6 +699,7 @@ class PolicyUpdater:
             with torch.no_grad():
                 self._adam(st, na, n_all, 1, self.step_dev_c)
                 st["c_loss"] = st["vl"][1].float()   # (the all-reduced sum of the ranks' shares, already divided by B_global)
+                self._stats_add(st["c_loss"], self.stats_critic)
 
         # (host order = enqueue order: the critic's segments are interleaved so that its lane is fed early; each lane's own order is what
         #  the device sees.  p_stats comes first when present: it also prepares the step's inputs for both lanes.)

@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 /* ABI version (major*10000 + minor*100 + patch); grl_version() returns the value the library was built with. */
-#define GRL_HIP_VERSION 210   /* 210: grl_trpl_fwd_bwd_ent (scheduled entropy projection inside the fused TRPL launch) and grl_write_doubles added, no existing signature changed; 209: three exports removed (the device-cursor variant of grl_gather_rows_many, the hipStreamWaitValue32 capability query, the idle spin kernel of calib.hip); 208: cfg9[8] = 4 accepted (non-commuting Wasserstein projection), no signature change; 207: grl_ppo_fwd_bwd added (clipped PPO objective); 206: grl_build_features_noise, grl_step_head_noise[_bf16] added (training noise); 205 (round 6): grl_source_hash added; 204 (round 5): grl_head_fused / grl_head_fused_rows removed, grl_calib_mfma / grl_calib_copy added; the exports are exactly this header */
+#define GRL_HIP_VERSION 211   /* 211: csrc/stats_ops.hip added (grl_stats_accumulate, grl_explained_variance + its scratch query, grl_episode_scan), no existing signature changed; 210: grl_trpl_fwd_bwd_ent (scheduled entropy projection inside the fused TRPL launch) and grl_write_doubles added, no existing signature changed; 209: three exports removed (the device-cursor variant of grl_gather_rows_many, the hipStreamWaitValue32 capability query, the idle spin kernel of calib.hip); 208: cfg9[8] = 4 accepted (non-commuting Wasserstein projection), no signature change; 207: grl_ppo_fwd_bwd added (clipped PPO objective); 206: grl_build_features_noise, grl_step_head_noise[_bf16] added (training noise); 205 (round 6): grl_source_hash added; 204 (round 5): grl_head_fused / grl_head_fused_rows removed, grl_calib_mfma / grl_calib_copy added; the exports are exactly this header */
 int grl_version(void);
 /* The hash of the sources this binary was built from (16 hex digits + NUL into buf; returns the length).  geometry_rl_amd/hip.py
    source_hash() recomputes it from csrc/, this header and the build's flag tables and refuses a library that disagrees. */
@@ -509,6 +509,31 @@ int grl_vecnorm(const float* x, long long rows, int K, float decay, float eps, i
                 void* scratch, float* y_norm, float* y_clip, hipStream_t stream);
 int grl_vecnorm_scratch_bytes(int K);
 int grl_knn_topology(const float* pos, const int* n_valid, int* out_nbr, int batch, int n_points, int k, hipStream_t stream);
+
+/* ---- (ABI 211) the read-out of a training run: examples/torchrl/train.py:237-246, 318-333 (csrc/stats_ops.hip) --------------------------
+ * Nothing here feeds an update.  Every kernel is deterministic (fixed summation order, no floating-point atomics: bitwise the same on a
+ * repeat) and capturable (no host read, no allocation).
+ *
+ * grl_stats_accumulate: acc[i] += (double)src[i] for i < n <= 32 (more: -2) and acc[n] += 1; one small workgroup.  The running sums
+ * behind the per-iteration means of every reported loss term (train.py:294,320: losses[j, k] = ..., losses.apply(mean)): the launch rides
+ * at the end of a lane of the recorded update, so no step is read from the host. */
+int grl_stats_accumulate(const float* src, int n, double* acc, hipStream_t stream);
+/* torchmetrics ExplainedVariance() on state_value against value_target (train.py:142,325), RESTATED (torchmetrics is no dependency and no
+ * fixture from the reference pins it: UNPINNED).  value / target: [n_env, n_steps] row-major.  With d = target - value, per column (time
+ * step) score = 1 - Var_env(d) / Var_env(target), biased variances from fp64 sums; where the denominator is 0 the score is 1 if the
+ * numerator is 0 too and 0 otherwise.  out[0] = the mean of the n_steps column scores (what the metric returns for [N, T, 1] inputs: it
+ * reduces over dimension 0 and averages its outputs uniformly); out[1] = the same score over all n_env * n_steps frames as one column.
+ * scratch: grl_explained_variance_scratch_bytes(n_env, n_steps) device bytes, fully written before they are read.  Two launches. */
+int grl_explained_variance_scratch_bytes(int n_env, int n_steps);
+int grl_explained_variance(const float* value, const float* target, int n_env, int n_steps, void* scratch, float* out, hipStream_t stream);
+/* torchrl's collector-side RewardSum / StepCounter transforms (configs/rigid_insertion_multi_hepi_trpl_cfg.yaml:74-76), RESTATED and
+ * UNPINNED as well.  reward float [n_env, n_steps], done uint8 [n_env, n_steps]; per frame episode_reward = running return + reward (float32,
+ * one add per step), step_count = running length + 1; the frame behind a done frame starts from 0.  ret_state / len_state [n_env]: the
+ * running values, read at the start and written at the end (episodes continue across rollouts).  sums fp64[3], WRITTEN: (sum of
+ * episode_reward, sum of step_count, count) over the done frames of this call -- train.py:238-246 logs sums[0] / sums[2] and
+ * sums[1] / sums[2].  Two launches. */
+int grl_episode_scan(const float* reward, const unsigned char* done, float* ret_state, int* len_state, float* episode_reward,
+                     int* step_count, double* sums, int n_env, int n_steps, hipStream_t stream);
 
 
 /* ---- measurement aid (no reference counterpart): timing of the individual kernels inside the entry points, recorded on the launch
