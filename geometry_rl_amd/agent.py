@@ -11,6 +11,7 @@ from . import hip
 from .graph import HyperData, TaskSpec
 from .hepi import HEPi, FiberBundleConv
 from .policy import BaseCritic, DeepSets, GNNGaussianPolicyDiag, GNNVFNet
+from .klpen import KLPENPPOLoss
 from .ppo import ClipPPOLoss2
 from .trpl import KLProjectionLayer, TRPLLoss
 from .updater import PolicyUpdater, _no_gc_while_capturing  # noqa: F401  (re-exported: the driver lives in updater.py)
@@ -44,9 +45,15 @@ class AgentConfig:
     # the actor's HyperData only (configs/rigid_pushing_multi_empn_trpl_cfg.yaml:105-106; every upstream critic config keeps it False)
     training_noise: bool = False
     training_noise_std: float = 0.01
-    # configs/algorithm/{trpl,ppo}.yaml: "trpl" (TRPLLoss + projection) or "ppo" (ClipPPOLoss2, no projection; objective/default.yaml)
+    # configs/algorithm/{trpl,ppo,kl_ppo}.yaml: "trpl" (TRPLLoss + projection), "ppo" (ClipPPOLoss2, no projection; objective/default.yaml)
     algorithm: str = "trpl"
     clip_epsilon: float = 0.2
+    # configs/algorithm/kl_ppo.yaml + objective/kl_ppo.yaml: "kl_ppo" (KLPENPPOLoss, no projection, no value clipping).  dtarg is a required
+    # key of that objective config (builders/agent.py:65-78 reads objective["dtarg"]): None = not given
+    dtarg: Optional[float] = None
+    kl_beta: float = 1.0
+    kl_increment: float = 2.0
+    kl_decrement: float = 0.5
     # entropy control of the projection (configs/algorithm/projection/*.yaml: entropy_schedule, target_entropy, temperature, entropy_eq,
     # entropy_first; utils_algo_graph.py:246-253 adds total_train_steps): None / False = off, "linear" | "exp" = the scheduled entropy
     # projection runs inside the fused loss launch (TRPLLoss(entropy_control=True))
@@ -60,9 +67,12 @@ class AgentConfig:
 
 def build_agent(spec: TaskSpec, cfg: AgentConfig, device="cuda", group=None):
     """-> (actor GNNGaussianPolicyDiag, critic BaseCritic, projection, loss_module)  (agent.py:31-64).  ``cfg.algorithm == "ppo"``: the
-    projection is None and the loss a ClipPPOLoss2 (utils_algo_graph.py:244-257 builds no projection for PPO)."""
-    if cfg.algorithm not in ("trpl", "ppo"):
-        raise ValueError(f"algorithm '{cfg.algorithm}': trpl | ppo (kl_ppo is not built)")
+    projection is None and the loss a ClipPPOLoss2 (utils_algo_graph.py:244-257 builds no projection for PPO); ``"kl_ppo"``: the
+    projection is None and the loss a KLPENPPOLoss (builders/agent.py:65-78), which needs ``cfg.dtarg``."""
+    if cfg.algorithm not in ("trpl", "ppo", "kl_ppo"):
+        raise ValueError(f"algorithm '{cfg.algorithm}': trpl | ppo | kl_ppo")
+    if cfg.algorithm == "kl_ppo" and cfg.dtarg is None:
+        raise ValueError("algorithm 'kl_ppo' needs dtarg (the target KL of configs/algorithm/objective/kl_ppo.yaml): AgentConfig(dtarg=...)")
     n_in = len(spec.node_types) + spec.n_vec  # utils_algo_graph.py:79
     if cfg.model == "hepi":
         mp = []  # utils_algo_graph.py:29-47: one fresh conv per (level, active round)
@@ -103,6 +113,11 @@ def build_agent(spec: TaskSpec, cfg: AgentConfig, device="cuda", group=None):
         loss = ClipPPOLoss2(actor, critic, clip_epsilon=cfg.clip_epsilon, entropy_coef=cfg.entropy_coef, critic_coef=cfg.critic_coef,
                             clip_value=cfg.clip_value, loss_critic_type="l2", normalize_advantage=True, in_features=a_in,
                             critic_in_features=spec.in_features, group=group)
+        return actor, critic, None, loss
+    if cfg.algorithm == "kl_ppo":   # builders/agent.py:65-78 (no clip_value: torchrl's class clips no value)
+        loss = KLPENPPOLoss(actor, critic, dtarg=cfg.dtarg, beta=cfg.kl_beta, increment=cfg.kl_increment, decrement=cfg.kl_decrement,
+                            entropy_coef=cfg.entropy_coef, critic_coef=cfg.critic_coef, loss_critic_type="l2", normalize_advantage=True,
+                            in_features=a_in, critic_in_features=spec.in_features, group=group)
         return actor, critic, None, loss
     projection = KLProjectionLayer(proj_type=cfg.proj_type, mean_bound=cfg.mean_bound, cov_bound=cfg.cov_bound,
                                    trust_region_coeff=cfg.trust_region_coeff, scale_prec=True, entropy_schedule=cfg.entropy_schedule or False,

@@ -218,6 +218,12 @@ struct TrplCfg {
 //       x_i / n is small they have not converged (1e-3: 2.4 %, 1e-4: 47 % below sqrt(x_i)).  The backward runs through t, d, n and the ten steps in
 //       reverse (their iterates kept in registers); frames inside the bound pass the gradient through.  Trust-region terms and metrics
 //       as 2 (trust_region_value = the non-commuting W2, which equals the commutative one on diagonal matrices).
+//       5 = no projection, the adaptive KL-penalty PPO surrogate (torchrl 0.3.1 KLPENPPOLoss.forward, restated): no clipping of the ratio,
+//       loss = -e^lw adv + beta kl_f with kl_f = KL(N(mo, diag(So)) || N(mean, diag(S))), OLD || NEW, in closed form
+//       1/2 sum_i [So_i / S_i + (mean_i - mo_i)^2 / S_i - 1 + log S_i - log So_i]  (exactly 0 where new == old); its gradient is analytic:
+//       d kl_f / d mean_i = (mean_i - mo_i) / S_i,  d kl_f / d S_i = (1 / S_i - So_i / S_i^2 - (mean_i - mo_i)^2 / S_i^2) / 2.  beta is read
+//       from a DEVICE float (the loss module's beta buffer, rewritten behind every step's report by grl_klpen_adapt): value and gradient
+//       of a step use the beta in force when its launch runs.  Column 11 carries sum kl_f; the trust-region columns and the maxes stay zero.
 // Covariance projection (KL): eta >= 0 with KL_cov(eta) = cov_bound.  With rho_i = v_i/o_i = (eta+1)/(eta+c_i), c_i = o_i/t_i:
 //   KL = 1/2 sum(rho_i - 1 - log rho_i),  dKL/deta = -1/2 sum (1-c_i)^2 / ((eta+1)(eta+c_i)^2) < 0, KL convex in eta: Newton from eta = 0
 //   approaches the root monotonically from the left (never overshoots).  Phase 1 runs the iteration in fp32 (hardware log2 / reciprocal)
@@ -273,7 +279,7 @@ struct TrplPtrs {
   double* slots;
   const float *tgt_mean, *tgt_S;
   int ms_row0;
-  const float* clip_eps;   // PROJ 3 only: device float[1]
+  const float* clip_eps;   // device float[1].  PROJ 3: the clip epsilon; PROJ 5: the KL penalty weight beta
   const double* ent_beta;  // ENT only: device double[1], the entropy bound of THIS launch (read when the kernel runs)
   int ent_mode;            // ENT only: bit 0 = equality form (every frame is scaled), bit 1 = entropy stage in FRONT of the trust region
 };
@@ -326,6 +332,7 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
   const size_t k = (size_t)b * A + ii, kms = (size_t)(b - q_.ms_row0) * A + ii;
   const double mu = mean[kms], sg = sigma[kms], ac = action[k];
   const double mo = PROJ == 3 ? 0.0 : (double)old_mean[k], So = PROJ == 3 ? 1.0 : (double)old_var[k];   // (PPO: no old distribution)
+  constexpr bool NOPROJ = PROJ == 3 || PROJ == 5;   // the two PPO modes: no projection, no trust-region terms
   const double S = sg * sg;                  // policy covariance diagonal == "std" seen by the projection (trpl.py:241)
   // ---- (ENT) scheduled entropy projection in FRONT of the trust region: the projection below runs on (mu, Sx = alpha S)
   bool e_act = false, e_first = false;
@@ -347,9 +354,9 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
   const double t = Sx * Sx, o = So * So;     // kl_projection_layer.py:60-63: covariance(std) = std**2
   // ---- mean projection (base_projection_layer.py:71-100)
   double mp = 0.0;
-  if (PROJ != 3) { const double d = (mu - mo) / So; mp = gsum<L>(M(d * d)); }
+  if (!NOPROJ) { const double d = (mu - mo) / So; mp = gsum<L>(M(d * d)); }
   if (PROJ == 0) mp *= 0.5;
-  const bool m_act = PROJ != 3 && PROJ != 4 && mp > cfg.mean_bound;   // (4: one joint bound, below)
+  const bool m_act = !NOPROJ && PROJ != 4 && mp > cfg.mean_bound;   // (4: one joint bound, below)
   double omega = 0.0, D = 1.0;
   if (m_act) { omega = sqrt(mp / cfg.mean_bound) - 1.0; D = 1.0 + omega + 1e-16; }
   double pm = m_act ? (mu + omega * mo) / D : mu;
@@ -394,7 +401,7 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
     }
     v = (eta + 1.0) / (eta / o + 1.0 / t);
     pS = sqrt(v);
-  } else if (PROJ == 3) {
+  } else if (NOPROJ) {
     c_act = false;
     v = t;
     pS = S;
@@ -472,8 +479,16 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
     acc[0] = -fmin(g1, g2);
     if ((lw > hi && adv > 0.0) || (lw < lo && adv < 0.0)) w_lw = 0.0;
   }
+  double kl_dm = 0.0;   // PROJ 5: mean - old mean
+  if (PROJ == 5) {   // KL penalty (the header above): beta in fp64 from the float32 buffer
+    const double beta = (double)q_.clip_eps[0];
+    kl_dm = mu - mo;
+    const double kl_f = 0.5 * gsum<L>(M(So / S + kl_dm * kl_dm / S - 1.0 + (log(S) - log(So))));
+    acc[0] += beta * kl_f;
+    acc[10] = kl_f;
+  }
   float mmax = 0.f, cmax = 0.f;
-  if (PROJ == 3) acc[8] = acc[2];   // "entropy": MultivariateNormal(mean, diag(S)).entropy (the reported PPO key)
+  if (NOPROJ) acc[8] = acc[2];   // "entropy": MultivariateNormal(mean, diag(S)).entropy (the reported PPO key)
   else {
   // ---- trust-region regression loss and metrics
   const double dmk = (mu - pm) / pS, rr = S / pS;
@@ -502,6 +517,11 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
   const double w_obj = w_lw * cfg.inv_batch;
   double g_pm = w_obj * da / pS;
   double g_pS = w_obj * 0.5 * (da * da / (pS * pS) - 1.0 / pS) - cfg.ent_coef * cfg.inv_batch * 0.5 / pS;
+  if (PROJ == 5) {
+    const double wb = (double)q_.clip_eps[0] * cfg.inv_batch;
+    g_pm += wb * kl_dm / S;
+    g_pS += wb * 0.5 * (1.0 / S - So / (S * S) - kl_dm * kl_dm / (S * S));
+  }
   const double ctr = cfg.tr_coeff * cfg.inv_batch;
   if (ext) { g_pm = 0.0; g_pS = 0.0; }
   else if (PROJ == 1) {
@@ -742,6 +762,15 @@ __global__ __launch_bounds__(FOLD_NT) void trpl_report_kernel(const double* __re
   trpl_report_body<FOLD_NT>(slots, n_blocks, sums, maxes, entropy_coef, out, sh, part);
 }
 
+// beta <- beta * increment where the reported mean KL exceeds hi, beta * decrement where it is below lo (strict), else unchanged
+__global__ __launch_bounds__(64) void klpen_adapt_kernel(const float* __restrict__ out14, float* __restrict__ beta, float hi, float lo,
+                                                        float increment, float decrement) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const float kl = out14[5], b = beta[0];
+  if (kl > hi) beta[0] = b * increment;
+  else if (kl < lo) beta[0] = b * decrement;
+}
+
 // ---- collector-side action sampling: torch.distributions.MultivariateNormal(loc, covariance_matrix = diag(sigma^2)).rsample()
 //      with return_log_prob (utils_algo_graph.py:146-158, configs/algorithm/policy/default.yaml:6): action = loc + sigma * eps,
 //      log p = -1/2 sum eps_eff^2 - sum log sigma - A/2 log(2 pi), eps_eff = (action - loc) / sigma as the distribution computes it
@@ -826,7 +855,7 @@ static int trpl_launch(const double* cfg9, int action_dim, const float* mean, co
   if (ent_mode >= 0 && (ent_mode > 3 || !ent_beta || tgt_mean)) return -2;
   TrplCfg c{cfg9[0], cfg9[1], cfg9[2], cfg9[3], cfg9[4], cfg9[5], cfg9[6], cfg9[7], action_dim, (int)cfg9[9]};
   const int proj = (int)cfg9[8];
-  if (proj < 0 || proj > 4 || proj == 3) return -3;   // (3, the PPO mode, has its own entry point: grl_ppo_fwd_bwd)
+  if (proj < 0 || proj > 4 || proj == 3) return -3;   // (3 and 5, the PPO modes, have their own entry points: grl_ppo_fwd_bwd, grl_klpen_fwd_bwd)
   const TrplPtrs tp{mean, sigma, action, old_mean, old_var, old_logp, advantage, value, old_value, value_target, dmean, dsigma, dvalue,
                     proj_mean, proj_var, adv_stats, slots, tgt_mean, tgt_S, 0, nullptr, ent_beta, ent_mode < 0 ? 0 : ent_mode};
 #define GRL_TRPL_LAUNCH(LL, PJ)                                                                                                           \
@@ -876,6 +905,40 @@ int grl_ppo_fwd_bwd(const double* cfg6, const float* clip_eps, int action_dim, c
     hipLaunchKernelGGL(trpl_fold_kernel, dim3(1), dim3(FOLD_NT), 0, stream, slots, trpl_blocks(batch), sums, maxes);
     GRL_CHECK_LAUNCH();
   }
+  return 0;
+}
+
+// The adaptive KL-penalty PPO objective (mode 5 of the kernel; include/grl_hip.h): the arguments of grl_ppo_fwd_bwd plus the old distribution;
+// beta: DEVICE float[1] in the place of clip_eps, read by the kernel
+int grl_klpen_fwd_bwd(const double* cfg6, const float* beta, int action_dim, const float* mean, const float* sigma, const float* action,
+                      const float* old_mean, const float* old_var, const float* old_logp, const float* advantage, const float* value,
+                      const float* old_value, const float* value_target, float* dmean, float* dsigma, float* dvalue, const double* adv_stats,
+                      double* sums, unsigned int* maxes, double* slots, int batch, hipStream_t stream) {
+  if (action_dim > 16 || action_dim < 1 || batch < 1 || !slots || !beta || !mean || !sigma || !action || !old_mean || !old_var || !old_logp ||
+      !advantage || !dmean || !dsigma)
+    return -2;
+  if (value && (!old_value || !value_target || !dvalue)) return -2;
+  const TrplCfg c{0.0, 0.0, 0.0, cfg6[0], cfg6[1], cfg6[2], cfg6[3], cfg6[4], action_dim, (int)cfg6[5]};
+  const TrplPtrs tp{mean, sigma, action, old_mean, old_var, old_logp, advantage, value, old_value, value_target, dmean, dsigma, dvalue,
+                    nullptr, nullptr, adv_stats, slots, nullptr, nullptr, 0, beta, nullptr, 0};
+  if (action_dim <= 4) hipLaunchKernelGGL((trpl_lanes_kernel<4, 5>), dim3(trpl_blocks(batch)), dim3(TRPL_FPB * 4), 0, stream, c, tp, batch);
+  else if (action_dim <= 8) hipLaunchKernelGGL((trpl_lanes_kernel<8, 5>), dim3(trpl_blocks(batch)), dim3(TRPL_FPB * 8), 0, stream, c, tp, batch);
+  else hipLaunchKernelGGL((trpl_lanes_kernel<16, 5>), dim3(trpl_blocks(batch)), dim3(TRPL_FPB * 16), 0, stream, c, tp, batch);
+  GRL_CHECK_LAUNCH();
+  if (sums) {
+    hipLaunchKernelGGL(trpl_fold_kernel, dim3(1), dim3(FOLD_NT), 0, stream, slots, trpl_blocks(batch), sums, maxes);
+    GRL_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
+// torchrl 0.3.1 KLPENPPOLoss.forward's tail: kl > 1.5 dtarg -> beta *= increment; kl < dtarg / 1.5 -> beta *= decrement.  kl = out14[5], the
+// float32 mean KL the step reported; hi / lo: the two thresholds, formed in double by the caller and rounded to float.  One thread, one
+// launch behind whichever tail wrote the report: the next loss launch on the stream reads the new beta.
+int grl_klpen_adapt(const float* out14, float* beta, float hi, float lo, float increment, float decrement, hipStream_t stream) {
+  if (!out14 || !beta) return -2;
+  hipLaunchKernelGGL(klpen_adapt_kernel, dim3(1), dim3(1), 0, stream, out14, beta, hi, lo, increment, decrement);
+  GRL_CHECK_LAUNCH();
   return 0;
 }
 

@@ -1031,6 +1031,61 @@ def ppo_fwd_bwd(loc, sigma, batch, value, *, clip_epsilon: torch.Tensor, entropy
     return sums, maxes, dloc, dsigma, dvalue
 
 
+def klpen_fwd_bwd(loc, sigma, batch, value, *, beta: torch.Tensor, entropy_coef, critic_coef, clip_value, global_batch: int,
+                  adv_stats: Optional[torch.Tensor], sums=None, maxes=None, defer_fold: bool = False, adv_local: bool = False):
+    """The adaptive KL-penalty PPO objective on the fused kernel (grl_klpen_fwd_bwd): the returns of ``ppo_fwd_bwd``, (sums, maxes, dloc,
+    dsigma, dvalue).  ``batch`` carries the old distribution ("loc", "var").  ``beta``: a device float32 tensor of one element, the penalty
+    weight, read by the kernel when it runs (a recorded launch sees every write to it: ``klpen_adapt``'s and the host's)."""
+    import ctypes
+    hip.check_f32(loc, sigma, beta)
+    if beta.numel() != 1 or beta.device != loc.device:
+        raise ValueError("beta must be a one-element float32 tensor on the policy's device")
+    B, A = loc.shape
+    dev = loc.device
+    cfg = (ctypes.c_double * 6)(entropy_coef, critic_coef, clip_value if clip_value else 0.0, 1.0 / global_batch, float(global_batch),
+                                1.0 if adv_local else 0.0)
+    if sums is None:
+        sums = torch.empty(12, device=dev, dtype=torch.float64)
+        maxes = torch.empty(2, device=dev, dtype=torch.int32)
+    slots = torch.empty(hip.query("grl_trpl_slot_doubles", B), device=dev, dtype=torch.float64)
+    dloc, dsigma = torch.empty_like(loc), torch.empty_like(sigma)
+    dvalue = torch.empty(B, device=dev, dtype=torch.float32) if value is not None else None
+    f = lambda t: t.reshape(B, -1).contiguous()
+    old_loc, old_var = f(batch["loc"]), f(batch["var"])
+    if old_loc.shape != loc.shape or old_var.shape != loc.shape:
+        raise ValueError(f"the old distribution is {tuple(old_loc.shape)} / {tuple(old_var.shape)}, the policy's {tuple(loc.shape)}")
+    hip.check_f32(old_loc, old_var)
+    hip.call("grl_klpen_fwd_bwd", cfg, beta, A, loc.contiguous(), sigma.contiguous(), f(batch["action"]), old_loc, old_var,
+             batch["sample_log_prob"].reshape(B).contiguous(), batch["advantage"].reshape(B).contiguous(),
+             value.reshape(B).contiguous() if value is not None else None,
+             batch["state_value"].reshape(B).contiguous() if value is not None else None,
+             batch["value_target"].reshape(B).contiguous() if value is not None else None,
+             dloc, dsigma, dvalue, adv_stats, None if defer_fold else sums, maxes, slots, B)
+    if defer_fold:
+        def fold(sums=sums, maxes=maxes, slots=slots):
+            hip.call("grl_trpl_fold", slots, B, sums, maxes)
+            return sums, maxes
+        fold.slots, fold.batch, fold.sums, fold.maxes = slots, B, sums, maxes
+        return fold, maxes, dloc, dsigma, dvalue
+    return sums, maxes, dloc, dsigma, dvalue
+
+
+def klpen_thresholds(dtarg: float):
+    """(hi, lo) = (dtarg * 1.5, dtarg / 1.5) formed in double and rounded to float32: what the float32 mean KL is compared with."""
+    import ctypes
+    return ctypes.c_float(float(dtarg) * 1.5).value, ctypes.c_float(float(dtarg) / 1.5).value
+
+
+def klpen_adapt(out14: torch.Tensor, beta: torch.Tensor, dtarg: float, increment: float, decrement: float) -> None:
+    """The penalty weight's update on the current stream (grl_klpen_adapt, one single-thread launch): ``beta *= increment`` where the
+    report's mean KL (``out14[5]``) exceeds 1.5 dtarg, ``beta *= decrement`` where it is below dtarg / 1.5."""
+    hip.check_f32(out14, beta)
+    if out14.numel() < 14 or beta.numel() != 1 or beta.device != out14.device:
+        raise ValueError("klpen_adapt: a 14-float report and a one-element beta on one device")
+    hi, lo = klpen_thresholds(dtarg)
+    hip.call("grl_klpen_adapt", out14, beta, hi, lo, float(increment), float(decrement))
+
+
 def trpl_target_terms(loc, sigma, tgt_mean, tgt_S, *, mean_bound, cov_bound, trust_region_coeff, global_batch: int, proj_type: int = 0):
     """Trust-region measure of (p, detached target) with its gradient -- the fused kernel with the projection skipped
     (grl_trpl_target_terms).  ``sigma`` = sqrt of the policy's covariance diagonal, ``tgt_S`` = the target's covariance diagonal.

@@ -212,7 +212,7 @@ class RolloutDriver:
         """The ``log_info`` of one training iteration (train.py:237-246, 318-333) after ``run``, as Python floats: ``train/<key>`` = the mean
         of every reported loss term over the pass's ppo_epochs x minibatches updates (``PolicyUpdater(track_stats=True).stats_read()``),
         ``train/explained_variance`` (+ ``_flat``: over all frames at once) of the buffer's state_value against value_target, ``train/lr``,
-        ``train/clip_epsilon`` (PPO), and ``train/reward`` / ``train/episode_length`` when ``episode_stats`` (the one ``collect`` scanned this
+        ``train/clip_epsilon`` (PPO), ``train/kl_beta`` (KL-penalty PPO: the penalty weight the pass left behind), and ``train/reward`` / ``train/episode_length`` when ``episode_stats`` (the one ``collect`` scanned this
         rollout with) saw at least one finished episode -- omitted otherwise, as in train.py:239.  The host-side timing keys are the
         caller's.  Everything is enqueued first; the host then waits ONCE per call, not once per step."""
         upd = self.updater
@@ -224,6 +224,8 @@ class RolloutDriver:
         log.update({"train/explained_variance": ev[0], "train/explained_variance_flat": ev[1], "train/lr": upd.lr})
         if torch.is_tensor(eps):
             log["train/clip_epsilon"] = float(eps)
+        if getattr(upd.loss_module, "algorithm", None) == "kl_ppo":
+            log["train/kl_beta"] = float(upd.loss_module.beta)
         if episode_stats is not None:
             ret, length, n = episode_stats.sums.tolist()
             if n > 0:

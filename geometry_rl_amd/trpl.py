@@ -334,11 +334,15 @@ def trpl_launch(m, loc, sigma, value, batch, adv_stats, sums=None, maxes=None, d
     losses with respect to loc, sigma and value.  ``defer_fold``: see ops.trpl_fwd_bwd (``sums`` comes back as the folding callable).
     ``adv_local`` (one rank): the advantage statistics are summed inside the kernel; ``value=None``: actor-only (the critic's share of
     the loss comes from ``value_loss`` on the critic's lane).  A PPO loss module (``m.algorithm == "ppo"``) takes the same launch in
-    its PPO mode (ppo.ppo_launch): same slots, same returns.  With entropy control (``entropy_active(m)``) the launch is the one with
+    its PPO mode (ppo.ppo_launch), a KL-penalty PPO module (``"kl_ppo"``) in its KL-penalty mode (klpen.klpen_launch): same slots, same
+    returns.  With entropy control (``entropy_active(m)``) the launch is the one with
     the entropy stage and reads its bound from ``beta`` (device float64[1]; default: the loss module's own buffer)."""
     if getattr(m, "algorithm", "trpl") == "ppo":
         from .ppo import ppo_launch
         return ppo_launch(m, loc, sigma, value, batch, adv_stats, sums=sums, maxes=maxes, defer_fold=defer_fold, adv_local=adv_local)
+    if getattr(m, "algorithm", "trpl") == "kl_ppo":
+        from .klpen import klpen_launch
+        return klpen_launch(m, loc, sigma, value, batch, adv_stats, sums=sums, maxes=maxes, defer_fold=defer_fold, adv_local=adv_local)
     p = m.projection
     B = loc.shape[0]
     sums, maxes, dloc, dsigma, dvalue, _, _ = ops.trpl_fwd_bwd(
@@ -368,10 +372,13 @@ def value_loss(m, value, batch):
 
 def report_dict(o, m=None):
     """The 14-float output of grl_trpl_report / grl_fold_adam_report as (actor loss, metrics dict of views); the PPO loss module
-    ``m`` reports its own keys (ppo.report_dict)."""
+    ``m`` reports its own keys (ppo.report_dict), the KL-penalty PPO module likewise (klpen.report_dict)."""
     if getattr(m, "algorithm", "trpl") == "ppo":
         from .ppo import report_dict as ppo_report_dict
         return ppo_report_dict(o, m)
+    if getattr(m, "algorithm", "trpl") == "kl_ppo":
+        from .klpen import report_dict as klpen_report_dict
+        return klpen_report_dict(o, m)
     return o[0], {"loss_trust_region": o[2], "loss_entropy": o[3], "ESS": o[4], "kl": o[5], "constraint": o[13], "mean_constraint": o[6],
                   "mean_constraint_max": o[7], "cov_constraint": o[8], "cov_constraint_max": o[9], "entropy": o[10],
                   "entropy_diff": o[11], "loss_objective_value": o[12]}
@@ -400,8 +407,9 @@ def loss_values(m, sums, maxes, out=None):
     return o[0], report_critic(o), report_dict(o, m)[1]
 
 
-def _run_trpl(m, loc, sigma, value, batch):
-    """Fused kernel (+ the advantage statistics launch) with the data-parallel reductions; everything detached."""
+def _run_trpl(m, loc, sigma, value, batch, out=None):
+    """Fused kernel (+ the advantage statistics launch) with the data-parallel reductions; everything detached.  ``out``: the float32[14]
+    buffer the reported values are written to."""
     with torch.no_grad():
         B = loc.shape[0]
         stats = None
@@ -416,7 +424,7 @@ def _run_trpl(m, loc, sigma, value, batch):
             import torch.distributed as dist
             dist.all_reduce(sums, group=m.group)
             dist.all_reduce(maxes, op=dist.ReduceOp.MAX, group=m.group)
-        actor, critic, metrics = loss_values(m, sums, maxes)
+        actor, critic, metrics = loss_values(m, sums, maxes, out=out)
     actor = _InjectGrad.apply(actor, 2, loc, sigma, dloc, dsigma)
     if value is not None:
         critic = _InjectGrad.apply(critic, 1, value, dvalue.reshape(value.shape))

@@ -67,7 +67,7 @@ def _job_arrays(jobs):
 
 
 class PolicyUpdater:
-    """One policy-update step = loss forward, actor + critic backward, optional clip_grad_norm_ per network, two Adam(lr,
+    """One policy-update step of a TRPLLoss, a ClipPPOLoss2 or a KLPENPPOLoss = loss forward, actor + critic backward, optional clip_grad_norm_ per network, two Adam(lr,
     eps=1e-5) steps (train.py:279-316).  Parameters of both networks live in ONE flat fp32 buffer (gradients likewise), so a
     data-parallel run needs a single RCCL all-reduce of the gradient per step and Adam is a single kernel per optimizer.
 
@@ -76,10 +76,16 @@ class PolicyUpdater:
     overhead disappears, which is what strong scaling over 8 GPUs needs (512 frames per GPU are < 1 ms of device time).  One program per
     case (``_plan_one_stream`` / ``_plan_lanes`` / ``_plan_dp``): see the comment above ``_plan``.
 
-    ``loss_module`` is a TRPLLoss or a ClipPPOLoss2: every program runs either (the fused loss kernel is the only launch that differs).
+    ``loss_module`` is a TRPLLoss, a ClipPPOLoss2 or a KLPENPPOLoss: every program runs each (the fused loss kernel is the launch that
+    differs; the KL-penalty loss adds ONE single-thread launch per step, below).
     PPO's ``clip_epsilon`` buffer is read from device memory by that launch, so an in-place write (``loss.clip_epsilon.copy_(eps)``)
     takes effect at the next step or replay without recording again; within one ``run_minibatches`` launch of several steps it is
     constant, like ``lr``.  Replacing the buffer by another tensor drops the recorded program (it is recorded again).
+    KLPENPPOLoss's ``beta`` buffer is device data in both directions: the loss launch reads it, and every program runs the adapt launch
+    (``grl_klpen_adapt``) exactly once per step on the actor's lane, behind whichever tail wrote the step's report and ahead of the next
+    step's loss launch -- the next step, also the next of the steps inside one ``run_minibatches`` launch, sees the adapted value with
+    nothing read back.  Data parallel it follows the tail behind the collective: every rank adapts on the GLOBAL mean KL, so beta stays
+    bitwise equal across the ranks.  An in-place host write (``loss.beta.fill_(x)``) takes effect at the next step or replay.
 
     ``track_stats=True``: every program ends each lane with one more small launch (``grl_stats_accumulate``) that adds the values the
     update reports to running fp64 sums in device memory -- ``stats_read()`` returns their means over all updates since ``stats_reset()``
@@ -235,9 +241,10 @@ class PolicyUpdater:
     max_norm = property(lambda self: self._hyper["max_norm"], lambda self, v: self._set_hyper("max_norm", float(v)))
 
     def _loss_storage(self):
-        """Device storage the recorded launches read from the loss module itself (PPO's clip_epsilon), or None."""
-        eps = getattr(self.loss_module, "clip_epsilon", None)
-        return eps.data_ptr() if torch.is_tensor(eps) else None
+        """Device storage the recorded launches read from (and, beta, write to) the loss module itself: PPO's clip_epsilon, KL-penalty
+        PPO's beta; None where the module has neither."""
+        ptrs = tuple(t.data_ptr() for t in (getattr(self.loss_module, name, None) for name in ("clip_epsilon", "beta")) if torch.is_tensor(t))
+        return ptrs or None
 
     def _check_loss_storage(self):
         """A loss buffer REPLACED by another tensor (not written in place) drops the recorded programs: they read the old storage."""
@@ -245,6 +252,13 @@ class PolicyUpdater:
         if ptr != self._loss_ptr:
             self._program, self._epoch = None, None
         self._loss_ptr = ptr
+
+    def _klpen_adapt(self, o14):
+        """KL-penalty PPO: beta <- beta * increment / decrement from the step's report ``o14``, on the current stream -- behind the tail
+        that wrote the report, ahead of the next step's loss launch (no-op for the other losses)."""
+        if getattr(self.loss_module, "algorithm", "trpl") == "kl_ppo":
+            from .klpen import klpen_adapt
+            klpen_adapt(self.loss_module, o14)
 
     def _entropy_prepare(self, batch, n_steps: int = 1):
         """TRPL with entropy control: latch the layer's initial entropy at the first update (from ``batch``; data parallel: the global
@@ -278,7 +292,7 @@ class PolicyUpdater:
 
     def stats_read(self) -> Dict[str, float]:
         """The fp64 means of every reported value over the updates since ``stats_reset()`` as Python floats, under the loss module's own
-        key names (``loss_objective``, ``loss_critic``, then the keys of ``trpl.report_dict`` / ``ppo.report_dict``), and ``"updates"``,
+        key names (``loss_objective``, ``loss_critic``, then the keys of ``trpl.report_dict`` / ``ppo.report_dict`` / ``klpen.report_dict``), and ``"updates"``,
         their number.  Joins the critic's lane and synchronises ONCE (two small device-to-host copies)."""
         from .trpl import report_critic, report_dict
         if not self.track_stats:
@@ -365,6 +379,8 @@ class PolicyUpdater:
         if not self._fold_overwrite and zero is not None:
             zero.zero_()
         b = dict(batch)
+        if getattr(m, "algorithm", "trpl") == "kl_ppo" and ("loc" not in b or ("var" not in b and "covariance_matrix" not in b)):
+            raise ValueError("KLPENPPOLoss needs the old distribution in the minibatch: keys 'loc' and 'var' (or 'covariance_matrix')")
         if "var" not in b:
             b["var"] = b["covariance_matrix"].diagonal(dim1=-2, dim2=-1).contiguous()
         st["b"] = b
@@ -456,9 +472,11 @@ class PolicyUpdater:
                 # clipping their two Adam steps are ONE launch over the flat buffer (element-wise: the same numbers)
                 for i_, (lo, hi) in enumerate(((0, na), (na, n)) if self.clip else ((0, n),)):
                     self._adam(st, lo, hi, i_)
-                o14 = torch.empty(14, device=self.flat.device, dtype=torch.float32) if self.track_stats else None
+                klpen = getattr(m, "algorithm", "trpl") == "kl_ppo"
+                o14 = torch.empty(14, device=self.flat.device, dtype=torch.float32) if (self.track_stats or klpen) else None
                 a_loss, c_loss, mt = loss_values(m, st["sums"], st["maxes"], out=o14)
                 st["lv_main"], st["c_loss"] = (a_loss, mt), c_loss
+                self._klpen_adapt(o14)
                 self._stats_add(o14, self.stats_actor)   # (one call: the report carries the critic loss)
 
         return [Entry("run", s0), Entry("run", s1), Entry("run", s2), Entry("run", s3), Entry("run_host", lambda: self._finish(st))]
@@ -591,11 +609,13 @@ class PolicyUpdater:
                     if not done:
                         ops.flush_deferred_grads(overwrite=ow)
                         self._adam(st, 0, na, 0)
-                        if self.track_stats and o14 is None:
+                        keep = self.track_stats or getattr(m, "algorithm", "trpl") == "kl_ppo"   # (the report is read again behind this launch)
+                        if keep and o14 is None:
                             o14 = torch.empty(14, device=self.flat.device, dtype=torch.float32)
-                        a_loss, _c, mt = report_values(m, fold_.slots, fold_.batch, fold_.sums, fold_.maxes, out=o14 if self.track_stats else None)
+                        a_loss, _c, mt = report_values(m, fold_.slots, fold_.batch, fold_.sums, fold_.maxes, out=o14 if keep else None)
             if gate and not (done and ops.SIGNAL_IN_KERNEL):   # ... and once more at the lane's end, whatever happened above (an actor without an edge convolution; a
                 self._signal_lane()                            # signal that carried a stale count): the critic's lane can be late, it can never be stuck
+            self._klpen_adapt(o14)                             # (KL-penalty PPO: beta for the NEXT step, from this step's report)
             self._stats_add(o14, self.stats_actor)             # (track_stats: the lane's last launch, whichever tail wrote the report)
             st.update(sums=fold_.sums, maxes=fold_.maxes, lv_main=(a_loss, mt))
 
@@ -686,6 +706,7 @@ class PolicyUpdater:
                     hip.call("grl_adam_report_record_pairs", self.flat[:na], self.gflat[:na], self.exp_avg[:na], self.exp_avg_sq[:na], na,
                              self.lr_dev, float(self.betas[0]), float(self.betas[1]), float(self.eps), self.step_dev,
                              self.gbuf[:self._rec], world, st["sums"], st["maxes"], float(ent), o14)
+                self._klpen_adapt(o14)                   # (KL-penalty PPO: every rank adapts on the GLOBAL mean KL -- beta stays equal across the ranks)
                 self._stats_add(o14, self.stats_actor)   # (the GLOBAL values: every rank adds the same numbers, no collective)
 
         q_fwd1, q_fwd2, q_fwd3, q_bwd2, bwd1 = self._critic_stages(batch, st, world, gate_dp)

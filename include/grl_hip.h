@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 /* ABI version (major*10000 + minor*100 + patch); grl_version() returns the value the library was built with. */
-#define GRL_HIP_VERSION 211   /* 211: csrc/stats_ops.hip added (grl_stats_accumulate, grl_explained_variance + its scratch query, grl_episode_scan), no existing signature changed; 210: grl_trpl_fwd_bwd_ent (scheduled entropy projection inside the fused TRPL launch) and grl_write_doubles added, no existing signature changed; 209: three exports removed (the device-cursor variant of grl_gather_rows_many, the hipStreamWaitValue32 capability query, the idle spin kernel of calib.hip); 208: cfg9[8] = 4 accepted (non-commuting Wasserstein projection), no signature change; 207: grl_ppo_fwd_bwd added (clipped PPO objective); 206: grl_build_features_noise, grl_step_head_noise[_bf16] added (training noise); 205 (round 6): grl_source_hash added; 204 (round 5): grl_head_fused / grl_head_fused_rows removed, grl_calib_mfma / grl_calib_copy added; the exports are exactly this header */
+#define GRL_HIP_VERSION 212   /* 212: grl_klpen_fwd_bwd (adaptive KL-penalty PPO objective on the fused loss kernel) and grl_klpen_adapt (its penalty weight's update) added, no existing signature changed; 211: csrc/stats_ops.hip added (grl_stats_accumulate, grl_explained_variance + its scratch query, grl_episode_scan), no existing signature changed; 210: grl_trpl_fwd_bwd_ent (scheduled entropy projection inside the fused TRPL launch) and grl_write_doubles added, no existing signature changed; 209: three exports removed (the device-cursor variant of grl_gather_rows_many, the hipStreamWaitValue32 capability query, the idle spin kernel of calib.hip); 208: cfg9[8] = 4 accepted (non-commuting Wasserstein projection), no signature change; 207: grl_ppo_fwd_bwd added (clipped PPO objective); 206: grl_build_features_noise, grl_step_head_noise[_bf16] added (training noise); 205 (round 6): grl_source_hash added; 204 (round 5): grl_head_fused / grl_head_fused_rows removed, grl_calib_mfma / grl_calib_copy added; the exports are exactly this header */
 int grl_version(void);
 /* The hash of the sources this binary was built from (16 hex digits + NUL into buf; returns the length).  geometry_rl_amd/hip.py
    source_hash() recomputes it from csrc/, this header and the build's flag tables and refuses a library that disagrees. */
@@ -286,6 +286,23 @@ int grl_ppo_fwd_bwd(const double* cfg6, const float* clip_eps, int action_dim, c
                     const float* old_logp, const float* advantage, const float* value, const float* old_value, const float* value_target,
                     float* dmean, float* dsigma, float* dvalue, const double* adv_stats, double* sums, unsigned int* maxes, double* slots,
                     int batch, hipStream_t stream);
+/* (ABI 212) the adaptive KL-penalty PPO objective (torchrl 0.3.1 KLPENPPOLoss.forward, restated; the loss of algorithm=kl_ppo) on the same
+ * kernel, no projection and no clipping of the ratio: per frame lw as above, kl_f = KL(N(old_mean, diag(old_var)) || N(mean, diag(sigma^2)))
+ * (OLD || NEW) = 1/2 sum_i [So_i / S_i + (mean_i - mo_i)^2 / S_i - 1 + log S_i - log So_i], loss = -e^lw adv + beta kl_f.
+ * Arguments of grl_ppo_fwd_bwd plus old_mean / old_var [batch, action_dim]; beta: DEVICE float[1] in the place of clip_eps, read when the
+ * kernel runs (value AND gradient of a launch use that value; grl_klpen_adapt rewrites it behind the step's report).  cfg6 as above (clip_value
+ * 0 = the plain l2 value loss, which is what torchrl's class computes).  sums[0] = sum (-e^lw adv + beta kl_f), sums[2] = sums[8] = sum of the
+ * policy's entropy, sums[3..5] as grl_ppo_fwd_bwd, sums[11] = sum kl_f, columns 1, 6, 7, 9 and both maxes zero: every fold / report / record
+ * entry point serves it unchanged (the report's out14[5] is the mean KL, out14[12] the objective).  dmean / dsigma = gradient of
+ * (sums[0] - entropy_coef * sum entropy) / B_global, dvalue as grl_trpl_fwd_bwd. */
+int grl_klpen_fwd_bwd(const double* cfg6, const float* beta, int action_dim, const float* mean, const float* sigma, const float* action,
+                      const float* old_mean, const float* old_var, const float* old_logp, const float* advantage, const float* value,
+                      const float* old_value, const float* value_target, float* dmean, float* dsigma, float* dvalue, const double* adv_stats,
+                      double* sums, unsigned int* maxes, double* slots, int batch, hipStream_t stream);
+/* (ABI 212) the penalty weight's update, one single-thread launch: kl = out14[5] (the float32 mean KL of a 14-float report);
+ * kl > hi -> beta[0] *= increment; kl < lo -> beta[0] *= decrement; else unchanged (both comparisons strict).  hi / lo = dtarg * 1.5 and
+ * dtarg / 1.5, formed in double by the caller and rounded to float.  Capturable; nothing else is written. */
+int grl_klpen_adapt(const float* out14, float* beta, float hi, float lo, float increment, float decrement, hipStream_t stream);
 /* (ABI 210) grl_trpl_fwd_bwd with the projection layer's second half inside the launch: the scheduled ENTROPY projection
  * (base_projection_layer.py:14-68 entropy_inequality_projection / entropy_equality_projection, :232-273 their place around the trust-region
  * projection; utils/projection_utils.py:252-280 the schedule that yields the bound).  Notation of the kernel: x = the "std" diagonal the
