@@ -33,6 +33,7 @@ class AgentConfig:
     mean_bound: float = 0.05
     cov_bound: float = 0.0025
     proj_type: str = "kl"  # kl | frob | w2 | w2_non_com
+    scale_prec: bool = True   # False: the Euclidean forms of kl (unchanged) | frob | w2 (the reference CONSTRUCTOR's default; its configs say True)
     trust_region_coeff: float = 1.0
     entropy_coef: float = 0.005
     critic_coef: float = 0.5
@@ -120,7 +121,7 @@ def build_agent(spec: TaskSpec, cfg: AgentConfig, device="cuda", group=None):
                             in_features=a_in, critic_in_features=spec.in_features, group=group)
         return actor, critic, None, loss
     projection = KLProjectionLayer(proj_type=cfg.proj_type, mean_bound=cfg.mean_bound, cov_bound=cfg.cov_bound,
-                                   trust_region_coeff=cfg.trust_region_coeff, scale_prec=True, entropy_schedule=cfg.entropy_schedule or False,
+                                   trust_region_coeff=cfg.trust_region_coeff, scale_prec=cfg.scale_prec, entropy_schedule=cfg.entropy_schedule or False,
                                    action_dim=A, total_train_steps=cfg.total_train_steps, target_entropy=cfg.target_entropy,
                                    temperature=cfg.temperature, entropy_eq=cfg.entropy_eq, entropy_first=cfg.entropy_first)
     loss = TRPLLoss(actor, critic, projection=projection, entropy_coef=cfg.entropy_coef, critic_coef=cfg.critic_coef,

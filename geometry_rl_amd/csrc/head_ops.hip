@@ -224,6 +224,12 @@ struct TrplCfg {
 //       d kl_f / d mean_i = (mean_i - mo_i) / S_i,  d kl_f / d S_i = (1 / S_i - So_i / S_i^2 - (mean_i - mo_i)^2 / S_i^2) / 2.  beta is read
 //       from a DEVICE float (the loss module's beta buffer, rewritten behind every step's report by grl_klpen_adapt): value and gradient
 //       of a step use the beta in force when its launch runs.  Column 11 carries sum kl_f; the trust-region columns and the maxes stay zero.
+//       6, 7 = the Euclidean forms (scale_prec=False; projection_utils.py:9-31,70-149) of 1 and 2.  Both: mean part mp = sum (mu - mo)^2 (no
+//       division by So, no 1/2); projection and backward as before with d mp / d mu_j = 2 (mu_j - mo_j).  6 = Frobenius: covariance part,
+//       projection and regression loss are those of 1 (the layer's own loss uses maha(mu, pm, S) whatever the flag); only the reported
+//       mean constraint (column 6, its maximum) is sum (mu - pm)^2.  7 = commutative Wasserstein: cp = sum (So - Sx)^2 = tr(So^2 + Sx^2 -
+//       2 So Sx), pS = (Sx + eta So) / (1 + eta), d cp / d Sx_j = -2 (So_j - Sx_j); regression loss and columns 6, 7 on the detached
+//       projection: md = sum (mu - pm)^2, cd = sum (S - pS)^2, direct gradient 2 (mu - pm), 2 (S - pS).  KL and entropy columns unchanged.
 // Covariance projection (KL): eta >= 0 with KL_cov(eta) = cov_bound.  With rho_i = v_i/o_i = (eta+1)/(eta+c_i), c_i = o_i/t_i:
 //   KL = 1/2 sum(rho_i - 1 - log rho_i),  dKL/deta = -1/2 sum (1-c_i)^2 / ((eta+1)(eta+c_i)^2) < 0, KL convex in eta: Newton from eta = 0
 //   approaches the root monotonically from the left (never overshoots).  Phase 1 runs the iteration in fp32 (hardware log2 / reciprocal)
@@ -354,7 +360,9 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
   const double t = Sx * Sx, o = So * So;     // kl_projection_layer.py:60-63: covariance(std) = std**2
   // ---- mean projection (base_projection_layer.py:71-100)
   double mp = 0.0;
-  if (!NOPROJ) { const double d = (mu - mo) / So; mp = gsum<L>(M(d * d)); }
+  constexpr bool EUC = PROJ == 6 || PROJ == 7;   // the Euclidean (scale_prec=False) forms: mean part sum (mu - mo)^2
+  constexpr bool FROB = PROJ == 1 || PROJ == 6;
+  if (!NOPROJ) { const double d = EUC ? mu - mo : (mu - mo) / So; mp = gsum<L>(M(d * d)); }
   if (PROJ == 0) mp *= 0.5;
   const bool m_act = !NOPROJ && PROJ != 4 && mp > cfg.mean_bound;   // (4: one joint bound, below)
   double omega = 0.0, D = 1.0;
@@ -429,12 +437,12 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
     }
     v = pS * pS;
   } else {
-    const double d = PROJ == 1 ? o - t : 1.0 - Sx / So;
+    const double d = FROB ? o - t : PROJ == 7 ? So - Sx : 1.0 - Sx / So;
     const double part = gsum<L>(M(d * d));
     c_act = part > cfg.cov_bound;
     if (c_act) eta = fabs(sqrt(part / cfg.cov_bound) - 1.0);
     const double den = 1.0 + eta + 1e-16;
-    if (PROJ == 1) { v = c_act ? (t + eta * o) / den : t; pS = c_act ? sqrt(v) : Sx; }
+    if (FROB) { v = c_act ? (t + eta * o) / den : t; pS = c_act ? sqrt(v) : Sx; }
     else { pS = c_act ? (Sx + eta * So) / den : Sx; v = pS * pS; }
   }
   if (ext) {
@@ -494,12 +502,14 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
   const double dmk = (mu - pm) / pS, rr = S / pS;
   double mk = gsum<L>(M(dmk * dmk)), ck = gsum<L>(M(rr * rr));
   const double ldS = gsum<L>(M(log(S))), ldP = sl;
-  double cd = 0.0, mS = 0.0, sq = 0.0;
-  if (PROJ == 1) {
+  double cd = 0.0, mS = 0.0, sq = 0.0, me = 0.0;
+  if (FROB) {
     const double f = pS * pS - S * S, dm = (mu - pm) / S, ds = S - pS;
     cd = gsum<L>(M(f * f)); mS = gsum<L>(M(dm * dm)); sq = gsum<L>(M(ds * ds));
   }
   if (PROJ == 2 || PROJ == 4) cd = gsum<L>(M((1.0 - rr) * (1.0 - rr)));
+  if (EUC) me = gsum<L>(M((mu - pm) * (mu - pm)));
+  if (PROJ == 7) cd = gsum<L>(M((S - pS) * (S - pS)));
   const double md = mk;
   mk *= 0.5;
   ck = 0.5 * (ck - A + 2.0 * ldP - 2.0 * ldS);
@@ -507,6 +517,8 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
   if (PROJ == 0) { acc[1] = (mk + ck) * cfg.tr_coeff; acc[6] = mk; acc[7] = ck; }
   if (PROJ == 1) { acc[1] = (mS + sq) * cfg.tr_coeff; acc[6] = md; acc[7] = cd; }
   if (PROJ == 2 || PROJ == 4) { acc[1] = (md + cd) * cfg.tr_coeff; acc[6] = md; acc[7] = cd; }
+  if (PROJ == 6) { acc[1] = (mS + sq) * cfg.tr_coeff; acc[6] = me; acc[7] = cd; }
+  if (PROJ == 7) { acc[1] = (me + cd) * cfg.tr_coeff; acc[6] = me; acc[7] = cd; }
   const double c_ent = 0.5 * A * 2.8378770664093454836;
   acc[8] = c_ent + ldS;
   acc[9] = (c_ent + ldP) - (c_ent + ldS);
@@ -524,7 +536,7 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
   }
   const double ctr = cfg.tr_coeff * cfg.inv_batch;
   if (ext) { g_pm = 0.0; g_pS = 0.0; }
-  else if (PROJ == 1) {
+  else if (FROB) {
     g_pm -= ctr * 2.0 * (mu - pm) / (S * S);
     g_pS -= ctr * 2.0 * (S - pS);
   }
@@ -536,7 +548,7 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
   if (m_act && !ext) {
     const double dot = gsum<L>(M(g_pm * (mo - pm) / D));
     const double kk = dot / (2.0 * (omega + 1.0) * cfg.mean_bound) * (PROJ == 0 ? 1.0 : 2.0);
-    gmu = g_pm / D + kk * (mu - mo) / (So * So);
+    gmu = EUC ? g_pm / D + kk * (mu - mo) : g_pm / D + kk * (mu - mo) / (So * So);
   } else gmu = g_pm;
   if (ext) gS = 0.0;
   else if (PROJ == 0) {
@@ -569,8 +581,9 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
     }
   } else if (c_act) {
     const double den = 1.0 + eta + 1e-16, deta = 1.0 / (2.0 * (eta + 1.0) * cfg.cov_bound);
-    const double st_ = gsum<L>(M(PROJ == 1 ? g_pS / (2.0 * pS0) * (o - v) / den : g_pS * (So - pS0) / den));
-    if (PROJ == 1) gS = g_pS / (2.0 * pS0) * 2.0 * Sx / den + st_ * deta * (-4.0 * (o - t) * Sx);
+    const double st_ = gsum<L>(M(FROB ? g_pS / (2.0 * pS0) * (o - v) / den : g_pS * (So - pS0) / den));
+    if (FROB) gS = g_pS / (2.0 * pS0) * 2.0 * Sx / den + st_ * deta * (-4.0 * (o - t) * Sx);
+    else if (PROJ == 7) gS = g_pS / den + st_ * deta * (-2.0 * (So - Sx));
     else gS = g_pS / den + st_ * deta * (-2.0 * (1.0 - Sx / So) / So);
   } else gS = g_pS;
   if (ENT && e_first && e_act) {   // y = alpha(x) x, x = S: between the projection's backward and the regression term's direct gradient
@@ -580,13 +593,16 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
   if (PROJ == 0) {
     gmu += ctr * (mu - pm) / (pS * pS);
     gS += ctr * (S / (pS * pS) - 1.0 / S);
-  } else if (PROJ == 1) {
+  } else if (FROB) {
     const double dm = mu - pm;
     gmu += ctr * 2.0 * dm / (S * S);
     gS += ctr * (-2.0 * dm * dm / (S * S * S) + 2.0 * (S - pS));
   } else if (PROJ == 2 || PROJ == 4) {
     gmu += ctr * 2.0 * (mu - pm) / (pS * pS);
     gS += ctr * (-2.0 * (1.0 - S / pS) / pS);
+  } else if (PROJ == 7) {
+    gmu += ctr * 2.0 * (mu - pm);
+    gS += ctr * 2.0 * (S - pS);
   }
   if (act) {
     dmean[kms] = (float)gmu;
@@ -828,7 +844,8 @@ int grl_adv_stats(const float* advantage, double* stats, int batch, hipStream_t 
 }
 
 // cfg9 (HOST pointer): TEN doubles since ABI 203 {mean_bound, cov_bound, trust_region_coeff, entropy_coef, critic_coef, clip_value,
-// 1/B_global, B_global, projection type (0 KL, 1 Frobenius, 2 Wasserstein, 4 non-commuting Wasserstein), adv_local (1: the advantage statistics are summed inside the
+// 1/B_global, B_global, projection type (0 KL, 1 Frobenius, 2 Wasserstein, 4 non-commuting Wasserstein, 6 / 7 the Euclidean
+// forms of 1 / 2), adv_local (1: the advantage statistics are summed inside the
 // kernel from this launch's batch -- adv_stats is then ignored; 0: adv_stats as below)}.  adv_stats: device fp64[2] = (sum, sum of squares) of the GLOBAL batch's advantages (from
 // grl_adv_stats, all-reduced when data parallel) or NULL for no normalisation.  sums: fp64[12], maxes: u32[2], zeroed by the caller.  value/old_value/value_target/dvalue may be
 // NULL together (actor-only call); proj_mean/proj_var may be NULL.
@@ -855,7 +872,8 @@ static int trpl_launch(const double* cfg9, int action_dim, const float* mean, co
   if (ent_mode >= 0 && (ent_mode > 3 || !ent_beta || tgt_mean)) return -2;
   TrplCfg c{cfg9[0], cfg9[1], cfg9[2], cfg9[3], cfg9[4], cfg9[5], cfg9[6], cfg9[7], action_dim, (int)cfg9[9]};
   const int proj = (int)cfg9[8];
-  if (proj < 0 || proj > 4 || proj == 3) return -3;   // (3 and 5, the PPO modes, have their own entry points: grl_ppo_fwd_bwd, grl_klpen_fwd_bwd)
+  if (proj != 0 && proj != 1 && proj != 2 && proj != 4 && proj != 6 && proj != 7)
+    return -3;   // (3 and 5, the PPO modes, have their own entry points: grl_ppo_fwd_bwd, grl_klpen_fwd_bwd)
   const TrplPtrs tp{mean, sigma, action, old_mean, old_var, old_logp, advantage, value, old_value, value_target, dmean, dsigma, dvalue,
                     proj_mean, proj_var, adv_stats, slots, tgt_mean, tgt_S, 0, nullptr, ent_beta, ent_mode < 0 ? 0 : ent_mode};
 #define GRL_TRPL_LAUNCH(LL, PJ)                                                                                                           \
@@ -874,7 +892,9 @@ static int trpl_launch(const double* cfg9, int action_dim, const float* mean, co
   if (proj == 0) GRL_TRPL_WIDTH(0);
   else if (proj == 1) GRL_TRPL_WIDTH(1);
   else if (proj == 2) GRL_TRPL_WIDTH(2);
-  else GRL_TRPL_WIDTH(4);
+  else if (proj == 4) GRL_TRPL_WIDTH(4);
+  else if (proj == 6) GRL_TRPL_WIDTH(6);
+  else GRL_TRPL_WIDTH(7);
 #undef GRL_TRPL_WIDTH
 #undef GRL_TRPL_LAUNCH
   GRL_CHECK_LAUNCH();

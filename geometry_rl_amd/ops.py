@@ -943,7 +943,8 @@ def trpl_fwd_bwd(loc, sigma, batch, value, *, mean_bound, cov_bound, trust_regio
                  global_batch: int, adv_stats: Optional[torch.Tensor], want_projection: bool = False, sums=None, maxes=None,
                  proj_type: int = 0, defer_fold: bool = False, adv_local: bool = False, ent_mode: Optional[int] = None,
                  ent_beta: Optional[torch.Tensor] = None):
-    """Launches the fused TRPL kernel (proj_type 0 KL | 1 Frobenius | 2 Wasserstein | 4 non-commuting Wasserstein).  Returns (sums fp64[12], maxes u32[2], dloc,
+    """Launches the fused TRPL kernel (proj_type 0 KL | 1 Frobenius | 2 Wasserstein | 4 non-commuting Wasserstein | 6, 7 the Euclidean,
+    scale_prec=False, forms of 1 and 2).  Returns (sums fp64[12], maxes u32[2], dloc,
     dsigma, dvalue, proj_mean, proj_var).  ``defer_fold``: the per-workgroup slots are not folded into ``sums`` / ``maxes`` by this call;
     the returned ``sums`` is then a callable that does it (on whatever stream is current when it is called) and returns (sums, maxes).
     ``ent_mode`` (not None): the scheduled entropy projection runs inside the launch (grl_trpl_fwd_bwd_ent) -- bit 0 equality form, bit 1
@@ -1089,6 +1090,7 @@ def klpen_adapt(out14: torch.Tensor, beta: torch.Tensor, dtarg: float, increment
 def trpl_target_terms(loc, sigma, tgt_mean, tgt_S, *, mean_bound, cov_bound, trust_region_coeff, global_batch: int, proj_type: int = 0):
     """Trust-region measure of (p, detached target) with its gradient -- the fused kernel with the projection skipped
     (grl_trpl_target_terms).  ``sigma`` = sqrt of the policy's covariance diagonal, ``tgt_S`` = the target's covariance diagonal.
+    ``proj_type``: the codes of ``trpl_fwd_bwd`` (6, 7: the Euclidean measures).
     Returns (sums fp64[12], maxes u32[2], dloc, dsigma)."""
     import ctypes
     hip.check_f32(loc, sigma, tgt_mean, tgt_S)

@@ -124,11 +124,17 @@ class KLProjectionLayer:
         self.target_entropy, self.temperature = float(target_entropy), float(temperature)
         self.entropy_first, self.entropy_eq = bool(entropy_first), bool(entropy_eq)
         kinds = {"kl": 0, "frob": 1, "frobenius": 1, "w2": 2, "wasserstein": 2, "w2_non_com": 4}
-        if proj_type.lower() not in kinds or mean_eq or not scale_prec:
-            raise NotImplementedError("projections: kl | frob | w2 (commutative) | w2_non_com, each with the Mahalanobis (scale_prec) "
-                                      "mean bound")
+        # scale_prec=False (the Euclidean forms, projection_utils.py:9-31,70-149): kernel codes 6 (Frobenius) and 7 (commutative W2); the
+        # KL layer never reads the flag (kl_projection_layer.py; gaussian_kl takes none): code 0 either way.  NB the default here is True,
+        # what every reference config sets (configs/algorithm/projection/*.yaml); the reference CONSTRUCTOR defaults to False.
+        euclid = {0: 0, 1: 6, 2: 7}
+        code = kinds.get(proj_type.lower())
+        if code is None or mean_eq or (not scale_prec and code not in euclid):
+            raise NotImplementedError("projections: kl | frob | w2 (commutative), each with the Mahalanobis (scale_prec=True) or the "
+                                      "Euclidean (scale_prec=False) mean bound, | w2_non_com (scale_prec=True only); no mean_eq")
         self.proj_type, self.mean_bound, self.cov_bound = proj_type, float(mean_bound), float(cov_bound)
-        self.proj_code = kinds[proj_type.lower()]
+        self.scale_prec = bool(scale_prec)
+        self.proj_code = code if self.scale_prec else euclid[code]
         self.trust_region_coeff = float(trust_region_coeff)
         self.initial_entropy = None
 
@@ -230,17 +236,37 @@ class KLProjectionLayer:
 
 
 class FrobeniusProjectionLayer(KLProjectionLayer):
-    """frob_projection_layer.py:9-88 on the diagonal policy (closed form; its regression loss is NOT detached from the projection)."""
+    """frob_projection_layer.py:9-88 on the diagonal policy (closed form; its regression loss is NOT detached from the projection).
+    ``scale_prec=False``: the Euclidean mean part (kernel code 6); covariance part and regression loss do not read the flag."""
 
     def __init__(self, proj_type="frob", **kw):
         super().__init__(proj_type="frob", **kw)
 
+    def trust_region_value(self, policy, p, q):
+        """projection_utils.py gaussian_frobenius -> per-frame (mean part, |S_o^2 - S^2|_F^2); mean part: maha(mean, mean_o, S_o) with
+        ``scale_prec``, sum (mean - mean_o)^2 without.  On the tensors as given (matrices or diagonals), differentiable."""
+        (mean, S), (mean_o, S_o) = p, q
+        S, S_o = _diag(S), _diag(S_o)
+        d = (mean - mean_o) / S_o if self.scale_prec else mean - mean_o
+        return d.pow(2).sum(-1), (S_o.pow(2) - S.pow(2)).pow(2).sum(-1)
+
 
 class WassersteinProjectionLayer(KLProjectionLayer):
-    """w2_projection_layer.py:14-76 (commutative W2, precision-scaled) on the diagonal policy."""
+    """w2_projection_layer.py:14-76 (commutative W2) on the diagonal policy: precision-scaled (``scale_prec=True``, kernel code 2) or
+    Euclidean (``scale_prec=False``, code 7)."""
 
     def __init__(self, proj_type="w2", **kw):
         super().__init__(proj_type="w2", **kw)
+
+    def trust_region_value(self, policy, p, q):
+        """projection_utils.py gaussian_wasserstein_commutative -> per-frame (mean part, covariance part): (maha(mean, mean_o, S_o),
+        sum (1 - S / S_o)^2) with ``scale_prec``, (sum (mean - mean_o)^2, tr(S_o^2 + S^2 - 2 S_o S) = sum (S_o - S)^2) without.  On the
+        tensors as given (matrices or diagonals), differentiable."""
+        (mean, S), (mean_o, S_o) = p, q
+        S, S_o = _diag(S), _diag(S_o)
+        if self.scale_prec:
+            return ((mean - mean_o) / S_o).pow(2).sum(-1), (1.0 - S / S_o).pow(2).sum(-1)
+        return (mean - mean_o).pow(2).sum(-1), (S_o - S).pow(2).sum(-1)
 
 
 class WassersteinProjectionLayerNonCommuting(KLProjectionLayer):

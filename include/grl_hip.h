@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 /* ABI version (major*10000 + minor*100 + patch); grl_version() returns the value the library was built with. */
-#define GRL_HIP_VERSION 212   /* 212: grl_klpen_fwd_bwd (adaptive KL-penalty PPO objective on the fused loss kernel) and grl_klpen_adapt (its penalty weight's update) added, no existing signature changed; 211: csrc/stats_ops.hip added (grl_stats_accumulate, grl_explained_variance + its scratch query, grl_episode_scan), no existing signature changed; 210: grl_trpl_fwd_bwd_ent (scheduled entropy projection inside the fused TRPL launch) and grl_write_doubles added, no existing signature changed; 209: three exports removed (the device-cursor variant of grl_gather_rows_many, the hipStreamWaitValue32 capability query, the idle spin kernel of calib.hip); 208: cfg9[8] = 4 accepted (non-commuting Wasserstein projection), no signature change; 207: grl_ppo_fwd_bwd added (clipped PPO objective); 206: grl_build_features_noise, grl_step_head_noise[_bf16] added (training noise); 205 (round 6): grl_source_hash added; 204 (round 5): grl_head_fused / grl_head_fused_rows removed, grl_calib_mfma / grl_calib_copy added; the exports are exactly this header */
+#define GRL_HIP_VERSION 213   /* 213: cfg9[8] accepts 6 and 7, the Euclidean (scale_prec=False) forms of the Frobenius and commutative Wasserstein projections, no signature changed; 212: grl_klpen_fwd_bwd (adaptive KL-penalty PPO objective on the fused loss kernel) and grl_klpen_adapt (its penalty weight's update) added, no existing signature changed; 211: csrc/stats_ops.hip added (grl_stats_accumulate, grl_explained_variance + its scratch query, grl_episode_scan), no existing signature changed; 210: grl_trpl_fwd_bwd_ent (scheduled entropy projection inside the fused TRPL launch) and grl_write_doubles added, no existing signature changed; 209: three exports removed (the device-cursor variant of grl_gather_rows_many, the hipStreamWaitValue32 capability query, the idle spin kernel of calib.hip); 208: cfg9[8] = 4 accepted (non-commuting Wasserstein projection), no signature change; 207: grl_ppo_fwd_bwd added (clipped PPO objective); 206: grl_build_features_noise, grl_step_head_noise[_bf16] added (training noise); 205 (round 6): grl_source_hash added; 204 (round 5): grl_head_fused / grl_head_fused_rows removed, grl_calib_mfma / grl_calib_copy added; the exports are exactly this header */
 int grl_version(void);
 /* The hash of the sources this binary was built from (16 hex digits + NUL into buf; returns the length).  geometry_rl_amd/hip.py
    source_hash() recomputes it from csrc/, this header and the build's flag tables and refuses a library that disagrees. */
@@ -238,7 +238,10 @@ int grl_readout_bwd(const float* lat, const float* grid, const float* Wd, const 
  *      projections/frob_projection_layer.py:9-88, projections/w2_projection_layer.py:14-76 (diagonal policy, closed forms)
  * cfg9 (HOST, TEN doubles since ABI 203): {mean_bound, cov_bound, trust_region_coeff, entropy_coef, critic_coef, clip_value, 1/B_global, B_global,
  *               projection type: 0 KL | 1 Frobenius | 2 Wasserstein (commutative, precision-scaled) | 4 (ABI 208) Wasserstein,
- *               non-commuting (w2_projection_layer_non_com.py: one joint bound, ten Newton-Schulz steps; precision-scaled), 3 is refused,
+ *               non-commuting (w2_projection_layer_non_com.py: one joint bound, ten Newton-Schulz steps; precision-scaled) | 6, 7 (ABI 213) the
+ *               Euclidean forms (scale_prec=False, projection_utils.py:9-31,70-149) of 1 and 2: mean part sum (mu - mo)^2; 7: covariance
+ *               part sum (So - S)^2, regression loss and constraints sum (mu - pm)^2, sum (S - pS)^2; 6: covariance part and regression
+ *               loss of 1, reported mean constraint sum (mu - pm)^2.  3 and 5 (the PPO modes' own entry points) are refused,
  *               adv_local: 1 = the advantage statistics are summed inside the kernel from this launch's batch (one rank), 0 = adv_stats}
  * sums fp64[12]: loss_objective, loss_trust_region, entropy(dist), loss_critic, sum w, sum w^2, mean_constraint,
  *               cov_constraint, entropy(p), entropy_diff, count, kl  (per-frame sums; divide by count);  maxes u32[2] (float bits) */

@@ -1,0 +1,354 @@
+"""The Euclidean (``scale_prec=False``) Frobenius and commutative Wasserstein projections (kernel codes 6 and 7) on the GPU:
+  (a) the kernel against the reference layers' own numbers (tier2g fixtures): projection, trust-region loss and gradient, metrics,
+      trust_region_value;
+  (b) the whole fused loss (objective, entropy, trust region, critic) and its gradients against the float64 restatement
+      (tests/euclid_ref.py through the oracle's TRPL loss) on random batches at A = 3, 6, 12, 16 (lane widths 4, 8, 16, 16), B = 37;
+  (c) the scheduled entropy stage in front of and behind the new codes against tests/entropy_ref.py;
+  (d) three updates against the oracle with the restatements registered, rigid HEPi;
+  (e) recorded programs against the step-by-step loop (lanes, one stream, both forms of run_minibatches), bitwise;
+  (f) two data-parallel ranks against one rank (code 7); two runs bitwise identical."""
+import contextlib
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import entropy_cases as ec
+import entropy_ref
+import euclid_ref
+import test_gpu_trpl_kernel as tk
+import trpl_cases as tc
+from oracle import step as ost, trpl as otr
+from geometry_rl_amd import synthetic as syn
+from parity_util import adam_first_step_bound, grad_scales
+from updater_cases import DEV, assert_ranks_match, dp_ref, make_rollout, run_loop_and_launches, run_step_modes, run_two_ranks
+
+pytestmark = pytest.mark.gpu
+EPS, EPS_COV = 0.05, 0.0025
+NAMES = ("frob", "w2")
+CODE = euclid_ref.CODE
+
+
+@pytest.fixture
+def registered(monkeypatch):
+    """The oracle's "frob" / "w2" entries are the Euclidean restatements for the test's duration (the key "frob" keeps trpl_loss on the
+    Frobenius layer's own regression loss)."""
+    for name in NAMES:
+        monkeypatch.setitem(otr.PROJECTIONS, name, (euclid_ref.PROJECTION[name], euclid_ref.VALUE[name]))
+
+
+def _fixture(golden_dir, name, grp):
+    z = np.load(os.path.join(golden_dir, f"tier2g_projection_{name}_euclid.npz"))
+    out = {k[len(grp) + 1:]: torch.from_numpy(np.asarray(z[k])) for k in z.files if k.startswith(grp + ".")}
+    out.update({k: float(z[k]) for k in ("mean_bound", "cov_bound", "coeff")})
+    return out
+
+
+def _rel(name, got, want, tol, floor=1.0):
+    got, want = got.detach().cpu().double(), want.detach().double()
+    err = float((got - want).abs().max())
+    scale = max(floor, float(want.abs().max()))
+    print(f"{name}: max err {err:.3e} of scale {scale:.3e}")
+    assert np.isfinite(err) and err <= tol * scale, (name, err, tol * scale)
+
+
+def _states(mp, cp, eps=EPS, eps_cov=EPS_COV):
+    """All four activity states occur and no float64 part lies within a relative 1e-3 of its bound."""
+    states = {(bool(a), bool(b)) for a, b in zip(mp > eps, cp > eps_cov)}
+    assert states == {(False, False), (False, True), (True, False), (True, True)}, states
+    assert float((mp / eps - 1.0).abs().min()) > 1e-3 and float((cp / eps_cov - 1.0).abs().min()) > 1e-3
+
+
+# ------------------------------------------------------------------------------------------------------------- (a) fixture
+@pytest.mark.parametrize("grp", ["a6", "a3", "a12"])
+@pytest.mark.parametrize("name", NAMES)
+def test_kernel_matches_the_reference_fixture(golden_dir, name, grp):
+    from geometry_rl_amd import ops, trpl
+    z = _fixture(golden_dir, name, grp)
+    B, A = z["mean"].shape
+    cls = trpl.FrobeniusProjectionLayer if name == "frob" else trpl.WassersteinProjectionLayer
+    layer = cls(mean_bound=z["mean_bound"], cov_bound=z["cov_bound"], trust_region_coeff=z["coeff"], scale_prec=False)
+    assert layer.proj_code == CODE[name]
+    mean, S = z["mean"].float().to(DEV), z["S"].float().to(DEV)
+    q = (z["mean_o"].float().to(DEV), z["S_o"].float().to(DEV))
+    pm, pS = layer(None, (mean, S.diag_embed()), (q[0], q[1].diag_embed()))
+    assert pS.dim() == 3
+    _rel("proj_mean", pm, z["proj_mean"], 1e-5)
+    _rel("proj_S", pS.diagonal(dim1=-2, dim2=-1), z["proj_S"], 1e-5, floor=0.0)
+    # the same launch through ops directly (proj_type = 6 | 7, want_projection=True): proj_var is the projected "std" diagonal
+    batch = {"action": mean, "loc": q[0], "var": q[1], "sample_log_prob": torch.zeros(B, device=DEV), "advantage": torch.zeros(B, device=DEV)}
+    out = ops.trpl_fwd_bwd(mean, S.sqrt(), batch, None, mean_bound=z["mean_bound"], cov_bound=z["cov_bound"], trust_region_coeff=z["coeff"],
+                           entropy_coef=0.0, critic_coef=0.0, clip_value=0.0, global_batch=B, adv_stats=None, want_projection=True,
+                           proj_type=CODE[name])
+    assert torch.equal(out[5], pm) and torch.equal(out[6], pS.diagonal(dim1=-2, dim2=-1))
+    # that launch's gradient (advantage 0, no entropy bonus) is the regression loss's WHOLE gradient: for the Frobenius layer through the
+    # projection too (its loss is not detached), which is what the reference's backward recorded; for W2 the direct gradient alone
+    _rel("tr_loss (fused)", out[0][1] / out[0][10], z["tr_loss"], 1e-5)
+    _rel("tr_grad_mean (fused)", out[2], z["tr_grad_mean"], 2e-5, floor=0.0)
+    _rel("tr_grad_S (fused)", out[3] / (2.0 * S.sqrt()), z["tr_grad_S"], 2e-5, floor=0.0)
+    # boundary methods: trust-region loss (value and gradient w.r.t. mean and S) for the projection as a constant target
+    m_g = mean.clone().requires_grad_(True)
+    S_g = S.clone().requires_grad_(True)
+    tr = layer.get_trust_region_loss(None, (m_g, S_g.diag_embed()), (pm, pS))
+    tr.backward()
+    _rel("tr_loss", tr, z["tr_loss"], 1e-5)
+    if name == "w2":
+        want_m, want_S = z["tr_grad_mean"], z["tr_grad_S"]
+    else:   # the direct gradient of the Frobenius loss: the restatement on the fixture's own projection, held constant
+        m64, S64 = z["mean"].clone().requires_grad_(True), z["S"].clone().requires_grad_(True)
+        want_m, want_S = torch.autograd.grad(euclid_ref.TR_LOSS[name]((m64, S64), (z["proj_mean"], z["proj_S"]), z["coeff"]), [m64, S64])
+    _rel("tr_grad_mean", m_g.grad, want_m, 2e-5, floor=0.0)
+    _rel("tr_grad_S", S_g.grad, want_S, 2e-5, floor=0.0)
+    mt = layer.compute_metrics(None, (mean, S.diag_embed()), (pm, pS), step=0)
+    for k in ("kl", "constraint", "mean_constraint", "cov_constraint", "mean_constraint_max", "cov_constraint_max", "entropy", "entropy_diff"):
+        _rel("metric." + k, mt[k], z["metric." + k], 2e-5)
+    vm, vc = layer.trust_region_value(None, (mean, S.diag_embed()), (q[0], q[1].diag_embed()))
+    _rel("value_mean", vm, z["value_mean"], 1e-5)
+    _rel("value_cov", vc, z["value_cov"], 1e-5)
+
+
+# ------------------------------------------------------------------------------------------------------------- (b) vs restatement
+def _random_case(B, A, seed):
+    """Frame b is of kind b % 4: 0 both bounds active, 1 inside the mean bound only, 2 inside the covariance bound only, 3 inside both.
+    An active mean part is f eps with f in [2, 20]; an active covariance step |S_o - S|^2 = f eps_cov with f in [6, 30] (the W2 part
+    itself; the Frobenius part sum ((S_o + S)(S_o - S))^2 is then above 2 eps_cov with S >= 0.36).  Inside: the mean part at 0.4 eps,
+    |S_o - S| = 0.012 -- W2 part 0.06 eps_cov, Frobenius part at most 4 * 1.45^2 * 1.44e-4 = 0.5 eps_cov: no gradient is trivially small."""
+    g = torch.Generator().manual_seed(seed)
+    loc = torch.randn(B, A, generator=g, dtype=torch.float64)
+    sigma = torch.rand(B, A, generator=g, dtype=torch.float64) * 0.6 + 0.6
+    S = sigma ** 2
+    u = torch.randn(B, A, generator=g, dtype=torch.float64)
+    u = u / u.norm(dim=-1, keepdim=True)
+    w = torch.randn(B, A, generator=g, dtype=torch.float64)
+    w = w / w.norm(dim=-1, keepdim=True)
+    fm = 2.0 + 18.0 * torch.rand(B, generator=g, dtype=torch.float64)
+    fc = 6.0 + 24.0 * torch.rand(B, generator=g, dtype=torch.float64)
+    kind = torch.arange(B) % 4
+    m_in, c_in = (kind == 1) | (kind == 3), (kind == 2) | (kind == 3)
+    old = loc + u * torch.where(m_in, torch.full_like(fm, 0.4 * EPS), fm * EPS).sqrt()[:, None]
+    S_o = S + w * torch.where(c_in, torch.full_like(fc, 0.012 ** 2), fc * EPS_COV).sqrt()[:, None]
+    sigma, S_o, old, loc = sigma.float(), S_o.float(), old.float(), loc.float()
+    var_f = S_o.double()
+    action = (old.double() + var_f.sqrt() * torch.randn(B, A, generator=g, dtype=torch.float64)).float()
+    logp = otr.mvn_diag_log_prob(action.double(), old.double(), var_f).float() + 0.1 * torch.randn(B, generator=g).float()
+    batch = {"action": action, "loc": old, "var": S_o, "sample_log_prob": logp, "advantage": torch.randn(B, generator=g).float(),
+             "state_value": torch.randn(B, generator=g).float(), "value_target": torch.randn(B, generator=g).float()}
+    value = (batch["state_value"] + 0.3 * torch.randn(B, generator=g)).float()
+    return loc, sigma, value, batch, kind
+
+
+@pytest.mark.parametrize("A", [3, 6, 12, 16])
+@pytest.mark.parametrize("name", NAMES)
+def test_kernel_matches_the_restatement(registered, name, A):
+    from geometry_rl_amd import ops
+    B = 37   # three workgroups of 16 frames, the last one partial: its clamped padding frames are exercised
+    loc, sigma, value, batch, kind = _random_case(B, A, seed=200 + A)
+    kw = dict(mean_bound=EPS, cov_bound=EPS_COV, trust_region_coeff=1.7, entropy_coef=0.01, critic_coef=0.5, clip_value=0.2)
+    loc_r = loc.double().requires_grad_(True)
+    sig_r = sigma.double().requires_grad_(True)
+    val_r = value.double().requires_grad_(True)
+    bd = {k: v.double() for k, v in batch.items()}
+    ref = otr.trpl_loss(loc_r, sig_r ** 2, bd, val_r, proj_type=name, **kw)
+    d_loc, d_sig = torch.autograd.grad(ref["loss_objective"] + ref["loss_entropy"] + ref["loss_trust_region"], [loc_r, sig_r])
+    (d_val,) = torch.autograd.grad(ref["loss_critic"], [val_r])
+    # the cases are where they are meant to be (float64 parts of the fp32 inputs)
+    mp, cp = euclid_ref.VALUE[name]((loc.double(), sigma.double() ** 2), (bd["loc"], bd["var"]))
+    _states(mp, cp)
+    for k, (m_act, c_act) in enumerate(((True, True), (False, True), (True, False), (False, False))):
+        assert bool(((mp > EPS) == m_act)[kind == k].all()) and bool(((cp > EPS_COV) == c_act)[kind == k].all()), k
+    db = {k: v.to(DEV) for k, v in batch.items()}
+    sums, maxes, dloc, dsigma, dvalue, pm, pv = ops.trpl_fwd_bwd(loc.to(DEV), sigma.to(DEV), db, value.to(DEV), global_batch=B, adv_stats=None,
+                                                                 want_projection=True, proj_type=CODE[name], adv_local=True, **kw)
+    _rel("proj_mean", pm, ref["proj_mean"], 1e-5)
+    _rel("proj_S", pv, ref["proj_S"], 1e-5, floor=0.0)
+    s = sums.cpu()
+    n = float(s[10])
+    assert n == B
+    mx = maxes.cpu().view(torch.float32)
+    got = {"loss_objective": s[0] / n, "loss_trust_region": s[1] / n, "entropy_dist": s[2] / n, "loss_entropy": -kw["entropy_coef"] * s[2] / n,
+           "loss_critic": s[3] / n, "ESS": s[4] ** 2 / s[5] / n, "kl": s[11] / n, "constraint": (s[6] + s[7]) / n, "mean_constraint": s[6] / n,
+           "cov_constraint": s[7] / n, "entropy": s[8] / n, "entropy_diff": s[9] / n, "mean_constraint_max": mx[0],
+           "cov_constraint_max": mx[1]}
+    assert set(got) == set(ref) - {"proj_mean", "proj_S"}
+    for k, v in got.items():
+        want = float(ref[k])
+        print(f"{k}: {float(v):.9g} want {want:.9g}")
+        assert abs(float(v) - want) <= 1e-5 * max(1.0, abs(want)), (k, float(v), want)
+    _rel("dloc", dloc, d_loc, 1e-5, floor=0.0)
+    _rel("dsigma", dsigma, d_sig, 1e-5, floor=0.0)
+    _rel("dvalue", dvalue, d_val, 1e-5, floor=0.0)
+    # per kind of frame, so that one kind cannot hide behind the largest gradient of another
+    for k in range(4):
+        sel = kind == k
+        _rel(f"dsigma[kind {k}]", dsigma.cpu()[sel], d_sig[sel], 2e-5, floor=0.0)
+        _rel(f"dloc[kind {k}]", dloc.cpu()[sel], d_loc[sel], 2e-5, floor=0.0)
+
+
+# ------------------------------------------------------------------------------------------------------------- (c) entropy control
+@pytest.mark.parametrize("first", (True, False), ids=("first", "last"))
+@pytest.mark.parametrize("name", NAMES)
+def test_entropy_stage_around_the_new_codes(registered, name, first):
+    """Inequality form at A = 6 on the entropy cases of the precision-scaled sibling code (tests/entropy_cases.py): the same checks and
+    allowances as tests/test_gpu_entropy_control.py, the reference being entropy_ref's composition around the registered restatement."""
+    from geometry_rl_amd import ops
+    e = ec.ECase(tc.Case(B=37, A=6, proj={"frob": 1, "w2": 2}[name]), False, first)
+    d = ec.make_case(e)
+    ref = ec.reference(e, d)
+    c = e.base
+    p = (d["loc"].double(), d["sigma"].double() ** 2)
+    qd = (d["batch"]["loc"].double(), d["batch"]["var"].double())
+    # activity of the three stages, from float64 values: both entropy states and both states of either bound occur, nothing sits on a bound
+    S_in = entropy_ref.entropy_stage(p[1], d["beta"], False)[0] if first else p[1]
+    mp, cp = euclid_ref.VALUE[name]((p[0], S_in), qd)
+    assert float((mp / EPS - 1.0).abs().min()) > 1e-3 and float((cp / EPS_COV - 1.0).abs().min()) > 1e-3
+    assert len({bool(x) for x in mp > EPS}) == 2 and len({bool(x) for x in cp > EPS_COV}) == 2
+    with torch.no_grad():   # the entropy stage's input: S itself (first) or the trust-region projection's output (last)
+        ent_in = otr.entropy_std(p[1] if first else euclid_ref.PROJECTION[name](p, qd, EPS, EPS_COV)[1])
+    e_act = ent_in < d["beta"]
+    assert torch.equal(e_act, ec.activity(e, d)[0]) and bool(e_act.any()) and not bool(e_act.all())
+    assert float((ent_in - d["beta"]).abs().min()) > 1e-3
+    kap = tc.adv_error_bound(c, d)
+    db = {k: v.to(DEV) for k, v in d["batch"].items()}
+    sums, maxes, dloc, dsigma, dvalue, pm, pv = ops.trpl_fwd_bwd(
+        d["loc"].to(DEV), d["sigma"].to(DEV), db, d["value"].to(DEV), mean_bound=tc.EPS, cov_bound=tc.EPS_COV, trust_region_coeff=c.tr_coeff,
+        entropy_coef=c.ent_coef, critic_coef=c.critic_coef, clip_value=c.clip_value, global_batch=c.global_batch, adv_stats=None,
+        want_projection=True, proj_type=CODE[name], adv_local=True, ent_mode=e.mode,
+        ent_beta=torch.tensor([d["beta"]], dtype=torch.float64, device=DEV))
+    tk._sums_close("sums", sums, ref["sums"], c.B, kap * ref["sens_sums"])
+    tk._maxes_close("maxes", maxes, ref["maxes"])
+    tk._close("proj_mean", pm, ref["proj_mean"])
+    tk._close("proj_S", pv, ref["proj_S"])
+    tk._close("dloc", dloc, ref["dloc"], kap * ref["sens_dloc"])
+    tk._close("dsigma", dsigma, ref["dsigma"], kap * ref["sens_dsigma"])
+    tk._close("dvalue", dvalue, ref["dvalue"])
+
+
+# ------------------------------------------------------------------------------------------------------------- (d) vs oracle
+@pytest.mark.parametrize("name", NAMES)
+def test_three_updates_match_the_oracle(registered, name):
+    from geometry_rl_amd import agent
+    from test_gpu_step import load_params, make_case
+    torch.set_num_threads(min(16, os.cpu_count() or 1))
+    B, K = 32, 3
+    o_spec, spec, kw, _ = make_case("rigid_g1", B)
+    kw = dict(kw, proj_type=name, trust_region_coeff=2.0)
+    o_cfg, cfg = ost.AgentConfig(**kw), agent.AgentConfig(scale_prec=False, **kw)
+    a_par, c_par = ost.init_agent_params(o_spec, o_cfg, seed=21)
+    oracle = ost.OracleAgent(o_spec, o_cfg, a_par, c_par)
+    actor, critic, proj, loss = agent.build_agent(spec, cfg, device=DEV)
+    assert proj.proj_code == CODE[name]
+    load_params(actor, a_par, DEV)
+    load_params(critic, {"_network1." + k: v for k, v in c_par.items()}, DEV)
+    A = spec.num_actuators * cfg.output_dim_vec * 3
+    batches = []
+    for i in range(K):
+        b = dict(syn.make_rigid_obs(B, seed=30 + i))
+        b.update(syn.make_ppo_fields(B, A, seed=40 + i))
+        batches.append(b)
+    with torch.no_grad():
+        oracle.actor_forward({k: batches[0][k] for k in o_spec.in_features}, calibrate=True)
+    actor.load_state_dict({k: v.detach().to(DEV) for k, v in oracle.actor.items()}, strict=False)
+    for mod in actor.modules():
+        if hasattr(mod, "callibrated"):
+            mod.callibrated.fill_(True)
+    actor._calib_checked = True
+    upd = agent.PolicyUpdater(loss, lr=cfg.lr, clip_grad_norm=cfg.clip_grad_norm, max_grad_norm=cfg.max_grad_norm, use_graph=True)
+    g_scale = None
+    for i, b in enumerate(batches):
+        ref, ref_grads = oracle.update(b)
+        out = upd.step({k: v.to(DEV) for k, v in b.items()})
+        sc = {net: grad_scales(ref_grads[net]) for net in ("actor", "critic")}
+        g_scale = sc if g_scale is None else {net: {k: max(v, g_scale[net].get(k, 0.0)) for k, v in sc[net].items()} for net in sc}
+        assert float(ref["kl"]) > 0.0   # frames were projected
+        for k in ("loss_objective", "loss_trust_region", "loss_critic", "kl", "constraint", "mean_constraint", "cov_constraint", "entropy"):
+            e = abs(float(out[k]) - float(ref[k]))
+            print(i, k, float(out[k]), float(ref[k]))
+            assert e <= 1e-4 * max(1.0, abs(float(ref[k]))), (i, k, e)
+    assert upd.mode.startswith("graph") and upd._program is not None
+    torch.cuda.synchronize()
+    off = lambda p: (p.data_ptr() - upd.flat.data_ptr()) // 4
+    bad = []
+    for net, mod, ref_p, optim, strip in (("actor", actor, oracle.actor, oracle.actor_optim, 0),
+                                          ("critic", critic, oracle.critic, oracle.critic_optim, len("_network1."))):
+        states = {kk: optim.state.get(ref_p[kk], {}) for kk in ref_p}
+        m_ref = {kk: s_["exp_avg"] for kk, s_ in states.items() if "exp_avg" in s_}
+        v_ref = {kk: s_["exp_avg_sq"] for kk, s_ in states.items() if "exp_avg_sq" in s_}
+        m_sc, v_sc = grad_scales(m_ref), grad_scales(v_ref)
+        for k, p in mod.named_parameters():
+            kk = k[strip:]
+            if kk not in m_ref:
+                continue
+            o, n = off(p), p.numel()
+            em = float((upd.exp_avg[o:o + n].view_as(p).cpu().double() - m_ref[kk].double()).abs().max())
+            ev = float((upd.exp_avg_sq[o:o + n].view_as(p).cpu().double() - v_ref[kk].double()).abs().max())
+            ep = float((p.detach().cpu().double() - ref_p[kk].detach().double()).abs().max())
+            allowed_p = K * adam_first_step_bound(cfg.lr, 1e-5, g_scale[net].get(kk, 0.0), cfg.clip_grad_norm, p_ref=ref_p[kk])
+            if not (em <= 5e-4 * m_sc[kk] and ev <= 1e-3 * v_sc[kk] and ep <= allowed_p and np.isfinite(em + ev + ep)):
+                bad.append((net, kk, em / m_sc[kk], ev / v_sc[kk], ep, allowed_p))
+    assert not bad, bad
+
+
+# ------------------------------------------------------------------------------------------------------------- (e) programs
+KEYS = ("loss_objective", "loss_trust_region", "loss_critic", "kl", "constraint", "entropy", "ESS")
+
+
+@pytest.mark.parametrize("form", ["unrolled", "per_step"])
+@pytest.mark.parametrize("name", NAMES)
+def test_run_minibatches_equals_the_step_loop(name, form):
+    N, T = 8, 10
+    res = run_loop_and_launches(lambda: make_rollout(N, T, seed=33, proj_type=name, scale_prec=False), form, N=N, T=T, ppo_epochs=2,
+                                driver_seed=9, unroll=4, keys=KEYS)
+    for a, b in zip(res["loop"][:3], res["launches"][:3]):
+        assert torch.equal(a, b), (a - b).abs().max().item()
+    for k in KEYS:
+        assert torch.equal(res["loop"][3][-1][k], res["launches"][3][-1][k]), k
+
+
+@contextlib.contextmanager
+def _graph_modes_are_recorded(mode, r, upd):
+    assert r.proj.proj_code in (6, 7)
+    yield
+    if mode in ("graph", "one_stream"):
+        assert upd.mode.startswith("graph") and upd._program is not None
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_recorded_programs_equal_the_eager_loop(name):
+    res = run_step_modes(lambda: make_rollout(8, 2, seed=41, proj_type=name, scale_prec=False),
+                         ("eager", "graph", "one_stream", "one_stream_eager"), 4, KEYS,
+                         lambda mode: dict(use_graph=mode in ("graph", "one_stream"), overlap_critic=not mode.startswith("one_stream")),
+                         per_mode=_graph_modes_are_recorded)
+    for a, b in (("eager", "graph"), ("one_stream_eager", "one_stream")):
+        for x, y in zip(res[a][:3], res[b][:3]):
+            assert torch.equal(x, y), (a, b, (x - y).abs().max().item())
+        for oa, ob in zip(res[a][3], res[b][3]):
+            for kk in KEYS:
+                assert torch.equal(oa[kk], ob[kk]), (a, b, kk)
+    assert (res["graph"][0] - res["one_stream"][0]).abs().max().item() <= 1e-6
+    # the Euclidean form is not the precision-scaled one: the constraint it reports differs from the first update on
+    assert float(res["graph"][3][0]["constraint"]) > 0.0
+
+
+def test_two_runs_are_bitwise_identical():
+    from geometry_rl_amd import agent
+    res = []
+    for _ in range(2):
+        r = make_rollout(16, 3, seed=45, proj_type="w2", scale_prec=False)
+        upd = agent.PolicyUpdater(r.loss, lr=r.cfg.lr, use_graph=True)
+        outs = [{kk: v.clone() for kk, v in upd.step({k: v[:, t].contiguous() for k, v in r.data.items()}).items() if kk in KEYS}
+                for t in range(3)]
+        torch.cuda.synchronize()
+        res.append((upd.flat.detach().clone(), outs))
+    assert torch.equal(res[0][0], res[1][0])
+    for oa, ob in zip(res[0][1], res[1][1]):
+        for kk in KEYS:
+            assert torch.equal(oa[kk], ob[kk]), kk
+
+
+# ------------------------------------------------------------------------------------------------------------- (f) data parallel
+def test_two_ranks_match_single_rank():
+    world = 2
+    ref_losses, ref_flat, ret = run_two_ranks(dp_ref(16, cfg_kw=dict(proj_type="w2", scale_prec=False)), world, use_graph=True,
+                                              dp_use_graph=True, n_steps=3, keys=KEYS, updater_kw=dict(clip_grad_norm=False))
+    assert_ranks_match(ref_losses, ref_flat, ret, world, 1e-5, 2e-6)

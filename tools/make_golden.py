@@ -625,6 +625,79 @@ def tier2f():
     print("tier2f:", len(rec), "arrays,", os.path.getsize(os.path.join(OUT, "tier2f_projection_w2_non_com.npz")), "bytes")
 
 
+# ----------------------------------------------------------------------------------------------- tier 2g
+def tier2g():
+    """The Euclidean forms (``scale_prec=False``, the reference constructor's default) of the Frobenius and the commutative Wasserstein
+    projection layer (frob_projection_layer.py:9-88, w2_projection_layer.py:14-76, projection_utils.py:9-31,70-149) on the diagonal
+    policy.  Records what tier2c records -- inputs, projection outputs, gradients through the projection under two random cotangents,
+    trust-region loss + gradients, compute_metrics(p, proj_p), trust_region_value(p, q), the bounds -- in the groups of tier2f (A = 3, 6,
+    12: every lane width of the kernel; B = 11 each) and, like tier2f, in float64 on float32-representable inputs, so that the float64
+    restatement (tests/euclid_ref.py) is pinned at rounding level and the kernel at its own float32 outputs' resolution.
+
+    Inputs as tier2c (S, S_o in [0.5, 1.5], mean_o = mean + 0.3 N(0, 1): both bounds active) plus hand-placed rows inside the mean bound
+    only (0), inside the covariance bound only (1) and inside both (2).  Asserted here and by tests/test_euclid_proj_cpu.py: every group
+    holds all four activity states and no part lies within a relative 1e-3 of its bound."""
+    from geometry_rl.algorithms.trust_region_projections.projections.frob_projection_layer import FrobeniusProjectionLayer
+    from geometry_rl.algorithms.trust_region_projections.projections.w2_projection_layer import WassersteinProjectionLayer
+    from geometry_rl.algorithms.trust_region_projections.models.policy.gnn_gaussian_policy_diag import GNNGaussianPolicyDiag
+
+    class FakeGNN(nn.Module):
+        device = "cpu"
+
+    class FakeData:
+        pass
+
+    eps, eps_cov, coeff = 0.05, 0.0025, 4.0
+    torch.manual_seed(3)
+    for name, cls in (("frob", FrobeniusProjectionLayer), ("w2", WassersteinProjectionLayer)):
+        rec = {"mean_bound": torch.tensor(eps, dtype=torch.float64), "cov_bound": torch.tensor(eps_cov, dtype=torch.float64),
+               "coeff": torch.tensor(coeff, dtype=torch.float64)}
+        for A, B, seed in ((6, 11, 41), (3, 11, 44), (12, 11, 47)):   # seeds: the asserts below hold (3: not with 43)
+            policy = GNNGaussianPolicyDiag(gnn=FakeGNN(), hyper_data=FakeData(), action_dim=A, num_actuators=1, init="orthogonal",
+                                           hidden_sizes=(64, 64), contextual_std=True, init_std=1.0, minimal_std=1e-5,
+                                           share_action_dim=True, post_fc=False)
+            g = torch.Generator().manual_seed(seed)
+            f32 = lambda t: t.float().double()
+            mean = f32(torch.randn(B, A, generator=g, dtype=torch.float64))
+            S = f32(torch.rand(B, A, generator=g, dtype=torch.float64) + 0.5)
+            mean_o = f32(mean + 0.3 * torch.randn(B, A, generator=g, dtype=torch.float64))
+            S_o = f32(torch.rand(B, A, generator=g, dtype=torch.float64) + 0.5)
+            lin = torch.linspace(-1, 1, A, dtype=torch.float64)
+            mean_o[0] = f32(mean[0] + 1e-3 * (1 + 0.5 * lin))          # inside the mean bound only
+            S_o[1] = f32(S[1] * (1 + 1e-3 * (1 + 0.5 * lin)))          # inside the covariance bound only
+            mean_o[2] = f32(mean[2] - 1e-3 * (1 + 0.5 * lin))          # inside both
+            S_o[2] = f32(S[2] * (1 - 1e-3 * (1 + 0.5 * lin)))
+            R1, R2 = torch.randn(B, A, generator=g, dtype=torch.float64), torch.randn(B, A, generator=g, dtype=torch.float64)
+            layer = cls(proj_type=name, mean_bound=eps, cov_bound=eps_cov, trust_region_coeff=coeff, scale_prec=False,
+                        entropy_schedule=False, action_dim=A, total_train_steps=100, cpu=True, dtype=torch.float64)
+            mean_g = mean.clone().requires_grad_(True)
+            S_g = S.clone().requires_grad_(True)
+            p = (mean_g, S_g.diag_embed())
+            q = (mean_o, S_o.diag_embed())
+            pm, pS = layer(policy, p, q, 0)
+            r = {"mean": mean, "S": S, "mean_o": mean_o, "S_o": S_o, "R1": R1, "R2": R2, "proj_mean": pm,
+                 "proj_S": pS.diagonal(dim1=-2, dim2=-1)}
+            ((pm * R1).sum() + (pS.diagonal(dim1=-2, dim2=-1) * R2).sum()).backward(retain_graph=True)
+            r["grad_mean"], r["grad_S"] = mean_g.grad.clone(), S_g.grad.clone()
+            mean_g.grad = None
+            S_g.grad = None
+            trl = layer.get_trust_region_loss(policy, p, (pm, pS))
+            trl.backward()
+            r["tr_loss"], r["tr_grad_mean"], r["tr_grad_S"] = trl, mean_g.grad.clone(), S_g.grad.clone()
+            m = layer.compute_metrics(policy, (mean, S.diag_embed()), (pm.detach(), pS.detach()), step=0)
+            for k, v in m.items():
+                r["metric." + k] = v
+            mp, cp = layer.trust_region_value(policy, (mean, S.diag_embed()), q)
+            r["value_mean"], r["value_cov"] = mp, cp
+            states = {(bool(a), bool(b)) for a, b in zip(mp > eps, cp > eps_cov)}
+            assert len(states) == 4, (name, A, states)
+            assert float((mp / eps - 1).abs().min()) > 1e-3 and float((cp / eps_cov - 1).abs().min()) > 1e-3, (name, A)
+            rec.update({f"a{A}.{k}": v for k, v in r.items()})
+        path = os.path.join(OUT, f"tier2g_projection_{name}_euclid.npz")
+        np.savez(path, **npd(rec))
+        print("tier2g:", name, len(rec), "arrays,", os.path.getsize(path), "bytes")
+
+
 # ----------------------------------------------------------------------------------------------- tier 3: data classes + critic wrapper
 def _plain(key):
     """A str / tuple-of-str key from the reference's str- and tuple-valued enum members."""
@@ -1049,6 +1122,10 @@ if __name__ == "__main__":
         install_stubs()
         tier2f()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "tier2g":
+        install_stubs()
+        tier2g()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "tier2e":
         install_stubs()
         tier2e()
@@ -1070,6 +1147,7 @@ if __name__ == "__main__":
     tier2b(attention=True)
     tier2e()
     tier2f()
+    tier2g()
     tier3()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
