@@ -79,6 +79,13 @@ def lift_case(n, grid_kind, S=3, V=4, tag=0):
     return Case(f"lift n={n} {grid_kind} S{S} V{V}", inputs, ["w"], ref, {"x": torch.randn(n, 16, 64, generator=g)})
 
 
+# LiftEncodeMulti: (node counts per type, index of a type whose output is left out of the loss or None, S, V, grid)
+LIFT_MULTI = [([77], None, 3, 4, "3d"), ([5, 130], None, 3, 4, "3d"), ([9001, 3, 77], None, 3, 4, "3d"), ([4, 301, 1, 77], None, 3, 4, "3d"),
+              ([0, 77, 5], None, 3, 4, "3d"), ([77, 0, 5], None, 3, 4, "2d"), ([77, 5, 0], None, 3, 4, "3d"), ([130, 77, 301], 0, 3, 4, "3d"),
+              ([130, 77, 301], 1, 3, 4, "2d"), ([130, 0, 301, 4], 3, 3, 4, "3d"), ([70001, 77], None, 3, 4, "2d")]
+LIFT_MULTI += [([301, 5, 77], None, S, V, k) for S, V in LIFT_SPLITS for k in ("3d", "2d")]
+
+
 # ------------------------------------------------------------------------------------------------ fiber basis + fiber kernels
 def fiber_basis_case(grid_kind, n_conv, unused=None):
     """``unused``: index of a convolution whose fk gets no gradient (the NULL dfk pointer of the backward)."""
@@ -143,6 +150,11 @@ FMA_FAMILIES = {
 # ------------------------------------------------------------------------------------------------ node block inputs
 LN_MEAN_OVER_SPREAD = 256.0   # rows m + s randn: the largest power of two m / s torch's own fp32 layer_norm handles (test_ops_ref_cpu.py)
 NODE_MLP_FAMILIES = ["randn", "constant_rows", "offset_rows", "times_1e3", "times_1e-3"]
+
+
+# 700 / 1601 nodes: several chunks per workgroup of the backward; 4112 = 257 x 16 and 4101: above the forward's 256 workgroups x 256 rows.
+# The other input families at three sizes: below one chunk, several chunks, the grid-stride loop with a partial block.
+NODE_MLP_CASES = [("randn", n) for n in (1, 7, 130, 700, 1601, 4112, 4101)] + [(f, n) for f in NODE_MLP_FAMILIES[1:] for n in (7, 700, 4101)]
 
 
 def node_mlp_rows(family, n, g):

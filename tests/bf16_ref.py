@@ -9,7 +9,10 @@ Rounding points, as the GRL_PREC branches of csrc/edge_conv16.hip, csrc/node_mlp
   here in float64 -- and adds the fp32 bias in the accumulator (``mm``, forward and backward: the backward rounds the incoming gradient
   and reuses the rounded forward operands; the first basis layer's bias gradient is an MFMA column of that rounded gradient too);
 * GELU is the build's logistic approximant x sigma(1.5976 x + 0.07056 x^3) with its exact derivative (the GRL_PREC branches of csrc/grl_common.h);
-* polynomial features, LayerNorm, the per-edge product K_e * x_src and the softmax stay in fp32 arithmetic (float64 here).
+* polynomial features, LayerNorm, the per-edge product K_e * x_src and the softmax stay in fp32 arithmetic (float64 here);
+* the fiber convolution and the lift (csrc/node_ops.hip) have no MFMA: fp32 multiply-adds on the values as loaded (bf16 latents widened
+  exactly; fk, bias, the node features and the encoder stay fp32), so ``fiber_conv`` / ``lift_encode`` round nothing but their one store;
+  their weight gradients are fp32 partial sums of products of bf16-exact gradients (autograd's, in float64 here).
 
 ``rounding=False, logistic=False`` turns every rounding off and restores the erf GELU: the functions then reproduce the oracle
 (tests/test_bf16_ref_cpu.py pins that to 1e-12)."""
@@ -129,6 +132,19 @@ def node_mlp(x2, x_dst, gamma, beta, w3, b3, w4, b4, prev=None, rounding=True, l
     return store(out, rounding and stored)
 
 
+def fiber_conv(x1, fk, bias, rounding=True, stored=True):
+    """x2[n,p,c] = 1/16 sum_o x1[n,o,c] fk[o,p,c] + bias[c] (FiberConv): fp32 arithmetic on the loaded values, stored once."""
+    return store(torch.einsum("boc,opc->bpc", x1, fk) / fk.shape[-2] + bias, rounding and stored)
+
+
+def lift_encode(scal, vec, grid, w_enc, rounding=True, stored=True):
+    """x[n,o,:] = [scal[n,:] | vec[n,v,:] . grid[o,:]] W_enc^T (LiftEncode; scal [N,S], vec [N,V,3], grid [16,dim], dim 2: the z parts are
+    unused): fp32 arithmetic on fp32 inputs, stored once."""
+    n, dim = scal.shape[0], grid.shape[1]
+    feat = torch.cat([scal[:, None, :].expand(n, grid.shape[0], scal.shape[1]), torch.einsum("nvd,od->nov", vec[..., :dim], grid)], -1)
+    return store(F.linear(feat, w_enc), rounding and stored)
+
+
 def softmax_aggregate(gate, msg, dst, n_dst):
     """PyG softmax (gate given directly) and the weighted sum: exp(g - max) / (sum + 1e-16), max detached -> x1 [n_dst,...]."""
     idx = dst.reshape(-1, *([1] * (gate.dim() - 1))).expand_as(gate)
@@ -149,3 +165,86 @@ def softmax_aggregate_bwd(alpha, msg, x1, dx1, dst):
     dgate = alpha * g * (msg - x1[dst])
     mag = alpha * g.abs() * (msg.abs() + x1[dst].abs())
     return dmsg, dgate, mag
+
+
+# ------------------------------------------------------------------------------------------------ cases of the per-op tests
+# The fp32 suite's inputs (tests/actor_cases.py) as the bf16 build sees them: every latent-typed input and every upstream gradient rounded
+# to bf16 first, the emulation above in place of the oracle's maths, the output BEFORE its store rounding (the tests allow the store's half
+# ulp on top of the bar: margin16).  tests/test_gpu_bf16_ops.py feeds them to the kernels; tests/test_bf16_ref_cpu.py evaluates them in
+# fp32 and in float64 to measure how far last-bit differences alone move the emulation.
+LATENTS = ("x1", "x2", "x_dst", "prev", "x_src", "dres", "x")
+
+
+def as_bf16_case(case, ref):
+    import actor_cases as ac
+    inputs = {k: (bf16(v) if k in LATENTS else v) for k, v in case.inputs.items()}
+    ups = {k: (bf16(u) if u is not None else None) for k, u in case.ups.items()}
+    c = ac.Case(case.name + " (bf16 build)", inputs, case.diff, ref, ups)
+    c.meta = getattr(case, "meta", None)
+    return c
+
+
+def fiber_conv_case(n):
+    import actor_cases as ac
+    return as_bf16_case(ac.fiber_conv_case(n), lambda t: {"x2": fiber_conv(t["x1"], t["fk"], t["bias"], stored=False)})
+
+
+def lift_case(n, grid_kind, S=3, V=4, tag=0):
+    import actor_cases as ac
+    return as_bf16_case(ac.lift_case(n, grid_kind, S, V, tag), lambda t: {"x": lift_encode(t["scal"], t["vec"], t["grid"], t["w"], stored=False)})
+
+
+def lift_multi_case(ns, left_out, S, V, grid_kind):
+    """Several node types behind one encoder (LiftEncodeMulti): type i is lift_case(ns[i], ..., tag=i); the first type's encoder is
+    everybody's; ``left_out``: index of a type whose output gets no gradient."""
+    import actor_cases as ac
+    cases = [lift_case(n, grid_kind, S, V, tag=i) for i, n in enumerate(ns)]
+    inputs = {"w": cases[0].inputs["w"], "grid": ac.grid_of(grid_kind)}
+    for i, c in enumerate(cases):
+        inputs[f"scal{i}"], inputs[f"vec{i}"] = c.inputs["scal"], c.inputs["vec"]
+    ref = lambda t: {f"x{i}": lift_encode(t[f"scal{i}"], t[f"vec{i}"], t["grid"], t["w"], stored=False) for i in range(len(ns))}
+    ups = {f"x{i}": (None if i == left_out else c.ups["x"]) for i, c in enumerate(cases)}
+    return ac.Case(f"lift multi {ns} left out {left_out} S{S} V{V} {grid_kind} (bf16 build)", inputs, ["w"], ref, ups)
+
+
+def node_mlp_case(family, n, use_prev):
+    import actor_cases as ac
+    ref = lambda t: {"out": node_mlp(t["x2"], t["x_dst"], t["gamma"], t["beta"], t["w3"], t["b3"], t["w4"], t["b4"], t.get("prev"), stored=False)}
+    return as_bf16_case(ac.node_mlp_case(family, n, use_prev), ref)
+
+
+def edge_case(kind, with_dres):
+    import actor_cases as ac
+    c0 = ac.edge_case(kind, with_dres)
+    ei, n_src, n_dst, dim, gk = c0.meta
+
+    def ref(t):
+        ps, pd = t["pos_s"][t["src"]][:, :dim], t["pos_d"][t["dst"]][:, :dim]
+        out = {"x1": edge_conv(t["x_src"], t["src"], t["dst"], n_dst, t["grid"], ps, pd, t["w1"], t["b1"], t["w2"], t["b2"], t["wk"], stored=False)}
+        if with_dres:   # the residual gradient enters as a second, linear use of x_src: d x_src = the convolution's + dres
+            out["res"] = (t["x_src"] * t["dres"]).sum().reshape(1)
+        return out
+    return as_bf16_case(c0, ref)
+
+
+def conv_block_case(n, E):
+    """hepi._conv: x feeds the convolution AND the residual of its own node block.  x1 is STORED between the two kernels (rounded once);
+    d x is the sum of both branches (the node block hands d out to the edge backward, which adds it inside its d x_src kernel)."""
+    import actor_cases as ac
+    g = ac.gen(9, n, E)
+    ei = torch.stack([torch.randint(0, n, (E,), generator=g), torch.randint(0, n, (E,), generator=g)])
+    pos = torch.rand(n, 3, generator=g) * 2 - 1
+    we = ac.weights(g, [(64, 14), (64,), (64, 64), (64,), (64, 64)])
+    wm = [torch.rand(64, generator=g) + 0.5, torch.randn(64, generator=g) * 0.1] + ac.weights(g, [(256, 64), (256,), (64, 256), (64,)])
+    inputs = {"x": torch.randn(n, 16, 64, generator=g), "pos": pos, "grid": ac.grid_of("upper"), "src": ei[0], "dst": ei[1]}
+    inputs.update({f"e{i}": w for i, w in enumerate(we)})
+    inputs.update({f"m{i}": w for i, w in enumerate(wm)})
+
+    def ref(t):
+        x1 = edge_conv(t["x"], t["src"], t["dst"], n, t["grid"], t["pos"][t["src"]], t["pos"][t["dst"]], *[t[f"e{i}"] for i in range(5)], stored=True)
+        return {"out": node_mlp(x1, t["x"], *[t[f"m{i}"] for i in range(6)], stored=False)}
+    c = ac.Case(f"conv + node block n={n} E={E}", inputs, ["x"] + [f"e{i}" for i in range(5)] + [f"m{i}" for i in range(6)], ref,
+                {"out": torch.randn(n, 16, 64, generator=g)})
+    c = as_bf16_case(c, ref)
+    c.meta = (ei, n)
+    return c

@@ -1,10 +1,13 @@
 """Pins tests/bf16_ref.py, the float64 emulation of the plain-bf16 kernels that tests/test_gpu_attention_ops.py checks them against:
 with its roundings switched off and the erf GELU it must BE the oracle's maths (values and gradients to 1e-12), the normal CDF of its GELU
-approximant must stay within 1.4e-4 of Phi (csrc/grl_common.h), and with roundings on it must round where it says it does."""
+approximant must stay within 1.4e-4 of Phi (csrc/grl_common.h), and with roundings on it must round where it says it does.  The last test
+measures how far last-bit differences alone move the emulation on the cases of tests/test_gpu_bf16_ops.py (fp32 against float64
+evaluation) and holds that under half of each bar of that file."""
 import torch
 import torch.nn.functional as F
 
 import bf16_ref as br
+import ops_ref
 from oracle import equivariant as eq
 
 
@@ -123,3 +126,74 @@ def test_rounding_points():
     dout = torch.randn(x.shape, generator=g, dtype=torch.float64)
     out.backward(dout)
     assert torch.equal(s.grad, br.bf16(dout))
+
+
+def test_fiber_conv_and_lift_without_rounding_are_the_oracle():
+    g = torch.Generator().manual_seed(12)
+    n = 9
+    x1, fk, bias = (torch.randn(*s, generator=g, dtype=torch.float64) for s in [(n, 16, 64), (16, 16, 64), (64,)])
+    la = [t.clone().requires_grad_(True) for t in (x1, fk, bias)]
+    lb = [t.clone().requires_grad_(True) for t in (x1, fk, bias)]
+    out, ref = br.fiber_conv(*la, rounding=False), ops_ref.fiber_conv(*lb)
+    close("fiber conv", out, ref)
+    R = torch.randn(out.shape, generator=g, dtype=torch.float64)
+    (out * R).sum().backward()
+    (ref * R).sum().backward()
+    for a, b in zip(la, lb):
+        close("fiber conv grad", a.grad, b.grad)
+    for dim, S, V in ((3, 3, 4), (2, 3, 4), (3, 8, 0), (2, 1, 7)):
+        grid = eq.make_grid(dim, 16).double()
+        scal, vec, w = (torch.randn(*s, generator=g, dtype=torch.float64) for s in [(n, S), (n, V, 3), (64, S + V)])
+        wa, wb = w.clone().requires_grad_(True), w.clone().requires_grad_(True)
+        out, ref = br.lift_encode(scal, vec, grid, wa, rounding=False), ops_ref.lift_encode(scal, vec, grid, wb)
+        close("lift", out, ref)
+        (out * R).sum().backward()
+        (ref * R).sum().backward()
+        close("lift grad", wa.grad, wb.grad)
+
+
+def test_fiber_conv_and_lift_round_only_their_store():
+    g = torch.Generator().manual_seed(13)
+    x1, fk, bias = br.bf16(torch.randn(5, 16, 64, generator=g, dtype=torch.float64)), torch.randn(16, 16, 64, generator=g, dtype=torch.float64), \
+        torch.randn(64, generator=g, dtype=torch.float64)
+    xa = x1.clone().requires_grad_(True)
+    out = br.fiber_conv(xa, fk, bias)
+    exact = ops_ref.fiber_conv(x1, fk, bias)
+    assert torch.equal(out, br.bf16(exact)) and torch.equal(br.fiber_conv(x1, fk, bias, stored=False), exact)
+    dout = torch.randn(out.shape, generator=g, dtype=torch.float64)
+    out.backward(dout)
+    close("fiber conv dx1 (the gradient as read from bf16 memory)", xa.grad, torch.einsum("bpc,opc->boc", br.bf16(dout), fk) / 16)
+
+
+def test_last_bit_sensitivity_of_the_emulation_stays_under_half_of_each_gpu_bar():
+    """Every case tests/test_gpu_bf16_ops.py compares with the emulation, evaluated once in fp32 and once in float64 on the same
+    bf16-rounded inputs: the worst difference per family and tensor kind as a fraction of the tensor's own scale -- the reference's own
+    sensitivity to last-bit differences (rounding flips at bf16 boundaries) -- must stay under HALF of the bar the GPU test holds that
+    tensor to, which leaves the kernel the other half."""
+    from test_gpu_bf16_ops import BARS, reference_cases, tensor_kind
+    kinds = ("values", "stored gradients", "weight gradients")
+    worst = {}
+    for fam, c in reference_cases():
+        o64, g64 = c.evaluate(torch.float64)
+        o32, g32 = c.evaluate(torch.float32)
+        line = []
+        for is_out, d32, d64 in ((True, o32, o64), (False, g32, g64)):
+            for k in d64:
+                if is_out and k == "res":   # (the scalar that carries the residual gradient into d x_src: not a tensor of the op)
+                    continue
+                e, kind = ops_ref.rel_err(d32[k], d64[k]), tensor_kind(k, is_out)
+                line.append(f"{'' if is_out else 'd '}{k} {e:.2e}")
+                w = worst.setdefault(fam, [(0.0, "")] * 3)
+                if e >= w[kind][0]:
+                    w[kind] = (e, f"{c.name}: {'' if is_out else 'd '}{k}")
+        print(f"  {c.name}: " + ", ".join(line))
+        del o64, g64, o32, g32
+    print()
+    bad = []
+    for fam, w in worst.items():
+        for kind in range(3):
+            e, where = w[kind]
+            print(f"{fam:10s} {kinds[kind]:17s} worst fp32 vs float64 {e:.2e}  half bar {0.5 * BARS[fam][kind]:.1e}   ({where})")
+            if not e <= 0.5 * BARS[fam][kind]:
+                bad.append((fam, kinds[kind], e, where))
+    assert not bad, bad

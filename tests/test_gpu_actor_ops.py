@@ -187,12 +187,7 @@ def run_node_mlp(family, n, use_prev, off=0):
     return c, out.detach(), {k: v.grad for k, v in L.items()}
 
 
-# 700 / 1601 nodes: several chunks per workgroup of the backward; 4112 = 257 x 16 and 4101: above the forward's 256 workgroups x 256 rows.
-# The other input families at three sizes: below one chunk, several chunks, the grid-stride loop with a partial block.
-NODE_MLP_CASES = [("randn", n) for n in (1, 7, 130, 700, 1601, 4112, 4101)] + [(f, n) for f in ac.NODE_MLP_FAMILIES[1:] for n in (7, 700, 4101)]
-
-
-@pytest.mark.parametrize("family,n", NODE_MLP_CASES)
+@pytest.mark.parametrize("family,n", ac.NODE_MLP_CASES)
 def test_node_mlp(family, n):
     """randn rows, constant rows (variance 0), rows with a mean far above their spread, rows scaled by 1e3 and 1e-3; with and without prev."""
     for use_prev in (False, True):
@@ -241,14 +236,7 @@ def test_lift_encode_feature_splits(S, V, kind):
     compare("LiftEncode", c, {"x": x}, {"w": dw}, *ops_ref.BARS["lift"])
 
 
-# (node counts per type, index of a type whose output is left out of the loss or None, S, V, grid)
-MULTI = [([77], None, 3, 4, "3d"), ([5, 130], None, 3, 4, "3d"), ([9001, 3, 77], None, 3, 4, "3d"), ([4, 301, 1, 77], None, 3, 4, "3d"),
-         ([0, 77, 5], None, 3, 4, "3d"), ([77, 0, 5], None, 3, 4, "2d"), ([77, 5, 0], None, 3, 4, "3d"), ([130, 77, 301], 0, 3, 4, "3d"),
-         ([130, 77, 301], 1, 3, 4, "2d"), ([130, 0, 301, 4], 3, 3, 4, "3d"), ([70001, 77], None, 3, 4, "2d")]
-MULTI += [([301, 5, 77], None, S, V, k) for S, V in ac.LIFT_SPLITS for k in ("3d", "2d")]
-
-
-@pytest.mark.parametrize("ns,left_out,S,V,kind", MULTI)
+@pytest.mark.parametrize("ns,left_out,S,V,kind", ac.LIFT_MULTI)
 def test_lift_encode_multi(ns, left_out, S, V, kind):
     """Several node types in one launch each way: 1..4 types, a type without nodes in first / middle / last position, one type's output
     left out of the loss (its dx is None), every S / V split, 2-d and 3-d grids.  Forward bitwise equal to the single-type launches."""
