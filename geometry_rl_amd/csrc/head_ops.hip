@@ -809,6 +809,39 @@ __global__ __launch_bounds__(256) void gaussian_sample_kernel(const float* __res
   logp[b] = -0.5f * q - ls - 0.5f * (float)A * 1.8378770664093454836f;
 }
 
+// The ONE host-side launch of the fused loss kernel, behind all five entry points.  mode: the kernel's PROJ (0, 1, 2, 4, 6, 7 the TRPL
+// projections; 3 clipped PPO; 5 KL-penalty PPO); ent: the instance with the entropy stage (TRPL modes only).  Lane width from the action
+// dimension (<= 4 / 8 / 16), the launch, and -- sums != NULL -- the fold of the slots behind it (sums == NULL: the caller folds later,
+// grl_trpl_fold, on a stream of its choice: the sums are reported values only).  -3: no such instance.
+using TrplKernel = void (*)(TrplCfg, TrplPtrs, int);
+template <int L>
+static TrplKernel trpl_kernel_of(int mode, bool ent) {
+  switch (mode) {
+    case 0: return ent ? trpl_lanes_ent_kernel<L, 0> : trpl_lanes_kernel<L, 0>;
+    case 1: return ent ? trpl_lanes_ent_kernel<L, 1> : trpl_lanes_kernel<L, 1>;
+    case 2: return ent ? trpl_lanes_ent_kernel<L, 2> : trpl_lanes_kernel<L, 2>;
+    case 4: return ent ? trpl_lanes_ent_kernel<L, 4> : trpl_lanes_kernel<L, 4>;
+    case 6: return ent ? trpl_lanes_ent_kernel<L, 6> : trpl_lanes_kernel<L, 6>;
+    case 7: return ent ? trpl_lanes_ent_kernel<L, 7> : trpl_lanes_kernel<L, 7>;
+    case 3: return ent ? nullptr : trpl_lanes_kernel<L, 3>;
+    case 5: return ent ? nullptr : trpl_lanes_kernel<L, 5>;
+    default: return nullptr;
+  }
+}
+static int trpl_run(int mode, bool ent, const TrplCfg& c, const TrplPtrs& tp, int batch, double* sums, unsigned int* maxes,
+                    hipStream_t stream) {
+  const int lanes = c.A <= 4 ? 4 : c.A <= 8 ? 8 : 16;
+  const TrplKernel kernel = lanes == 4 ? trpl_kernel_of<4>(mode, ent) : lanes == 8 ? trpl_kernel_of<8>(mode, ent) : trpl_kernel_of<16>(mode, ent);
+  if (!kernel) return -3;
+  hipLaunchKernelGGL(kernel, dim3(trpl_blocks(batch)), dim3(TRPL_FPB * lanes), 0, stream, c, tp, batch);
+  GRL_CHECK_LAUNCH();
+  if (sums) {
+    hipLaunchKernelGGL(trpl_fold_kernel, dim3(1), dim3(FOLD_NT), 0, stream, tp.slots, trpl_blocks(batch), sums, maxes);
+    GRL_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -870,39 +903,12 @@ static int trpl_launch(const double* cfg9, int action_dim, const float* mean, co
                        int ent_mode = -1, const double* ent_beta = nullptr) {
   if (action_dim > 16 || action_dim < 1 || batch < 1 || !slots) return -2;
   if (ent_mode >= 0 && (ent_mode > 3 || !ent_beta || tgt_mean)) return -2;
-  TrplCfg c{cfg9[0], cfg9[1], cfg9[2], cfg9[3], cfg9[4], cfg9[5], cfg9[6], cfg9[7], action_dim, (int)cfg9[9]};
+  const TrplCfg c{cfg9[0], cfg9[1], cfg9[2], cfg9[3], cfg9[4], cfg9[5], cfg9[6], cfg9[7], action_dim, (int)cfg9[9]};
   const int proj = (int)cfg9[8];
-  if (proj != 0 && proj != 1 && proj != 2 && proj != 4 && proj != 6 && proj != 7)
-    return -3;   // (3 and 5, the PPO modes, have their own entry points: grl_ppo_fwd_bwd, grl_klpen_fwd_bwd)
+  if (proj == 3 || proj == 5) return -3;   // (the PPO modes have their own entry points: grl_ppo_fwd_bwd, grl_klpen_fwd_bwd)
   const TrplPtrs tp{mean, sigma, action, old_mean, old_var, old_logp, advantage, value, old_value, value_target, dmean, dsigma, dvalue,
                     proj_mean, proj_var, adv_stats, slots, tgt_mean, tgt_S, 0, nullptr, ent_beta, ent_mode < 0 ? 0 : ent_mode};
-#define GRL_TRPL_LAUNCH(LL, PJ)                                                                                                           \
-  do {                                                                                                                                    \
-    if (ent_mode < 0)                                                                                                                     \
-      hipLaunchKernelGGL((trpl_lanes_kernel<LL, PJ>), dim3(trpl_blocks(batch)), dim3(TRPL_FPB * LL), 0, stream, c, tp, batch);            \
-    else                                                                                                                                  \
-      hipLaunchKernelGGL((trpl_lanes_ent_kernel<LL, PJ>), dim3(trpl_blocks(batch)), dim3(TRPL_FPB * LL), 0, stream, c, tp, batch);        \
-  } while (0)
-#define GRL_TRPL_WIDTH(PJ)                                        \
-  do {                                                            \
-    if (action_dim <= 4) GRL_TRPL_LAUNCH(4, PJ);                  \
-    else if (action_dim <= 8) GRL_TRPL_LAUNCH(8, PJ);             \
-    else GRL_TRPL_LAUNCH(16, PJ);                                 \
-  } while (0)
-  if (proj == 0) GRL_TRPL_WIDTH(0);
-  else if (proj == 1) GRL_TRPL_WIDTH(1);
-  else if (proj == 2) GRL_TRPL_WIDTH(2);
-  else if (proj == 4) GRL_TRPL_WIDTH(4);
-  else if (proj == 6) GRL_TRPL_WIDTH(6);
-  else GRL_TRPL_WIDTH(7);
-#undef GRL_TRPL_WIDTH
-#undef GRL_TRPL_LAUNCH
-  GRL_CHECK_LAUNCH();
-  if (sums) {   // sums == NULL: the caller folds the slots later (grl_trpl_fold, on a stream of its choice: the sums are reported values only)
-    hipLaunchKernelGGL(trpl_fold_kernel, dim3(1), dim3(FOLD_NT), 0, stream, slots, trpl_blocks(batch), sums, maxes);
-    GRL_CHECK_LAUNCH();
-  }
-  return 0;
+  return trpl_run(proj, ent_mode >= 0, c, tp, batch, sums, maxes, stream);
 }
 
 // cfg6 (HOST): {entropy_coef, critic_coef, clip_value, 1/B_global, B_global, adv_local}; clip_eps: DEVICE float[1], read by the kernel
@@ -917,15 +923,7 @@ int grl_ppo_fwd_bwd(const double* cfg6, const float* clip_eps, int action_dim, c
   const TrplCfg c{0.0, 0.0, 0.0, cfg6[0], cfg6[1], cfg6[2], cfg6[3], cfg6[4], action_dim, (int)cfg6[5]};
   const TrplPtrs tp{mean, sigma, action, nullptr, nullptr, old_logp, advantage, value, old_value, value_target, dmean, dsigma, dvalue,
                     nullptr, nullptr, adv_stats, slots, nullptr, nullptr, 0, clip_eps, nullptr, 0};
-  if (action_dim <= 4) hipLaunchKernelGGL((trpl_lanes_kernel<4, 3>), dim3(trpl_blocks(batch)), dim3(TRPL_FPB * 4), 0, stream, c, tp, batch);
-  else if (action_dim <= 8) hipLaunchKernelGGL((trpl_lanes_kernel<8, 3>), dim3(trpl_blocks(batch)), dim3(TRPL_FPB * 8), 0, stream, c, tp, batch);
-  else hipLaunchKernelGGL((trpl_lanes_kernel<16, 3>), dim3(trpl_blocks(batch)), dim3(TRPL_FPB * 16), 0, stream, c, tp, batch);
-  GRL_CHECK_LAUNCH();
-  if (sums) {
-    hipLaunchKernelGGL(trpl_fold_kernel, dim3(1), dim3(FOLD_NT), 0, stream, slots, trpl_blocks(batch), sums, maxes);
-    GRL_CHECK_LAUNCH();
-  }
-  return 0;
+  return trpl_run(3, false, c, tp, batch, sums, maxes, stream);
 }
 
 // The adaptive KL-penalty PPO objective (mode 5 of the kernel; include/grl_hip.h): the arguments of grl_ppo_fwd_bwd plus the old distribution;
@@ -941,15 +939,7 @@ int grl_klpen_fwd_bwd(const double* cfg6, const float* beta, int action_dim, con
   const TrplCfg c{0.0, 0.0, 0.0, cfg6[0], cfg6[1], cfg6[2], cfg6[3], cfg6[4], action_dim, (int)cfg6[5]};
   const TrplPtrs tp{mean, sigma, action, old_mean, old_var, old_logp, advantage, value, old_value, value_target, dmean, dsigma, dvalue,
                     nullptr, nullptr, adv_stats, slots, nullptr, nullptr, 0, beta, nullptr, 0};
-  if (action_dim <= 4) hipLaunchKernelGGL((trpl_lanes_kernel<4, 5>), dim3(trpl_blocks(batch)), dim3(TRPL_FPB * 4), 0, stream, c, tp, batch);
-  else if (action_dim <= 8) hipLaunchKernelGGL((trpl_lanes_kernel<8, 5>), dim3(trpl_blocks(batch)), dim3(TRPL_FPB * 8), 0, stream, c, tp, batch);
-  else hipLaunchKernelGGL((trpl_lanes_kernel<16, 5>), dim3(trpl_blocks(batch)), dim3(TRPL_FPB * 16), 0, stream, c, tp, batch);
-  GRL_CHECK_LAUNCH();
-  if (sums) {
-    hipLaunchKernelGGL(trpl_fold_kernel, dim3(1), dim3(FOLD_NT), 0, stream, slots, trpl_blocks(batch), sums, maxes);
-    GRL_CHECK_LAUNCH();
-  }
-  return 0;
+  return trpl_run(5, false, c, tp, batch, sums, maxes, stream);
 }
 
 // torchrl 0.3.1 KLPENPPOLoss.forward's tail: kl > 1.5 dtarg -> beta *= increment; kl < dtarg / 1.5 -> beta *= decrement.  kl = out14[5], the

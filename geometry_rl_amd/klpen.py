@@ -26,39 +26,10 @@ reproduced (it would put a global reduction between the forward and the backward
 import torch
 
 from . import ops
-from .trpl import LossDict, _as_batch, _LossBase, _run_trpl, _TensorDict, _unwrap
+from .trpl import FusedLoss, _as_batch, _run_trpl
 
 
-def klpen_launch(m, loc, sigma, value, batch, adv_stats, sums=None, maxes=None, defer_fold=False, adv_local=False):
-    """The KL-penalty counterpart of trpl.trpl_launch (which dispatches here): one launch of the fused kernel on detached inputs ->
-    (sums, maxes, dloc, dsigma, dvalue); the slots and sums have the TRPL layout (column 11 = sum of the per-frame KL, trust-region
-    columns zero)."""
-    B = loc.shape[0]
-    if "loc" not in batch or ("var" not in batch and "covariance_matrix" not in batch):
-        raise ValueError("KLPENPPOLoss needs the old distribution in the minibatch: keys 'loc' and 'var' (or 'covariance_matrix')")
-    if "var" not in batch:
-        batch = dict(batch, var=batch["covariance_matrix"].diagonal(dim1=-2, dim2=-1).contiguous())
-    return ops.klpen_fwd_bwd(loc.detach(), sigma.detach(), batch, value.detach() if value is not None else None, beta=m.beta,
-                             entropy_coef=m.entropy_coef if m.entropy_bonus else 0.0, critic_coef=m.critic_coef, clip_value=0.0,
-                             global_batch=B * m.world_size, adv_stats=adv_stats, sums=sums, maxes=maxes, defer_fold=defer_fold,
-                             adv_local=adv_local)
-
-
-def klpen_adapt(m, out14):
-    """The penalty weight's update from a step's 14-float report, on the current stream (ops.klpen_adapt)."""
-    ops.klpen_adapt(out14, m.beta, m.dtarg, m.increment, m.decrement)
-
-
-def report_dict(o, m):
-    """The 14-float report (grl_trpl_report / grl_fold_adam_report / the record reports) as (actor loss, metrics dict of views): the keys
-    KLPENPPOLoss.forward sets besides loss_objective and loss_critic.  No ESS: torchrl's class computes none."""
-    mt = {"kl": o[5], "loss_objective_value": o[12]}
-    if m.entropy_bonus:
-        mt.update(entropy=o[10], loss_entropy=o[3])
-    return o[0], mt
-
-
-class KLPENPPOLoss(_LossBase):
+class KLPENPPOLoss(FusedLoss):
     """torchrl 0.3.1 ``KLPENPPOLoss`` (signature of the reference builder's call).  ``actor_network`` is a GNNGaussianPolicyDiag (or a
     ProbabilisticActor wrapping one), ``critic_network`` a BaseCritic (or a ValueOperator around one).  ``forward(tensordict)`` runs the
     loss launch, the report and the beta update ONCE, like torchrl's forward, and returns a TensorDict when ``tensordict`` is installed,
@@ -70,12 +41,12 @@ class KLPENPPOLoss(_LossBase):
     importable the class is a ``torchrl.objectives.LossModule``."""
     algorithm = "kl_ppo"
     clip_value = None   # (torchrl 0.3.1's PPOLoss.loss_critic has no value clipping)
+    keeps_report = True   # (after_report reads the step's mean KL from it)
 
     def __init__(self, actor_network=None, critic_network=None, *, dtarg=0.01, beta=1.0, increment=2, decrement=0.5, samples_mc_kl=1,
                  entropy_bonus=True, samples_mc_entropy=1, entropy_coef=0.01, critic_coef=1.0, loss_critic_type="smooth_l1",
                  normalize_advantage=True, gamma=None, separate_losses=False, in_features=None, group=None, critic_in_features=None,
                  **kwargs):
-        super().__init__()
         if loss_critic_type != "l2":
             raise NotImplementedError("loss_critic_type: only l2 is built (configs/algorithm/objective/kl_ppo.yaml passes l2; the "
                                       "reference's default smooth_l1 is not)")
@@ -83,27 +54,18 @@ class KLPENPPOLoss(_LossBase):
             raise ValueError(f"increment should be >= 1.0 in KLPENPPOLoss, got {increment:4.4f}")
         if decrement > 1.0:
             raise ValueError(f"decrement should be <= 1.0 in KLPENPPOLoss, got {decrement:4.4f}")
-        actor_network = _unwrap(actor_network, "forward_diag")
-        critic_network = _unwrap(critic_network, "_network1")
-        self.actor_network, self.critic_network = actor_network, critic_network
-        dev = next((p.device for p in actor_network.parameters()), torch.device("cpu"))
+        super().__init__(actor_network, critic_network, entropy_bonus=entropy_bonus, entropy_coef=entropy_coef, critic_coef=critic_coef,
+                         normalize_advantage=normalize_advantage, in_features=in_features, critic_in_features=critic_in_features,
+                         group=group)
+        dev = next((p.device for p in self.actor_network.parameters()), torch.device("cpu"))
         self.register_buffer("beta", torch.tensor(float(beta), dtype=torch.float32, device=dev))
         self.dtarg, self.increment, self.decrement = float(dtarg), float(increment), float(decrement)
         self.samples_mc_kl = samples_mc_kl
-        self.entropy_bonus, self.entropy_coef, self.critic_coef = bool(entropy_bonus), float(entropy_coef), float(critic_coef)
         self.samples_mc_entropy, self.gamma, self.separate_losses = samples_mc_entropy, gamma, separate_losses
-        self.normalize_advantage = normalize_advantage
-        self.in_features = list(in_features or actor_network.hyper_data.spec.in_features)
-        self.critic_in_features = list(critic_in_features or self.in_features)
-        self.group = group
-        self._global_steps = 0
 
     @property
-    def world_size(self):
-        if self.group is None:
-            return 1
-        import torch.distributed as dist
-        return dist.get_world_size(self.group)
+    def device_scalars(self):
+        return {"kl_beta": self.beta}
 
     @property
     def out_keys(self):   # torchrl 0.3.1 KLPENPPOLoss.forward's keys
@@ -114,24 +76,35 @@ class KLPENPPOLoss(_LossBase):
             keys.append("loss_critic")
         return keys
 
-    def forward(self, tensordict):
-        b = _as_batch(tensordict, self.in_features + self.critic_in_features)
+    def check_batch(self, b):
         if "loc" not in b or ("var" not in b and "covariance_matrix" not in b):
             raise ValueError("KLPENPPOLoss needs the old distribution in the minibatch: keys 'loc' and 'var' (or 'covariance_matrix')")
-        loc, sigma = self.actor_network.forward_diag(*[b[k] for k in self.in_features], train=True)
-        value = self.critic_network(*[b[k] for k in self.critic_in_features]) if self.critic_coef else None
+
+    def launch(self, loc, sigma, value, batch, adv_stats, *, sums=None, maxes=None, defer_fold=False, adv_local=False, beta=None):
+        """FusedLoss.launch in the kernel's KL-penalty mode (column 11 = sum of the per-frame KL, trust-region columns zero)."""
+        self.check_batch(batch)
+        if "var" not in batch:
+            batch = dict(batch, var=batch["covariance_matrix"].diagonal(dim1=-2, dim2=-1).contiguous())
+        args, kw = self._launch_args(loc, sigma, value, batch, adv_stats, sums, maxes, defer_fold, adv_local)
+        return ops.klpen_fwd_bwd(*args, beta=self.beta, **kw)
+
+    def after_report(self, o14):
+        """The penalty weight's update from a step's 14-float report, on the current stream (ops.klpen_adapt)."""
+        ops.klpen_adapt(o14, self.beta, self.dtarg, self.increment, self.decrement)
+
+    def report_dict(self, o):
+        """The keys KLPENPPOLoss.forward sets besides loss_objective and loss_critic.  No ESS: torchrl's class computes none."""
+        mt = {"kl": o[5], "loss_objective_value": o[12]}
+        if self.entropy_bonus:
+            mt.update(entropy=o[10], loss_entropy=o[3])
+        return o[0], mt
+
+    def forward(self, tensordict):
+        b = _as_batch(tensordict, self.in_features + self.critic_in_features)
+        self.check_batch(b)
+        loc, sigma, value = self._networks(b)
         o14 = torch.empty(14, device=loc.device, dtype=torch.float32)
         actor, critic, mt = _run_trpl(self, loc, sigma, value, b, out=o14)
         with torch.no_grad():
-            klpen_adapt(self, o14)   # (behind the report: the launch above has read the old beta)
-        out = {"loss_objective": actor - mt["loss_entropy"] if self.entropy_bonus else actor, "kl": mt["kl"]}
-        if self.entropy_bonus:
-            out.update(entropy=mt["entropy"], loss_entropy=mt["loss_entropy"])
-        if self.critic_coef:
-            out["loss_critic"] = critic
-        if _TensorDict is not None:
-            td = _TensorDict(out, [])
-            td.__dict__["_grl_outputs"] = {"loc": loc, "sigma": sigma, "state_value": value}
-            return td
-        out.update(loc=loc, sigma=sigma, state_value=value)
-        return LossDict(out)
+            self.after_report(o14)   # (behind the report: the launch above has read the old beta)
+        return self._loss_output(self._ppo_out(actor, critic, mt, first=("kl",)), loc, sigma, value)

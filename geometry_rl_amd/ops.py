@@ -939,6 +939,59 @@ TRPL_SUM_KEYS = ("loss_objective", "loss_trust_region", "entropy_dist", "loss_cr
                  "cov_constraint", "entropy", "entropy_diff", "count", "kl")
 
 
+def _loss_launch(entry, lead, loc, sigma, batch, value, *, old=True, proj_out=None, trail=(), target=None, adv_stats=None, sums=None,
+                 maxes=None, defer_fold=False):
+    """The one launch of the fused loss kernel behind ``trpl_fwd_bwd`` / ``ppo_fwd_bwd`` / ``klpen_fwd_bwd`` / ``trpl_target_terms``: the
+    workspace (``sums`` fp64[12] / ``maxes`` u32[2] -- the caller's views of its per-step workspace, written in full by the launch, or fresh
+    ones --, the per-workgroup ``slots``, ``dloc`` / ``dsigma`` / ``dvalue``), the batch's columns as contiguous [B, A] / [B] arrays, and the
+    call of ``entry``(*lead, A, loc, sigma, <columns>, <outputs>, B, *trail).  ``old``: the entry point takes the old distribution;
+    ``proj_out`` (not None): it takes the projection outputs (True: allocated here, False: NULL); ``target`` = (mean, S): the argument list of grl_trpl_target_terms
+    (the target in the batch's place, a column of zeros standing in for advantage and old log-prob).
+    -> (sums, maxes, dloc, dsigma, dvalue, proj_mean, proj_var); ``defer_fold``: the slots are not folded by this call and ``sums`` comes
+    back as the callable that does it (on whatever stream is current when it is called), -> (sums, maxes)."""
+    B, A = loc.shape
+    dev = loc.device
+    if sums is None:
+        sums = torch.empty(12, device=dev, dtype=torch.float64)
+        maxes = torch.empty(2, device=dev, dtype=torch.int32)
+    slots = torch.empty(hip.query("grl_trpl_slot_doubles", B), device=dev, dtype=torch.float64)   # per-workgroup sums
+    dloc, dsigma = torch.empty_like(loc), torch.empty_like(sigma)
+    dvalue = torch.empty(B, device=dev, dtype=torch.float32) if value is not None else None
+    pm, pv = (torch.empty_like(loc), torch.empty_like(loc)) if proj_out else (None, None)
+    if target is not None:
+        args = (*(t.contiguous() for t in target), dloc, dsigma, sums, maxes, slots, torch.zeros(B, device=dev, dtype=torch.float32), B)
+    else:
+        mat = lambda k: batch[k].reshape(B, -1).contiguous()
+        row = lambda k: batch[k].reshape(B).contiguous()
+        args = (mat("action"), *((mat("loc"), mat("var")) if old else ()), row("sample_log_prob"), row("advantage"),
+                *((value.reshape(B).contiguous(), row("state_value"), row("value_target")) if value is not None else (None, None, None)),
+                dloc, dsigma, dvalue, *((pm, pv) if proj_out is not None else ()), adv_stats, None if defer_fold else sums, maxes,
+                slots, B, *trail)
+    hip.call(entry, *lead, A, loc.contiguous(), sigma.contiguous(), *args)
+    if defer_fold:
+        def fold(sums=sums, maxes=maxes, slots=slots):
+            hip.call("grl_trpl_fold", slots, B, sums, maxes)
+            return sums, maxes
+        fold.slots, fold.batch, fold.sums, fold.maxes = slots, B, sums, maxes   # (for a caller that folds and reports in one launch)
+        sums = fold
+    return sums, maxes, dloc, dsigma, dvalue, pm, pv
+
+
+def _trpl_cfg(mean_bound, cov_bound, trust_region_coeff, entropy_coef, critic_coef, clip_value, global_batch, proj_type, adv_local):
+    """cfg9 of grl_trpl_fwd_bwd[_ent] / grl_trpl_target_terms (host doubles; adv_local: the batch's advantage statistics are summed inside
+    the kernel)."""
+    import ctypes
+    return (ctypes.c_double * 10)(mean_bound, cov_bound, trust_region_coeff, entropy_coef, critic_coef, clip_value if clip_value else 0.0,
+                                  1.0 / global_batch, float(global_batch), float(proj_type), 1.0 if adv_local else 0.0)
+
+
+def _ppo_cfg(entropy_coef, critic_coef, clip_value, global_batch, adv_local):
+    """cfg6 of grl_ppo_fwd_bwd / grl_klpen_fwd_bwd (host doubles)."""
+    import ctypes
+    return (ctypes.c_double * 6)(entropy_coef, critic_coef, clip_value if clip_value else 0.0, 1.0 / global_batch, float(global_batch),
+                                 1.0 if adv_local else 0.0)
+
+
 def trpl_fwd_bwd(loc, sigma, batch, value, *, mean_bound, cov_bound, trust_region_coeff, entropy_coef, critic_coef, clip_value,
                  global_batch: int, adv_stats: Optional[torch.Tensor], want_projection: bool = False, sums=None, maxes=None,
                  proj_type: int = 0, defer_fold: bool = False, adv_local: bool = False, ent_mode: Optional[int] = None,
@@ -950,39 +1003,13 @@ def trpl_fwd_bwd(loc, sigma, batch, value, *, mean_bound, cov_bound, trust_regio
     ``ent_mode`` (not None): the scheduled entropy projection runs inside the launch (grl_trpl_fwd_bwd_ent) -- bit 0 equality form, bit 1
     entropy in front of the trust region; ``ent_beta``: a device float64 tensor of one element, the bound, read by the kernel when it
     runs (a recorded launch sees every write to it)."""
-    import ctypes
     hip.check_f32(loc, sigma)
-    B, A = loc.shape
-    dev = loc.device
-    if ent_mode is not None and (ent_beta is None or ent_beta.dtype != torch.float64 or ent_beta.numel() != 1 or ent_beta.device != dev):
+    if ent_mode is not None and (ent_beta is None or ent_beta.dtype != torch.float64 or ent_beta.numel() != 1 or ent_beta.device != loc.device):
         raise ValueError("ent_beta must be a one-element float64 tensor on the policy's device")
-    cfg = (ctypes.c_double * 10)(mean_bound, cov_bound, trust_region_coeff, entropy_coef, critic_coef,
-                                 clip_value if clip_value else 0.0, 1.0 / global_batch, float(global_batch), float(proj_type),
-                                 1.0 if adv_local else 0.0)   # adv_local: the batch's advantage statistics are summed inside the kernel
-    if sums is None:   # otherwise: views of the caller's per-step workspace (written in full by the launch)
-        sums = torch.empty(12, device=dev, dtype=torch.float64)
-        maxes = torch.empty(2, device=dev, dtype=torch.int32)
-    slots = torch.empty(hip.query("grl_trpl_slot_doubles", B), device=dev, dtype=torch.float64)   # per-workgroup sums
-    dloc, dsigma = torch.empty_like(loc), torch.empty_like(sigma)
-    dvalue = torch.empty(B, device=dev, dtype=torch.float32) if value is not None else None
-    pm = torch.empty_like(loc) if want_projection else None
-    pv = torch.empty_like(loc) if want_projection else None
-    f = lambda t: t.reshape(B, -1).contiguous() if t.dim() > 1 else t.contiguous()
-    hip.call("grl_trpl_fwd_bwd" if ent_mode is None else "grl_trpl_fwd_bwd_ent", cfg, A, loc.contiguous(), sigma.contiguous(),
-             f(batch["action"]), f(batch["loc"]), f(batch["var"]),
-             batch["sample_log_prob"].reshape(B).contiguous(), batch["advantage"].reshape(B).contiguous(),
-             value.reshape(B).contiguous() if value is not None else None,
-             batch["state_value"].reshape(B).contiguous() if value is not None else None,
-             batch["value_target"].reshape(B).contiguous() if value is not None else None,
-             dloc, dsigma, dvalue, pm, pv, adv_stats, None if defer_fold else sums, maxes, slots, B,
-             *(() if ent_mode is None else (int(ent_mode), ent_beta)))
-    if defer_fold:
-        def fold(sums=sums, maxes=maxes, slots=slots):
-            hip.call("grl_trpl_fold", slots, B, sums, maxes)
-            return sums, maxes
-        fold.slots, fold.batch, fold.sums, fold.maxes = slots, B, sums, maxes   # (for a caller that folds and reports in one launch)
-        return fold, maxes, dloc, dsigma, dvalue, pm, pv
-    return sums, maxes, dloc, dsigma, dvalue, pm, pv
+    cfg = _trpl_cfg(mean_bound, cov_bound, trust_region_coeff, entropy_coef, critic_coef, clip_value, global_batch, proj_type, adv_local)
+    return _loss_launch("grl_trpl_fwd_bwd" if ent_mode is None else "grl_trpl_fwd_bwd_ent", (cfg,), loc, sigma, batch, value,
+                        proj_out=bool(want_projection), trail=() if ent_mode is None else (int(ent_mode), ent_beta), adv_stats=adv_stats,
+                        sums=sums, maxes=maxes, defer_fold=defer_fold)
 
 
 def write_doubles(dst: torch.Tensor, values) -> None:
@@ -1002,34 +1029,12 @@ def ppo_fwd_bwd(loc, sigma, batch, value, *, clip_epsilon: torch.Tensor, entropy
     """The clipped PPO objective on the fused kernel (grl_ppo_fwd_bwd): the same returns as ``trpl_fwd_bwd`` without the projection
     outputs, (sums, maxes, dloc, dsigma, dvalue).  ``clip_epsilon``: a device float32 tensor of one element, read by the kernel when it
     runs (a recorded launch sees every in-place write to it)."""
-    import ctypes
     hip.check_f32(loc, sigma, clip_epsilon)
     if clip_epsilon.numel() != 1 or clip_epsilon.device != loc.device:
         raise ValueError("clip_epsilon must be a one-element float32 tensor on the policy's device")
-    B, A = loc.shape
-    dev = loc.device
-    cfg = (ctypes.c_double * 6)(entropy_coef, critic_coef, clip_value if clip_value else 0.0, 1.0 / global_batch, float(global_batch),
-                                1.0 if adv_local else 0.0)
-    if sums is None:
-        sums = torch.empty(12, device=dev, dtype=torch.float64)
-        maxes = torch.empty(2, device=dev, dtype=torch.int32)
-    slots = torch.empty(hip.query("grl_trpl_slot_doubles", B), device=dev, dtype=torch.float64)
-    dloc, dsigma = torch.empty_like(loc), torch.empty_like(sigma)
-    dvalue = torch.empty(B, device=dev, dtype=torch.float32) if value is not None else None
-    f = lambda t: t.reshape(B, -1).contiguous()
-    hip.call("grl_ppo_fwd_bwd", cfg, clip_epsilon, A, loc.contiguous(), sigma.contiguous(), f(batch["action"]),
-             batch["sample_log_prob"].reshape(B).contiguous(), batch["advantage"].reshape(B).contiguous(),
-             value.reshape(B).contiguous() if value is not None else None,
-             batch["state_value"].reshape(B).contiguous() if value is not None else None,
-             batch["value_target"].reshape(B).contiguous() if value is not None else None,
-             dloc, dsigma, dvalue, adv_stats, None if defer_fold else sums, maxes, slots, B)
-    if defer_fold:
-        def fold(sums=sums, maxes=maxes, slots=slots):
-            hip.call("grl_trpl_fold", slots, B, sums, maxes)
-            return sums, maxes
-        fold.slots, fold.batch, fold.sums, fold.maxes = slots, B, sums, maxes
-        return fold, maxes, dloc, dsigma, dvalue
-    return sums, maxes, dloc, dsigma, dvalue
+    cfg = _ppo_cfg(entropy_coef, critic_coef, clip_value, global_batch, adv_local)
+    return _loss_launch("grl_ppo_fwd_bwd", (cfg, clip_epsilon), loc, sigma, batch, value, old=False, adv_stats=adv_stats, sums=sums,
+                        maxes=maxes, defer_fold=defer_fold)[:5]
 
 
 def klpen_fwd_bwd(loc, sigma, batch, value, *, beta: torch.Tensor, entropy_coef, critic_coef, clip_value, global_batch: int,
@@ -1037,38 +1042,17 @@ def klpen_fwd_bwd(loc, sigma, batch, value, *, beta: torch.Tensor, entropy_coef,
     """The adaptive KL-penalty PPO objective on the fused kernel (grl_klpen_fwd_bwd): the returns of ``ppo_fwd_bwd``, (sums, maxes, dloc,
     dsigma, dvalue).  ``batch`` carries the old distribution ("loc", "var").  ``beta``: a device float32 tensor of one element, the penalty
     weight, read by the kernel when it runs (a recorded launch sees every write to it: ``klpen_adapt``'s and the host's)."""
-    import ctypes
     hip.check_f32(loc, sigma, beta)
     if beta.numel() != 1 or beta.device != loc.device:
         raise ValueError("beta must be a one-element float32 tensor on the policy's device")
-    B, A = loc.shape
-    dev = loc.device
-    cfg = (ctypes.c_double * 6)(entropy_coef, critic_coef, clip_value if clip_value else 0.0, 1.0 / global_batch, float(global_batch),
-                                1.0 if adv_local else 0.0)
-    if sums is None:
-        sums = torch.empty(12, device=dev, dtype=torch.float64)
-        maxes = torch.empty(2, device=dev, dtype=torch.int32)
-    slots = torch.empty(hip.query("grl_trpl_slot_doubles", B), device=dev, dtype=torch.float64)
-    dloc, dsigma = torch.empty_like(loc), torch.empty_like(sigma)
-    dvalue = torch.empty(B, device=dev, dtype=torch.float32) if value is not None else None
-    f = lambda t: t.reshape(B, -1).contiguous()
-    old_loc, old_var = f(batch["loc"]), f(batch["var"])
+    B = loc.shape[0]
+    old_loc, old_var = batch["loc"].reshape(B, -1), batch["var"].reshape(B, -1)
     if old_loc.shape != loc.shape or old_var.shape != loc.shape:
         raise ValueError(f"the old distribution is {tuple(old_loc.shape)} / {tuple(old_var.shape)}, the policy's {tuple(loc.shape)}")
     hip.check_f32(old_loc, old_var)
-    hip.call("grl_klpen_fwd_bwd", cfg, beta, A, loc.contiguous(), sigma.contiguous(), f(batch["action"]), old_loc, old_var,
-             batch["sample_log_prob"].reshape(B).contiguous(), batch["advantage"].reshape(B).contiguous(),
-             value.reshape(B).contiguous() if value is not None else None,
-             batch["state_value"].reshape(B).contiguous() if value is not None else None,
-             batch["value_target"].reshape(B).contiguous() if value is not None else None,
-             dloc, dsigma, dvalue, adv_stats, None if defer_fold else sums, maxes, slots, B)
-    if defer_fold:
-        def fold(sums=sums, maxes=maxes, slots=slots):
-            hip.call("grl_trpl_fold", slots, B, sums, maxes)
-            return sums, maxes
-        fold.slots, fold.batch, fold.sums, fold.maxes = slots, B, sums, maxes
-        return fold, maxes, dloc, dsigma, dvalue
-    return sums, maxes, dloc, dsigma, dvalue
+    cfg = _ppo_cfg(entropy_coef, critic_coef, clip_value, global_batch, adv_local)
+    return _loss_launch("grl_klpen_fwd_bwd", (cfg, beta), loc, sigma, batch, value, adv_stats=adv_stats, sums=sums, maxes=maxes,
+                        defer_fold=defer_fold)[:5]
 
 
 def klpen_thresholds(dtarg: float):
@@ -1092,17 +1076,6 @@ def trpl_target_terms(loc, sigma, tgt_mean, tgt_S, *, mean_bound, cov_bound, tru
     (grl_trpl_target_terms).  ``sigma`` = sqrt of the policy's covariance diagonal, ``tgt_S`` = the target's covariance diagonal.
     ``proj_type``: the codes of ``trpl_fwd_bwd`` (6, 7: the Euclidean measures).
     Returns (sums fp64[12], maxes u32[2], dloc, dsigma)."""
-    import ctypes
     hip.check_f32(loc, sigma, tgt_mean, tgt_S)
-    B, A = loc.shape
-    dev = loc.device
-    cfg = (ctypes.c_double * 10)(mean_bound, cov_bound, trust_region_coeff, 0.0, 0.0, 0.0, 1.0 / global_batch, float(global_batch),
-                                 float(proj_type), 0.0)
-    sums = torch.empty(12, device=dev, dtype=torch.float64)
-    maxes = torch.empty(2, device=dev, dtype=torch.int32)
-    slots = torch.empty(hip.query("grl_trpl_slot_doubles", B), device=dev, dtype=torch.float64)
-    dloc, dsigma = torch.empty_like(loc), torch.empty_like(sigma)
-    zeros_b = torch.zeros(B, device=dev, dtype=torch.float32)
-    hip.call("grl_trpl_target_terms", cfg, A, loc.contiguous(), sigma.contiguous(), tgt_mean.contiguous(), tgt_S.contiguous(), dloc,
-             dsigma, sums, maxes, slots, zeros_b, B)
-    return sums, maxes, dloc, dsigma
+    cfg = _trpl_cfg(mean_bound, cov_bound, trust_region_coeff, 0.0, 0.0, 0.0, global_batch, proj_type, False)
+    return _loss_launch("grl_trpl_target_terms", (cfg,), loc, sigma, None, None, target=(tgt_mean, tgt_S))[:4]

@@ -217,15 +217,11 @@ class RolloutDriver:
         caller's.  Everything is enqueued first; the host then waits ONCE per call, not once per step."""
         upd = self.updater
         ev = explained_variance(buf.data["state_value"], buf.data["value_target"])
-        eps = getattr(upd.loss_module, "clip_epsilon", None)
         means = upd.stats_read()                                   # (the synchronisation)
         log = {f"train/{k}": v for k, v in means.items() if k != "updates"}
         ev = ev.tolist()
         log.update({"train/explained_variance": ev[0], "train/explained_variance_flat": ev[1], "train/lr": upd.lr})
-        if torch.is_tensor(eps):
-            log["train/clip_epsilon"] = float(eps)
-        if getattr(upd.loss_module, "algorithm", None) == "kl_ppo":
-            log["train/kl_beta"] = float(upd.loss_module.beta)
+        log.update({f"train/{name}": float(t) for name, t in upd.loss_module.device_scalars.items()})
         if episode_stats is not None:
             ret, length, n = episode_stats.sums.tolist()
             if n > 0:

@@ -356,29 +356,8 @@ def latch_initial_entropy(m, batch) -> None:
 
 
 def trpl_launch(m, loc, sigma, value, batch, adv_stats, sums=None, maxes=None, defer_fold=False, adv_local=False, beta=None):
-    """One launch of the fused kernel on detached inputs: rank-local (sums, maxes) and the gradients of the (1/B_global-scaled)
-    losses with respect to loc, sigma and value.  ``defer_fold``: see ops.trpl_fwd_bwd (``sums`` comes back as the folding callable).
-    ``adv_local`` (one rank): the advantage statistics are summed inside the kernel; ``value=None``: actor-only (the critic's share of
-    the loss comes from ``value_loss`` on the critic's lane).  A PPO loss module (``m.algorithm == "ppo"``) takes the same launch in
-    its PPO mode (ppo.ppo_launch), a KL-penalty PPO module (``"kl_ppo"``) in its KL-penalty mode (klpen.klpen_launch): same slots, same
-    returns.  With entropy control (``entropy_active(m)``) the launch is the one with
-    the entropy stage and reads its bound from ``beta`` (device float64[1]; default: the loss module's own buffer)."""
-    if getattr(m, "algorithm", "trpl") == "ppo":
-        from .ppo import ppo_launch
-        return ppo_launch(m, loc, sigma, value, batch, adv_stats, sums=sums, maxes=maxes, defer_fold=defer_fold, adv_local=adv_local)
-    if getattr(m, "algorithm", "trpl") == "kl_ppo":
-        from .klpen import klpen_launch
-        return klpen_launch(m, loc, sigma, value, batch, adv_stats, sums=sums, maxes=maxes, defer_fold=defer_fold, adv_local=adv_local)
-    p = m.projection
-    B = loc.shape[0]
-    sums, maxes, dloc, dsigma, dvalue, _, _ = ops.trpl_fwd_bwd(
-        loc.detach(), sigma.detach(), batch, value.detach() if value is not None else None, mean_bound=p.mean_bound,
-        cov_bound=p.cov_bound, trust_region_coeff=p.trust_region_coeff,
-        entropy_coef=m.entropy_coef if m.entropy_bonus else 0.0, critic_coef=m.critic_coef,
-        clip_value=float(m.clip_value) if m.clip_value is not None else 0.0, global_batch=B * m.world_size, adv_stats=adv_stats,
-        sums=sums, maxes=maxes, proj_type=getattr(p, "proj_code", 0), defer_fold=defer_fold, adv_local=adv_local,
-        **(dict(ent_mode=p.entropy_mode, ent_beta=beta if beta is not None else m.entropy_beta(loc.device)) if entropy_active(m) else {}))
-    return sums, maxes, dloc, dsigma, dvalue
+    """``m.launch(...)``: one launch of the fused kernel in the loss module's own mode (FusedLoss.launch)."""
+    return m.launch(loc, sigma, value, batch, adv_stats, sums=sums, maxes=maxes, defer_fold=defer_fold, adv_local=adv_local, beta=beta)
 
 
 def value_loss(m, value, batch):
@@ -397,17 +376,9 @@ def value_loss(m, value, batch):
 
 
 def report_dict(o, m=None):
-    """The 14-float output of grl_trpl_report / grl_fold_adam_report as (actor loss, metrics dict of views); the PPO loss module
-    ``m`` reports its own keys (ppo.report_dict), the KL-penalty PPO module likewise (klpen.report_dict)."""
-    if getattr(m, "algorithm", "trpl") == "ppo":
-        from .ppo import report_dict as ppo_report_dict
-        return ppo_report_dict(o, m)
-    if getattr(m, "algorithm", "trpl") == "kl_ppo":
-        from .klpen import report_dict as klpen_report_dict
-        return klpen_report_dict(o, m)
-    return o[0], {"loss_trust_region": o[2], "loss_entropy": o[3], "ESS": o[4], "kl": o[5], "constraint": o[13], "mean_constraint": o[6],
-                  "mean_constraint_max": o[7], "cov_constraint": o[8], "cov_constraint_max": o[9], "entropy": o[10],
-                  "entropy_diff": o[11], "loss_objective_value": o[12]}
+    """The 14-float output of grl_trpl_report / grl_fold_adam_report / the record reports as (actor loss, metrics dict of views) under the
+    keys of loss module ``m`` (its ``report_dict``); without a module: TRPL's."""
+    return (TRPLLoss if m is None else m).report_dict(o)
 
 
 def report_critic(o):
@@ -487,7 +458,101 @@ def _unwrap(m, attr):
     return m
 
 
-class TRPLLoss(_LossBase):
+class FusedLoss(_LossBase):
+    """What the three objectives of the fused loss kernel (TRPLLoss, ppo.ClipPPOLoss2, klpen.KLPENPPOLoss) share: the two networks dug out
+    of their torchrl wrappers, the coefficients, the process group, the tail of ``forward`` -- and the interface ``PolicyUpdater`` and the
+    rollout driver talk to, so that neither asks which objective it is:
+      ``launch``          one launch of the kernel in the objective's mode;
+      ``report_dict``     the objective's keys into the 14-float report;
+      ``check_batch``     what the objective needs of a minibatch beyond the common keys;
+      ``after_report``    what it launches behind a step's report;
+      ``keeps_report``    must the report buffer outlive the tail launch that writes it (``after_report`` reads it)?
+      ``device_scalars``  name -> one-element device tensor that the recorded launches read from (or write to) the module itself."""
+    algorithm = None
+    clip_value = None
+    keeps_report = False
+
+    def __init__(self, actor_network, critic_network, *, entropy_bonus, entropy_coef, critic_coef, normalize_advantage, in_features,
+                 critic_in_features, group):
+        super().__init__()
+        self.actor_network, self.critic_network = _unwrap(actor_network, "forward_diag"), _unwrap(critic_network, "_network1")
+        self.entropy_bonus, self.entropy_coef, self.critic_coef = bool(entropy_bonus), float(entropy_coef), float(critic_coef)
+        self.normalize_advantage = normalize_advantage
+        # tensordict keys handed POSITIONALLY to the actor / the critic (the in_keys of their TensorDictModules,
+        # utils_algo_graph.py:113-116,160-176).  They may differ: config 1 feeds its transformer actor the normalised vectors in the
+        # raw-vector slots (configs/rigid_insertion_multi_transformer_trpl_cfg.yaml:88-94) while the critic reads the raw ones.
+        self.in_features = list(in_features or self.actor_network.hyper_data.spec.in_features)
+        self.critic_in_features = list(critic_in_features or self.in_features)
+        self.group = group
+        self._global_steps = 0
+
+    @property
+    def world_size(self):
+        if self.group is None:
+            return 1
+        import torch.distributed as dist
+        return dist.get_world_size(self.group)
+
+    @property
+    def device_scalars(self) -> Dict[str, torch.Tensor]:
+        return {}
+
+    def check_batch(self, b) -> None:
+        pass
+
+    def after_report(self, o14) -> None:
+        pass
+
+    def launch(self, loc, sigma, value, batch, adv_stats, *, sums=None, maxes=None, defer_fold=False, adv_local=False, beta=None):
+        """One launch of the fused kernel on detached inputs: rank-local (sums, maxes) and the gradients of the (1/B_global-scaled) losses
+        with respect to loc, sigma and value, -> (sums, maxes, dloc, dsigma, dvalue); the slots and sums have one layout in every mode
+        (columns a mode does not produce are zero).  ``defer_fold``: see ops.trpl_fwd_bwd (``sums`` comes back as the folding callable).
+        ``adv_local`` (one rank): the advantage statistics are summed inside the kernel; ``value=None``: actor-only (the critic's share of
+        the loss comes from ``value_loss`` on the critic's lane).  ``beta``: TRPL with entropy control only (TRPLLoss.launch)."""
+        raise NotImplementedError
+
+    def report_dict(self, o14):
+        """The 14-float report as (actor loss, metrics dict of views): the keys the objective's ``forward`` sets besides loss_objective
+        and loss_critic, plus ``loss_objective_value``."""
+        raise NotImplementedError
+
+    def _launch_args(self, loc, sigma, value, batch, adv_stats, sums, maxes, defer_fold, adv_local):
+        """The positional and keyword arguments every ``ops.*_fwd_bwd`` takes, from this module's coefficients."""
+        return ((loc.detach(), sigma.detach(), batch, value.detach() if value is not None else None),
+                dict(entropy_coef=self.entropy_coef if self.entropy_bonus else 0.0, critic_coef=self.critic_coef,
+                     clip_value=float(self.clip_value) if self.clip_value is not None else 0.0,
+                     global_batch=loc.shape[0] * self.world_size, adv_stats=adv_stats, sums=sums, maxes=maxes, defer_fold=defer_fold,
+                     adv_local=adv_local))
+
+    def _networks(self, b):
+        """(loc, sigma, value) of the two networks on the minibatch ``b``; value None without a critic term."""
+        loc, sigma = self.actor_network.forward_diag(*[b[k] for k in self.in_features], train=True)
+        return loc, sigma, self.critic_network(*[b[k] for k in self.critic_in_features]) if self.critic_coef else None
+
+    def _ppo_out(self, actor, critic, mt, first=(), last=()):
+        """The loss dict of the two PPO objectives: ``loss_objective`` (value = objective; gradient = d(actor loss)), the metrics ``first``,
+        entropy / loss_entropy with ``entropy_bonus``, loss_critic with a critic term, the metrics ``last``."""
+        out = {"loss_objective": actor - mt["loss_entropy"] if self.entropy_bonus else actor, **{k: mt[k] for k in first}}
+        if self.entropy_bonus:
+            out.update(entropy=mt["entropy"], loss_entropy=mt["loss_entropy"])
+        if self.critic_coef:
+            out["loss_critic"] = critic
+        out.update({k: mt[k] for k in last})
+        return out
+
+    @staticmethod
+    def _loss_output(out, loc, sigma, value):
+        """The return value of ``forward``: a TensorDict of the loss terms (the reference's return type, trpl.py:302) carrying the networks'
+        outputs as ``_grl_outputs``, or -- without ``tensordict`` -- a :class:`LossDict` with them under loc / sigma / state_value."""
+        extra = {"loc": loc, "sigma": sigma, "state_value": value}
+        if _TensorDict is not None:
+            td = _TensorDict(out, [])
+            td.__dict__["_grl_outputs"] = extra
+            return td
+        return LossDict(out, **extra)
+
+
+class TRPLLoss(FusedLoss):
     """trpl.py:105-321.  ``actor_network`` is a GNNGaussianPolicyDiag (the reference digs the same module out of the
     ProbabilisticActor, trpl.py:243: ``actor_network.get_submodule("0").module`` is tried first, so a ProbabilisticActor wrapping
     the policy is accepted too); ``critic_network`` a GNNVFNet/BaseCritic (or a ValueOperator around one).
@@ -503,37 +568,20 @@ class TRPLLoss(_LossBase):
                  samples_mc_entropy=1, entropy_coef=0.01, critic_coef=1.0, trust_region_coef=1.0, loss_critic_type="l2",
                  normalize_advantage=True, gamma=None, separate_losses=False, clip_value=None, in_features=None, group=None,
                  critic_in_features=None, entropy_control=False, **kwargs):
-        super().__init__()
         if loss_critic_type != "l2":
             raise NotImplementedError("loss_critic_type is l2 in configs/algorithm/objective/trpl.yaml:12")
-        actor_network = _unwrap(actor_network, "forward_diag")
-        critic_network = _unwrap(critic_network, "_network1")
         # ``entropy_control=True`` (opt-in): a layer with an entropy schedule is accepted and its entropy projection runs inside the fused
         # launch, the bound of update ``_global_steps`` read from device memory; without a schedule the flag changes nothing
-        self.entropy_control = bool(entropy_control)
-        self._entropy_beta = None
-        if getattr(projection, "entropy_schedule_type", None) and not self.entropy_control:
+        if getattr(projection, "entropy_schedule_type", None) and not entropy_control:
             raise NotImplementedError("an entropy schedule (base_projection_layer.py:266-283) is not applied by the fused update kernel; the "
                                       "projection layer offers it on its own (KLProjectionLayer.entropy_projection / __call__); pass "
                                       "entropy_control=True to run it inside the fused launch")
-        self.actor_network, self.critic_network, self.projection = actor_network, critic_network, projection
-        self.trust_region_coef = trust_region_coef
-        self.entropy_bonus, self.entropy_coef, self.critic_coef = entropy_bonus, float(entropy_coef), float(critic_coef)
-        self.normalize_advantage, self.clip_value = normalize_advantage, clip_value
-        # tensordict keys handed POSITIONALLY to the actor / the critic (the in_keys of their TensorDictModules,
-        # utils_algo_graph.py:113-116,160-176).  They may differ: config 1 feeds its transformer actor the normalised vectors in the
-        # raw-vector slots (configs/rigid_insertion_multi_transformer_trpl_cfg.yaml:88-94) while the critic reads the raw ones.
-        self.in_features = list(in_features or actor_network.hyper_data.spec.in_features)
-        self.critic_in_features = list(critic_in_features or self.in_features)
-        self.group = group
-        self._global_steps = 0
-
-    @property
-    def world_size(self):
-        if self.group is None:
-            return 1
-        import torch.distributed as dist
-        return dist.get_world_size(self.group)
+        super().__init__(actor_network, critic_network, entropy_bonus=entropy_bonus, entropy_coef=entropy_coef, critic_coef=critic_coef,
+                         normalize_advantage=normalize_advantage, in_features=in_features, critic_in_features=critic_in_features,
+                         group=group)
+        self.entropy_control = bool(entropy_control)
+        self._entropy_beta = None
+        self.projection, self.trust_region_coef, self.clip_value = projection, trust_region_coef, clip_value
 
     def entropy_beta(self, device):
         """The loss module's own one-element device buffer (float64) of the entropy bound: what the eager ``forward`` writes and its launch
@@ -552,25 +600,32 @@ class TRPLLoss(_LossBase):
         return keys + ["ESS", "kl", "constraint", "mean_constraint", "mean_constraint_max", "cov_constraint", "cov_constraint_max",
                        "entropy_diff"]
 
+    def launch(self, loc, sigma, value, batch, adv_stats, *, sums=None, maxes=None, defer_fold=False, adv_local=False, beta=None):
+        """FusedLoss.launch in the projection's mode.  With entropy control (``entropy_active``) the launch is the one with the entropy
+        stage and reads its bound from ``beta`` (device float64[1]; default: the loss module's own buffer)."""
+        p = self.projection
+        args, kw = self._launch_args(loc, sigma, value, batch, adv_stats, sums, maxes, defer_fold, adv_local)
+        if entropy_active(self):
+            kw.update(ent_mode=p.entropy_mode, ent_beta=beta if beta is not None else self.entropy_beta(loc.device))
+        return ops.trpl_fwd_bwd(*args, mean_bound=p.mean_bound, cov_bound=p.cov_bound, trust_region_coeff=p.trust_region_coeff,
+                                proj_type=getattr(p, "proj_code", 0), **kw)[:5]
+
+    @staticmethod
+    def report_dict(o):
+        return o[0], {"loss_trust_region": o[2], "loss_entropy": o[3], "ESS": o[4], "kl": o[5], "constraint": o[13], "mean_constraint": o[6],
+                      "mean_constraint_max": o[7], "cov_constraint": o[8], "cov_constraint_max": o[9], "entropy": o[10],
+                      "entropy_diff": o[11], "loss_objective_value": o[12]}
+
     def forward(self, tensordict):
         b = _as_batch(tensordict, self.in_features + self.critic_in_features)
         if "var" not in b:
             b["var"] = b["covariance_matrix"].diagonal(dim1=-2, dim2=-1).contiguous()
-        obs = [b[k] for k in self.in_features]
-        loc, sigma = self.actor_network.forward_diag(*obs, train=True)
-        value = self.critic_network(*[b[k] for k in self.critic_in_features]) if self.critic_coef else None
+        loc, sigma, value = self._networks(b)
         if entropy_active(self):   # the bound of update ``_global_steps`` (train.py:275: the count before the update), stream-ordered
             latch_initial_entropy(self, b)
             ops.write_doubles(self.entropy_beta(loc.device), self.projection.entropy_bounds([self._global_steps]))
         actor, critic, mt = _run_trpl(self, loc, sigma, value, b)
-        out = {
-            "loss_objective": actor - (mt["loss_trust_region"] + mt["loss_entropy"]),  # value = objective; gradient = d(actor loss)
-            "loss_critic": critic, "loc": loc, "sigma": sigma, "state_value": value,
-        }
+        # loss_objective: value = objective; gradient = d(actor loss)
+        out = {"loss_objective": actor - (mt["loss_trust_region"] + mt["loss_entropy"]), "loss_critic": critic}
         out.update({k: v for k, v in mt.items() if k != "loss_objective_value"})
-        if _TensorDict is not None:   # the reference's return type (trpl.py:302)
-            extra = {k: out.pop(k) for k in ("loc", "sigma", "state_value")}
-            td = _TensorDict(out, [])
-            td.__dict__["_grl_outputs"] = extra
-            return td
-        return LossDict(out)
+        return self._loss_output(out, loc, sigma, value)

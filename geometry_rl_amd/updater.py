@@ -241,10 +241,9 @@ class PolicyUpdater:
     max_norm = property(lambda self: self._hyper["max_norm"], lambda self, v: self._set_hyper("max_norm", float(v)))
 
     def _loss_storage(self):
-        """Device storage the recorded launches read from (and, beta, write to) the loss module itself: PPO's clip_epsilon, KL-penalty
-        PPO's beta; None where the module has neither."""
-        ptrs = tuple(t.data_ptr() for t in (getattr(self.loss_module, name, None) for name in ("clip_epsilon", "beta")) if torch.is_tensor(t))
-        return ptrs or None
+        """Device storage the recorded launches read from (and, KL-penalty PPO's beta, write to) the loss module itself
+        (``loss_module.device_scalars``); None where the module has none."""
+        return tuple(t.data_ptr() for t in self.loss_module.device_scalars.values()) or None
 
     def _check_loss_storage(self):
         """A loss buffer REPLACED by another tensor (not written in place) drops the recorded programs: they read the old storage."""
@@ -252,13 +251,6 @@ class PolicyUpdater:
         if ptr != self._loss_ptr:
             self._program, self._epoch = None, None
         self._loss_ptr = ptr
-
-    def _klpen_adapt(self, o14):
-        """KL-penalty PPO: beta <- beta * increment / decrement from the step's report ``o14``, on the current stream -- behind the tail
-        that wrote the report, ahead of the next step's loss launch (no-op for the other losses)."""
-        if getattr(self.loss_module, "algorithm", "trpl") == "kl_ppo":
-            from .klpen import klpen_adapt
-            klpen_adapt(self.loss_module, o14)
 
     def _entropy_prepare(self, batch, n_steps: int = 1):
         """TRPL with entropy control: latch the layer's initial entropy at the first update (from ``batch``; data parallel: the global
@@ -292,9 +284,9 @@ class PolicyUpdater:
 
     def stats_read(self) -> Dict[str, float]:
         """The fp64 means of every reported value over the updates since ``stats_reset()`` as Python floats, under the loss module's own
-        key names (``loss_objective``, ``loss_critic``, then the keys of ``trpl.report_dict`` / ``ppo.report_dict`` / ``klpen.report_dict``), and ``"updates"``,
+        key names (``loss_objective``, ``loss_critic``, then the keys of the loss module's ``report_dict``), and ``"updates"``,
         their number.  Joins the critic's lane and synchronises ONCE (two small device-to-host copies)."""
-        from .trpl import report_critic, report_dict
+        from .trpl import report_critic
         if not self.track_stats:
             raise RuntimeError("PolicyUpdater(track_stats=True) keeps the running sums; this updater was built without them")
         if self._cstream is not None:
@@ -310,7 +302,7 @@ class PolicyUpdater:
             raise RuntimeError(f"the actor's lane counted {n} updates, the critic's {n_c}: the running sums do not belong to one sequence")
         out = {"updates": n}
         if n:
-            _, mt = report_dict(a[:14] / n, self.loss_module)
+            _, mt = self.loss_module.report_dict(a[:14] / n)
             mt = {k: float(v) for k, v in mt.items()}
             out.update(loss_objective=mt.pop("loss_objective_value"), loss_critic=float(critic_sum / n), **mt)
         return out
@@ -379,8 +371,7 @@ class PolicyUpdater:
         if not self._fold_overwrite and zero is not None:
             zero.zero_()
         b = dict(batch)
-        if getattr(m, "algorithm", "trpl") == "kl_ppo" and ("loc" not in b or ("var" not in b and "covariance_matrix" not in b)):
-            raise ValueError("KLPENPPOLoss needs the old distribution in the minibatch: keys 'loc' and 'var' (or 'covariance_matrix')")
+        m.check_batch(b)
         if "var" not in b:
             b["var"] = b["covariance_matrix"].diagonal(dim1=-2, dim2=-1).contiguous()
         st["b"] = b
@@ -392,14 +383,13 @@ class PolicyUpdater:
     def _actor_head(self, st, adv, adv_local):
         """Actor forward + fused loss kernel (actor terms only) + actor backward; -> the loss kernel's fold handle.  The caller has armed the
         fold queue (ops.deferred_folds): the leaf-gradient folds of this backward are queued and executed by one launch at the lane's end."""
-        from .trpl import trpl_launch
         m, actor = self.loss_module, self.loss_module.actor_network
         zw = st["zw"]
         sums, maxes = zw[10:22], zw[22:23].view(torch.int32)
         loc, sigma = actor.forward_diag(*st["obs"], train=True)
         with torch.no_grad():
-            fold_, _mx, dloc, dsigma, _ = trpl_launch(m, loc, sigma, None, st["b"], adv, sums=sums, maxes=maxes, defer_fold=True,
-                                                      adv_local=adv_local, beta=st["beta"])
+            fold_, _mx, dloc, dsigma, _ = m.launch(loc, sigma, None, st["b"], adv, sums=sums, maxes=maxes, defer_fold=True,
+                                                   adv_local=adv_local, beta=st["beta"])
         st.update(loc=loc.detach(), sigma=sigma.detach())
         # the lift's and the fiber basis' backward launches only feed the tail's fold: the first of the two waits for the other and they
         # share ONE launch (ops._tail_pre_offer)
@@ -424,7 +414,7 @@ class PolicyUpdater:
     def _plan_one_stream(self, batch, st):
         """One rank, one stream: critic forward, actor forward, the fused loss kernel WITH the value terms, both backward passes, one fold,
         the optimizer step(s), reported values -- four closures on the caller's stream (one hipGraph when recorded)."""
-        from .trpl import adv_stats_local, loss_values, trpl_launch
+        from .trpl import adv_stats_local, loss_values
         m = self.loss_module
         actor, vf = m.actor_network, m.critic_network._network1
         leaves = self._critic_leaves()
@@ -453,8 +443,8 @@ class PolicyUpdater:
                 loc, sigma = actor.forward_diag(*st["obs"], train=True)
                 with torch.no_grad():
                     zw = st["zw"]
-                    sums, maxes, dloc, dsigma, dvalue = trpl_launch(m, loc, sigma, value, st["b"], st["adv"], sums=zw[10:22],
-                                                                    maxes=zw[22:23].view(torch.int32), beta=st["beta"])
+                    sums, maxes, dloc, dsigma, dvalue = m.launch(loc, sigma, value, st["b"], st["adv"], sums=zw[10:22],
+                                                                 maxes=zw[22:23].view(torch.int32), beta=st["beta"])
                 torch.autograd.backward([loc, sigma], [dloc, dsigma])
                 with torch.no_grad():
                     pipe.bwd3(dvalue)
@@ -472,11 +462,10 @@ class PolicyUpdater:
                 # clipping their two Adam steps are ONE launch over the flat buffer (element-wise: the same numbers)
                 for i_, (lo, hi) in enumerate(((0, na), (na, n)) if self.clip else ((0, n),)):
                     self._adam(st, lo, hi, i_)
-                klpen = getattr(m, "algorithm", "trpl") == "kl_ppo"
-                o14 = torch.empty(14, device=self.flat.device, dtype=torch.float32) if (self.track_stats or klpen) else None
+                o14 = torch.empty(14, device=self.flat.device, dtype=torch.float32) if (self.track_stats or m.keeps_report) else None
                 a_loss, c_loss, mt = loss_values(m, st["sums"], st["maxes"], out=o14)
                 st["lv_main"], st["c_loss"] = (a_loss, mt), c_loss
-                self._klpen_adapt(o14)
+                m.after_report(o14)
                 self._stats_add(o14, self.stats_actor)   # (one call: the report carries the critic loss)
 
         return [Entry("run", s0), Entry("run", s1), Entry("run", s2), Entry("run", s3), Entry("run_host", lambda: self._finish(st))]
@@ -575,7 +564,7 @@ class PolicyUpdater:
         Actor and critic share no parameter and no intermediate (train.py:279-316 runs two backward passes and two optimizers); the lanes
         are forked at the step's start and joined at its end.  Each lane zeroes ITS OWN slice of the flat gradient when the folds
         accumulate (attention gate: torch's AccumulateGrad adds into .grad)."""
-        from .trpl import report_dict, report_values
+        from .trpl import report_values
         m = self.loss_module
         ow = self._fold_overwrite
         na, n_all = self.n_actor, self.flat.numel()
@@ -605,17 +594,17 @@ class PolicyUpdater:
                                                     dict(slots=fold_.slots, batch=fold_.batch, sums=fold_.sums, maxes=fold_.maxes,
                                                          ent_coef=ent, out14=o14), signal=(self.lane_flag, self.step_dev) if (gate and ops.SIGNAL_IN_KERNEL) else None)
                         if done:
-                            a_loss, mt = report_dict(o14, m)
+                            a_loss, mt = m.report_dict(o14)
                     if not done:
                         ops.flush_deferred_grads(overwrite=ow)
                         self._adam(st, 0, na, 0)
-                        keep = self.track_stats or getattr(m, "algorithm", "trpl") == "kl_ppo"   # (the report is read again behind this launch)
+                        keep = self.track_stats or m.keeps_report   # (the report is read again behind this launch)
                         if keep and o14 is None:
                             o14 = torch.empty(14, device=self.flat.device, dtype=torch.float32)
                         a_loss, _c, mt = report_values(m, fold_.slots, fold_.batch, fold_.sums, fold_.maxes, out=o14 if keep else None)
             if gate and not (done and ops.SIGNAL_IN_KERNEL):   # ... and once more at the lane's end, whatever happened above (an actor without an edge convolution; a
                 self._signal_lane()                            # signal that carried a stale count): the critic's lane can be late, it can never be stuck
-            self._klpen_adapt(o14)                             # (KL-penalty PPO: beta for the NEXT step, from this step's report)
+            m.after_report(o14)                                # (KL-penalty PPO: beta for the NEXT step, from this step's report)
             self._stats_add(o14, self.stats_actor)             # (track_stats: the lane's last launch, whichever tail wrote the report)
             st.update(sums=fold_.sums, maxes=fold_.maxes, lv_main=(a_loss, mt))
 
@@ -647,7 +636,7 @@ class PolicyUpdater:
                          behind it).  GRL_DP_ONE_COMM=1: both lanes on ``group`` (the documented fallback; same results).
         Every rank enqueues the SAME sequence of collectives per communicator, in the order of this list (host order = enqueue order);
         tests/test_dp_program_order.py checks that property of the program itself."""
-        from .trpl import adv_stats_local, report_dict
+        from .trpl import adv_stats_local
         m = self.loss_module
         world = m.world_size
         ow = self._fold_overwrite
@@ -694,7 +683,7 @@ class PolicyUpdater:
 
         # (the reported values live in ONE buffer per recorded program: the tail may run as an eager launch behind the collective, below)
         o14 = torch.empty(14, device=self.flat.device, dtype=torch.float32)
-        st["lv_main"] = report_dict(o14, m)
+        st["lv_main"] = m.report_dict(o14)
 
         def p_tail():   # behind the lane's collective: Adam on the reduced gradient, reported values of the delivered records
             with torch.no_grad():
@@ -706,7 +695,7 @@ class PolicyUpdater:
                     hip.call("grl_adam_report_record_pairs", self.flat[:na], self.gflat[:na], self.exp_avg[:na], self.exp_avg_sq[:na], na,
                              self.lr_dev, float(self.betas[0]), float(self.betas[1]), float(self.eps), self.step_dev,
                              self.gbuf[:self._rec], world, st["sums"], st["maxes"], float(ent), o14)
-                self._klpen_adapt(o14)                   # (KL-penalty PPO: every rank adapts on the GLOBAL mean KL -- beta stays equal across the ranks)
+                m.after_report(o14)                      # (KL-penalty PPO: every rank adapts on the GLOBAL mean KL -- beta stays equal across the ranks)
                 self._stats_add(o14, self.stats_actor)   # (the GLOBAL values: every rank adds the same numbers, no collective)
 
         q_fwd1, q_fwd2, q_fwd3, q_bwd2, bwd1 = self._critic_stages(batch, st, world, gate_dp)
