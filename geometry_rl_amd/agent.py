@@ -14,7 +14,8 @@ from .policy import BaseCritic, DeepSets, GNNGaussianPolicyDiag, GNNVFNet
 from .klpen import KLPENPPOLoss
 from .ppo import ClipPPOLoss2
 from .trpl import KLProjectionLayer, TRPLLoss
-from .updater import PolicyUpdater, _no_gc_while_capturing  # noqa: F401  (re-exported: the driver lives in updater.py)
+from .program import _no_gc_while_capturing  # noqa: F401  (re-exported)
+from .updater import PolicyUpdater  # noqa: F401  (re-exported: the driver lives in updater.py)
 
 
 @dataclass

@@ -26,6 +26,7 @@ from typing import Dict, Iterator, Optional
 import torch
 
 from . import agent as _agent, hip as _hip, updater as _updater
+from .program import capture
 
 PPO_KEYS = ("action", "loc", "var", "sample_log_prob", "state_value", "advantage", "value_target")
 
@@ -175,38 +176,34 @@ class RolloutDriver:
         idx = torch.stack([i.reshape(-1) for i in idxs])                           # [n_mb, frames per rank]
         a = buf.flat("advantage").reshape(-1).double()[idx]
         s = torch.stack([a.sum(1), (a * a).sum(1)], dim=1).contiguous()
-        upd._reduce("sum", s, "advantage_stats_epoch")
+        upd.all_reduce_sum(s, "advantage_stats_epoch")
         if "adv_stats" not in buf.data:
             buf.data["adv_stats"] = torch.zeros(buf.N, buf.T, 2, device=s.device, dtype=torch.float64)
         buf.flat("adv_stats")[idx.reshape(-1)] = s.repeat_interleave(idx.shape[1], dim=0)
 
-    def minibatches(self, buf: RolloutBuffer) -> Iterator[torch.Tensor]:
+    def epochs(self, buf: RolloutBuffer) -> Iterator[list]:
+        """Per PPO epoch the list of its minibatches' index tensors, their advantage statistics published (data parallel)."""
         dev = next(iter(buf.data.values())).device
         for _ in range(self.ppo_epochs):
             idxs = self.epoch_minibatches(buf.N, buf.T, dev)
             self.publish_advantage_stats(buf, idxs)
-            for idx in idxs:
-                yield idx
+            yield idxs
+
+    def minibatches(self, buf: RolloutBuffer) -> Iterator[torch.Tensor]:
+        for idxs in self.epochs(buf):
+            yield from idxs
 
     def run(self, buf: RolloutBuffer, next_last: Optional[Dict[str, torch.Tensor]] = None):
         """One rollout pass: [GAE] + ppo_epochs * T policy updates.  Returns the loss dict of the last update."""
         if next_last is not None:
             self.compute_advantages(buf, next_last)
-        if getattr(self.updater, "track_stats", False):
+        if self.updater.track_stats:
             self.updater.stats_reset()   # (the means iteration_log reports are those of THIS pass)
         out = None
-        dev = next(iter(buf.data.values())).device
-        for _ in range(self.ppo_epochs):
-            idxs = self.epoch_minibatches(buf.N, buf.T, dev)
-            self.publish_advantage_stats(buf, idxs)
-            if idxs and all(i.numel() == idxs[0].numel() for i in idxs) and hasattr(self.updater, "run_minibatches"):
-                # the epoch's minibatches in one call: one rank with recorded lanes takes several steps per launch (PolicyUpdater.run_minibatches)
+        for idxs in self.epochs(buf):
+            if idxs:   # one call per epoch (epoch_minibatches cuts one size): one rank with recorded lanes takes several steps per launch
                 out = self.updater.run_minibatches(buf, torch.stack([i.reshape(-1) for i in idxs]))
-            else:
-                for idx in idxs:
-                    out = self.updater.step_from(buf, idx)
         return out
-
 
     def iteration_log(self, buf: RolloutBuffer, episode_stats: Optional["EpisodeStats"] = None) -> Dict[str, float]:
         """The ``log_info`` of one training iteration (train.py:237-246, 318-333) after ``run``, as Python floats: ``train/<key>`` = the mean
@@ -250,13 +247,12 @@ class PolicyActor:
         self._graph, self._static, self._out, self._calls = None, None, None, 0
 
     def _pass(self, obs):
-        from . import hip
         loc, sigma = self.policy.forward_diag(*[obs[k] for k in self.spec.in_features], train=self.train)
         B, A = loc.shape
         eps = torch.zeros_like(loc) if self.deterministic else torch.randn(loc.shape, device=loc.device, dtype=loc.dtype, generator=self.gen)
         action, var = torch.empty_like(loc), torch.empty_like(loc)
         logp = torch.empty(B, device=loc.device, dtype=torch.float32)
-        hip.call("grl_gaussian_sample", loc.contiguous(), sigma.contiguous(), eps, action, logp, var, B, A)
+        _hip.call("grl_gaussian_sample", loc.contiguous(), sigma.contiguous(), eps, action, logp, var, B, A)
         return {"loc": loc, "var": var, "action": action, "sample_log_prob": logp}
 
     @torch.no_grad()
@@ -273,7 +269,7 @@ class PolicyActor:
 
             def record():
                 self._out = self._pass(self._static)
-            self._graph = _updater.capture([record], generator=self.gen)
+            self._graph = capture([record], generator=self.gen)
         for k in self.spec.in_features:
             self._static[k].copy_(obs[k])
         self._graph.replay()

@@ -1,62 +1,16 @@
 """The policy-update driver that replaces the inner loop of ``examples/torchrl/train.py:258-316``: ``PolicyUpdater`` lays one update out
-as a program of ``Entry`` objects, runs it eagerly or records it into hipGraphs (``capture``) and replays it."""
+as a program of ``Entry`` objects and runs it eagerly or recorded into hipGraphs (program.py records and issues programs)."""
 import contextlib
 import ctypes
 import os
-from typing import Dict, NamedTuple, Optional
+from typing import Dict, Optional
 
 import torch
 
 from . import hip, ops
+from .program import Entry, capture, execute, record  # noqa: F401  (capture: re-exported, the collector-side actor's name for it)
 
 _CRITIC_GROUPS = {}   # (id of the actor lane's process group, its ranks) -> the critic lane's communicator
-
-
-class Entry(NamedTuple):
-    """One entry of a step's program.  "run" entries that follow each other on one lane are recorded into ONE hipGraph (a "graph" entry of the
-    recorded program); "sum" is an all-reduce of the tensor the getter returns, on the lane's communicator; "fork": the critic's lane waits
-    for the caller's stream, "join": the reverse; "run_host" is host-only bookkeeping (at every eager step; once, when a step is recorded)."""
-    kind: str                    # "run" | "graph" | "sum" | "fork" | "join" | "run_host"
-    item: object                 # closure | CUDAGraph | tensor getter | None
-    lane: str = "m"              # "m": the caller's stream, "s": the critic's
-    label: Optional[str] = None
-    eager: bool = False          # "run" only: issued as plain launches at every step, never recorded
-
-
-@contextlib.contextmanager
-def _no_gc_while_capturing():
-    """Python's cyclic collector must not run while a stream is capturing: if it frees an object that owns device resources -- the hipGraphs
-    or events of an updater that went out of use -- their destruction inside the capture is an error raised from a destructor, and the
-    process aborts (seen once in six runs of tests/test_gpu_rollout.py: "Fatal Python error: Aborted ... Garbage-collecting" under
-    _compile_epoch; this torch's ``torch.cuda.graph`` no longer collects on entry).  Garbage is collected BEFORE the capture, and the
-    collector is held for its duration."""
-    import gc
-    gc.collect()
-    was_enabled = gc.isenabled()
-    gc.disable()
-    try:
-        yield
-    finally:
-        if was_enabled:
-            gc.enable()
-
-
-def capture(fns, pool=None, generator=None, stream=None):
-    """Record the launches of the closures ``fns`` into one hipGraph (torch.cuda.CUDAGraph) and return it: captured on a side stream
-    (``stream``: a recorder of several graphs passes ONE, so that the graphs of a pool reuse each other's freed blocks) that waits for the
-    current stream and is waited for, with the collector held.  ``pool``: the allocator pool to share with an earlier graph;
-    ``generator``: a torch.Generator whose draws inside the graph advance with every replay."""
-    g = torch.cuda.CUDAGraph()
-    if generator is not None and hasattr(g, "register_generator_state"):
-        g.register_generator_state(generator)
-    side = stream if stream is not None else torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    # thread_local: background threads of the process (the collectives' watchdog) may keep issuing event queries
-    with _no_gc_while_capturing(), torch.cuda.graph(g, pool=pool, stream=side, capture_error_mode="thread_local"):
-        for fn in fns:
-            fn()
-    torch.cuda.current_stream().wait_stream(side)
-    return g
 
 
 def _job_arrays(jobs):
@@ -111,7 +65,6 @@ class PolicyUpdater:
         self.dp_gate_from_frames = int(os.environ.get("GRL_DP_GATE_FROM", "1024"))
         self.epoch_unroll_max_gated_frames = 64   # run_minibatches: the gated multi-step launch up to this many work-frames ...
         self.epoch_gated_from_frames = 3072       # ... and the gated per-step program from here on
-        self._epoch = None
         # which recorded form run_minibatches takes above 64 work-frames is measured once per size (_tune_form); False: the table
         self.autotune_form = True
         self.form_by_size, self.form_times = {}, {}
@@ -171,8 +124,7 @@ class PolicyUpdater:
             # workspaces are not capture-safe on this stack), so that step is issued eagerly -- it is the reference's CPU-sized
             # plumbing case (64 envs x 32 steps), not a throughput path
             self.use_graph, self.mode = False, "eager (stock-torch transformer actor: not recorded)"
-        self._static = None
-        self._program = None
+        self._drop_recordings()                    # (nothing is recorded yet: _program, _static, _epoch)
         self._eager_sizes = set()                  # minibatch sizes whose first, eager step has run (_step)
         self._cstream = None                       # the critic lane's stream, made when a program first needs it (_critic_stream)
         self._loss_ptr = self._loss_storage()      # (_check_loss_storage)
@@ -233,12 +185,16 @@ class PolicyUpdater:
     def _set_hyper(self, key, value):
         if self._hyper[key] != value:
             self._hyper[key] = value
-            self._program, self._epoch = None, None   # recorded launches carry the old scalar
+            self._drop_recordings()   # recorded launches carry the old scalar
 
     eps = property(lambda self: self._hyper["eps"], lambda self, v: self._set_hyper("eps", v))
     betas = property(lambda self: self._hyper["betas"], lambda self, v: self._set_hyper("betas", tuple(v)))
     clip = property(lambda self: self._hyper["clip"], lambda self, v: self._set_hyper("clip", bool(v)))
     max_norm = property(lambda self: self._hyper["max_norm"], lambda self, v: self._set_hyper("max_norm", float(v)))
+
+    def _drop_recordings(self):
+        """Forget the recorded step (with its static inputs) and the recorded multi-step launch: the next step / launch records again."""
+        self._program, self._static, self._epoch = None, None, None
 
     def _loss_storage(self):
         """Device storage the recorded launches read from (and, KL-penalty PPO's beta, write to) the loss module itself
@@ -249,7 +205,7 @@ class PolicyUpdater:
         """A loss buffer REPLACED by another tensor (not written in place) drops the recorded programs: they read the old storage."""
         ptr = self._loss_storage()
         if ptr != self._loss_ptr:
-            self._program, self._epoch = None, None
+            self._drop_recordings()
         self._loss_ptr = ptr
 
     def _entropy_prepare(self, batch, n_steps: int = 1):
@@ -289,8 +245,7 @@ class PolicyUpdater:
         from .trpl import report_critic
         if not self.track_stats:
             raise RuntimeError("PolicyUpdater(track_stats=True) keeps the running sums; this updater was built without them")
-        if self._cstream is not None:
-            torch.cuda.current_stream().wait_stream(self._cstream)
+        self.join_lanes()
         a, c = self.stats_actor.cpu(), self.stats_critic.cpu()
         n, n_c = int(a[14]), int(c[1])
         if self._stats_one_stream and n_c == 0:
@@ -378,7 +333,7 @@ class PolicyUpdater:
         st["obs"] = [b[k] for k in m.in_features]
         st["cobs"] = [b[k] for k in m.critic_in_features]
         st["zw"] = torch.empty(26, device=self.flat.device, dtype=torch.float64)
-        st.setdefault("beta", self.beta_table[0:1])   # (entropy control: the bound this step's loss launch reads; _compile_epoch sets entry j)
+        st.setdefault("beta", self.beta_table[0:1])   # (entropy control: the bound this step's loss launch reads; _epoch_entries sets entry j)
 
     def _actor_head(self, st, adv, adv_local):
         """Actor forward + fused loss kernel (actor terms only) + actor backward; -> the loss kernel's fold handle.  The caller has armed the
@@ -504,12 +459,16 @@ class PolicyUpdater:
             self._signal_lane()
         assert hd.bump_next is None, "the actor's feature launch did not take the step count"
 
-    def _critic_stages(self, cb, st, world, gate):
+    def _critic_wait(self):
+        """A gated critic lane's first launch: waits until the actor's lane has signalled THIS step (flag >= the lane's finished steps + 1)."""
+        hip.call("grl_wait_flag_ge", self.lane_flag, self.step_dev_c, 1, 200000)
+
+    def _critic_stages(self, cb, st, world):
         """The critic lane's stages as closures (fwd1, fwd2, fwd3, bwd2, bwd1), each free of host synchronisation: between two of them the
         whole-tensor LayerNorm sums are summed over the ranks (_plan_dp places the collectives; one rank runs the stages back to back).
         ``cb``: the batch the lane reads -- straight from it, the lane depends on nothing the actor's lane prepares, so it can be enqueued
-        first; ``gate``: the lane starts with a launch that waits until the actor's lane has signalled THIS step.  The caller arms the fold
-        queue around bwd1 (the only stage that emits leaf gradients) and appends its tail."""
+        first (a gated lane puts ``_critic_wait`` in front of them).  The caller arms the fold queue around bwd1 (the only stage that emits
+        leaf gradients) and appends its tail."""
         from .trpl import value_loss
         m = self.loss_module
         vf = m.critic_network._network1
@@ -518,11 +477,6 @@ class PolicyUpdater:
 
         @torch.no_grad()
         def fwd1():
-            if gate:   # flag >= the steps this lane has finished + 1
-                hip.call("grl_wait_flag_ge", self.lane_flag, self.step_dev_c, 1, 200000)
-            pre = st.pop("critic_pre", None)
-            if pre is not None:           # (epoch program: the lane's own minibatch gather)
-                pre()
             if not self._fold_overwrite:
                 self.gflat[na:].zero_()   # on THIS lane, in front of its folds (never from the actor's lane)
             vf.train(True)
@@ -552,7 +506,7 @@ class PolicyUpdater:
 
         return fwd1, fwd2, fwd3, bwd2, bwd1
 
-    def _plan_lanes(self, batch, st, cbatch=None, gate_override=None):
+    def _plan_lanes(self, batch, st):
         """One rank as a two-lane PROGRAM of single-stream graphs.  This HIP runtime replays a captured graph with two branches through
         the host (hipGraphLaunch returned after 2/3 of the DEVICE time of a forked step; tools/ubench/graph_branches.py) and every
         cross-branch edge costs a 6-11 us gap; a graph boundary on a lane costs ~15 us as well.  So each lane is ONE graph and the lanes
@@ -564,6 +518,17 @@ class PolicyUpdater:
         Actor and critic share no parameter and no intermediate (train.py:279-316 runs two backward passes and two optimizers); the lanes
         are forked at the step's start and joined at its end.  Each lane zeroes ITS OWN slice of the flat gradient when the folds
         accumulate (attention gate: torch's AccumulateGrad adds into .grad)."""
+        # Gate the critic's lane behind the actor's first edge convolution?  It pays where the critic then finishes inside the actor's FORWARD
+        # (its kernels cost the one-wave-per-SIMD backward launches far more than the forward ones: gated at the forward's END the step is 6 %
+        # slower): measured on rigid HEPi +1.1 % at 4096 frames, +3 % at 512, +1 % at 32, 0 at 2048, -1.5 % at 1024, where a forward of
+        # 0.35 ms is too short for it (profiles/r05_ab_critic_gate.txt, r05_ab_critic_gate_points.txt).  True (default) = that table.
+        frames = next(int(v.shape[0]) for v in batch.values() if torch.is_tensor(v))
+        actor_lane, critic_lane = self._lane_entries(batch, batch, st, self._gate_for(frames))
+        return [Entry("fork", None), *actor_lane, *critic_lane, Entry("join", None), Entry("run_host", lambda: self._finish(st))]
+
+    def _lane_entries(self, batch, cbatch, st, gate):
+        """The lanes of ``_plan_lanes`` as "run" entries -> (the actor's, reading ``batch``; the critic's, reading ``cbatch``: the gate's wait
+        when ``gate``, then the stages with the tail).  The multi-step launch puts each lane's gather in front of the lane's step."""
         from .trpl import report_values
         m = self.loss_module
         ow = self._fold_overwrite
@@ -572,12 +537,6 @@ class PolicyUpdater:
         # finished gradient norm before Adam)
         fuse_tail = not self.clip and ow
         self._stats_one_stream = False
-        # Gate the critic's lane behind the actor's first edge convolution?  It pays where the critic then finishes inside the actor's FORWARD
-        # (its kernels cost the one-wave-per-SIMD backward launches far more than the forward ones: gated at the forward's END the step is 6 %
-        # slower): measured on rigid HEPi +1.1 % at 4096 frames, +3 % at 512, +1 % at 32, 0 at 2048, -1.5 % at 1024, where a forward of
-        # 0.35 ms is too short for it (profiles/r05_ab_critic_gate.txt, r05_ab_critic_gate_points.txt).  True (default) = that table.
-        frames = next(int(v.shape[0]) for v in batch.values() if torch.is_tensor(v))
-        gate = self._gate_for(frames) if gate_override is None else bool(gate_override)
 
         def main_all():
             self._prep(batch, st, zero=self.gflat[:na])
@@ -608,8 +567,7 @@ class PolicyUpdater:
             self._stats_add(o14, self.stats_actor)             # (track_stats: the lane's last launch, whichever tail wrote the report)
             st.update(sums=fold_.sums, maxes=fold_.maxes, lv_main=(a_loss, mt))
 
-        # (the critic lane's inputs: the epoch program gives each lane a private copy)
-        stages = self._critic_stages(cbatch if cbatch is not None else batch, st, 1, gate)
+        stages = self._critic_stages(cbatch, st, 1)
 
         def critic_all():
             with ops.deferred_folds(), torch.no_grad():
@@ -620,9 +578,8 @@ class PolicyUpdater:
                     self._adam(st, na, n_all, 1, self.step_dev_c)
                 self._stats_add(st["c_loss"], self.stats_critic)
 
-        st["lanes"] = (main_all, critic_all)
-        return [Entry("fork", None), Entry("run", main_all), Entry("run", critic_all, "s"), Entry("join", None),
-                Entry("run_host", lambda: self._finish(st))]
+        wait = [Entry("run", self._critic_wait, "s", "critic_gate_wait")] if gate else []
+        return [Entry("run", main_all)], [*wait, Entry("run", critic_all, "s")]
 
     def _plan_dp(self, batch, st):
         """Several ranks: the same two lanes, graph segments between the collectives (which stay eager torch.distributed calls).
@@ -698,7 +655,8 @@ class PolicyUpdater:
                 m.after_report(o14)                      # (KL-penalty PPO: every rank adapts on the GLOBAL mean KL -- beta stays equal across the ranks)
                 self._stats_add(o14, self.stats_actor)   # (the GLOBAL values: every rank adds the same numbers, no collective)
 
-        q_fwd1, q_fwd2, q_fwd3, q_bwd2, bwd1 = self._critic_stages(batch, st, world, gate_dp)
+        q_fwd1, q_fwd2, q_fwd3, q_bwd2, bwd1 = self._critic_stages(batch, st, world)
+        q_wait = [Entry("run", self._critic_wait, S, "critic_gate_wait")] if gate_dp else []
 
         def q_bwd1():
             with ops.deferred_folds(), torch.no_grad():   # the critic's slabs are folded here, on its lane, into its slice of the flat gradient
@@ -717,7 +675,7 @@ class PolicyUpdater:
         # p_tail without clipping is ONE launch, cheaper issued eagerly than replayed as a one-node graph (a graph launch behind a collective
         # costs ~13 us of lane time, an eager kernel launch ~4; -1.5 % at 512 frames per rank)
         return [Entry("fork", None), *head_,
-                Entry("run", q_fwd1, S), Entry("sum", lambda: st["pipe"].stats1, S, "critic_ln1_fwd_stats"),
+                *q_wait, Entry("run", q_fwd1, S), Entry("sum", lambda: st["pipe"].stats1, S, "critic_ln1_fwd_stats"),
                 Entry("run", q_fwd2, S), Entry("sum", lambda: st["pipe"].stats2, S, "critic_ln2_fwd_stats"),
                 Entry("run", p_main),
                 Entry("sum", lambda: self.gbuf[:self._rec + na], "m", "flat_gradient_actor+loss_records"),
@@ -755,7 +713,6 @@ class PolicyUpdater:
                 except Exception:
                     prio = 0
             self._cstream = torch.cuda.Stream(priority=prio)
-            self._cstream_priority = prio
         return self._cstream
 
     # ``collective_log``: None, or {} to record -- per label a list of (start event, end event, payload bytes) on the lane's stream: how long
@@ -766,15 +723,13 @@ class PolicyUpdater:
         """Context manager: HIP events on the current stream around a collective / cross-lane wait when the log is on."""
         if self.collective_log is None or label is None:
             return contextlib.nullcontext()
-        upd = self
-
         @contextlib.contextmanager
         def span():
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             yield
             e1.record()
-            upd.collective_log.setdefault(label, []).append((e0, e1, nbytes))
+            self.collective_log.setdefault(label, []).append((e0, e1, nbytes))
         return span()
 
     def collective_summary(self, n_steps: int):
@@ -786,58 +741,30 @@ class PolicyUpdater:
             out[label] = {"per_step": len(recs) / max(1, n_steps), "mean_ms": sum(ms) / len(ms), "max_ms": max(ms), "bytes": recs[0][2]}
         return out
 
-    def _reduce(self, kind, t, label=None, lane="m"):
-        """A collective of the program: "sum" all-reduce of ``t`` on the lane's communicator (the critic's lane: ``group_c``)."""
+    def all_reduce_sum(self, t, label=None, lane="m"):
+        """The collective of the programs: "sum" all-reduce of ``t`` on the lane's communicator (the critic's lane: ``group_c``)."""
         import torch.distributed as dist
         if t is None:
             return
-        if kind != "sum":
-            raise ValueError(f"unknown program entry '{kind}'")
         group = self.group_c if (lane == "s" and self.group_c is not None) else self.group
-        with self._log_span(label or kind, t.numel() * t.element_size()):
+        with self._log_span(label or "sum", t.numel() * t.element_size()):
             if self._oneshot is not None and lane == "m" and t.data_ptr() == self._oneshot.payload.data_ptr() and t.numel() == self._oneshot.n:
                 self._oneshot.all_reduce()   # (GRL_DP_ONESHOT=1: in place, on this lane's stream; every rank enqueues it at this point of the program)
             else:
                 dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
 
-    def _compile(self, batch):
-        """Record the plan's segments into hipGraphs (adjacent segments without a reduction between them share one graph)."""
+    def _check_topology(self, batch, cbatch):
+        """One sync, before anything is captured: the cached topology fits the minibatch the actor's (``batch``) and the critic's lane read."""
         m = self.loss_module
-        # one sync, before anything is captured: the cached topology fits this minibatch
         m.actor_network.hyper_data.check_topology(*[batch[k] for k in m.in_features])
-        m.critic_network._network1.hyper_data.check_topology(*[batch[k] for k in m.critic_in_features])
+        m.critic_network._network1.hyper_data.check_topology(*[cbatch[k] for k in m.critic_in_features])
+
+    def _compile(self, batch):
+        """Record the step's program on static copies of the minibatch (adjacent "run" entries of a lane share one hipGraph)."""
+        self._check_topology(batch, batch)
         self._static = {k: v.clone() for k, v in batch.items() if torch.is_tensor(v)}
-        self._compile_one()
-
-    def _compile_one(self):
-        """One pass over the plan: "run" entries that follow each other on one lane are recorded into one hipGraph; anything else closes
-        the open group.  Eager runs and collectives are kept as they are; "run_host" entries run once, here."""
         st = self._st = {}
-        program, pools, cur = [], {}, []
-        side = torch.cuda.Stream()
-
-        def close():
-            if cur:
-                lane = cur[0].lane
-                # one allocator pool per lane: graphs of different lanes are replayed concurrently and must not share scratch memory
-                g = capture([e.item for e in cur], pool=pools.get(lane), stream=side)
-                pools[lane] = g.pool()
-                program.append(Entry("graph", g, lane))
-                cur.clear()
-
-        for e in self._plan(self._static, st):
-            if e.kind == "run" and not e.eager:
-                if cur and cur[0].lane != e.lane:
-                    close()
-                cur.append(e)
-                continue
-            close()
-            if e.kind == "run_host":   # host-only bookkeeping (output dict of views): once, when the step is recorded
-                e.item()
-            else:
-                program.append(e)
-        close()
-        self._program = program
+        self._program = record(self._plan(self._static, st))
 
     def _refresh_static(self, batch):
         """Copy the minibatch into the static input buffers the recorded graphs read: one launch for all tensors."""
@@ -859,22 +786,23 @@ class PolicyUpdater:
     def step_from(self, buf, idx: torch.Tensor) -> Dict[str, torch.Tensor]:
         """One update on the minibatch made of rows ``idx`` (device int64 [B]) of a device-resident ``rollout.RolloutBuffer``.
         With recorded graphs the rows are gathered by ONE launch straight into the static input buffers."""
-        keys = list(dict.fromkeys(list(self.loss_module.in_features) + list(self.loss_module.critic_in_features))) + ["action", "loc", "var" if "var" in buf.data else "covariance_matrix",
-                                                     "sample_log_prob", "state_value", "advantage", "value_target"]
-        if "adv_stats" in buf.data and self.group is not None:   # the epoch's published advantage statistics (rollout.RolloutDriver)
-            keys.append("adv_stats")
-        if not self.use_graph or self._program is None or int(idx.numel()) != self._static[keys[0]].shape[0]:
+        keys = self._rollout_keys(buf)[2]
+        jobs = None
+        # (recorded without a key that is gathered now, e.g. adv_stats: the plain minibatch makes the step record again)
+        if self.use_graph and self._program is not None and int(idx.numel()) == self._static[keys[0]].shape[0] and all(k in self._static for k in keys):
+            jobs = self._gather_jobs(self._static, buf, keys)
+        if jobs is None:
             return self.step(buf.rows(idx, keys))
-        if any(k not in self._static for k in keys):   # (recorded without a key that is gathered now, e.g. adv_stats: re-record)
-            return self.step(buf.rows(idx, keys))
-        jobs = []
-        for k in keys:
-            dst, src = self._static[k], buf.flat(k)
-            if dst.dtype != src.dtype or dst[0].numel() != src.shape[1]:
-                return self.step(buf.rows(idx, keys))
-            jobs.append((dst.data_ptr(), src.data_ptr(), src.shape[1] * src.element_size()))
         hip.call("grl_gather_rows_many", *_job_arrays(jobs), idx, int(idx.numel()))
         return self.step(self._static)
+
+    @staticmethod
+    def _gather_jobs(static, buf, keys):
+        """The jobs of one grl_gather_rows_many launch, rows of the rollout's tensors ``keys`` into ``static``; None where one does not fit."""
+        src = [buf.flat(k) for k in keys]
+        if any(static[k].dtype != v.dtype or static[k][0].numel() != v.shape[1] for k, v in zip(keys, src)):
+            return None
+        return [(static[k].data_ptr(), v.data_ptr(), v.shape[1] * v.element_size()) for k, v in zip(keys, src)]
 
     # ---- several minibatch steps per launch (round 6).  A shard-sized step is ~35 dependent launches of 5-15 us; what it pays on top of
     #      them is the boundary of every replay (~13 us between two graph launches on a stream, ~7 us between the eager minibatch gather
@@ -887,76 +815,63 @@ class PolicyUpdater:
         return bool(self.use_graph and m.world_size == 1 and not (self.group is not None and self.force_dp_plan) and self.overlap_critic
                     and m.critic_coef and self.epoch_unroll > 1)
 
-    def _lane_keys(self, buf):
+    def _rollout_keys(self, buf):
+        """-> (the rollout tensors the actor's lane reads, the critic's, their union in ``step_from``'s gather order + the epoch's published
+        advantage statistics (rollout.RolloutDriver) where a data-parallel run has them)."""
         m = self.loss_module
         var = "var" if "var" in buf.data else "covariance_matrix"
-        a = list(dict.fromkeys(list(m.in_features) + ["action", "loc", var, "sample_log_prob", "advantage"]))
-        c = list(dict.fromkeys(list(m.critic_in_features) + ["state_value", "value_target"]))
-        return a, c
+        lane_of = {"action": "m", "loc": "m", var: "m", "sample_log_prob": "m", "state_value": "s", "advantage": "m", "value_target": "s"}
+        a = list(dict.fromkeys(list(m.in_features) + [k for k, lane in lane_of.items() if lane == "m"]))
+        c = list(dict.fromkeys(list(m.critic_in_features) + [k for k, lane in lane_of.items() if lane == "s"]))
+        both = list(dict.fromkeys(list(m.in_features) + list(m.critic_in_features) + list(lane_of)))
+        if "adv_stats" in buf.data and self.group is not None:
+            both.append("adv_stats")
+        return a, c, both
 
     def _epoch_key(self, buf, B, U):
         """What a recorded multi-step launch depends on: its sizes and the rollout tensors its gathers read (RolloutDriver.compute_advantages
         REPLACES the buffer's state_value / advantage / value_target, so the next rollout through the same buffer object records again)."""
-        ka, kc = self._lane_keys(buf)
+        ka, kc, _ = self._rollout_keys(buf)
         # (four entries: bench.py reads key[1] as the steps per launch and key[2] as the flag of the retired cursor form, now always False)
         return (B, U, False, tuple(buf.flat(k).data_ptr() for k in ka + kc))
 
-    def _compile_epoch(self, buf, idx0, U, gate=None):
-        """Record ``U`` consecutive steps into one graph per lane: step j of a launch gathers the FIXED row j of a static [U, B] index
-        matrix (filled per launch)."""
-        m = self.loss_module
+    def _epoch_entries(self, buf, idx0, U, gate):
+        """``U`` consecutive steps as ONE program (recorded: one graph per lane): step j gathers the FIXED row j of a static [U, B] index
+        matrix (filled per launch) into its lane's own inputs.  -> (entries, what ``_epoch`` keeps of them); nothing is launched."""
         B = int(idx0.numel())
-        ka, kc = self._lane_keys(buf)
+        ka, kc, _ = self._rollout_keys(buf)
         sa, sc = buf.rows(idx0, ka), buf.rows(idx0, kc)      # static inputs, one private set per lane
-        m.actor_network.hyper_data.check_topology(*[sa[k] for k in m.in_features])
-        m.critic_network._network1.hyper_data.check_topology(*[sc[k] for k in m.critic_in_features])
         idx_static = torch.zeros(U, B, device=idx0.device, dtype=torch.int64)
         src = {k: buf.flat(k) for k in ka + kc}   # (held by the recording: its gathers read these storages)
+        ga, gc = _job_arrays(self._gather_jobs(sa, buf, ka)), _job_arrays(self._gather_jobs(sc, buf, kc))   # (rows of ``buf`` itself: they fit)
 
-        def gather_args(static, keys):
-            for k in keys:
-                if static[k].dtype != src[k].dtype or static[k][0].numel() != src[k].shape[1]:
-                    raise RuntimeError(f"rollout tensor '{k}' cannot be gathered row-wise into the recorded step's inputs")
-            return _job_arrays([(static[k].data_ptr(), src[k].data_ptr(), src[k].shape[1] * src[k].element_size()) for k in keys])
-        ga, gc = gather_args(sa, ka), gather_args(sc, kc)
-
-        def gather(args, j):
+        def gather(args, j, lane):
             row = idx_static[j]
-            return lambda: hip.call("grl_gather_rows_many", *args, row, B)
+            return Entry("run", lambda: hip.call("grl_gather_rows_many", *args, row, B), lane, "gather")
         sts, mains, critics = [], [], []
         for j in range(U):
             st = {"beta": self.beta_table[j:j + 1]}   # (entropy control: step j of a launch reads ITS bound)
-            self._plan_lanes(sa, st, cbatch=sc, gate_override=gate)
-            main_all, critic_all = st.pop("lanes")
-            mains += [gather(ga, j), main_all]
-            st["critic_pre"] = gather(gc, j)          # (behind the lane's gate, in front of its features: the lane's first stage runs it)
-            critics.append(critic_all)
+            actor_lane, (*wait, critic_all) = self._lane_entries(sa, sc, st, bool(gate))
+            mains += [gather(ga, j, "m"), *actor_lane]
+            critics += [*wait, gather(gc, j, "s"), critic_all]   # (behind the lane's gate, in front of its features)
             sts.append(st)
-        side = torch.cuda.Stream()
-        ga_graph = capture(mains, stream=side)
-        gc_graph = capture(critics, stream=side)
-        for st in sts:
-            self._finish(st)
-        self._epoch = dict(key=self._epoch_key(buf, B, U), idx=idx_static, sts=sts, keep=(sa, sc, src),
-                           program=[Entry("fork", None), Entry("graph", ga_graph), Entry("graph", gc_graph, "s"), Entry("join", None)])
+        entries = [Entry("fork", None), *mains, *critics, Entry("join", None),
+                   *[Entry("run_host", lambda st=st: self._finish(st)) for st in sts]]
+        return entries, dict(key=self._epoch_key(buf, B, U), idx=idx_static, sts=sts, keep=(sa, sc, src))
 
     def _launch_epoch(self, buf, rows, key, gate):
         """``rows`` [U, B] (device int64): U steps as ONE recorded launch per lane, recorded first when ``key`` (_epoch_key) is not the
         recording's.  Returns the loss dict of the last step; ``self.last_outs`` holds those of all U."""
         U = int(rows.shape[0])
-        self._entropy_prepare(None, U)   # (the first update of a size has run eagerly: nothing is latched here)
-        if self._epoch is None or self._epoch["key"] != key:
-            self.loss_module._global_steps = self.steps
-            self._compile_epoch(buf, rows[0], U, gate=gate)
-        ep = self._epoch
-        ep["idx"].copy_(rows)
-        self.steps += U
-        try:
-            self._execute(ep["program"])
-        except BaseException:
-            self.steps -= U
-            raise
-        self.last_outs = [st["out"] for st in ep["sts"]]
+        def issue():
+            if self._epoch is None or self._epoch["key"] != key:
+                entries, ep = self._epoch_entries(buf, rows[0], U, gate)
+                self._check_topology(*ep["keep"][:2])
+                self._epoch = dict(ep, program=record(entries))
+            self._epoch["idx"].copy_(rows)
+            self._execute(self._epoch["program"])
+        self._advance(None, U, issue)   # (the first update of a size has run eagerly: no initial entropy is latched here)
+        self.last_outs = [st["out"] for st in self._epoch["sts"]]
         return self.last_outs[-1]
 
     # The size thresholds of the lane policy (_gate_for, run_minibatches) were measured on rigid_insertion_multi HEPi, whose compact graph has
@@ -993,9 +908,7 @@ class PolicyUpdater:
         self._check_loss_storage()
         out, j = None, 0
         if not self._epoch_ok() or U <= 1:
-            for j in range(M):
-                out = self.step_from(buf, idx_rows[j])
-            return out
+            return self._step_rows(buf, idx_rows)
         while j < M and B not in self._eager_sizes:     # the first step of a size runs eagerly (topology, calibration, checks)
             out = self.step_from(buf, idx_rows[j])
             j += 1
@@ -1023,9 +936,12 @@ class PolicyUpdater:
             while M - j >= U:
                 out = self._launch_epoch(buf, idx_rows[j:j + U], key, gate_here)
                 j += U
-        while j < M:
-            out = self.step_from(buf, idx_rows[j])
-            j += 1
+        return self._step_rows(buf, idx_rows[j:], out)
+
+    def _step_rows(self, buf, rows, out=None):
+        """``step_from`` on the rows of ``rows`` [M, B], in order -> the last step's loss dict (``out`` where M = 0)."""
+        for r in rows:
+            out = self.step_from(buf, r)
         return out
 
     TUNE_ROUNDS = 2   # alternating blocks per form in _tune_form
@@ -1042,30 +958,23 @@ class PolicyUpdater:
         ONE host synchronisation at the end.  Every step is an ordinary update of the next minibatch, and the two forms produce bitwise the
         same update (tests/test_gpu_rollout.py), so the measurement changes nothing but the time.  -> (next j, last loss dict)."""
         B = int(idx_rows.shape[1])
-        main, cs = torch.cuda.current_stream(), self._critic_stream()
-        out = None
+        main = torch.cuda.current_stream()
         key = self._epoch_key(buf, B, U)
 
         def unrolled(rows):
             return self._launch_epoch(buf, rows, key, False)
 
-        def per_step(rows):
-            o = None
-            for r in rows:
-                o = self.step_from(buf, r)
-            return o
-
         out = unrolled(idx_rows[j:j + U]); j += U          # records (and runs) the multi-step launch
-        out = per_step(idx_rows[j:j + 3]); j += 3          # records the per-step program, first replays
+        out = self._step_rows(buf, idx_rows[j:j + 3]); j += 3          # records the per-step program, first replays
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2 * self.TUNE_ROUNDS + 1)]
-        main.wait_stream(cs)
+        self.join_lanes()
         ev[0].record(main)
         for r in range(self.TUNE_ROUNDS):
             out = unrolled(idx_rows[j:j + U]); j += U
-            main.wait_stream(cs)
+            self.join_lanes()
             ev[2 * r + 1].record(main)
-            out = per_step(idx_rows[j:j + U]); j += U
-            main.wait_stream(cs)
+            out = self._step_rows(buf, idx_rows[j:j + U]); j += U
+            self.join_lanes()
             ev[2 * r + 2].record(main)
         ev[-1].synchronize()
         t_u = min(ev[2 * r].elapsed_time(ev[2 * r + 1]) for r in range(self.TUNE_ROUNDS)) / U
@@ -1076,9 +985,8 @@ class PolicyUpdater:
 
     def reset_graph(self):
         """Drop the recorded step (next step re-records): needed when the minibatch size changes."""
-        self._program, self._static, self._epoch = None, None, None
-        self._eager_sizes = set()
-        self.form_by_size, self.form_times = {}, {}
+        self._drop_recordings()
+        self._eager_sizes, self.form_by_size, self.form_times = set(), {}, {}
 
     def _check_calibrated(self):
         """Data parallel: the first training forward of a fresh actor re-initialises the conv kernels from rank-local data
@@ -1095,25 +1003,29 @@ class PolicyUpdater:
         self._calib_synced = True
         return not gnn.calibrated   # True: this rank's actor still has to calibrate -> the caller syncs afterwards
 
-    def step(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    def _advance(self, batch, n, issue):
+        """The bookkeeping around ``n`` updates that ``issue()`` enqueues: the loss module's count, the entropy bounds of the updates (from
+        ``batch`` the initial entropy, at the first one), the host's step count -- taken back when issuing raised.  -> what ``issue`` returns."""
         self.loss_module._global_steps = self.steps
-        need_sync = self._check_calibrated()
-        if need_sync:
+        self._entropy_prepare(batch, n)
+        self.steps += n
+        try:
+            return issue()
+        except BaseException:
+            # the critic lane's gate waits until the DEVICE-side step count (advanced by the actor's feature launch) reaches the HOST's: a
+            # step that raised before that launch was enqueued must not leave the host ahead for good -- the next step's wait would
+            # never be satisfied and the process would hang on the device instead of raising (ADVICE r5).  After a failure the host count
+            # is at most the device's: the gate may then release early, it can never be stuck.
+            self.steps -= n
+            raise
+
+    def step(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        if self._check_calibrated():
             actor, m = self.loss_module.actor_network, self.loss_module
             with torch.no_grad():
                 actor.forward_diag(*[batch[k] for k in m.in_features], train=True)   # calibrates on this rank's shard
             self.sync_replicas()                                                       # ... and rank 0's factors win everywhere
-        self._entropy_prepare(batch)
-        self.steps += 1
-        try:
-            return self._step(batch)
-        except BaseException:
-            # the critic lane's gate waits until the DEVICE-side step count (advanced by the actor's feature launch) reaches the HOST's: a
-            # step that raised before that launch was enqueued must not leave the host one ahead for good -- the next step's wait would
-            # never be satisfied and the process would hang on the device instead of raising.  After a failure the host count
-            # is at most the device's: the gate may then release early, it can never be stuck.
-            self.steps -= 1
-            raise
+        return self._advance(batch, 1, lambda: self._step(batch))
 
     def _step(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         B = next(v.shape[0] for v in batch.values() if torch.is_tensor(v))
@@ -1162,24 +1074,13 @@ class PolicyUpdater:
         return self._st["out"]
 
     def _execute(self, program):
-        """Run a program (a list of ``Entry``): lane "m" is the caller's stream, lane "s" the critic's stream; "fork": the side lane waits
-        for the main lane, "join": the reverse; everything else is issued by ``_do`` on its lane's stream."""
-        main = torch.cuda.current_stream()
-        side = None
-        for e in program:
-            if e.kind in ("fork", "join"):
-                side = side or self._critic_stream()
-                if e.kind == "join":
-                    with self._log_span(e.label):   # how long the main lane stood waiting for the critic's lane
-                        main.wait_stream(side)
-                else:
-                    side.wait_stream(main)
-            elif e.lane == "s":
-                side = side or self._critic_stream()
-                with torch.cuda.stream(side):
-                    self._do(e)
-            else:
-                self._do(e)
+        """Issue a program, eager or recorded (program.execute): lane "s" is the critic's stream, every entry goes through ``_do``."""
+        execute(program, self._do, self._critic_stream, self._log_span)
+
+    def join_lanes(self):
+        """The caller's stream waits for the critic's stream, if there is one (for callers that read or time both lanes' work)."""
+        if self._cstream is not None:
+            torch.cuda.current_stream().wait_stream(self._cstream)
 
     def _do(self, e: Entry):
         """Issue one entry on the current stream (tools that time entries wrap this method)."""
@@ -1187,5 +1088,5 @@ class PolicyUpdater:
             e.item()
         elif e.kind == "graph":
             e.item.replay()
-        else:
-            self._reduce(e.kind, e.item() if e.item is not None else None, e.label, e.lane)
+        else:   # "sum", the programs' one collective
+            self.all_reduce_sum(e.item(), e.label, e.lane)

@@ -92,10 +92,10 @@ def _stats_worker(rank, world, port, ret):
     buf = RolloutBuffer({"advantage": torch.randn(N, T, 1, generator=g)})
     calls = []
 
-    def reduce_(kind, t, label=None, lane="m"):
+    def reduce_(t, label=None, lane="m"):
         calls.append(label)
         dist.all_reduce(t)
-    upd = SimpleNamespace(group=dist.group.WORLD, loss_module=SimpleNamespace(normalize_advantage=True), _reduce=reduce_)
+    upd = SimpleNamespace(group=dist.group.WORLD, loss_module=SimpleNamespace(normalize_advantage=True), all_reduce_sum=reduce_)
     drv = RolloutDriver(updater=upd, spec=None, seed=5 + rank)    # every rank shuffles its own environments
     ok = True
     for epoch in range(2):
