@@ -1,0 +1,295 @@
+"""CPU restatement of ONE WHOLE TRAINING ITERATION, composed from the oracle's pieces.  TEST INFRASTRUCTURE ONLY, a plain module like
+tests/train_ops_ref.py: tests/test_gpu_iteration_oracle.py compares the HIP chain with it stage by stage, tests/test_iteration_ref_cpu.py
+shows on the oracle alone that the comparison would notice the wiring mistakes it exists for.
+
+The chain (examples/torchrl/train.py:114-140, 232-316): raw observation -> running normalisation + clip (oracle.transforms) -> collector-side
+actor (OracleAgent.actor_forward, action = loc + sigma eps, MultivariateNormal.log_prob) -> rollout [N, T] -> critic over the T frames and the
+frame behind the last (OracleAgent.critic_forward) -> shifted GAE (oracle.trpl.gae_shifted) -> the sampler's minibatches -> OracleAgent.update.
+
+THE CASE.  rigid HEPi (the spec whose ragged per-environment point counts, synthetic.RIGID_NUM_POINTS, put the topology cache and the
+dropped padding in play), N = 16 environments, two consecutive iterations of T = 3 and T = 2 steps on the same objects: five updates.  The
+environment is a pure function of its step counter s: raw groups synthetic.make_rigid_obs(N, seed=ENV_BASE + s) without the norm_* keys,
+rewards on the lattice 2^-8 in [-4, 4] (every float32 episode sum is exact), and the explicit done / terminated table PATTERN below.
+
+Both sides start from oracle.step.init_agent_params with the critic's last layer scaled by VALUE_GAIN: at the reference's orthogonal gain of
+0.01 every value is ~1e-2, below the value allowance of 1e-4 carried through the GAE scan ((1 + gamma) / (1 - gamma lambda) = 33 times), so
+a T+1 column taken from the wrong frame would be invisible; with the scaled head the values are O(1) as they are after training."""
+from typing import Dict, List
+
+import numpy as np
+import torch
+
+import stats_ref
+from oracle import graph as ogr, step as ost, transforms as otf, trpl as otr
+from geometry_rl_amd import synthetic as syn
+
+N, T_ITERS, A = 16, (3, 2), 6
+STEPS = sum(T_ITERS)
+GAMMA, LMBDA = 0.99, 0.95
+KW = dict(only_upper_hemisphere=True, output_dim=2, output_dim_vec=2)
+PARAM_SEED, ACTOR_SEED, DRIVER_SEED, ENV_BASE = 17, 11, 5, 300
+VALUE_GAIN = 100.0
+DECAY, EPS, LOW, HIGH = 0.99999, 1e-2, -20.0, 20.0       # configs/rigid_insertion_multi_hepi_trpl_cfg.yaml:47-72
+VECTOR_KEYS, SCALAR_KEYS = ("position_vectors", "velocity_vectors"), ("scalars",)
+PPO_KEYS = ("action", "loc", "var", "sample_log_prob", "state_value", "advantage", "value_target")
+TOL = 1e-4              # tests/test_gpu_step.py
+NORM_TOL = 2e-5         # tests/test_gpu_transforms.py
+U32 = 2.0 ** -24
+
+# (environment, step s) -> what the transition s -> s + 1 reports; steps 0..2 are iteration 1, steps 3..4 iteration 2
+PATTERN = {
+    (0, 1): "terminated",    # done and terminated in the middle of a rollout
+    (1, 1): "truncated",     # done, not terminated, in the middle: bootstraps from the next frame's value, the scan restarts
+    (2, 2): "terminated",    # terminated at the last step of iteration 1: must NOT bootstrap from next_last
+    (3, 2): "truncated",     # done only at the last step of iteration 1: must bootstrap from next_last
+    (4, 3): "terminated",    # no done in iteration 1: the episode runs across the boundary and ends in iteration 2
+    (5, 4): "truncated",     # the two last-step situations once more in iteration 2
+    (6, 4): "terminated",
+    (7, 0): "truncated",
+}
+
+
+def pattern():
+    """done, terminated bool [N, STEPS]: PATTERN on environments 0..7, seeded random ends (a fifth of the frames, half of them terminated)
+    on environments 8..15 -- except environment 8, which never ends (a second episode across the boundary)."""
+    done, term = torch.zeros(N, STEPS, dtype=torch.bool), torch.zeros(N, STEPS, dtype=torch.bool)
+    for (i, s), what in PATTERN.items():
+        done[i, s] = True
+        term[i, s] = what == "terminated"
+    g = torch.Generator().manual_seed(ENV_BASE + 77)
+    d = torch.rand(N - 9, STEPS, generator=g) < 0.2
+    done[9:] = d
+    term[9:] = d & (torch.rand(N - 9, STEPS, generator=g) < 0.5)
+    return done, term
+
+
+def situations(done, term, T1=T_ITERS[0]) -> Dict[str, bool]:
+    """Which of the five situations the case is built around the pattern contains (done / terminated [N, STEPS], iteration 1 = the first T1
+    steps): each is a place where the GAE call, the T+1 column or the carried episode state can be wired wrongly."""
+    d1, t1 = done[:, :T1], term[:, :T1]
+    return {
+        "terminated mid-rollout": bool((d1[:, 1:-1] & t1[:, 1:-1]).any()),
+        "truncated mid-rollout": bool((d1[:, :-1] & ~t1[:, :-1]).any()),
+        "terminated at the last step": bool(t1[:, -1].any()),
+        "done only at the last step": bool((d1[:, -1] & ~t1[:, -1]).any()),
+        "episode across the iterations": bool((~d1.any(1) & done[:, T1:].any(1)).any()),
+    }
+
+
+class SyntheticEnv:
+    """A pure function of its step counter: ``raw_obs(s)``, ``outcome(s)`` = (reward, done, terminated) of the transition s -> s + 1;
+    ``step(action)`` is what ``rollout.collect`` calls.  The action is checked for its shape and otherwise unused."""
+
+    def __init__(self, device=None):
+        self.t, self.device = 0, device
+        self.done, self.term = pattern()
+
+    def _to(self, x):
+        return x if self.device is None else x.to(self.device)
+
+    def raw_obs(self, s: int) -> Dict[str, torch.Tensor]:
+        o = syn.make_rigid_obs(N, seed=ENV_BASE + s)
+        return {k: self._to(v) for k, v in o.items() if not k.startswith("norm_")}
+
+    def reward(self, s: int) -> torch.Tensor:
+        g = torch.Generator().manual_seed(ENV_BASE + 1000 + s)
+        return torch.randint(-4 * 256, 4 * 256 + 1, (N,), generator=g).float() / 256
+
+    def outcome(self, s: int):
+        return self._to(self.reward(s)), self._to(self.done[:, s].clone()), self._to(self.term[:, s].clone())
+
+    def step(self, action):
+        assert tuple(action.shape) == (N, A), action.shape
+        s = self.t
+        self.t += 1
+        return (self.raw_obs(self.t), *self.outcome(s))
+
+
+def make_oracle():
+    """-> (o_spec, o_cfg, actor params, critic params, OracleAgent): init_agent_params with the value head scaled (module docstring)."""
+    o_spec, o_cfg = ogr.rigid_spec(), ost.AgentConfig(**KW)
+    a_par, c_par = ost.init_agent_params(o_spec, o_cfg, seed=PARAM_SEED)
+    c_par = dict(c_par)
+    c_par["final.weight"] = c_par["final.weight"] * VALUE_GAIN
+    return o_spec, o_cfg, a_par, c_par, ost.OracleAgent(o_spec, o_cfg, a_par, c_par)
+
+
+def cpu(d: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    return {k: v.detach().cpu() for k, v in d.items()}
+
+
+# ------------------------------------------------------------------------------------------------------------- stage a: normalisation
+def new_norm_state():
+    return {"position_vectors": otf.VecNormState(3), "velocity_vectors": otf.VecNormState(3), "scalars": otf.VecNormState(1)}
+
+
+def ref_normalise(raw: Dict[str, torch.Tensor], st, update: bool = True) -> Dict[str, torch.Tensor]:
+    """The transform stack on one set of raw groups [B, D]: per-axis statistics for the vector groups (norm_<key> added, the raw group
+    clipped), per-column statistics for the scalars (normalised in place), every group clipped.  ``update=False``: the frozen call on the
+    final observation of a rollout (the state is left as it is and carried into the next iteration by the caller)."""
+    out = dict(raw)
+    B = raw["scalars"].shape[0]
+    for k in VECTOR_KEYS:
+        out["norm_" + k] = otf.clip(otf.vecnorm_update(raw[k].reshape(B, -1, 3), st[k], DECAY, EPS, update).reshape(B, -1), LOW, HIGH)
+        out[k] = otf.clip(raw[k], LOW, HIGH)
+    for k in SCALAR_KEYS:
+        out[k] = otf.clip(otf.vecnorm_update(raw[k], st[k], DECAY, EPS, update), LOW, HIGH)
+    return out
+
+
+def norm_state_vector(st, key) -> torch.Tensor:
+    """[sum | ssq | count], the layout of ObservationNormalizer.state[key]."""
+    return torch.cat([st[key].sum, st[key].ssq, st[key].count])
+
+
+# ------------------------------------------------------------------------------------------------------------- stage b: collector step
+def ref_collect_step(oracle, obs, eps, action, loc_in=None, var_in=None):
+    """One collector step on the groups ``obs`` (CPU): loc, var from OracleAgent.actor_forward; ``action_ref`` = loc_in + sqrt(var_in) eps in
+    float64 (``loc_in`` / ``var_in``: the loc and var the sampler under test started from; the oracle's own where None); ``logp`` the float64
+    log-density of ``action`` (the sampler's own) under the ORACLE's loc and var; ``z``, ``sigma``: of that density."""
+    with torch.no_grad():
+        loc, var = oracle.actor_forward({k: obs[k] for k in oracle.spec.in_features})
+    loc_in = loc if loc_in is None else loc_in
+    var_in = var if var_in is None else var_in
+    action_ref = loc_in.double() + var_in.double().sqrt() * eps.double()
+    action = action_ref.float() if action is None else action
+    logp = otr.mvn_diag_log_prob(action.double(), loc.double(), var.double())
+    sigma = var.double().sqrt()
+    return {"loc": loc, "var": var, "action_ref": action_ref, "action": action, "logp": logp, "z": (action.double() - loc.double()) / sigma,
+            "sigma": sigma}
+
+
+def tol_of(ref, tol=TOL) -> float:
+    """The absolute allowance of test_gpu_step.check: tol * max(1, the reference's largest entry)."""
+    return tol * max(1.0, float(torch.as_tensor(ref).abs().max()))
+
+
+def logp_allowance(c, e_loc: float, e_var: float) -> torch.Tensor:
+    """Allowance [B] of the sampler's fp32 log-prob (evaluated under ITS loc / var) against ``c["logp"]`` (under the oracle's):
+    the fp32 evaluation bound of trpl_cases.sample_reference,  (A + 4) U (q / 2 + sum |log sigma| + A / 2 log 2 pi) + 4 U q,  q = sum z^2,
+    plus the first-order propagation of this stage's loc / var allowances through log p = -1/2 sum z^2 - sum log sigma - A / 2 log 2 pi:
+    |d log p / d loc_i| = |z_i| / sigma_i,  |d log p / d var_i| = |z_i^2 - 1| / (2 sigma_i^2)   (z, sigma: the reference's)."""
+    z, s = c["z"], c["sigma"]
+    q = (z * z).sum(-1)
+    k = z.shape[-1]
+    kernel = (k + 4) * U32 * (0.5 * q + s.log().abs().sum(-1) + 0.5 * k * otr.LOG_2PI) + 4 * U32 * q
+    return kernel + (z.abs() / s).sum(-1) * e_loc + ((z * z - 1.0).abs() / (2.0 * s * s)).sum(-1) * e_var
+
+
+# ------------------------------------------------------------------------------------------------------------- stage c: advantages
+def ref_values(oracle, frames: List[Dict[str, torch.Tensor]], next_last: Dict[str, torch.Tensor]) -> torch.Tensor:
+    """V [N, T + 1]: critic_forward per time step and on the frame behind the last (train.py:249-251)."""
+    with torch.no_grad():
+        cols = [oracle.critic_forward({k: f[k] for k in oracle.spec.in_features}).reshape(-1) for f in list(frames) + [next_last]]
+    return torch.stack(cols, dim=1)
+
+
+def ref_advantages(oracle, frames, next_last, reward, done, terminated):
+    """-> (V [N, T + 1], state_value = V[:, :T], advantage, value_target), the scan in float64 (oracle.trpl.gae_shifted)."""
+    V = ref_values(oracle, frames, next_last)
+    adv, tgt = otr.gae_shifted(reward.double(), done, terminated, V.double(), GAMMA, LMBDA)
+    return V, V[:, :-1], adv, tgt
+
+
+def value_propagation(e_value: float) -> float:
+    """A per-value allowance e carried through the scan: delta moves by at most (1 + gamma) e, the run sums it with weights (gamma lambda)^k."""
+    return (1.0 + GAMMA) / (1.0 - GAMMA * LMBDA) * e_value
+
+
+def gae_from(reward, done, terminated, v, nv):
+    """The scan of gae_shifted with the next value given explicitly (for the mutations; gae_from(V[:, :-1], V[:, 1:]) IS gae_shifted(V))."""
+    nd, nt = 1.0 - done.to(reward.dtype), 1.0 - terminated.to(reward.dtype)
+    delta = reward + GAMMA * nt * nv - v
+    adv, run = torch.zeros_like(reward), torch.zeros_like(reward[:, 0])
+    for t in range(reward.shape[1] - 1, -1, -1):
+        run = delta[:, t] + GAMMA * LMBDA * nd[:, t] * run
+        adv[:, t] = run
+    return adv, adv + v
+
+
+# ------------------------------------------------------------------------------------------------------------- stage d: episode statistics
+def new_episode_state():
+    return {"ret": np.zeros(N, np.float32), "len": np.zeros(N, np.int32)}
+
+
+def ref_episode_stats(reward, done, state):
+    """RewardSum / StepCounter over one rollout (stats_ref.episode_scan), the running values carried in ``state`` to the next rollout.
+    -> (episode_reward float32 [N, T], step_count int32 [N, T], sums float64[3] over this rollout's done frames)."""
+    er, sc, state["ret"], state["len"], sums = stats_ref.episode_scan(reward.numpy(), done.numpy(), state["ret"], state["len"])
+    return er, sc, sums
+
+
+# ------------------------------------------------------------------------------------------------------------- stage e: updates
+def rows(data: Dict[str, torch.Tensor], idx: torch.Tensor, keys) -> Dict[str, torch.Tensor]:
+    """The minibatch of the [N, T, ...] rollout ``data``: rows ``idx`` of the flattened [N * T] frames (frame (i, t) is row i * T + t)."""
+    some = data[keys[0]]
+    NT = some.shape[0] * some.shape[1]
+    out = {k: data[k].reshape(NT, -1).index_select(0, idx) for k in keys}
+    out["sample_log_prob"] = out["sample_log_prob"].reshape(-1)
+    return out
+
+
+def batch_keys(oracle):
+    return list(oracle.spec.in_features) + list(PPO_KEYS)
+
+
+def ref_updates(oracle, data, idx_list):
+    """OracleAgent.update on the minibatches ``idx_list`` of ``data``, in order -> [(loss dict, gradients)]."""
+    keys = batch_keys(oracle)
+    return [oracle.update(rows(data, idx.cpu(), keys)) for idx in idx_list]
+
+
+def sampler_indices(device, T_list=T_ITERS):
+    """The minibatches of every iteration from a twin RolloutDriver(seed=DRIVER_SEED, ppo_epochs=1) through epoch_minibatches."""
+    from geometry_rl_amd.rollout import RolloutDriver
+    twin = RolloutDriver(updater=None, spec=None, gamma=GAMMA, lmbda=LMBDA, ppo_epochs=1, seed=DRIVER_SEED)
+    return [twin.epoch_minibatches(N, T, device) for T in T_list]
+
+
+# ------------------------------------------------------------------------------------------------------------- the whole chain, oracle alone
+def run_oracle_chain():
+    """Both iterations on the CPU with the oracle as BOTH sides (its own outputs are every stage's inputs): what tests/test_iteration_ref_cpu.py
+    mutates.  -> a list of per-iteration dicts: data ([N, T, ...] rollout incl. the advantage keys), frames, next_last, V, reward / done /
+    terminated [N, T], episode_reward, step_count, sums, idx (the minibatches), params (actor, critic clones from BEFORE the updates), topo,
+    losses (every update's loss dict), norm_state (the normaliser's state vectors behind the iteration)."""
+    o_spec, o_cfg, a_par, c_par, oracle = make_oracle()
+    env, st, ep = SyntheticEnv(), new_norm_state(), new_episode_state()
+    gen = torch.Generator().manual_seed(ACTOR_SEED)
+    idx_all = sampler_indices(torch.device("cpu"))
+    raw, out = env.raw_obs(0), []
+    for it, T in enumerate(T_ITERS):
+        frames = []
+        for t in range(T):
+            obs = ref_normalise(raw, st)
+            if it == 0 and t == 0:   # the first training call calibrates
+                with torch.no_grad():
+                    oracle.actor_forward({k: obs[k] for k in o_spec.in_features}, calibrate=True)
+            eps = torch.randn(N, A, generator=gen)
+            c = ref_collect_step(oracle, obs, eps, None)
+            raw, reward, done, term = env.step(c["action"])
+            rec = dict(obs)
+            rec.update(loc=c["loc"], var=c["var"], action=c["action"], sample_log_prob=c["logp"].float(), reward=reward.reshape(-1, 1),
+                       done=done.reshape(-1, 1), terminated=term.reshape(-1, 1))
+            frames.append(rec)
+        next_last = ref_normalise(raw, st, update=False)
+        data = {k: torch.stack([f[k] for f in frames], dim=1) for k in frames[0]}
+        r, d, tm = (data[k].reshape(N, T) for k in ("reward", "done", "terminated"))
+        er, sc, sums = ref_episode_stats(r, d, ep)
+        V, sv, adv, tgt = ref_advantages(oracle, frames, next_last, r, d, tm)
+        data.update(state_value=sv.reshape(N, T, 1), advantage=adv.float().reshape(N, T, 1), value_target=tgt.float().reshape(N, T, 1))
+        params = ({k: v.detach().clone() for k, v in oracle.actor.items()}, {k: v.detach().clone() for k, v in oracle.critic.items()})
+        losses = [o for o, _ in ref_updates(oracle, data, idx_all[it])]
+        out.append(dict(data=data, frames=frames, next_last=next_last, V=V, reward=r, done=d, terminated=tm, episode_reward=er, step_count=sc,
+                        sums=sums, idx=idx_all[it], params=params, topo=dict(oracle._topo), losses=losses, T=T, norm_state={k: norm_state_vector(st, k) for k in st}))
+    return out
+
+
+def loss_at(params, topo, batch):
+    """The loss dict of a fresh OracleAgent with ``params`` = (actor, critic) and the chain's cached topologies ``topo`` (the kNN edges are
+    those of the FIRST batch of a size, rigid_tasks_data.py:254-255) on ``batch``; nothing is updated."""
+    o_spec, o_cfg = ogr.rigid_spec(), ost.AgentConfig(**KW)
+    agent = ost.OracleAgent(o_spec, o_cfg, params[0], params[1])
+    agent._topo = dict(topo)
+    with torch.no_grad():
+        out = agent.loss(batch)
+    return {k: (v.detach() if torch.is_tensor(v) else v) for k, v in out.items()}

@@ -17,13 +17,12 @@ BASELINE.json names: rigid HEPi at config 2's exact minibatch (B = 1024, P = 32,
 comparison also covers replayed launches.  Reference semantics: examples/torchrl/train.py:264-316."""
 import os
 
-import numpy as np
 import pytest
 import torch
 
 from oracle import step as ost
 from geometry_rl_amd import synthetic as syn
-from parity_util import NET_FLOOR, adam_first_step_bound, grad_scales
+from updater_cases import merge_grad_scales, moments_and_params_after
 
 pytestmark = pytest.mark.gpu
 M_TOL, V_TOL = 5e-4, 1e-3
@@ -74,35 +73,10 @@ def test_five_updates_match_the_oracle(name, B, K):
     for i, b in enumerate(batches):
         ref, ref_grads = oracle.update(b)
         out = upd.step({k: v.to(dev) for k, v in b.items()})
-        sc = {net: grad_scales(ref_grads[net]) for net in ("actor", "critic")}
-        g_scale = sc if g_scale is None else {net: {k: max(v, g_scale[net].get(k, 0.0)) for k, v in sc[net].items()} for net in sc}
+        g_scale = merge_grad_scales(g_scale, ref_grads)
         for k in ("loss_objective", "loss_trust_region", "loss_critic", "kl"):   # the trajectories stay together step by step
             e = abs(float(out[k]) - float(ref[k]))
             assert e <= 1e-4 * max(1.0, abs(float(ref[k]))), (i, k, e)
     assert upd.mode.startswith("graph") and upd._program is not None
-    torch.cuda.synchronize()
-    off = lambda p: (p.data_ptr() - upd.flat.data_ptr()) // 4
-    bad, worst = [], {"exp_avg": 0.0, "exp_avg_sq": 0.0, "param": 0.0}
-    for net, mod, ref_p, optim, strip in (("actor", actor, oracle.actor, oracle.actor_optim, 0),
-                                          ("critic", critic, oracle.critic, oracle.critic_optim, len("_network1."))):
-        states = {kk: optim.state.get(ref_p[kk], {}) for kk in ref_p}
-        m_ref = {kk: s_["exp_avg"] for kk, s_ in states.items() if "exp_avg" in s_}
-        v_ref = {kk: s_["exp_avg_sq"] for kk, s_ in states.items() if "exp_avg_sq" in s_}
-        m_sc, v_sc = grad_scales(m_ref), grad_scales(v_ref)
-        for k, p in mod.named_parameters():
-            kk = k[strip:]
-            if kk not in m_ref:
-                continue
-            o, n = off(p), p.numel()
-            em = float((upd.exp_avg[o:o + n].view_as(p).cpu().double() - m_ref[kk].double()).abs().max())
-            ev = float((upd.exp_avg_sq[o:o + n].view_as(p).cpu().double() - v_ref[kk].double()).abs().max())
-            ep = float((p.detach().cpu().double() - ref_p[kk].detach().double()).abs().max())
-            allowed_p = K * adam_first_step_bound(cfg.lr, 1e-5, g_scale[net].get(kk, 0.0), cfg.clip_grad_norm, p_ref=ref_p[kk])
-            print(f"{net} {kk}: exp_avg {em / m_sc[kk]:.2e} of scale, exp_avg_sq {ev / v_sc[kk]:.2e} of scale, param err {ep:.2e} (allowed {allowed_p:.2e})")
-            worst["exp_avg"] = max(worst["exp_avg"], em / m_sc[kk])
-            worst["exp_avg_sq"] = max(worst["exp_avg_sq"], ev / v_sc[kk])
-            worst["param"] = max(worst["param"], ep / allowed_p)
-            if not (em <= M_TOL * m_sc[kk] and ev <= V_TOL * v_sc[kk] and ep <= allowed_p and np.isfinite(em + ev + ep)):
-                bad.append((net, kk, em / m_sc[kk], ev / v_sc[kk], ep, allowed_p))
-    print("worst (fraction of scale / of allowed):", worst)
+    bad, _ = moments_and_params_after(upd, actor, critic, oracle, cfg, g_scale, K, M_TOL, V_TOL)   # (the rules: updater_cases)
     assert not bad, bad

@@ -162,7 +162,8 @@ def test_launch_forms_can_be_mixed_and_follow_a_changed_hyper_parameter():
 def test_collect_normalise_update_round_trip():
     """One whole training iteration on the device with a synthetic environment: raw observations -> running normalisation + clip ->
     collector-side actor (sampling) -> rollout buffer -> critic values + shifted GAE -> minibatch updates.  Checks the plumbing (keys,
-    shapes, finite losses, parameters move) -- every piece is checked numerically by its own test."""
+    shapes, finite losses, parameters move) -- every piece is checked numerically by its own test, and the chain as a whole, stage by
+    stage against the oracle, by tests/test_gpu_iteration_oracle.py."""
     from geometry_rl_amd import agent, graph, synthetic as syn
     from geometry_rl_amd.rollout import PolicyActor, RolloutDriver, collect
     from geometry_rl_amd.transforms import ObservationNormalizer

@@ -121,6 +121,48 @@ def run_step_modes(make, modes, k, keys, updater_kw_of_mode, before_step=None, p
     return res
 
 
+# ------------------------------------------------------------------------------------------------------------- K updates against the oracle
+def merge_grad_scales(g_scale, ref_grads):
+    """The running largest gradient scale of every tensor over the updates so far (``g_scale`` None before the first)."""
+    from parity_util import grad_scales
+    sc = {net: grad_scales(ref_grads[net]) for net in ("actor", "critic")}
+    return sc if g_scale is None else {net: {k: max(v, g_scale[net].get(k, 0.0)) for k, v in sc[net].items()} for net in sc}
+
+
+def moments_and_params_after(upd, actor, critic, oracle, cfg, g_scale, K, m_tol, v_tol):
+    """After K updates on both sides (tests/test_gpu_multistep_oracle.py's rules): exp_avg of every parameter tensor against ``m_tol``,
+    exp_avg_sq against ``v_tol`` (of the tensor's own largest reference entry, floored as for gradients), the parameters against K times the
+    first-step bound.  Prints every margin -> (the tensors that miss a rule, the worst fractions); the assertion stays with the caller."""
+    import numpy as np
+    from parity_util import adam_first_step_bound, grad_scales
+    torch.cuda.synchronize()
+    off = lambda p: (p.data_ptr() - upd.flat.data_ptr()) // 4
+    bad, worst = [], {"exp_avg": 0.0, "exp_avg_sq": 0.0, "param": 0.0}
+    for net, mod, ref_p, optim, strip in (("actor", actor, oracle.actor, oracle.actor_optim, 0),
+                                          ("critic", critic, oracle.critic, oracle.critic_optim, len("_network1."))):
+        states = {kk: optim.state.get(ref_p[kk], {}) for kk in ref_p}
+        m_ref = {kk: s_["exp_avg"] for kk, s_ in states.items() if "exp_avg" in s_}
+        v_ref = {kk: s_["exp_avg_sq"] for kk, s_ in states.items() if "exp_avg_sq" in s_}
+        m_sc, v_sc = grad_scales(m_ref), grad_scales(v_ref)
+        for k, p in mod.named_parameters():
+            kk = k[strip:]
+            if kk not in m_ref:
+                continue
+            o, n = off(p), p.numel()
+            em = float((upd.exp_avg[o:o + n].view_as(p).cpu().double() - m_ref[kk].double()).abs().max())
+            ev = float((upd.exp_avg_sq[o:o + n].view_as(p).cpu().double() - v_ref[kk].double()).abs().max())
+            ep = float((p.detach().cpu().double() - ref_p[kk].detach().double()).abs().max())
+            allowed_p = K * adam_first_step_bound(cfg.lr, 1e-5, g_scale[net].get(kk, 0.0), cfg.clip_grad_norm, p_ref=ref_p[kk])
+            print(f"{net} {kk}: exp_avg {em / m_sc[kk]:.2e} of scale, exp_avg_sq {ev / v_sc[kk]:.2e} of scale, param err {ep:.2e} (allowed {allowed_p:.2e})")
+            worst["exp_avg"] = max(worst["exp_avg"], em / m_sc[kk])
+            worst["exp_avg_sq"] = max(worst["exp_avg_sq"], ev / v_sc[kk])
+            worst["param"] = max(worst["param"], ep / allowed_p)
+            if not (em <= m_tol * m_sc[kk] and ev <= v_tol * v_sc[kk] and ep <= allowed_p and np.isfinite(em + ev + ep)):
+                bad.append((net, kk, em / m_sc[kk], ev / v_sc[kk], ep, allowed_p))
+    print("worst (fraction of scale / of allowed):", worst)
+    return bad, worst
+
+
 # ------------------------------------------------------------------------------------------------------------- data parallel
 def dp_case(B, group, *, cfg_kw, batch_hook=None, calibrate_first=True):
     """The data-parallel tests' agent and minibatch: two-gripper rigid spec, ``seed=4`` fields, replicas from one seed, calibrated on the
