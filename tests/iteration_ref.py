@@ -32,7 +32,7 @@ VALUE_GAIN = 100.0
 DECAY, EPS, LOW, HIGH = 0.99999, 1e-2, -20.0, 20.0       # configs/rigid_insertion_multi_hepi_trpl_cfg.yaml:47-72
 VECTOR_KEYS, SCALAR_KEYS = ("position_vectors", "velocity_vectors"), ("scalars",)
 PPO_KEYS = ("action", "loc", "var", "sample_log_prob", "state_value", "advantage", "value_target")
-TOL = 1e-4              # tests/test_gpu_step.py
+TOL = 1e-4              # tests/oracle_cases.py
 NORM_TOL = 2e-5         # tests/test_gpu_transforms.py
 U32 = 2.0 ** -24
 
@@ -160,7 +160,7 @@ def ref_collect_step(oracle, obs, eps, action, loc_in=None, var_in=None):
 
 
 def tol_of(ref, tol=TOL) -> float:
-    """The absolute allowance of test_gpu_step.check: tol * max(1, the reference's largest entry)."""
+    """The absolute allowance of oracle_cases.check: tol * max(1, the reference's largest entry)."""
     return tol * max(1.0, float(torch.as_tensor(ref).abs().max()))
 
 

@@ -410,7 +410,7 @@ def test_node_mlp_bf16_build(n):
 def _attn_setup(B, precision):
     from geometry_rl_amd import agent
     from oracle import step as ost
-    from test_gpu_step import load_params, make_case
+    from oracle_cases import load_params, make_case
     from geometry_rl_amd import synthetic as syn
     dv = dev()
     o_spec, spec, kw, obs = make_case("rigid_attn", B)

@@ -25,7 +25,7 @@ LOSS_KEYS = ["loss_objective", "loss_trust_region", "loss_entropy", "loss_critic
 
 def _setup(B, n_links, precision="fp32", variable_length=True, seed=6):
     from geometry_rl_amd import agent, graph
-    from test_gpu_step import load_params
+    from oracle_cases import load_params
     dev = torch.device("cuda:0")
     o_spec = ogr.rope_spec(n_links=n_links, variable_length=variable_length)
     spec = graph.rope_spec(n_links=n_links, variable_length=variable_length)
@@ -53,7 +53,7 @@ def _setup(B, n_links, precision="fp32", variable_length=True, seed=6):
 @pytest.mark.parametrize("B,n_links", [(9, 20), (64, 80)])
 def test_variable_length_rope_matches_oracle(B, n_links):
     from geometry_rl_amd import agent
-    from test_gpu_step import check
+    from oracle_cases import check
     spec, cfg, oracle, actor, critic, loss, batch, dbatch = _setup(B, n_links)
     counts = batch["infos"][:, 0].long()
     assert counts.min() < counts.max() == n_links                       # the batch really mixes rope lengths

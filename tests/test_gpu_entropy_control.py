@@ -2,7 +2,7 @@
 path around it, on the GPU:
   * the kernel per op against tests/entropy_ref.py (float64, same fp32 inputs): sums, maxes, dmean, dsigma, proj_mean, proj_var over
     A_SWEEP x four projections x four modes and the batch / fold edges of B_SWEEP, with the allowances of tests/test_gpu_trpl_kernel.py
-    (its helpers are used as they are);
+    (tests/trpl_cases.py's comparisons, as they are);
   * an inactive stage is free of effect: beta = -inf (inequality) is BITWISE grl_trpl_fwd_bwd;
   * properties that need no reference (projected entropy == / >= beta; the KL bound's residual with the stage in front);
   * TRPLLoss.forward (opt-in) against the oracle actor + entropy_ref; compute_metrics' entropy_constraint;
@@ -17,7 +17,6 @@ import torch
 
 import entropy_cases as ec
 import entropy_ref
-import test_gpu_trpl_kernel as tk
 import trpl_cases as tc
 from geometry_rl_amd import ops
 from oracle import trpl as otr
@@ -45,14 +44,7 @@ def _check_case(e):
     ref = ec.reference(e, d)
     kap = tc.adv_error_bound(e.base, d)
     print(f"{e.name}: beta {d['beta']:.6f}, adv bound {kap:.2e}")
-    sums, maxes, dloc, dsigma, dvalue, pm, pv = _launch(e, d)
-    tk._sums_close("sums", sums, ref["sums"], e.base.B, kap * ref["sens_sums"])
-    tk._maxes_close("maxes", maxes, ref["maxes"])
-    tk._close("proj_mean", pm, ref["proj_mean"])
-    tk._close("proj_S", pv, ref["proj_S"])
-    tk._close("dloc", dloc, ref["dloc"], kap * ref["sens_dloc"])
-    tk._close("dsigma", dsigma, ref["dsigma"], kap * ref["sens_dsigma"])
-    tk._close("dvalue", dvalue, ref["dvalue"])
+    tc.launch_close(_launch(e, d), ref, e.base.B, kap)
 
 
 @pytest.mark.parametrize("e", ec.lane_cases(), ids=lambda e: e.name)
@@ -125,28 +117,19 @@ def _initial_of(batch):
 def test_loss_forward_matches_the_oracle_with_entropy_ref(proj_type, eq, first):
     """The small rigid HEPi case of tests/test_gpu_step.py: all 13 loss-dict entries and the actor's parameter gradients, at that file's
     tolerances, for update number 3 of a linear schedule."""
-    import test_gpu_step as ts
-    from oracle import step as ost
+    import oracle_cases as oc
     from geometry_rl_amd import agent, synthetic as syn
-    from parity_util import G_TOL, grad_error, grad_scales
     B, step, total = 24, 3, 10
-    o_spec, spec, kw, obs = ts.make_case("rigid_g1", B)
+    o_spec, spec, kw, obs = oc.make_case("rigid_g1", B)
     kw = dict(kw, proj_type=proj_type, trust_region_coeff=2.0)
     batch = dict(obs)
     batch.update(syn.make_ppo_fields(B, 6, seed=B))
     initial = float(_initial_of(batch))
     ekw = dict(entropy_schedule="linear", target_entropy=initial + 4.0, entropy_eq=eq, entropy_first=first, total_train_steps=total)
-    a_par, c_par = ost.init_agent_params(o_spec, ost.AgentConfig(**kw), seed=11)
-    oracle = ost.OracleAgent(o_spec, ost.AgentConfig(**kw), a_par, c_par)
-    actor, critic, proj, loss = agent.build_agent(spec, agent.AgentConfig(**kw, **ekw), device=DEV)
-    ts.load_params(actor, a_par, DEV)
-    ts.load_params(critic, {"_network1." + k: v for k, v in c_par.items()}, DEV)
+    pair = oc.build_pair((o_spec, spec, kw), seed=11, d_kw=ekw, dev=DEV)
+    oracle, actor, proj, loss = pair.oracle, pair.actor, pair.proj, pair.loss
     dbatch = {k: v.to(DEV) for k, v in batch.items()}
-    with torch.no_grad():
-        oracle.actor_forward({k: batch[k] for k in o_spec.in_features}, calibrate=True)
-        actor.forward_diag(*[dbatch[k] for k in spec.in_features], train=True)
-    actor.load_state_dict({k: v.detach().to(DEV) for k, v in oracle.actor.items()}, strict=False)
-    actor._calib_checked = True
+    oc.adopt_calibration(pair, batch, device_first=True)
     upd = agent.PolicyUpdater(loss, lr=3e-4)
     upd.gflat.zero_()
     loss._global_steps = step
@@ -157,15 +140,9 @@ def test_loss_forward_matches_the_oracle_with_entropy_ref(proj_type, eq, first):
     (out["loss_objective"] + out["loss_entropy"] + out["loss_trust_region"]).backward()
     with tc.w2nc_registered(), entropy_ref.registered(beta, eq, first):
         ref, ref_grads = oracle.update(batch)
-    for k in ts.LOSS_KEYS:
-        ts.check(k, out[k], ref[k])
-    scales = grad_scales(ref_grads["actor"])
-    bad = []
-    for k, p in actor.named_parameters():
-        if k in ref_grads["actor"]:
-            err, sc = grad_error(p.grad, ref_grads["actor"][k]), scales[k]
-            if not (np.isfinite(err) and err <= G_TOL * sc):
-                bad.append((k, err, sc))
+    for k in oc.LOSS_KEYS:
+        oc.check(k, out[k], ref[k])
+    bad, _ = oc.gradients_off_scale(actor, pair.critic, ref_grads, nets=("actor",))
     assert not bad, bad
     # compute_metrics of the scheduled layer: entropy_constraint = mean(entropy - bound(step)) (base_projection_layer.py:380-382)
     p = (out["loc"].detach(), (out["sigma"].detach() ** 2).diag_embed())

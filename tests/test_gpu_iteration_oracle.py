@@ -38,8 +38,7 @@ import torch
 
 import iteration_ref as ir
 import train_ops_ref
-from test_gpu_multistep_oracle import M_TOL, V_TOL
-from test_gpu_step import LOSS_KEYS, TOL, check, load_params
+from oracle_cases import LOSS_KEYS, M_TOL, TOL, V_TOL, cap_oracle_threads, check, load_params
 from updater_cases import merge_grad_scales, moments_and_params_after
 
 pytestmark = pytest.mark.gpu
@@ -120,7 +119,7 @@ def _ratio(got, ref, allow):
 
 
 def test_two_iterations_match_the_oracle():
-    torch.set_num_threads(min(16, torch.get_num_threads()))   # the oracle: more intra-op threads than this only slow its small CPU ops down
+    cap_oracle_threads()
     worst = {}
 
     def note(name, r):

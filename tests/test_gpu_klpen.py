@@ -12,18 +12,17 @@ torchrl is not installed here: the restatement is UNPINNED (tests/klpen_ref.py).
 import contextlib
 import ctypes
 import functools
-import os
 
-import numpy as np
 import pytest
 import torch
 
-from oracle import step as ost
+import oracle_cases as oc
 from oracle import trpl as otr
 from geometry_rl_amd import synthetic as syn
 from klpen_ref import KLPenOracleAgent, klpen_loss, thresholds
-from parity_util import adam_first_step_bound, grad_scales
-from updater_cases import DEV, dp_case, dp_ref, make_rollout, run_loop_and_launches, run_step_modes, snapshot, spawn_dp
+from oracle_cases import M_TOL, V_TOL
+from updater_cases import (DEV, assert_stats_means, dp_case, dp_ref, make_rollout, moments_and_params_after, run_loop_and_launches,
+                           run_stats_epoch, run_step_modes, snapshot, spawn_dp)
 
 pytestmark = pytest.mark.gpu
 
@@ -179,14 +178,6 @@ def test_adapt_launch(factor, want):
 
 
 # ------------------------------------------------------------------------------------------------------------- (c) vs oracle
-def _obs(name, B, seed):
-    if name == "rigid_g1":
-        return syn.make_rigid_obs(B, seed=seed)
-    if name == "cloth":
-        return syn.make_cloth_obs(B, n_particles=25, E_cloth=40, seed=seed)
-    return syn.make_rigid_obs(B, G=2, angular_velocity=False, object_velocity=False, seed=seed)
-
-
 def _fields(B, A, seed, spread):
     """syn.make_ppo_fields with the old means drawn ``spread`` wide: the old distribution's KL to a fresh policy (mean ~ 0, variance ~ 1)
     grows with spread^2, which is how the steps of one case land on different sides of the thresholds."""
@@ -213,33 +204,29 @@ DTARG = {"rigid_g1": 1.0, "cloth": 2.0, "empn_g2": 1.0}
 def oracle_sequence(name, B, K, dtarg):
     """The oracle's side of (c), CPU only: -> everything the GPU side needs."""
     from geometry_rl_amd import agent
-    from test_gpu_step import make_case
-    torch.set_num_threads(min(32, os.cpu_count() or 1))
-    o_spec, spec, kw, _ = make_case(name, B)
-    o_cfg = ost.AgentConfig(**dict(kw, critic_coef=1.0, entropy_coef=0.0, clip_grad_norm=True))
+    oc.cap_oracle_threads()
+    o_spec, spec, kw, _ = oc.make_case(name, B)
     cfg = agent.AgentConfig(**dict(kw, dtarg=dtarg, **KL_KW))
-    a_par, c_par = ost.init_agent_params(o_spec, o_cfg, seed=21)
-    oracle = KLPenOracleAgent(o_spec, o_cfg, a_par, c_par)
+    o_cfg, a_par, c_par, oracle = oc.make_oracle(o_spec, dict(kw, critic_coef=1.0, entropy_coef=0.0, clip_grad_norm=True), 21, KLPenOracleAgent)
     oracle.dtarg = dtarg
     A = spec.num_actuators * cfg.output_dim_vec * 3
     batches = []
     for i in range(K):
-        b = dict(_obs(name, B, 30 + i))
+        b = dict(oc.obs_of(name, B, 30 + i))
         b.update(_fields(B, A, 40 + i, SPREADS[i]))
         batches.append(b)
     with torch.no_grad():
         oracle.actor_forward({k: batches[0][k] for k in o_spec.in_features}, calibrate=True)
     calibrated = {k: v.detach().clone() for k, v in oracle.actor.items()}
     steps = [oracle.update(b) for b in batches]
-    return spec, cfg, a_par, c_par, calibrated, batches, steps, oracle
+    return o_spec, spec, o_cfg, cfg, a_par, c_par, calibrated, batches, steps, oracle
 
 
 @pytest.mark.parametrize("name,B,K", [("rigid_g1", 64, 5), ("cloth", 16, 5), ("empn_g2", 32, 5)])
 def test_five_updates_match_the_klpen_oracle(name, B, K):
     from geometry_rl_amd import agent
-    from test_gpu_step import load_params
     dtarg = DTARG[name]
-    spec, cfg, a_par, c_par, calibrated, batches, steps, oracle = oracle_sequence(name, B, K, dtarg)
+    o_spec, spec, o_cfg, cfg, a_par, c_par, calibrated, batches, steps, oracle = oracle_sequence(name, B, K, dtarg)
     hi, lo = thresholds(dtarg)
     kls = [float(ref["kl"]) for ref, _ in steps]
     betas = [ref["beta"] for ref, _ in steps] + [steps[-1][0]["beta_next"]]
@@ -248,49 +235,27 @@ def test_five_updates_match_the_klpen_oracle(name, B, K):
         assert abs(kl - hi) >= 0.05 * hi and abs(kl - lo) >= 0.05 * lo, (kl, lo, hi)
     moves = [b1 / b0 for b0, b1 in zip(betas[:-1], betas[1:])]
     assert 2.0 in moves and 0.5 in moves, moves   # beta rises and falls within the five steps
-    actor, critic, proj, loss = agent.build_agent(spec, cfg, device=DEV)
-    assert proj is None and loss.algorithm == "kl_ppo"
-    load_params(actor, a_par, DEV)
-    load_params(critic, {"_network1." + k: v for k, v in c_par.items()}, DEV)
-    actor.load_state_dict({k: v.to(DEV) for k, v in calibrated.items()}, strict=False)
-    for mod in actor.modules():
-        if hasattr(mod, "callibrated"):
-            mod.callibrated.fill_(True)
-    actor._calib_checked = True
+    pair = oc.Pair(o_spec, spec, o_cfg, cfg, oracle, *oc.make_device(spec, cfg, a_par, c_par, DEV))
+    loss = pair.loss
+    assert pair.proj is None and loss.algorithm == "kl_ppo"
+    oc.adopt_calibration(pair, weights=calibrated)
     upd = agent.PolicyUpdater(loss, lr=cfg.lr, clip_grad_norm=cfg.clip_grad_norm, max_grad_norm=cfg.max_grad_norm, use_graph=True)
-    g_scale = None
-    for i, b in enumerate(batches):
-        ref, ref_grads = steps[i]
-        assert float(loss.beta) == ref["beta"], (i, float(loss.beta), ref["beta"])
-        out = upd.step({k: v.to(DEV) for k, v in b.items()})
+
+    def beta_is(i):   # in front of update i the device holds the beta the oracle ran that update with
+        assert float(loss.beta) == steps[i][0]["beta"], (i, float(loss.beta), steps[i][0]["beta"])
+
+    def per_step(i, out, ref):
         assert set(out) >= {"loss_objective", "loss_critic", "kl", "entropy", "loss_entropy"} and "ESS" not in out
         assert float(loss.beta) == ref["beta_next"], (i, float(loss.beta), ref["beta_next"])   # x2 and x0.5 are exact
-        sc = {net: grad_scales(ref_grads[net]) for net in ("actor", "critic")}
-        g_scale = sc if g_scale is None else {net: {k: max(v, g_scale[net].get(k, 0.0)) for k, v in sc[net].items()} for net in sc}
         for k in ("loss_objective", "loss_critic", "loss_entropy", "entropy", "kl"):
             e = abs(float(out[k]) - float(ref[k]))
             assert e <= 1e-4 * max(1.0, abs(float(ref[k]))), (i, k, e)
+        if i + 1 < K:
+            beta_is(i + 1)
+    beta_is(0)
+    g_scale = oc.run_updates(pair, batches, upd, per_step, refs=steps)
     assert upd.mode.startswith("graph") and upd._program is not None
-    torch.cuda.synchronize()
-    off = lambda p: (p.data_ptr() - upd.flat.data_ptr()) // 4
-    bad = []
-    for net, mod, ref_p, optim, strip in (("actor", actor, oracle.actor, oracle.actor_optim, 0),
-                                          ("critic", critic, oracle.critic, oracle.critic_optim, len("_network1."))):
-        states = {kk: optim.state.get(ref_p[kk], {}) for kk in ref_p}
-        m_ref = {kk: s_["exp_avg"] for kk, s_ in states.items() if "exp_avg" in s_}
-        v_ref = {kk: s_["exp_avg_sq"] for kk, s_ in states.items() if "exp_avg_sq" in s_}
-        m_sc, v_sc = grad_scales(m_ref), grad_scales(v_ref)
-        for k, p in mod.named_parameters():
-            kk = k[strip:]
-            if kk not in m_ref:
-                continue
-            o, n = off(p), p.numel()
-            em = float((upd.exp_avg[o:o + n].view_as(p).cpu().double() - m_ref[kk].double()).abs().max())
-            ev = float((upd.exp_avg_sq[o:o + n].view_as(p).cpu().double() - v_ref[kk].double()).abs().max())
-            ep = float((p.detach().cpu().double() - ref_p[kk].detach().double()).abs().max())
-            allowed_p = K * adam_first_step_bound(cfg.lr, 1e-5, g_scale[net].get(kk, 0.0), cfg.clip_grad_norm, p_ref=ref_p[kk])
-            if not (em <= 5e-4 * m_sc[kk] and ev <= 1e-3 * v_sc[kk] and ep <= allowed_p and np.isfinite(em + ev + ep)):
-                bad.append((net, kk, em / m_sc[kk], ev / v_sc[kk], ep, allowed_p))
+    bad, _ = moments_and_params_after(upd, pair.actor, pair.critic, oracle, cfg, g_scale, K, M_TOL, V_TOL)
     assert not bad, bad
 
 
@@ -402,11 +367,10 @@ def test_statistics_carry_the_modes_keys():
     """track_stats through the multi-step launches: the keys of klpen.report_dict plus loss_objective and loss_critic, their means those
     of the per-step reports, the update bitwise the one without tracking; the iteration log carries train/kl and train/kl_beta."""
     from geometry_rl_amd.rollout import RolloutDriver
-    from test_gpu_training_log import _check_means, _run
     cfg_kw = dict(algorithm="kl_ppo", dtarg=1.0)
-    ref_upd, ref_r, _, vals = _run("launches", False, cfg_kw, KEYS)
-    upd, r, buf, _ = _run("launches", True, cfg_kw, KEYS)
-    _check_means(upd.stats_read(), vals, KEYS)
+    ref_upd, ref_r, _, vals = run_stats_epoch("launches", False, cfg_kw, KEYS)
+    upd, r, buf, _ = run_stats_epoch("launches", True, cfg_kw, KEYS)
+    assert_stats_means(upd.stats_read(), vals, KEYS)
     for a, b in zip(snapshot(upd, None)[:3], snapshot(ref_upd, None)[:3]):
         assert torch.equal(a, b), float((a - b).abs().max())
     assert torch.equal(r.loss.beta, ref_r.loss.beta)

@@ -76,7 +76,7 @@ def _err(got, ref):
 def _run(name, B, with_f64):
     """One update on both sides -> {tensor name: (abs err, scale, tol)} (+ the f64 attribution table)."""
     from geometry_rl_amd import agent
-    from test_gpu_step import load_params
+    from oracle_cases import load_params
     dev = torch.device("cuda:0")
     o_spec, spec, kw, obs = _case(name, B)
     o_cfg, cfg = ost.AgentConfig(**kw), agent.AgentConfig(**kw)

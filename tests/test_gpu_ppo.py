@@ -6,17 +6,16 @@
   (e) two data-parallel ranks against one rank on the whole batch;
   (f) the reference loop protocol (loss_module(td), two backward passes, two Adam steps) against PolicyUpdater.step."""
 import math
-import os
 
-import numpy as np
 import pytest
 import torch
 
-from oracle import step as ost
+import oracle_cases as oc
 from geometry_rl_amd import synthetic as syn
-from parity_util import adam_first_step_bound, grad_scales
+from oracle_cases import M_TOL, V_TOL
 from ppo_ref import PPOOracleAgent, ppo_loss
-from updater_cases import DEV, assert_ranks_match, dp_ref, make_rollout, run_loop_and_launches, run_step_modes, run_two_ranks
+from updater_cases import (DEV, assert_ranks_match, dp_ref, make_rollout, moments_and_params_after, run_loop_and_launches, run_step_modes,
+                           run_two_ranks)
 
 pytestmark = pytest.mark.gpu
 
@@ -84,81 +83,39 @@ def test_kernel_matches_the_restatement(A):
 
 
 # ------------------------------------------------------------------------------------------------------------- (b) vs oracle
-def _obs(name, B, seed):
-    if name == "rigid_g1":
-        return syn.make_rigid_obs(B, seed=seed)
-    if name == "cloth":
-        return syn.make_cloth_obs(B, n_particles=25, E_cloth=40, seed=seed)
-    return syn.make_rigid_obs(B, G=2, angular_velocity=False, object_velocity=False, seed=seed)
-
-
 PPO_KW = dict(algorithm="ppo", clip_epsilon=0.2, critic_coef=1.0, clip_value=0.2, clip_grad_norm=True, max_grad_norm=1.0)   # objective/default.yaml
 
 
 @pytest.mark.parametrize("name,B,K", [("rigid_g1", 64, 5), ("cloth", 16, 5), ("empn_g2", 32, 5)])
 def test_five_updates_match_the_ppo_oracle(name, B, K):
     from geometry_rl_amd import agent
-    from test_gpu_step import load_params, make_case
-    torch.set_num_threads(min(32, os.cpu_count() or 1))
-    o_spec, spec, kw, _ = make_case(name, B)
-    o_cfg = ost.AgentConfig(**dict(kw, critic_coef=1.0, clip_value=0.2, clip_grad_norm=True))
-    cfg = agent.AgentConfig(**dict(kw, **PPO_KW))
-    a_par, c_par = ost.init_agent_params(o_spec, o_cfg, seed=21)
-    oracle = PPOOracleAgent(o_spec, o_cfg, a_par, c_par)
-    actor, critic, proj, loss = agent.build_agent(spec, cfg, device=DEV)
-    assert proj is None
-    load_params(actor, a_par, DEV)
-    load_params(critic, {"_network1." + k: v for k, v in c_par.items()}, DEV)
+    oc.cap_oracle_threads()
+    pair = oc.build_pair(name, B, seed=21, o_kw=dict(critic_coef=1.0, clip_value=0.2, clip_grad_norm=True), d_kw=PPO_KW,
+                         oracle_cls=PPOOracleAgent)
+    spec, cfg, loss = pair.spec, pair.cfg, pair.loss
+    assert pair.proj is None
     A = spec.num_actuators * cfg.output_dim_vec * 3
     batches = []
     for i in range(K):
-        b = dict(_obs(name, B, 30 + i))
+        b = dict(oc.obs_of(name, B, 30 + i))
         b.update(syn.make_ppo_fields(B, A, seed=40 + i))
         batches.append(b)
-    with torch.no_grad():
-        oracle.actor_forward({k: batches[0][k] for k in o_spec.in_features}, calibrate=True)
-    actor.load_state_dict({k: v.detach().to(DEV) for k, v in oracle.actor.items()}, strict=False)
-    for mod in actor.modules():
-        if hasattr(mod, "callibrated"):
-            mod.callibrated.fill_(True)
-    actor._calib_checked = True
+    oc.adopt_calibration(pair, batches[0])
     upd = agent.PolicyUpdater(loss, lr=cfg.lr, clip_grad_norm=cfg.clip_grad_norm, max_grad_norm=cfg.max_grad_norm, use_graph=True)
-    g_scale = None
     clipped_frac = []
-    for i, b in enumerate(batches):
-        ref, ref_grads = oracle.update(b)
-        out = upd.step({k: v.to(DEV) for k, v in b.items()})
+
+    def per_step(i, out, ref):
         assert set(out) >= {"loss_objective", "loss_critic", "ESS", "entropy", "loss_entropy"} and "kl" not in out
         lw = ref["lw"]
         clipped_frac.append(float(((lw > math.log1p(0.2)) | (lw < math.log1p(-0.2))).double().mean()))
-        sc = {net: grad_scales(ref_grads[net]) for net in ("actor", "critic")}
-        g_scale = sc if g_scale is None else {net: {k: max(v, g_scale[net].get(k, 0.0)) for k, v in sc[net].items()} for net in sc}
         for k in ("loss_objective", "loss_critic", "loss_entropy", "entropy", "ESS"):
             e = abs(float(out[k]) - float(ref[k]))
             assert e <= 1e-4 * max(1.0, abs(float(ref[k]))), (i, k, e)
+    g_scale = oc.run_updates(pair, batches, upd, per_step)
     print("fraction of frames outside the clip bounds per update:", clipped_frac)
     assert min(clipped_frac) > 0.0   # the clipped branch is exercised
     assert upd.mode.startswith("graph") and upd._program is not None
-    torch.cuda.synchronize()
-    off = lambda p: (p.data_ptr() - upd.flat.data_ptr()) // 4
-    bad = []
-    for net, mod, ref_p, optim, strip in (("actor", actor, oracle.actor, oracle.actor_optim, 0),
-                                          ("critic", critic, oracle.critic, oracle.critic_optim, len("_network1."))):
-        states = {kk: optim.state.get(ref_p[kk], {}) for kk in ref_p}
-        m_ref = {kk: s_["exp_avg"] for kk, s_ in states.items() if "exp_avg" in s_}
-        v_ref = {kk: s_["exp_avg_sq"] for kk, s_ in states.items() if "exp_avg_sq" in s_}
-        m_sc, v_sc = grad_scales(m_ref), grad_scales(v_ref)
-        for k, p in mod.named_parameters():
-            kk = k[strip:]
-            if kk not in m_ref:
-                continue
-            o, n = off(p), p.numel()
-            em = float((upd.exp_avg[o:o + n].view_as(p).cpu().double() - m_ref[kk].double()).abs().max())
-            ev = float((upd.exp_avg_sq[o:o + n].view_as(p).cpu().double() - v_ref[kk].double()).abs().max())
-            ep = float((p.detach().cpu().double() - ref_p[kk].detach().double()).abs().max())
-            allowed_p = K * adam_first_step_bound(cfg.lr, 1e-5, g_scale[net].get(kk, 0.0), cfg.clip_grad_norm, p_ref=ref_p[kk])
-            if not (em <= 5e-4 * m_sc[kk] and ev <= 1e-3 * v_sc[kk] and ep <= allowed_p and np.isfinite(em + ev + ep)):
-                bad.append((net, kk, em / m_sc[kk], ev / v_sc[kk], ep, allowed_p))
+    bad, _ = moments_and_params_after(upd, pair.actor, pair.critic, pair.oracle, cfg, g_scale, K, M_TOL, V_TOL)
     assert not bad, bad
 
 

@@ -2,92 +2,15 @@
 gradients, and the parameters after one Adam step -- on identical parameters and inputs.  Tolerance 1e-4 (north_star) for the values;
 every gradient tensor within 2e-4 of ITS OWN largest reference entry and the post-Adam parameters within what that gradient tolerance
 implies through Adam's first step (tests/parity_util.py); several consecutive updates: tests/test_gpu_multistep_oracle.py."""
-import numpy as np
 import pytest
 import torch
 
-from oracle import graph as ogr, step as ost, trpl as otr
+import oracle_cases as oc
+from oracle import trpl as otr
 from geometry_rl_amd import synthetic as syn
-from parity_util import G_TOL, adam_first_step_bound, adam_first_step_bound_elem, grad_error, grad_scales, param_excess
+from oracle_cases import LOSS_KEYS, check
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-4
-LOSS_KEYS = ["loss_objective", "loss_trust_region", "loss_entropy", "loss_critic", "ESS", "kl", "constraint", "mean_constraint",
-             "mean_constraint_max", "cov_constraint", "cov_constraint_max", "entropy", "entropy_diff"]
-
-
-def check(name, got, ref, tol=TOL):
-    got, ref = torch.as_tensor(got).detach().cpu().double(), torch.as_tensor(ref).detach().cpu().double()
-    assert got.shape == ref.shape, (name, got.shape, ref.shape)
-    err = (got - ref).abs().max().item() if got.numel() else 0.0
-    scale = max(1.0, ref.abs().max().item()) if ref.numel() else 1.0
-    print(f"{name}: max|err|={err:.3e} ref_max={ref.abs().max().item() if ref.numel() else 0:.3e}")
-    assert np.isfinite(err) and err <= tol * scale, f"{name}: err {err:.3e} > {tol * scale:.3e}"
-
-
-def make_case(name, B):
-    from geometry_rl_amd import agent, graph
-    if name == "rigid_g1":
-        o_spec, spec = ogr.rigid_spec(), graph.rigid_spec()
-        kw = dict(only_upper_hemisphere=True, output_dim=2, output_dim_vec=2)
-        obs = syn.make_rigid_obs(B, seed=3)
-    elif name in ("rigid_tiny", "rigid_one"):
-        # edge cases of the ragged graph: samples with 1, 2 and 3 valid object points (fewer than the k = 3 neighbours kNN asks
-        # for: missing neighbours give no edge; a 1-point sample has no internal edge at all), next to a full 32-point sample;
-        # "rigid_one": a single frame (the advantage is not normalised for a batch of one, trpl.py:248)
-        o_spec, spec = ogr.rigid_spec(), graph.rigid_spec()
-        kw = dict(only_upper_hemisphere=True, output_dim=2, output_dim_vec=2)
-        obs = syn.make_rigid_obs(B, seed=9)
-        P = 32
-        counts = torch.tensor([1, 2, 3, 32, 5, 4])[torch.arange(B) % 6] if name == "rigid_tiny" else torch.tensor([7])
-        valid = (torch.arange(P)[None, :] < counts[:, None]).float()[..., None]
-        pos = obs["position_vectors"].clone()
-        G = 1
-        gen = torch.Generator().manual_seed(99)
-        for blk in range(2):  # object points, target points: fresh distinct positions (coincident points = kNN ties), then padding
-            sl = slice(3 * G + blk * 3 * P, 3 * G + (blk + 1) * 3 * P)
-            pos[:, sl] = ((torch.rand(B, P, 3, generator=gen) * 2 - 1) * valid).reshape(B, -1)
-        obs["position_vectors"] = pos
-        obs["infos"][:, 0] = counts.float()
-    elif name == "rigid_g2":
-        o_spec = ogr.rigid_spec(G=2, angular_velocity=False, object_velocity=False)
-        spec = graph.rigid_spec(G=2, angular_velocity=False, object_velocity=False)
-        kw = dict()
-        obs = syn.make_rigid_obs(B, G=2, angular_velocity=False, object_velocity=False, seed=4)
-    elif name == "empn_g2":
-        o_spec = ogr.rigid_spec(G=2, angular_velocity=False, object_velocity=False)
-        spec = graph.rigid_spec(G=2, angular_velocity=False, object_velocity=False)
-        kw = dict(model="empn")
-        obs = syn.make_rigid_obs(B, G=2, angular_velocity=False, object_velocity=False, seed=8)
-    elif name == "rigid_attn":   # FiberBundleConv(aggr="AttentionalAggregation") in every round (hepi_attention.yaml)
-        o_spec = ogr.rigid_spec(G=2, angular_velocity=False, object_velocity=False)
-        spec = graph.rigid_spec(G=2, angular_velocity=False, object_velocity=False)
-        kw = dict(aggr="AttentionalAggregation")
-        obs = syn.make_rigid_obs(B, G=2, angular_velocity=False, object_velocity=False, seed=14)
-    elif name in ("rigid_frob", "rigid_w2"):   # the other two projection layers (frob_projection_layer.py, w2_projection_layer.py)
-        o_spec = ogr.rigid_spec(G=2, angular_velocity=False, object_velocity=False)
-        spec = graph.rigid_spec(G=2, angular_velocity=False, object_velocity=False)
-        kw = dict(proj_type=name.split("_")[1], trust_region_coeff=2.0)
-        obs = syn.make_rigid_obs(B, G=2, angular_velocity=False, object_velocity=False, seed=12)
-    elif name == "cloth":
-        o_spec, spec = ogr.cloth_spec(n_particles=25, E_cloth=40), graph.cloth_spec(n_particles=25, E_cloth=40)
-        kw = dict(trust_region_coeff=4.0, cov_bound=0.001)
-        obs = syn.make_cloth_obs(B, n_particles=25, E_cloth=40, seed=5)
-    elif name == "rope":
-        o_spec, spec = ogr.rope_spec(n_links=20), graph.rope_spec(n_links=20)
-        kw = dict(dim=2, clip_grad_norm=True)
-        obs = syn.make_rope_obs(B, n_links=20, seed=6)
-    return o_spec, spec, kw, obs
-
-
-def load_params(module, params, dev):
-    sd = module.state_dict()
-    for k, v in params.items():
-        assert k in sd, k
-        assert sd[k].shape == v.shape, (k, sd[k].shape, v.shape)
-    missing = [k for k in sd if k not in params and not k.endswith("callibrated")]
-    assert not missing, missing
-    module.load_state_dict({k: v.to(dev) for k, v in params.items()}, strict=False)
 
 
 @pytest.mark.parametrize("name,B", [("rigid_g1", 24), ("rigid_g2", 16), ("cloth", 8), ("rope", 8), ("empn_g2", 12),
@@ -95,30 +18,20 @@ def load_params(module, params, dev):
 def test_policy_update_step(name, B):
     from geometry_rl_amd import agent
     dev = torch.device("cuda:0")
-    o_spec, spec, kw, obs = make_case(name, B)
-    o_cfg = ost.AgentConfig(**kw)
-    cfg = agent.AgentConfig(**kw)
-    a_par, c_par = ost.init_agent_params(o_spec, o_cfg, seed=11)
-    oracle = ost.OracleAgent(o_spec, o_cfg, a_par, c_par)
-    actor, critic, proj, loss = agent.build_agent(spec, cfg, device=dev)
-    load_params(actor, a_par, dev)
-    load_params(critic, {"_network1." + k: v for k, v in c_par.items()}, dev)
+    o_spec, spec, kw, obs = oc.make_case(name, B)
+    pair = oc.build_pair((o_spec, spec, kw), seed=11)
+    cfg, oracle, actor, critic, loss = pair.cfg, pair.oracle, pair.actor, pair.critic, pair.loss
     A = spec.num_actuators * cfg.output_dim_vec * 3
     batch = dict(obs)
     batch.update(syn.make_ppo_fields(B, A, seed=B))
     dbatch = {k: v.to(dev) for k, v in batch.items()}
-    obs_d = [dbatch[k] for k in spec.in_features]
 
     # --- calibration (first training call) must reproduce the reference re-initialisation
-    with torch.no_grad():
-        oracle.actor_forward({k: batch[k] for k in o_spec.in_features}, calibrate=True)
-        actor.forward_diag(*obs_d, train=True)
+    own = oc.adopt_calibration(pair, batch, device_first=True)
     for k, v in oracle.actor.items():
         if "kernel.weight" in k:
-            check("calibrated " + k, actor.state_dict()[k], v, 1e-4)
-    # continue from bit-identical (oracle-calibrated) weights so that the update comparison below isolates the update itself
-    actor.load_state_dict({k: v.detach().to(dev) for k, v in oracle.actor.items()}, strict=False)
-    actor._calib_checked = True
+            check("calibrated " + k, own[k], v, 1e-4)
+    # (both sides continue from bit-identical, oracle-calibrated weights so that the update comparison below isolates the update itself)
 
     # --- one full update on both sides
     upd = agent.PolicyUpdater(loss, lr=cfg.lr, clip_grad_norm=cfg.clip_grad_norm, max_grad_norm=cfg.max_grad_norm)
@@ -133,33 +46,11 @@ def test_policy_update_step(name, B):
     check("state_value", out["state_value"], ref["state_value"])
     for k in LOSS_KEYS:
         check(k, out[k], ref[k])
-    # every gradient tensor against its OWN scale (parity_util: 2e-4 of the tensor's largest reference entry, no max(1, .) floor)
-    scales = {"actor": grad_scales(ref_grads["actor"]), "critic": grad_scales(ref_grads["critic"])}
-    got = {"actor": {k: p.grad for k, p in actor.named_parameters() if k in ref_grads["actor"]},
-           "critic": {k[len("_network1."):]: p.grad for k, p in critic.named_parameters()}}
-    bad = []
-    for net in ("actor", "critic"):
-        for k, g in got[net].items():
-            e, sc = grad_error(g, ref_grads[net][k]), scales[net][k]
-            print(f"grad {net} {k}: err {e:.3e} = {e / sc:.2e} of its scale {sc:.3e}")
-            if not (np.isfinite(e) and e <= G_TOL * sc):
-                bad.append((net, k, e, sc))
+    bad, scales = oc.gradients_off_scale(actor, critic, ref_grads)
     assert not bad, bad
     # --- Adam: run the real step from the same starting point (parameters untouched so far)
-    out2 = upd.step(dbatch)
-    bad = []
-    for net, mod, ref_p, strip in (("actor", actor, oracle.actor, 0), ("critic", critic, oracle.critic, len("_network1."))):
-        for k, p in mod.named_parameters():
-            kk = k[strip:]
-            # entry-wise allowance from the reference gradient (parity_util); with gradient clipping Adam sees rescaled gradients: per tensor
-            if cfg.clip_grad_norm or kk not in ref_grads[net]:
-                allowed = adam_first_step_bound(cfg.lr, 1e-5, scales[net].get(kk, 0.0), clip=cfg.clip_grad_norm, p_ref=ref_p[kk])
-            else:
-                allowed = adam_first_step_bound_elem(cfg.lr, 1e-5, ref_grads[net][kk], scales[net][kk], p_ref=ref_p[kk])
-            e, x = grad_error(p, ref_p[kk]), param_excess(p, ref_p[kk], allowed)
-            print(f"param {net} {kk}: err {e:.3e} = {x:.2f} of allowed")
-            if not (np.isfinite(x) and x <= 1.0):
-                bad.append((net, kk, e, x))
+    upd.step(dbatch)
+    bad = oc.first_step_params_off(actor, critic, oracle, cfg, ref_grads, scales)
     assert not bad, bad
 
 

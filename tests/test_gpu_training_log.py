@@ -9,75 +9,22 @@ import pytest
 import torch
 
 import stats_ref
-from updater_cases import DEV, dp_ref, make_rollout, snapshot, spawn_dp
+from updater_cases import DEV, STATS_FORMS as FORMS, STATS_N as N, STATS_T as T, assert_stats_means, dp_ref, make_rollout, run_stats_epoch, snapshot, spawn_dp
 
 pytestmark = pytest.mark.gpu
-N, T = 16, 12     # 16 frames per minibatch, 12 minibatches: one epoch of the rigid synthetic rollout
 TRPL_KEYS = ("loss_objective", "loss_critic", "loss_trust_region", "loss_entropy", "kl", "constraint", "mean_constraint", "mean_constraint_max",
              "cov_constraint", "cov_constraint_max", "entropy", "entropy_diff", "ESS")
 PPO_KEYS = ("loss_objective", "loss_critic", "ESS", "entropy", "loss_entropy")
-
-FORMS = {   # form -> (PolicyUpdater keywords, the calls of the tracked run as row ranges, the calls of the step-by-step run)
-    "one_stream": (dict(use_graph=True, overlap_critic=False), None, None),
-    "lanes": (dict(use_graph=True), None, None),
-    # unroll = 4: one eager step, two launches of four steps, three single steps
-    "launches": (dict(use_graph=True), [(0, 12)], [(0, 1), (1, 5), (5, 9), (9, 10), (10, 11), (11, 12)]),
-    "eager": (dict(use_graph=False), None, None),
-}
-
-
-def _run(form, track, cfg_kw, keys):
-    """The 12 minibatches of one epoch through ``form`` -> (updater, rollout, buffer, every step's reported values [12] as dicts of 0-d
-    tensors -- collected only with tracking off, where the sequence is cut into calls whose steps can all be read)."""
-    from geometry_rl_amd import agent
-    from geometry_rl_amd.rollout import RolloutBuffer, RolloutDriver
-    kw, tracked_calls, stepwise_calls = FORMS[form]
-    r = make_rollout(N, T, 21, **cfg_kw)
-    upd = agent.PolicyUpdater(r.loss, lr=r.cfg.lr, **kw, **(dict(track_stats=True) if track else {}))
-    upd.autotune_form = False
-    buf = RolloutBuffer(dict(r.data))
-    drv = RolloutDriver(upd, r.spec, ppo_epochs=1, seed=3)
-    drv.compute_advantages(buf, r.next_last)
-    rows = torch.stack(drv.epoch_minibatches(N, T, DEV))
-    assert rows.shape == (T, N)
-    vals = []
-    if tracked_calls is None:
-        for j in range(T):
-            out = upd.step_from(buf, rows[j])
-            if not track:
-                vals.append({k: out[k].clone() for k in keys})
-    else:
-        for lo, hi in (tracked_calls if track else stepwise_calls):
-            out = upd.run_minibatches(buf, rows[lo:hi], unroll=4)
-            if not track:
-                outs = upd.last_outs if hi - lo == 4 else [out]
-                assert len(outs) == hi - lo
-                vals += [{k: o[k].clone() for k in keys} for o in outs]
-        assert upd._epoch is not None, "the multi-step launch was not taken"
-    torch.cuda.synchronize()
-    assert upd.steps == T
-    return upd, r, buf, vals
-
-
-def _check_means(means, vals, keys):
-    assert means["updates"] == T
-    assert set(means) == set(keys) | {"updates"}, sorted(means)
-    for k in keys:
-        v = [float(s[k]) for s in vals]
-        want = math.fsum(v) / T
-        bound = T * 2.0 ** -53 * max(abs(x) for x in v)
-        print(f"{k}: mean {means[k]!r}, fsum / {T} = {want!r}, |diff| {abs(means[k] - want):.3e} (bound {bound:.3e})")
-        assert isinstance(means[k], float) and abs(means[k] - want) <= bound, (k, means[k], want)
 
 
 @pytest.mark.parametrize("form", list(FORMS))
 def test_means_of_twelve_updates_and_the_update_is_unchanged(form):
     """stats_read() after 12 minibatches = the fp64 mean of the values the steps report (to 12 * 2^-53 * max |v| of math.fsum / 12), the
     count is 12, and parameters and both Adam moments are bitwise those of the run without tracking."""
-    ref_upd, _, _, vals = _run(form, False, {}, TRPL_KEYS)
+    ref_upd, _, _, vals = run_stats_epoch(form, False, {}, TRPL_KEYS)
     assert len(vals) == T
-    upd, _, _, _ = _run(form, True, {}, TRPL_KEYS)
-    _check_means(upd.stats_read(), vals, TRPL_KEYS)
+    upd, _, _, _ = run_stats_epoch(form, True, {}, TRPL_KEYS)
+    assert_stats_means(upd.stats_read(), vals, TRPL_KEYS)
     for a, b in zip(snapshot(upd, None)[:3], snapshot(ref_upd, None)[:3]):
         assert torch.equal(a, b), float((a - b).abs().max())
     again = upd.stats_read()          # reading does not disturb the sums; a reset empties them
@@ -90,9 +37,9 @@ def test_ppo_reports_its_own_keys():
     """The clipped PPO objective through the multi-step launches: the keys of ppo.report_dict plus loss_objective and loss_critic; and the
     iteration log carries ``train/clip_epsilon``."""
     from geometry_rl_amd.rollout import RolloutDriver
-    _, _, _, vals = _run("launches", False, dict(algorithm="ppo"), PPO_KEYS)
-    upd, r, buf, _ = _run("launches", True, dict(algorithm="ppo"), PPO_KEYS)
-    _check_means(upd.stats_read(), vals, PPO_KEYS)
+    _, _, _, vals = run_stats_epoch("launches", False, dict(algorithm="ppo"), PPO_KEYS)
+    upd, r, buf, _ = run_stats_epoch("launches", True, dict(algorithm="ppo"), PPO_KEYS)
+    assert_stats_means(upd.stats_read(), vals, PPO_KEYS)
     log = RolloutDriver(upd, r.spec, ppo_epochs=1).iteration_log(buf)
     assert log["train/clip_epsilon"] == float(r.loss.clip_epsilon) and log["train/lr"] == upd.lr
     assert {f"train/{k}" for k in PPO_KEYS} <= set(log)

@@ -9,9 +9,8 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import graph as ogr, step as ost
+from oracle import graph as ogr
 from noise_ref import add_noise
-from parity_util import G_TOL, adam_first_step_bound, adam_first_step_bound_elem, grad_error, grad_scales, param_excess
 from updater_cases import DEV, dp_ref, make_rollout, run_loop_and_launches, run_step_modes, spawn_dp
 
 pytestmark = pytest.mark.gpu
@@ -179,25 +178,17 @@ def test_noise_statistics():
 # ---------------------------------------------------------------------------------------------------------- whole update vs the oracle
 @pytest.mark.parametrize("name,B", [("rigid_g1", 24), ("empn_g2", 12), ("rope", 8)])
 def test_update_matches_the_oracle_with_the_same_noise(name, B, monkeypatch):
+    import oracle_cases as oc
     from geometry_rl_amd import agent, synthetic as syn
-    from test_gpu_step import LOSS_KEYS, check, load_params, make_case
-    o_spec, spec, kw, obs = make_case(name, B)
-    o_cfg, cfg = ost.AgentConfig(**kw), agent.AgentConfig(**kw, training_noise=True, training_noise_std=0.01)
-    a_par, c_par = ost.init_agent_params(o_spec, o_cfg, seed=11)
-    oracle = ost.OracleAgent(o_spec, o_cfg, a_par, c_par)
-    actor, critic, proj, loss = agent.build_agent(spec, cfg, device=DEV)
-    load_params(actor, a_par, DEV)
-    load_params(critic, {"_network1." + k: v for k, v in c_par.items()}, DEV)
+    o_spec, spec, kw, obs = oc.make_case(name, B)
+    pair = oc.build_pair((o_spec, spec, kw), seed=11, d_kw=dict(training_noise=True, training_noise_std=0.01), dev=DEV)
+    cfg, oracle, actor, critic, loss = pair.cfg, pair.oracle, pair.actor, pair.critic, pair.loss
     A = spec.num_actuators * cfg.output_dim_vec * 3
     batch = dict(obs)
     batch.update(syn.make_ppo_fields(B, A, seed=B))
     dbatch = {k: v.to(DEV) for k, v in batch.items()}
     hd = actor.hyper_data
-    with torch.no_grad():   # calibration latches (the weights are replaced by the oracle's clean calibration below)
-        oracle.actor_forward({k: batch[k] for k in o_spec.in_features}, calibrate=True)
-        actor.forward_diag(*[dbatch[k] for k in spec.in_features], train=True)
-    actor.load_state_dict({k: v.detach().to(DEV) for k, v in oracle.actor.items()}, strict=False)
-    actor._calib_checked = True
+    oc.adopt_calibration(pair, batch, device_first=True)   # calibration latches (the weights are replaced by the oracle's clean calibration)
     seed, draw = hd.noise_state()
     assert draw == 1   # (the calibrating pass read draw 0 and left it; its forward consumed it)
     orig = ogr.build_features
@@ -215,29 +206,16 @@ def test_update_matches_the_oracle_with_the_same_noise(name, B, monkeypatch):
     (out["loss_objective"] + out["loss_entropy"] + out["loss_trust_region"]).backward()
     out["loss_critic"].backward()
     assert hd.noise_state() == (seed, draw + 1)
-    check("loc", out["loc"], ref["loc"])
-    check("state_value", out["state_value"], ref["state_value"])
-    for k in LOSS_KEYS:
-        check(k, out[k], ref[k])
-    scales = {"actor": grad_scales(ref_grads["actor"]), "critic": grad_scales(ref_grads["critic"])}
-    got = {"actor": {k: p.grad for k, p in actor.named_parameters() if k in ref_grads["actor"]},
-           "critic": {k[len("_network1."):]: p.grad for k, p in critic.named_parameters()}}
-    bad = [(net, k) for net in got for k, g in got[net].items()
-           if not (np.isfinite(grad_error(g, ref_grads[net][k])) and grad_error(g, ref_grads[net][k]) <= G_TOL * scales[net][k])]
+    oc.check("loc", out["loc"], ref["loc"])
+    oc.check("state_value", out["state_value"], ref["state_value"])
+    for k in oc.LOSS_KEYS:
+        oc.check(k, out[k], ref[k])
+    bad, scales = oc.gradients_off_scale(actor, critic, ref_grads)
     assert not bad, bad
     hd.set_noise_state(seed, draw)   # the real step from the same draw
     upd.step(dbatch)
     assert hd.noise_state() == (seed, draw + 1)
-    bad = []
-    for net, mod, ref_p, strip in (("actor", actor, oracle.actor, 0), ("critic", critic, oracle.critic, len("_network1."))):
-        for k, p in mod.named_parameters():
-            kk = k[strip:]
-            if cfg.clip_grad_norm or kk not in ref_grads[net]:
-                allowed = adam_first_step_bound(cfg.lr, 1e-5, scales[net].get(kk, 0.0), clip=cfg.clip_grad_norm, p_ref=ref_p[kk])
-            else:
-                allowed = adam_first_step_bound_elem(cfg.lr, 1e-5, ref_grads[net][kk], scales[net][kk], p_ref=ref_p[kk])
-            if not (np.isfinite(param_excess(p, ref_p[kk], allowed)) and param_excess(p, ref_p[kk], allowed) <= 1.0):
-                bad.append((net, kk))
+    bad = oc.first_step_params_off(actor, critic, oracle, cfg, ref_grads, scales)
     assert not bad, bad
 
 

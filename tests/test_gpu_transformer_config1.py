@@ -32,7 +32,7 @@ def _agent(dev):
 
 def test_one_update_matches_cpu_pipeline():
     from geometry_rl_amd import agent
-    from test_gpu_step import check
+    from oracle_cases import check
     dev = torch.device("cuda:0")
     B = 64
     spec, cfg, actor, critic, loss = _agent(dev)

@@ -3,7 +3,7 @@ against float64 references on the same fp32 inputs (tests/trpl_cases.py: the ora
 at fp32 output resolution:
   * fp64 sums: 1e-9 relative, plus 1e-11 per frame absolute; the count exact;
   * fp32 tensors: 4 fp32 ulp relative per element, plus 1e-6 of the largest |ref| of the element's frame (1-D tensors: of the tensor),
-    plus 1e-10 of the tensor's largest |ref| (fp64 cancellation, see CANCEL);
+    plus 1e-10 of the tensor's largest |ref| (fp64 cancellation, see trpl_cases.CANCEL);
   * where the advantages are normalised, plus trpl_cases.adv_error_bound (the one-pass variance s1 - n m^2) times the output's
     sensitivity to the normalised advantages.
 Axes: lane width and padding (A = 1 .. 16 at B = 37, every projection), batch and fold edges (B = 1 .. 4097), the eight per-frame
@@ -21,48 +21,6 @@ from geometry_rl_amd import hip, ops
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
-RTOL32 = 4 * tc.U32    # fp32 outputs: a few ulp
-FLOOR = 1e-6           # ... plus this much of the frame's largest |ref|
-RTOL64 = 1e-9          # fp64 sums
-ATOL64 = 1e-11         # ... plus this much per frame
-CANCEL = 1e-10         # fp32 tensors, plus this much of the tensor's largest |ref|: fp64 cancellation (the KL implicit gradient of a frame
-                       # with a huge eta subtracts two terms ~1e15 x their difference; 1e-14 absolute at sigma = 1e-5)
-
-
-def _close(name, got, want, extra=None, per_frame=True):
-    got, want = got.detach().cpu().double(), want.detach().cpu().double()
-    assert got.shape == want.shape, (name, got.shape, want.shape)
-    a = want.abs()
-    scale = a.reshape(a.shape[0], -1).amax(-1).reshape(-1, *([1] * (a.dim() - 1))) if (per_frame and a.dim() > 1) else a.max()
-    allowed = RTOL32 * a + FLOOR * scale + CANCEL * a.max()
-    if extra is not None:
-        allowed = allowed + extra
-    err = (got - want).abs()
-    assert bool(torch.isfinite(got).all()), name
-    bad = err > allowed
-    i = int((err - allowed).flatten().argmax())
-    print(f"  {name:12s} worst err {float(err.max()):.3e}  at [{i}]: err {float(err.flatten()[i]):.3e} allowed {float(allowed.flatten()[i]):.3e}")
-    assert not bool(bad.any()), (name, int(bad.sum()), float(err.flatten()[i]), float(allowed.flatten()[i]), float(want.flatten()[i]))
-
-
-def _sums_close(name, got, want, B, extra=None):
-    got, want = got.cpu().double(), want.double()
-    assert float(got[10]) == float(want[10]), (name, "count")
-    allowed = RTOL64 * want.abs() + ATOL64 * B
-    if extra is not None:
-        allowed = allowed + extra
-    err = (got - want).abs()
-    k = int((err / allowed).argmax())
-    print(f"  {name:12s} worst: {ops.TRPL_SUM_KEYS[k]} err {float(err[k]):.3e} allowed {float(allowed[k]):.3e}")
-    assert bool((err <= allowed).all()), [(j, float(got[j]), float(want[j]), float(allowed[j])) for j in range(12) if err[j] > allowed[j]]
-
-
-def _maxes_close(name, got_bits, want):
-    got = got_bits.cpu().view(torch.float32).double()
-    w32 = want.float().double()
-    allowed = 2 * tc.U32 * w32.abs() + 1e-30
-    print(f"  {name:12s} maxes {got.tolist()} want {w32.tolist()}")
-    assert bool(((got - w32).abs() <= allowed).all()), (name, got.tolist(), w32.tolist())
 
 
 def _launch(c, d, defer=False):
@@ -80,20 +38,6 @@ def _launch(c, d, defer=False):
                             proj_type=c.proj, defer_fold=defer, adv_local=c.adv_mode == "local")
 
 
-def _report_close(name, out, want, kap_obj):
-    out, want = out.cpu().double(), want.double()
-    scale = want.abs().clone()
-    scale[0] = scale[12] = abs(float(want[12])) + abs(float(want[2])) + abs(float(want[3]))
-    scale[13] = abs(float(want[6])) + abs(float(want[8]))
-    allowed = RTOL32 * scale + 1e-30
-    allowed[0] += kap_obj
-    allowed[12] += kap_obj
-    err = (out - want).abs()
-    j = int((err / allowed).argmax())
-    print(f"  {name:12s} worst out[{j}] err {float(err[j]):.3e} allowed {float(allowed[j]):.3e}")
-    assert bool((err <= allowed).all()), [(i, float(out[i]), float(want[i])) for i in range(14) if err[i] > allowed[i]]
-
-
 def _check_case(c):
     d = tc.make_case(c)
     ref = tc.reference(c, d)
@@ -101,16 +45,7 @@ def _check_case(c):
     print(f"{c.name}: adv bound {kap:.2e}")
     sums, maxes, dloc, dsigma, dvalue, pm, pv = _launch(c, d)
     fold, maxes_d, dloc_d, dsigma_d, dvalue_d, pm_d, pv_d = _launch(c, d, defer=True)
-    _sums_close("sums", sums, ref["sums"], c.B, kap * ref["sens_sums"])
-    _maxes_close("maxes", maxes, ref["maxes"])
-    _close("proj_mean", pm, ref["proj_mean"])
-    _close("proj_S", pv, ref["proj_S"])
-    _close("dloc", dloc, ref["dloc"], kap * ref["sens_dloc"])
-    _close("dsigma", dsigma, ref["dsigma"], kap * ref["sens_dsigma"])
-    if c.value:
-        _close("dvalue", dvalue, ref["dvalue"])
-    else:
-        assert dvalue is None
+    tc.launch_close((sums, maxes, dloc, dsigma, dvalue, pm, pv), ref, c.B, kap, value=c.value)
     # the report path: the deferred launch's slots through grl_trpl_report, the direct sums through grl_trpl_loss_values
     sums_r = torch.empty(12, device=DEV, dtype=torch.float64)
     maxes_r = torch.empty(2, device=DEV, dtype=torch.int32)
@@ -125,8 +60,8 @@ def _check_case(c):
     if c.value:
         assert torch.equal(dvalue_d, dvalue)
     kap_obj = kap * float(ref["sens_sums"][0]) / c.B
-    _report_close("report", out_r, ref["report"], kap_obj)
-    _report_close("loss_values", out_v, ref["report"], kap_obj)
+    tc.report_close("report", out_r, ref["report"], kap_obj)
+    tc.report_close("loss_values", out_v, ref["report"], kap_obj)
 
 
 @pytest.mark.parametrize("c", tc.lane_cases(), ids=lambda c: c.name)
@@ -156,11 +91,11 @@ def test_target_terms(A, proj):
     s = sums.cpu()
     assert float(s[10]) == c.B
     for k, want in ref["sums"].items():
-        allowed = RTOL64 * abs(want) + ATOL64 * c.B
+        allowed = tc.RTOL64 * abs(want) + tc.ATOL64 * c.B
         assert abs(float(s[k]) - want) <= allowed, (k, float(s[k]), want)
-    _maxes_close("maxes", maxes, ref["maxes"])
-    _close("dloc", dloc, ref["dloc"])
-    _close("dsigma", dsigma, ref["dsigma"])
+    tc.maxes_close("maxes", maxes, ref["maxes"])
+    tc.close("dloc", dloc, ref["dloc"])
+    tc.close("dsigma", dsigma, ref["dsigma"])
 
 
 @pytest.mark.parametrize("B,A", tc.PPO_GRID)
@@ -174,13 +109,13 @@ def test_ppo_mode(B, A):
                                                         entropy_coef=kw["ent_coef"], critic_coef=kw["critic_coef"],
                                                         clip_value=kw["clip_value"], global_batch=B, adv_stats=None, adv_local=True)
     print(f"PPO B={B} A={A}")
-    _sums_close("sums", sums, ref["sums"], B)
+    tc.sums_close("sums", sums, ref["sums"], B)
     for col in (1, 6, 7, 9, 11):
         assert float(sums[col]) == 0.0, col
     assert maxes.cpu().tolist() == [0, 0]
-    _close("dloc", dloc, ref["dloc"])
-    _close("dsigma", dsigma, ref["dsigma"])
-    _close("dvalue", dvalue, ref["dvalue"])
+    tc.close("dloc", dloc, ref["dloc"])
+    tc.close("dsigma", dsigma, ref["dsigma"])
+    tc.close("dvalue", dvalue, ref["dvalue"])
     lo, hi = tc.ppo_bounds()
     lw, a = ref["lw"], ref["adv_n"]
     zero = ((lw > hi) & (a > 0)) | ((lw < lo) & (a < 0))   # the clipped side wins: no objective gradient, and loc has no entropy term
@@ -274,5 +209,5 @@ def test_sample_then_loss_with_p_equal_q():
     assert float(s[6]) == 0.0 and abs(float(s[7])) <= 1e-12 * B and abs(float(s[11])) <= 1e-12 * B
     assert maxes.cpu().view(torch.float32).abs().max() <= 1e-12
     assert torch.equal(pm.cpu(), loc)
-    _close("proj_S", pv, var.cpu())
+    tc.close("proj_S", pv, var.cpu())
     assert abs(float(out[4]) - 1.0) <= 2 * tc.U32

@@ -6,18 +6,17 @@
   (d) five updates against the oracle with the restatement registered, rigid HEPi and two-agent EMPN;
   (e) recorded programs against the step-by-step loop (lanes, one stream, run_minibatches);
   (f) two data-parallel ranks against one rank; two runs bitwise identical."""
-import contextlib
-import os
-
-import numpy as np
 import pytest
 import torch
 
+import oracle_cases as oc
+import trpl_cases as tc
 import w2nc_ref
-from oracle import step as ost, trpl as otr
+from oracle import trpl as otr
 from geometry_rl_amd import synthetic as syn
-from parity_util import adam_first_step_bound, grad_scales
-from updater_cases import DEV, assert_ranks_match, dp_ref, make_rollout, run_loop_and_launches, run_step_modes, run_two_ranks
+from oracle_cases import M_TOL, V_TOL
+from updater_cases import (DEV, assert_ranks_match, assert_two_runs_bitwise_identical, dp_ref, graph_modes_are_recorded, make_rollout,
+                           moments_and_params_after, run_loop_and_launches, run_step_modes, run_two_ranks)
 
 pytestmark = pytest.mark.gpu
 EPS, EPS_COV = 0.05, 0.0025
@@ -29,18 +28,7 @@ def registered(monkeypatch):
 
 
 def _fixture(golden_dir, grp):
-    z = np.load(os.path.join(golden_dir, "tier2f_projection_w2_non_com.npz"))
-    out = {k[len(grp) + 1:]: torch.from_numpy(np.asarray(z[k])) for k in z.files if k.startswith(grp + ".")}
-    out.update({k: float(z[k]) for k in ("mean_bound", "cov_bound", "coeff")})
-    return out
-
-
-def _rel(name, got, want, tol, floor=1.0):
-    got, want = got.detach().cpu().double(), want.double()
-    err = float((got - want).abs().max())
-    scale = max(floor, float(want.abs().max()))
-    print(f"{name}: max err {err:.3e} of scale {scale:.3e}")
-    assert np.isfinite(err) and err <= tol * scale, (name, err, tol * scale)
+    return tc.projection_fixture(golden_dir, "tier2f_projection_w2_non_com.npz", grp)
 
 
 # ------------------------------------------------------------------------------------------------------------- (a), (b) fixture
@@ -55,8 +43,8 @@ def test_kernel_matches_the_reference_fixture(golden_dir, grp):
     q = (z["mean_o"].float().to(DEV), z["S_o"].float().to(DEV))
     pm, pS = layer(None, (mean, S.diag_embed()), (q[0], q[1].diag_embed()))
     assert pS.dim() == 3
-    _rel("proj_mean", pm, z["proj_mean"], 1e-5)
-    _rel("proj_S", pS.diagonal(dim1=-2, dim2=-1), z["proj_S"], 1e-5, floor=0.0)
+    tc.rel_close("proj_mean", pm, z["proj_mean"], 1e-5)
+    tc.rel_close("proj_S", pS.diagonal(dim1=-2, dim2=-1), z["proj_S"], 1e-5, floor=0.0)
     # the same launch through ops directly (proj_type=4, want_projection=True): proj_var is the projected "std" diagonal
     batch = {"action": mean, "loc": q[0], "var": q[1], "sample_log_prob": torch.zeros(B, device=DEV), "advantage": torch.zeros(B, device=DEV)}
     out = ops.trpl_fwd_bwd(mean, S.sqrt(), batch, None, mean_bound=z["mean_bound"], cov_bound=z["cov_bound"], trust_region_coeff=z["coeff"],
@@ -68,15 +56,15 @@ def test_kernel_matches_the_reference_fixture(golden_dir, grp):
     p_g = (m_g, S_g.diag_embed())
     tr = layer.get_trust_region_loss(None, p_g, (pm, pS))
     tr.backward()
-    _rel("tr_loss", tr, z["tr_loss"], 1e-5)
-    _rel("tr_grad_mean", m_g.grad, z["tr_grad_mean"], 2e-5, floor=0.0)
-    _rel("tr_grad_S", S_g.grad, z["tr_grad_S"], 2e-5, floor=0.0)
+    tc.rel_close("tr_loss", tr, z["tr_loss"], 1e-5)
+    tc.rel_close("tr_grad_mean", m_g.grad, z["tr_grad_mean"], 2e-5, floor=0.0)
+    tc.rel_close("tr_grad_S", S_g.grad, z["tr_grad_S"], 2e-5, floor=0.0)
     mt = layer.compute_metrics(None, (mean, S.diag_embed()), (pm, pS), step=0)
     for k in ("kl", "constraint", "mean_constraint", "cov_constraint", "mean_constraint_max", "cov_constraint_max", "entropy", "entropy_diff"):
-        _rel("metric." + k, mt[k], z["metric." + k], 2e-5)
+        tc.rel_close("metric." + k, mt[k], z["metric." + k], 2e-5)
     vm, vc = layer.trust_region_value(None, (mean, S.diag_embed()), (q[0], q[1].diag_embed()))
-    _rel("value_mean", vm, z["value_mean"], 1e-5)
-    _rel("value_cov", vc, z["value_cov"], 1e-5)
+    tc.rel_close("value_mean", vm, z["value_mean"], 1e-5)
+    tc.rel_close("value_cov", vc, z["value_cov"], 1e-5)
 
 
 def test_kernel_runs_the_ten_steps_not_an_exact_square_root(golden_dir):
@@ -151,8 +139,8 @@ def test_kernel_matches_the_restatement(registered, A):
     db = {k: v.to(DEV) for k, v in batch.items()}
     sums, maxes, dloc, dsigma, dvalue, pm, pv = ops.trpl_fwd_bwd(loc.to(DEV), sigma.to(DEV), db, value.to(DEV), global_batch=B, adv_stats=None,
                                                                  want_projection=True, proj_type=4, adv_local=True, **kw)
-    _rel("proj_mean", pm, ref["proj_mean"], 1e-5)
-    _rel("proj_S", pv, ref["proj_S"], 1e-5, floor=0.0)
+    tc.rel_close("proj_mean", pm, ref["proj_mean"], 1e-5)
+    tc.rel_close("proj_S", pv, ref["proj_S"], 1e-5, floor=0.0)
     s = sums.cpu()
     n = float(s[10])
     assert n == B
@@ -163,77 +151,42 @@ def test_kernel_matches_the_restatement(registered, A):
     for k, v in got.items():
         want = float(ref[k])
         assert abs(float(v) - want) <= 1e-5 * max(1.0, abs(want)), (k, float(v), want)
-    _rel("dloc", dloc, d_loc, 1e-5, floor=0.0)
-    _rel("dsigma", dsigma, d_sig, 1e-5, floor=0.0)
-    _rel("dvalue", dvalue, d_val, 1e-5, floor=0.0)
+    tc.rel_close("dloc", dloc, d_loc, 1e-5, floor=0.0)
+    tc.rel_close("dsigma", dsigma, d_sig, 1e-5, floor=0.0)
+    tc.rel_close("dvalue", dvalue, d_val, 1e-5, floor=0.0)
     # per frame, so that one kind of frame cannot hide behind the largest gradient of another
     for k in range(6):
         sel = kind == k
-        _rel(f"dsigma[kind {k}]", dsigma.cpu()[sel], d_sig[sel], 2e-5, floor=0.0)
-        _rel(f"dloc[kind {k}]", dloc.cpu()[sel], d_loc[sel], 2e-5, floor=0.0)
+        tc.rel_close(f"dsigma[kind {k}]", dsigma.cpu()[sel], d_sig[sel], 2e-5, floor=0.0)
+        tc.rel_close(f"dloc[kind {k}]", dloc.cpu()[sel], d_loc[sel], 2e-5, floor=0.0)
 
 
 # ------------------------------------------------------------------------------------------------------------- (d) vs oracle
 @pytest.mark.parametrize("name,B,K", [("rigid_g1", 64, 5), ("empn_g2", 32, 5)])
 def test_five_updates_match_the_oracle(registered, name, B, K):
     from geometry_rl_amd import agent
-    from test_gpu_step import load_params, make_case
-    torch.set_num_threads(min(16, os.cpu_count() or 1))
-    o_spec, spec, kw, _ = make_case(name, B)
-    kw = dict(kw, proj_type="w2_non_com", trust_region_coeff=2.0)
-    o_cfg, cfg = ost.AgentConfig(**kw), agent.AgentConfig(**kw)
-    a_par, c_par = ost.init_agent_params(o_spec, o_cfg, seed=21)
-    oracle = ost.OracleAgent(o_spec, o_cfg, a_par, c_par)
-    actor, critic, proj, loss = agent.build_agent(spec, cfg, device=DEV)
-    assert proj.proj_code == 4
-    load_params(actor, a_par, DEV)
-    load_params(critic, {"_network1." + k: v for k, v in c_par.items()}, DEV)
+    oc.cap_oracle_threads()
+    kw = dict(proj_type="w2_non_com", trust_region_coeff=2.0)
+    pair = oc.build_pair(name, B, seed=21, o_kw=kw, d_kw=kw)
+    spec, cfg, loss = pair.spec, pair.cfg, pair.loss
+    assert pair.proj.proj_code == 4
     A = spec.num_actuators * cfg.output_dim_vec * 3
     batches = []
     for i in range(K):
-        b = dict(syn.make_rigid_obs(B, seed=30 + i) if name == "rigid_g1" else
-                 syn.make_rigid_obs(B, G=2, angular_velocity=False, object_velocity=False, seed=30 + i))
+        b = dict(oc.obs_of(name, B, 30 + i))
         b.update(syn.make_ppo_fields(B, A, seed=40 + i))
         batches.append(b)
-    with torch.no_grad():
-        oracle.actor_forward({k: batches[0][k] for k in o_spec.in_features}, calibrate=True)
-    actor.load_state_dict({k: v.detach().to(DEV) for k, v in oracle.actor.items()}, strict=False)
-    for mod in actor.modules():
-        if hasattr(mod, "callibrated"):
-            mod.callibrated.fill_(True)
-    actor._calib_checked = True
+    oc.adopt_calibration(pair, batches[0])
     upd = agent.PolicyUpdater(loss, lr=cfg.lr, clip_grad_norm=cfg.clip_grad_norm, max_grad_norm=cfg.max_grad_norm, use_graph=True)
-    g_scale = None
-    for i, b in enumerate(batches):
-        ref, ref_grads = oracle.update(b)
-        out = upd.step({k: v.to(DEV) for k, v in b.items()})
-        sc = {net: grad_scales(ref_grads[net]) for net in ("actor", "critic")}
-        g_scale = sc if g_scale is None else {net: {k: max(v, g_scale[net].get(k, 0.0)) for k, v in sc[net].items()} for net in sc}
+
+    def per_step(i, out, ref):
         assert float(ref["kl"]) > 0.0   # frames were projected
         for k in ("loss_objective", "loss_trust_region", "loss_critic", "kl", "constraint", "mean_constraint", "cov_constraint", "entropy"):
             e = abs(float(out[k]) - float(ref[k]))
             assert e <= 1e-4 * max(1.0, abs(float(ref[k]))), (i, k, e)
+    g_scale = oc.run_updates(pair, batches, upd, per_step)
     assert upd.mode.startswith("graph") and upd._program is not None
-    torch.cuda.synchronize()
-    off = lambda p: (p.data_ptr() - upd.flat.data_ptr()) // 4
-    bad = []
-    for net, mod, ref_p, optim, strip in (("actor", actor, oracle.actor, oracle.actor_optim, 0),
-                                          ("critic", critic, oracle.critic, oracle.critic_optim, len("_network1."))):
-        states = {kk: optim.state.get(ref_p[kk], {}) for kk in ref_p}
-        m_ref = {kk: s_["exp_avg"] for kk, s_ in states.items() if "exp_avg" in s_}
-        v_ref = {kk: s_["exp_avg_sq"] for kk, s_ in states.items() if "exp_avg_sq" in s_}
-        m_sc, v_sc = grad_scales(m_ref), grad_scales(v_ref)
-        for k, p in mod.named_parameters():
-            kk = k[strip:]
-            if kk not in m_ref:
-                continue
-            o, n = off(p), p.numel()
-            em = float((upd.exp_avg[o:o + n].view_as(p).cpu().double() - m_ref[kk].double()).abs().max())
-            ev = float((upd.exp_avg_sq[o:o + n].view_as(p).cpu().double() - v_ref[kk].double()).abs().max())
-            ep = float((p.detach().cpu().double() - ref_p[kk].detach().double()).abs().max())
-            allowed_p = K * adam_first_step_bound(cfg.lr, 1e-5, g_scale[net].get(kk, 0.0), cfg.clip_grad_norm, p_ref=ref_p[kk])
-            if not (em <= 5e-4 * m_sc[kk] and ev <= 1e-3 * v_sc[kk] and ep <= allowed_p and np.isfinite(em + ev + ep)):
-                bad.append((net, kk, em / m_sc[kk], ev / v_sc[kk], ep, allowed_p))
+    bad, _ = moments_and_params_after(upd, pair.actor, pair.critic, pair.oracle, cfg, g_scale, K, M_TOL, V_TOL)
     assert not bad, bad
 
 
@@ -252,17 +205,10 @@ def test_run_minibatches_equals_the_step_loop(form):
         assert torch.equal(res["loop"][3][-1][k], res["launches"][3][-1][k]), k
 
 
-@contextlib.contextmanager
-def _graph_modes_are_recorded(mode, r, upd):
-    yield
-    if mode in ("graph", "one_stream"):
-        assert upd.mode.startswith("graph") and upd._program is not None
-
-
 def test_recorded_programs_equal_the_eager_loop():
     res = run_step_modes(lambda: make_rollout(8, 2, seed=41, proj_type="w2_non_com"), ("eager", "graph", "one_stream", "one_stream_eager"), 4,
                          KEYS, lambda mode: dict(use_graph=mode in ("graph", "one_stream"), overlap_critic=not mode.startswith("one_stream")),
-                         per_mode=_graph_modes_are_recorded)
+                         per_mode=graph_modes_are_recorded)
     for a, b in (("eager", "graph"), ("one_stream_eager", "one_stream")):
         for x, y in zip(res[a][:3], res[b][:3]):
             assert torch.equal(x, y), (a, b, (x - y).abs().max().item())
@@ -273,19 +219,7 @@ def test_recorded_programs_equal_the_eager_loop():
 
 
 def test_two_runs_are_bitwise_identical():
-    from geometry_rl_amd import agent
-    res = []
-    for _ in range(2):
-        r = make_rollout(16, 3, seed=45, proj_type="w2_non_com")
-        upd = agent.PolicyUpdater(r.loss, lr=r.cfg.lr, use_graph=True)
-        outs = [{kk: v.clone() for kk, v in upd.step({k: v[:, t].contiguous() for k, v in r.data.items()}).items() if kk in KEYS}
-                for t in range(3)]
-        torch.cuda.synchronize()
-        res.append((upd.flat.detach().clone(), outs))
-    assert torch.equal(res[0][0], res[1][0])
-    for oa, ob in zip(res[0][1], res[1][1]):
-        for kk in KEYS:
-            assert torch.equal(oa[kk], ob[kk]), kk
+    assert_two_runs_bitwise_identical(KEYS, proj_type="w2_non_com")
 
 
 # ------------------------------------------------------------------------------------------------------------- (f) data parallel

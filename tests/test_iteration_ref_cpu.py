@@ -19,14 +19,14 @@ import torch
 
 import iteration_ref as ir
 import train_ops_ref
-from test_gpu_step import LOSS_KEYS
+from oracle_cases import LOSS_KEYS, cap_oracle_threads
 
 FACTOR = 10.0
 
 
 @pytest.fixture(scope="module")
 def chain():
-    torch.set_num_threads(min(16, torch.get_num_threads()))
+    cap_oracle_threads()
     return ir.run_oracle_chain()
 
 

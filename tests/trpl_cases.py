@@ -1,6 +1,7 @@
 """Cases and float64 references for the per-op tests of the fused TRPL / PPO loss kernel (trpl_lanes_kernel, head_ops.hip) and of the
 rollout sampler (gaussian_sample_kernel).  TEST INFRASTRUCTURE ONLY: tests/test_gpu_trpl_kernel.py compares the kernel with these
-references, tests/test_trpl_kernel_cases_cpu.py checks on the CPU that the cases still hit every regime they are meant to.
+references by the comparisons at the end of this file (the tests of the entropy stage and of the later projections use the same ones),
+tests/test_trpl_kernel_cases_cpu.py checks on the CPU that the cases still hit every regime they are meant to.
 
 Every 16-frame workgroup of a TRPL case holds the eight per-frame regimes of REGIMES twice (frame f has regime (f + shift) % 8):
 
@@ -18,9 +19,11 @@ Every 16-frame workgroup of a TRPL case holds the eight per-frame regimes of REG
 mean_bound + cov_bound, against which both parts are then scaled.  Independently, frame f has the value-loss regime f % 5 of VREGIMES."""
 import contextlib
 import math
+import os
 from dataclasses import dataclass, replace
 from typing import Dict
 
+import numpy as np
 import torch
 
 import w2nc_ref
@@ -386,3 +389,96 @@ def sample_reference(loc, sigma, eps, action):
     logp = -0.5 * q - s.log().sum(-1) - 0.5 * A * otr.LOG_2PI
     bound = (A + 4) * U32 * (0.5 * q + s.log().abs().sum(-1) + 0.5 * A * otr.LOG_2PI) + 4 * U32 * q
     return l + s * e, s * s, logp, bound
+
+
+# ------------------------------------------------------------------------------------------------------------- comparisons
+RTOL32 = 4 * U32       # fp32 outputs: a few ulp
+FLOOR = 1e-6           # ... plus this much of the frame's largest |ref|
+RTOL64 = 1e-9          # fp64 sums
+ATOL64 = 1e-11         # ... plus this much per frame
+CANCEL = 1e-10         # fp32 tensors, plus this much of the tensor's largest |ref|: fp64 cancellation (the KL implicit gradient of a frame
+                       # with a huge eta subtracts two terms ~1e15 x their difference; 1e-14 absolute at sigma = 1e-5)
+
+
+def close(name, got, want, extra=None, per_frame=True):
+    got, want = got.detach().cpu().double(), want.detach().cpu().double()
+    assert got.shape == want.shape, (name, got.shape, want.shape)
+    a = want.abs()
+    scale = a.reshape(a.shape[0], -1).amax(-1).reshape(-1, *([1] * (a.dim() - 1))) if (per_frame and a.dim() > 1) else a.max()
+    allowed = RTOL32 * a + FLOOR * scale + CANCEL * a.max()
+    if extra is not None:
+        allowed = allowed + extra
+    err = (got - want).abs()
+    assert bool(torch.isfinite(got).all()), name
+    bad = err > allowed
+    i = int((err - allowed).flatten().argmax())
+    print(f"  {name:12s} worst err {float(err.max()):.3e}  at [{i}]: err {float(err.flatten()[i]):.3e} allowed {float(allowed.flatten()[i]):.3e}")
+    assert not bool(bad.any()), (name, int(bad.sum()), float(err.flatten()[i]), float(allowed.flatten()[i]), float(want.flatten()[i]))
+
+
+def sums_close(name, got, want, B, extra=None):
+    from geometry_rl_amd import ops
+    got, want = got.cpu().double(), want.double()
+    assert float(got[10]) == float(want[10]), (name, "count")
+    allowed = RTOL64 * want.abs() + ATOL64 * B
+    if extra is not None:
+        allowed = allowed + extra
+    err = (got - want).abs()
+    k = int((err / allowed).argmax())
+    print(f"  {name:12s} worst: {ops.TRPL_SUM_KEYS[k]} err {float(err[k]):.3e} allowed {float(allowed[k]):.3e}")
+    assert bool((err <= allowed).all()), [(j, float(got[j]), float(want[j]), float(allowed[j])) for j in range(12) if err[j] > allowed[j]]
+
+
+def maxes_close(name, got_bits, want):
+    got = got_bits.cpu().view(torch.float32).double()
+    w32 = want.float().double()
+    allowed = 2 * U32 * w32.abs() + 1e-30
+    print(f"  {name:12s} maxes {got.tolist()} want {w32.tolist()}")
+    assert bool(((got - w32).abs() <= allowed).all()), (name, got.tolist(), w32.tolist())
+
+
+def report_close(name, out, want, kap_obj):
+    out, want = out.cpu().double(), want.double()
+    scale = want.abs().clone()
+    scale[0] = scale[12] = abs(float(want[12])) + abs(float(want[2])) + abs(float(want[3]))
+    scale[13] = abs(float(want[6])) + abs(float(want[8]))
+    allowed = RTOL32 * scale + 1e-30
+    allowed[0] += kap_obj
+    allowed[12] += kap_obj
+    err = (out - want).abs()
+    j = int((err / allowed).argmax())
+    print(f"  {name:12s} worst out[{j}] err {float(err[j]):.3e} allowed {float(allowed[j]):.3e}")
+    assert bool((err <= allowed).all()), [(i, float(out[i]), float(want[i])) for i in range(14) if err[i] > allowed[i]]
+
+
+def launch_close(outs, ref, B, kap, value=True):
+    """The seven outputs of one fused launch (ops.trpl_fwd_bwd, want_projection=True) against ``reference``'s entries, ``kap`` the case's
+    adv_error_bound; without a critic there is no dvalue."""
+    sums, maxes, dloc, dsigma, dvalue, pm, pv = outs
+    sums_close("sums", sums, ref["sums"], B, kap * ref["sens_sums"])
+    maxes_close("maxes", maxes, ref["maxes"])
+    close("proj_mean", pm, ref["proj_mean"])
+    close("proj_S", pv, ref["proj_S"])
+    close("dloc", dloc, ref["dloc"], kap * ref["sens_dloc"])
+    close("dsigma", dsigma, ref["dsigma"], kap * ref["sens_dsigma"])
+    if value:
+        close("dvalue", dvalue, ref["dvalue"])
+    else:
+        assert dvalue is None
+
+
+def rel_close(name, got, want, tol, floor=1.0):
+    """``got`` within ``tol`` of max(floor, the largest |want|)."""
+    got, want = got.detach().cpu().double(), want.detach().double()
+    err = float((got - want).abs().max())
+    scale = max(floor, float(want.abs().max()))
+    print(f"{name}: max err {err:.3e} of scale {scale:.3e}")
+    assert np.isfinite(err) and err <= tol * scale, (name, err, tol * scale)
+
+
+def projection_fixture(golden_dir, file_name, grp):
+    """Group ``grp`` of a projection layer's golden file (tier2f / tier2g): its tensors by name, and the layer's three settings."""
+    z = np.load(os.path.join(golden_dir, file_name))
+    out = {k[len(grp) + 1:]: torch.from_numpy(np.asarray(z[k])) for k in z.files if k.startswith(grp + ".")}
+    out.update({k: float(z[k]) for k in ("mean_bound", "cov_bound", "coeff")})
+    return out

@@ -1,12 +1,13 @@
 """Shared scaffolding of the GPU tests that drive ``PolicyUpdater``: the rollout-shaped inputs, the bodies that run one case through several
 program forms, and the data-parallel pair (one rank on the whole batch, ``world`` ranks on its shards).  TEST INFRASTRUCTURE ONLY, a plain
 module like tests/trpl_cases.py.  The runners return what each form left behind and compare NOTHING: every comparison, with its operator
-and tolerance, stays in the test that owns it.
+and tolerance, stays in the test that owns it, or in an ``assert_...`` body that several files share whole.
 
 Pieces that a spawned rank needs from a test file are named ``(module, function, ...)`` and looked up in the child: closures do not
 survive ``mp.spawn``, the test directory is importable there."""
 import contextlib
 import importlib
+import math
 import os
 from collections import namedtuple
 from functools import partial
@@ -121,6 +122,90 @@ def run_step_modes(make, modes, k, keys, updater_kw_of_mode, before_step=None, p
     return res
 
 
+@contextlib.contextmanager
+def graph_modes_are_recorded(mode, r, upd, proj_codes=None):
+    """A ``per_mode`` of run_step_modes: the recording modes did record (and the rollout's projection is one of ``proj_codes``)."""
+    assert proj_codes is None or r.proj.proj_code in proj_codes
+    yield
+    if mode in ("graph", "one_stream"):
+        assert upd.mode.startswith("graph") and upd._program is not None
+
+
+def assert_two_runs_bitwise_identical(keys, **rollout_kw):
+    """Two fresh ``make_rollout(16, 3, seed=45, **rollout_kw)`` through three recorded updates each: parameters and every step's ``keys``."""
+    from geometry_rl_amd import agent
+    res = []
+    for _ in range(2):
+        r = make_rollout(16, 3, seed=45, **rollout_kw)
+        upd = agent.PolicyUpdater(r.loss, lr=r.cfg.lr, use_graph=True)
+        outs = [{kk: v.clone() for kk, v in upd.step({k: v[:, t].contiguous() for k, v in r.data.items()}).items() if kk in keys}
+                for t in range(3)]
+        torch.cuda.synchronize()
+        res.append((upd.flat.detach().clone(), outs))
+    assert torch.equal(res[0][0], res[1][0])
+    for oa, ob in zip(res[0][1], res[1][1]):
+        for kk in keys:
+            assert torch.equal(oa[kk], ob[kk]), kk
+
+
+# ------------------------------------------------------------------------------------------------------------- tracked statistics
+STATS_N, STATS_T = 16, 12     # 16 frames per minibatch, 12 minibatches: one epoch of the rigid synthetic rollout
+STATS_FORMS = {   # form -> (PolicyUpdater keywords, the calls of the tracked run as row ranges, the calls of the step-by-step run)
+    "one_stream": (dict(use_graph=True, overlap_critic=False), None, None),
+    "lanes": (dict(use_graph=True), None, None),
+    # unroll = 4: one eager step, two launches of four steps, three single steps
+    "launches": (dict(use_graph=True), [(0, 12)], [(0, 1), (1, 5), (5, 9), (9, 10), (10, 11), (11, 12)]),
+    "eager": (dict(use_graph=False), None, None),
+}
+
+
+def run_stats_epoch(form, track, cfg_kw, keys):
+    """The 12 minibatches of one epoch through ``form`` -> (updater, rollout, buffer, every step's reported values [12] as dicts of 0-d
+    tensors -- collected only with tracking off, where the sequence is cut into calls whose steps can all be read)."""
+    from geometry_rl_amd import agent
+    from geometry_rl_amd.rollout import RolloutBuffer, RolloutDriver
+    N, T = STATS_N, STATS_T
+    kw, tracked_calls, stepwise_calls = STATS_FORMS[form]
+    r = make_rollout(N, T, 21, **cfg_kw)
+    upd = agent.PolicyUpdater(r.loss, lr=r.cfg.lr, **kw, **(dict(track_stats=True) if track else {}))
+    upd.autotune_form = False
+    buf = RolloutBuffer(dict(r.data))
+    drv = RolloutDriver(upd, r.spec, ppo_epochs=1, seed=3)
+    drv.compute_advantages(buf, r.next_last)
+    rows = torch.stack(drv.epoch_minibatches(N, T, DEV))
+    assert rows.shape == (T, N)
+    vals = []
+    if tracked_calls is None:
+        for j in range(T):
+            out = upd.step_from(buf, rows[j])
+            if not track:
+                vals.append({k: out[k].clone() for k in keys})
+    else:
+        for lo, hi in (tracked_calls if track else stepwise_calls):
+            out = upd.run_minibatches(buf, rows[lo:hi], unroll=4)
+            if not track:
+                outs = upd.last_outs if hi - lo == 4 else [out]
+                assert len(outs) == hi - lo
+                vals += [{k: o[k].clone() for k in keys} for o in outs]
+        assert upd._epoch is not None, "the multi-step launch was not taken"
+    torch.cuda.synchronize()
+    assert upd.steps == T
+    return upd, r, buf, vals
+
+
+def assert_stats_means(means, vals, keys):
+    """``stats_read()`` of a tracked epoch against the fp64 mean of the values its steps reported: to T * 2^-53 * max |v| of math.fsum / T."""
+    T = STATS_T
+    assert means["updates"] == T
+    assert set(means) == set(keys) | {"updates"}, sorted(means)
+    for k in keys:
+        v = [float(s[k]) for s in vals]
+        want = math.fsum(v) / T
+        bound = T * 2.0 ** -53 * max(abs(x) for x in v)
+        print(f"{k}: mean {means[k]!r}, fsum / {T} = {want!r}, |diff| {abs(means[k] - want):.3e} (bound {bound:.3e})")
+        assert isinstance(means[k], float) and abs(means[k] - want) <= bound, (k, means[k], want)
+
+
 # ------------------------------------------------------------------------------------------------------------- K updates against the oracle
 def merge_grad_scales(g_scale, ref_grads):
     """The running largest gradient scale of every tensor over the updates so far (``g_scale`` None before the first)."""
@@ -135,7 +220,8 @@ def moments_and_params_after(upd, actor, critic, oracle, cfg, g_scale, K, m_tol,
     first-step bound.  Prints every margin -> (the tensors that miss a rule, the worst fractions); the assertion stays with the caller."""
     import numpy as np
     from parity_util import adam_first_step_bound, grad_scales
-    torch.cuda.synchronize()
+    if upd.flat.is_cuda:
+        torch.cuda.synchronize()
     off = lambda p: (p.data_ptr() - upd.flat.data_ptr()) // 4
     bad, worst = [], {"exp_avg": 0.0, "exp_avg_sq": 0.0, "param": 0.0}
     for net, mod, ref_p, optim, strip in (("actor", actor, oracle.actor, oracle.actor_optim, 0),
