@@ -65,12 +65,26 @@ class AgentConfig:
     entropy_eq: bool = False
     entropy_first: bool = False
     total_train_steps: Optional[int] = None
+    # configs/algorithm/optim/default.yaml:5 anneal_lr, objective/default.yaml anneal_clip_epsilon (train.py:263-276): lr and PPO's clip
+    # epsilon of update n are base * (1 - n / total_train_steps), per update and inside every recorded program (PolicyUpdater).  The total is
+    # total_train_steps, the number the reference's builder hands the projection (= train.py:54-59, updater.total_network_updates).
+    # Both False here (the reference's configs say True): the schedule is opt-in, a caller's own anneal_lr loop keeps working
+    anneal_lr: bool = False
+    anneal_clip_epsilon: bool = False
+
+
+def updater_kwargs(cfg: AgentConfig) -> dict:
+    """The keywords of ``PolicyUpdater(loss, **updater_kwargs(cfg))`` that come from the config: the optimiser's settings
+    (configs/algorithm/optim/default.yaml) and the per-update schedule's switch and total."""
+    return dict(lr=cfg.lr, clip_grad_norm=cfg.clip_grad_norm, max_grad_norm=cfg.max_grad_norm, anneal_lr=cfg.anneal_lr,
+                total_network_updates=cfg.total_train_steps)
 
 
 def build_agent(spec: TaskSpec, cfg: AgentConfig, device="cuda", group=None):
     """-> (actor GNNGaussianPolicyDiag, critic BaseCritic, projection, loss_module)  (agent.py:31-64).  ``cfg.algorithm == "ppo"``: the
     projection is None and the loss a ClipPPOLoss2 (utils_algo_graph.py:244-257 builds no projection for PPO); ``"kl_ppo"``: the
-    projection is None and the loss a KLPENPPOLoss (builders/agent.py:65-78), which needs ``cfg.dtarg``."""
+    projection is None and the loss a KLPENPPOLoss (builders/agent.py:65-78), which needs ``cfg.dtarg``.  ``cfg.anneal_clip_epsilon``
+    reaches the PPO loss alone (train.py:272); ``cfg.anneal_lr`` is the updater's: ``PolicyUpdater(loss, **updater_kwargs(cfg))``."""
     if cfg.algorithm not in ("trpl", "ppo", "kl_ppo"):
         raise ValueError(f"algorithm '{cfg.algorithm}': trpl | ppo | kl_ppo")
     if cfg.algorithm == "kl_ppo" and cfg.dtarg is None:
@@ -114,9 +128,9 @@ def build_agent(spec: TaskSpec, cfg: AgentConfig, device="cuda", group=None):
     if cfg.algorithm == "ppo":   # builders/agent.py:53-64
         loss = ClipPPOLoss2(actor, critic, clip_epsilon=cfg.clip_epsilon, entropy_coef=cfg.entropy_coef, critic_coef=cfg.critic_coef,
                             clip_value=cfg.clip_value, loss_critic_type="l2", normalize_advantage=True, in_features=a_in,
-                            critic_in_features=spec.in_features, group=group)
+                            critic_in_features=spec.in_features, group=group, anneal_clip_epsilon=cfg.anneal_clip_epsilon)
         return actor, critic, None, loss
-    if cfg.algorithm == "kl_ppo":   # builders/agent.py:65-78 (no clip_value: torchrl's class clips no value)
+    if cfg.algorithm == "kl_ppo":  # builders/agent.py:65-78 (no clip_value: torchrl's class clips no value)
         loss = KLPENPPOLoss(actor, critic, dtarg=cfg.dtarg, beta=cfg.kl_beta, increment=cfg.kl_increment, decrement=cfg.kl_decrement,
                             entropy_coef=cfg.entropy_coef, critic_coef=cfg.critic_coef, loss_critic_type="l2", normalize_advantage=True,
                             in_features=a_in, critic_in_features=spec.in_features, group=group)

@@ -332,6 +332,23 @@ __global__ __launch_bounds__(256) void vecnorm_apply_kernel(const float* __restr
   }
 }
 
+// n <= 64 floats handed over BY VALUE (kernel arguments) and written to device memory by one small launch, stream-ordered (the float
+// counterpart of head_ops.hip's write_doubles_kernel): how the host fills the per-update learning rates and clip epsilons that the recorded
+// Adam and loss launches of a program read.  The values are formed on the host and only stored here: nothing the compiler could contract.
+// mirror (optional): one more float that receives values[mirror_index] -- the loss module's own epsilon buffer follows the table's last entry
+struct WriteFloats { float v[64]; };
+__global__ __launch_bounds__(64) void write_floats_kernel(WriteFloats w, float* __restrict__ dst, int n, float* __restrict__ mirror,
+                                                         int mirror_index) {
+  const int i = (int)threadIdx.x;
+  if (i < n) {
+    float x = w.v[0];
+#pragma unroll
+    for (int j = 1; j < 64; ++j) x = i == j ? w.v[j] : x;
+    dst[i] = x;
+    if (mirror && i == mirror_index) mirror[0] = x;
+  }
+}
+
 // ---- per-kernel timing (off by default; bench.py's roofline leg switches it on for a few steps) ---------------------------------
 // mode 1: HIP events around the kernels inside multi-kernel entry points (eagerly issued launches).
 // mode 2: one-thread kernels that store the device's wall clock (wall_clock64, constant rate) in front of and behind a launch.  They are
@@ -388,7 +405,17 @@ extern "C" {
 
 // ABI version of this library: major * 10000 + minor * 100 + patch.  Bumped whenever a declared signature changes
 // (include/grl_hip.h GRL_HIP_VERSION must agree: geometry_rl_amd/hip.py checks it at load time).
-int grl_version(void) { return 213; }
+int grl_version(void) { return 214; }
+// dst[0..n) = host_values[0..n), n <= 64, and mirror[0] = host_values[mirror_index] where mirror is given: one small launch whose kernel
+// arguments ARE the values (stream-ordered in front of the program that reads them; nothing is synchronised)
+int grl_write_floats(float* dst, const float* host_values, int n, float* mirror, int mirror_index, hipStream_t stream) {
+  if (!dst || !host_values || n < 1 || n > 64 || (mirror && (mirror_index < 0 || mirror_index >= n))) return -2;
+  WriteFloats w;
+  for (int j = 0; j < 64; ++j) w.v[j] = j < n ? host_values[j] : 0.f;
+  hipLaunchKernelGGL(write_floats_kernel, dim3(1), dim3(64), 0, stream, w, dst, n, mirror, mirror_index);
+  GRL_CHECK_LAUNCH();
+  return 0;
+}
 // The current stream waits (a one-thread kernel: capturable) until flag[0] >= count[0] + add, at most timeout_us microseconds.
 int grl_wait_flag_ge(const int* flag, const int* count, int add, int timeout_us, hipStream_t stream) {
   if (!flag || !count) return -2;

@@ -80,7 +80,7 @@ class KLPENPPOLoss(FusedLoss):
         if "loc" not in b or ("var" not in b and "covariance_matrix" not in b):
             raise ValueError("KLPENPPOLoss needs the old distribution in the minibatch: keys 'loc' and 'var' (or 'covariance_matrix')")
 
-    def launch(self, loc, sigma, value, batch, adv_stats, *, sums=None, maxes=None, defer_fold=False, adv_local=False, beta=None):
+    def launch(self, loc, sigma, value, batch, adv_stats, *, sums=None, maxes=None, defer_fold=False, adv_local=False, beta=None, eps=None):
         """FusedLoss.launch in the kernel's KL-penalty mode (column 11 = sum of the per-frame KL, trust-region columns zero)."""
         self.check_batch(batch)
         if "var" not in batch:

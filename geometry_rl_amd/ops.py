@@ -1024,6 +1024,20 @@ def write_doubles(dst: torch.Tensor, values) -> None:
         hip.call("grl_write_doubles", dst[i:i + len(part)], (ctypes.c_double * len(part))(*part), len(part))
 
 
+def write_floats(dst: torch.Tensor, values, mirror: Optional[torch.Tensor] = None, mirror_index: int = 0) -> None:
+    """dst[:len(values)] = values (a device float32 tensor; host floats, each rounded once to float32) by ONE launch on the current stream
+    (grl_write_floats, at most 64 values) -- stream-ordered, no staging buffer, no synchronisation.  ``mirror``: a one-element device
+    float32 tensor that receives ``values[mirror_index]`` from the same launch."""
+    import ctypes
+    vals = [float(v) for v in values]
+    hip.check_f32(dst, mirror)
+    if not 1 <= len(vals) <= 64 or dst.numel() < len(vals):
+        raise ValueError(f"write_floats: 1 .. 64 values into a tensor with room for them, got {len(vals)} for {dst.numel()}")
+    if mirror is not None and (mirror.numel() != 1 or mirror.device != dst.device or not 0 <= mirror_index < len(vals)):
+        raise ValueError("write_floats: the mirror is a one-element tensor on the table's device, its index one of the values'")
+    hip.call("grl_write_floats", dst, (ctypes.c_float * len(vals))(*vals), len(vals), mirror, int(mirror_index))
+
+
 def ppo_fwd_bwd(loc, sigma, batch, value, *, clip_epsilon: torch.Tensor, entropy_coef, critic_coef, clip_value, global_batch: int,
                 adv_stats: Optional[torch.Tensor], sums=None, maxes=None, defer_fold: bool = False, adv_local: bool = False):
     """The clipped PPO objective on the fused kernel (grl_ppo_fwd_bwd): the same returns as ``trpl_fwd_bwd`` without the projection

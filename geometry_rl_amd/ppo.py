@@ -17,8 +17,10 @@ fused TRPL kernel in its PPO mode (no projection, no trust-region terms), so eve
 
 ``clip_epsilon`` is a registered float32 buffer on the policy's device, and the kernel reads it from device memory when it runs: an
 annealed epsilon written in place (train.py:272-274, ``loss_module.clip_epsilon.copy_(eps * alpha)``) takes effect at the next step
-or replay of a recorded step, with nothing recorded again.  Within one launch of several minibatch steps (``run_minibatches``) it is
-constant, as the learning rate is."""
+or replay of a recorded step, with nothing recorded again.  ``anneal_clip_epsilon=True`` makes that schedule the updater's: a
+``PolicyUpdater`` that knows its total number of updates gives EVERY update -- also each of the steps inside one ``run_minibatches``
+launch -- its own ``base_clip_epsilon * (1 - n / total)`` from a device table it fills in front of the program, and leaves the last one
+in ``clip_epsilon``.  Without it the buffer is the caller's, and constant within a launch of several steps."""
 import torch
 
 from . import ops
@@ -38,7 +40,8 @@ class ClipPPOLoss2(FusedLoss):
 
     def __init__(self, actor_network=None, critic_network=None, *, clip_epsilon=0.2, entropy_bonus=True, samples_mc_entropy=1,
                  entropy_coef=0.01, critic_coef=1.0, loss_critic_type="smooth_l1", normalize_advantage=True, gamma=None,
-                 separate_losses=False, clip_value=None, in_features=None, group=None, critic_in_features=None, **kwargs):
+                 separate_losses=False, clip_value=None, in_features=None, group=None, critic_in_features=None,
+                 anneal_clip_epsilon=False, **kwargs):
         if loss_critic_type != "l2":
             raise NotImplementedError("loss_critic_type: only l2 is built (configs/algorithm/objective/default.yaml passes l2; the "
                                       "reference's default smooth_l1 is not)")
@@ -48,6 +51,8 @@ class ClipPPOLoss2(FusedLoss):
         dev = next((p.device for p in self.actor_network.parameters()), torch.device("cpu"))
         self.register_buffer("clip_epsilon", torch.tensor(float(clip_epsilon), dtype=torch.float32, device=dev))
         self.samples_mc_entropy, self.gamma, self.separate_losses, self.clip_value = samples_mc_entropy, gamma, separate_losses, clip_value
+        # train.py:272-274: clip_epsilon = base * (1 - n / total) before every update -- applied by PolicyUpdater, which counts the updates
+        self.anneal_clip_epsilon, self.base_clip_epsilon = bool(anneal_clip_epsilon), float(clip_epsilon)
 
     @property
     def device_scalars(self):
@@ -62,10 +67,11 @@ class ClipPPOLoss2(FusedLoss):
             keys.append("loss_critic")
         return keys + ["ESS"]
 
-    def launch(self, loc, sigma, value, batch, adv_stats, *, sums=None, maxes=None, defer_fold=False, adv_local=False, beta=None):
-        """FusedLoss.launch in the kernel's PPO mode (no projection: the trust-region / KL columns are zero)."""
+    def launch(self, loc, sigma, value, batch, adv_stats, *, sums=None, maxes=None, defer_fold=False, adv_local=False, beta=None, eps=None):
+        """FusedLoss.launch in the kernel's PPO mode (no projection: the trust-region / KL columns are zero).  ``eps``: the device
+        float32[1] this launch reads its clip epsilon from (an annealing updater's entry for the step; default: ``clip_epsilon``)."""
         args, kw = self._launch_args(loc, sigma, value, batch, adv_stats, sums, maxes, defer_fold, adv_local)
-        return ops.ppo_fwd_bwd(*args, clip_epsilon=self.clip_epsilon, **kw)
+        return ops.ppo_fwd_bwd(*args, clip_epsilon=eps if eps is not None else self.clip_epsilon, **kw)
 
     def report_dict(self, o):
         """The keys ClipPPOLoss.forward sets besides loss_objective and loss_critic."""

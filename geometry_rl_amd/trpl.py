@@ -503,12 +503,13 @@ class FusedLoss(_LossBase):
     def after_report(self, o14) -> None:
         pass
 
-    def launch(self, loc, sigma, value, batch, adv_stats, *, sums=None, maxes=None, defer_fold=False, adv_local=False, beta=None):
+    def launch(self, loc, sigma, value, batch, adv_stats, *, sums=None, maxes=None, defer_fold=False, adv_local=False, beta=None, eps=None):
         """One launch of the fused kernel on detached inputs: rank-local (sums, maxes) and the gradients of the (1/B_global-scaled) losses
         with respect to loc, sigma and value, -> (sums, maxes, dloc, dsigma, dvalue); the slots and sums have one layout in every mode
         (columns a mode does not produce are zero).  ``defer_fold``: see ops.trpl_fwd_bwd (``sums`` comes back as the folding callable).
         ``adv_local`` (one rank): the advantage statistics are summed inside the kernel; ``value=None``: actor-only (the critic's share of
-        the loss comes from ``value_loss`` on the critic's lane).  ``beta``: TRPL with entropy control only (TRPLLoss.launch)."""
+        the loss comes from ``value_loss`` on the critic's lane).  ``beta``: TRPL with entropy control only (TRPLLoss.launch); ``eps``: PPO
+        only (ClipPPOLoss2.launch) -- the device scalars an updater hands the launch of one step of a program."""
         raise NotImplementedError
 
     def report_dict(self, o14):
@@ -600,8 +601,8 @@ class TRPLLoss(FusedLoss):
         return keys + ["ESS", "kl", "constraint", "mean_constraint", "mean_constraint_max", "cov_constraint", "cov_constraint_max",
                        "entropy_diff"]
 
-    def launch(self, loc, sigma, value, batch, adv_stats, *, sums=None, maxes=None, defer_fold=False, adv_local=False, beta=None):
-        """FusedLoss.launch in the projection's mode.  With entropy control (``entropy_active``) the launch is the one with the entropy
+    def launch(self, loc, sigma, value, batch, adv_stats, *, sums=None, maxes=None, defer_fold=False, adv_local=False, beta=None, eps=None):
+        """FusedLoss.launch in the projection's mode. With entropy control (``entropy_active``) the launch is the one with the entropy
         stage and reads its bound from ``beta`` (device float64[1]; default: the loss module's own buffer)."""
         p = self.projection
         args, kw = self._launch_args(loc, sigma, value, batch, adv_stats, sums, maxes, defer_fold, adv_local)

@@ -13,6 +13,18 @@ from .program import Entry, capture, execute, record  # noqa: F401  (capture: re
 _CRITIC_GROUPS = {}   # (id of the actor lane's process group, its ranks) -> the critic lane's communicator
 
 
+def annealed(base: float, n: int, total: int) -> float:
+    """train.py:263-274: the linearly annealed value of update ``n`` (the count of updates BEFORE it) out of ``total``,
+    ``base * (1 - n / total)`` in float64.  Stored into a float32 tensor it is rounded once, which is what ``lr_dev.fill_(x)`` and
+    ``clip_epsilon.copy_(x)`` do with the same Python float."""
+    return base * (1.0 - n / float(total))
+
+
+def total_network_updates(total_frames: int, frames_per_batch: int, ppo_epochs: int, mini_batch_size: int) -> int:
+    """train.py:54-59: iterations x epochs x minibatches per epoch, each an integer division."""
+    return (total_frames // frames_per_batch) * ppo_epochs * (frames_per_batch // mini_batch_size)
+
+
 def _job_arrays(jobs):
     """[(destination pointer, source pointer, bytes)] as the three C arrays and the count that grl_copy_many / grl_gather_rows_many take."""
     n = len(jobs)
@@ -33,8 +45,9 @@ class PolicyUpdater:
     ``loss_module`` is a TRPLLoss, a ClipPPOLoss2 or a KLPENPPOLoss: every program runs each (the fused loss kernel is the launch that
     differs; the KL-penalty loss adds ONE single-thread launch per step, below).
     PPO's ``clip_epsilon`` buffer is read from device memory by that launch, so an in-place write (``loss.clip_epsilon.copy_(eps)``)
-    takes effect at the next step or replay without recording again; within one ``run_minibatches`` launch of several steps it is
-    constant, like ``lr``.  Replacing the buffer by another tensor drops the recorded program (it is recorded again).
+    takes effect at the next step or replay without recording again; written by the host like this it is constant within one
+    ``run_minibatches`` launch of several steps, like ``lr`` (the per-update schedule below moves both inside a launch).  Replacing the
+    buffer by another tensor drops the recorded program (it is recorded again).
     KLPENPPOLoss's ``beta`` buffer is device data in both directions: the loss launch reads it, and every program runs the adapt launch
     (``grl_klpen_adapt``) exactly once per step on the actor's lane, behind whichever tail wrote the step's report and ahead of the next
     step's loss launch -- the next step, also the next of the steps inside one ``run_minibatches`` launch, sees the adapted value with
@@ -44,11 +57,25 @@ class PolicyUpdater:
     ``track_stats=True``: every program ends each lane with one more small launch (``grl_stats_accumulate``) that adds the values the
     update reports to running fp64 sums in device memory -- ``stats_read()`` returns their means over all updates since ``stats_reset()``
     (what train.py:294,320 logs as ``train/<key>``) without a host synchronisation per step; the updates themselves are unchanged.  False
-    (default): nothing is allocated and every program is what it is without the argument."""
+    (default): nothing is allocated and every program is what it is without the argument.
+
+    ``anneal_lr=True`` with ``total_network_updates`` (train.py:54-59; ``total_network_updates()`` of this module), and a
+    ``ClipPPOLoss2(anneal_clip_epsilon=True)``: the schedule of train.py:263-276 per UPDATE, inside every program.  Update ``n`` (the count
+    of updates before it, what ``_global_steps`` gets) runs with ``annealed(base, n, total)``: ``_schedule_prepare`` writes the values of the
+    updates a program is about to run into ``sched_table`` by ONE launch in front of it, and the Adam launches of BOTH lanes and the PPO
+    loss launch of step j read entry j where they read ``lr_dev`` / ``clip_epsilon`` otherwise -- no launch inside a step is added or
+    changed.  An entry is written once per program and read-only while it runs, so the critic's Adam of step j reads step j's rate
+    wherever the actor's lane is; every rank forms the values from the same count, so they are bitwise equal across ranks.  ``lr``
+    then returns the rate of the last issued update and SETS the schedule's base rate (data of the next fill: nothing is recorded
+    again); ``loss.clip_epsilon`` is left at the last issued update's epsilon by the same launch.  An update with ``n >= total`` raises
+    ValueError before anything is enqueued (the reference would run a non-positive rate).  Default False: nothing is allocated, every
+    program is what it is without the arguments."""
+
+    SCHED_SLOTS = 32   # steps per program the schedule table has entries for ((lr, epsilon) pairs: one grl_write_floats launch)
 
     def __init__(self, loss_module, lr=3e-4, eps=1e-5, betas=(0.9, 0.999), clip_grad_norm=False, max_grad_norm=1.0,
                  group=None, use_graph=False, overlap_critic=True, allow_eager_fallback=False, force_dp_plan=False,
-                 critic_after_first_conv=True, track_stats=False):
+                 critic_after_first_conv=True, track_stats=False, anneal_lr=False, total_network_updates=None):
         self.loss_module, self.group = loss_module, group
         self.overlap_critic = overlap_critic   # one rank: False = everything on the caller's stream (_plan_one_stream)
         self.force_dp_plan = force_dp_plan     # a process group of ONE rank runs the data-parallel program (bench.py --dp-plan)
@@ -112,6 +139,17 @@ class PolicyUpdater:
         self.BETA_SLOTS = 64
         self.beta_table = torch.zeros(self.BETA_SLOTS, device=dev, dtype=torch.float64)
         self._lr = float(lr)
+        # the per-update schedule (class docstring): entry j of sched_table = (lr, clip epsilon) of step j of the program about to run.
+        # ``_lr`` is then the rate of the last issued update, ``_base_lr`` the rate the schedule starts from
+        self.anneals_lr = bool(anneal_lr)
+        self.anneals_eps = bool(getattr(loss_module, "anneal_clip_epsilon", False))
+        self.total_network_updates = None if total_network_updates is None else int(total_network_updates)
+        if (self.anneals_lr or self.anneals_eps) and (self.total_network_updates is None or self.total_network_updates < 1):
+            raise ValueError("anneal_lr=True / a loss module with anneal_clip_epsilon=True need total_network_updates >= 1 (train.py:54-59: "
+                             f"updater.total_network_updates(...)), got {total_network_updates!r}")
+        self._base_lr = float(lr)
+        self.sched_table = (torch.zeros(2 * self.SCHED_SLOTS, device=dev, dtype=torch.float32)
+                            if (self.anneals_lr or self.anneals_eps) else None)
         # running sums of the reported values (track_stats): the actor lane's 14 report values + the number of updates, the critic lane's
         # loss + its count; each lane adds to its own, so the lanes still share nothing
         self.track_stats = bool(track_stats)
@@ -178,7 +216,9 @@ class PolicyUpdater:
 
     @lr.setter
     def lr(self, value: float):
-        if float(value) != self._lr:
+        if self.anneals_lr:   # the schedule's base rate: data of the next fill (_schedule_prepare), no recorded launch reads it
+            self._base_lr = float(value)
+        elif float(value) != self._lr:
             self._lr = float(value)
             self.lr_dev.fill_(self._lr)
 
@@ -225,6 +265,40 @@ class PolicyUpdater:
             raise ValueError(f"{n_steps} steps per launch with entropy control: the bound table has {self.BETA_SLOTS} entries")
         ops.write_doubles(self.beta_table, m.projection.entropy_bounds(range(self.steps, self.steps + n_steps)))
 
+    def _schedule_check(self, n_steps: int = 1):
+        """The per-update schedule ends with update ``total - 1``: refuse the next ``n_steps`` updates on the host where one lies behind it
+        (train.py would run it at a rate <= 0) -- before the step count moves and before anything is enqueued."""
+        if self.sched_table is not None and self.steps + n_steps > self.total_network_updates:
+            raise ValueError(f"update {max(self.steps, self.total_network_updates)} of a schedule over total_network_updates = "
+                             f"{self.total_network_updates}: the annealed learning rate / clip epsilon would be <= 0")
+
+    def _schedule_prepare(self, n_steps: int = 1):
+        """The per-update schedule: the (lr, clip epsilon) of updates ``steps .. steps + n_steps - 1`` into the table's first entries, and the
+        last epsilon into the loss module's own buffer, by ONE launch on the current stream in front of the program (the program before it
+        has joined its lanes into this stream, so nothing still reads the entries).  Formed on the host in float64 from the update count alone
+        -- every rank writes the same bits -- and rounded once to float32 on the way."""
+        if self.sched_table is None:
+            return
+        if n_steps > self.SCHED_SLOTS:
+            raise ValueError(f"{n_steps} steps per launch with a per-update schedule: the table has {self.SCHED_SLOTS} entries")
+        m, total, vals = self.loss_module, self.total_network_updates, []
+        for n in range(self.steps, self.steps + n_steps):
+            vals += [annealed(self._base_lr, n, total) if self.anneals_lr else self._lr,
+                     annealed(m.base_clip_epsilon, n, total) if self.anneals_eps else 0.0]
+        ops.write_floats(self.sched_table, vals, m.clip_epsilon if self.anneals_eps else None, 2 * n_steps - 1)
+        if self.anneals_lr:
+            self._lr = vals[-2]
+
+    def _sched_slots(self, j: int) -> dict:
+        """What step ``j`` of a program reads instead of ``lr_dev`` / the loss module's ``clip_epsilon``: its entries of the schedule table
+        (a step's ``st["lr"]`` / ``st["eps"]``; empty without a schedule)."""
+        out = {}
+        if self.anneals_lr:
+            out["lr"] = self.sched_table[2 * j:2 * j + 1]
+        if self.anneals_eps:
+            out["eps"] = self.sched_table[2 * j + 1:2 * j + 2]
+        return out
+
     # ---- the means of the reported values over many updates (track_stats=True)
     def _stats_add(self, src, acc):
         """``acc[:n] += src``, ``acc[n] += 1`` on the current stream: the last launch of a lane (no-op without track_stats)."""
@@ -263,8 +337,11 @@ class PolicyUpdater:
         return out
 
     def anneal_lr(self, base_lr: float, iteration: int, total_iterations: int) -> float:
-        """train.py:264-271: ``alpha = 1 - i / total; lr = base_lr * alpha`` for both optimisers."""
-        self.lr = base_lr * (1.0 - iteration / float(total_iterations))
+        """train.py:264-271: ``alpha = 1 - i / total; lr = base_lr * alpha`` for both optimisers, written by the host for the updates that
+        follow (an updater built with ``anneal_lr=True`` follows the schedule per update by itself: this call is not for it)."""
+        if self.anneals_lr:
+            raise RuntimeError("PolicyUpdater(anneal_lr=True) anneals the rate per update itself; set ``lr`` to change the schedule's base rate")
+        self.lr = annealed(base_lr, iteration, total_iterations)
         return self.lr
 
     def sync_replicas(self):
@@ -294,6 +371,7 @@ class PolicyUpdater:
         if not m.critic_coef:
             raise NotImplementedError("PolicyUpdater expects the critic term (critic_coef > 0 in every TRPL config)")
         one_rank = m.world_size == 1 and not (self.group is not None and self.force_dp_plan)
+        st.update(self._sched_slots(0))   # (a per-update schedule: one step per program, its first entries)
         if one_rank and not self.overlap_critic:
             return self._plan_one_stream(batch, st)
         if one_rank:
@@ -315,7 +393,7 @@ class PolicyUpdater:
             coef = torch.empty(1, device=self.flat.device, dtype=torch.float32)
             hip.call("grl_clip_coef", self.gflat[lo:hi], hi - lo, float(self.max_norm), sq, coef)
         hip.call("grl_adam_step_dev", self.flat[lo:hi], self.gflat[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
-                 hi - lo, self.lr_dev, float(self.betas[0]), float(self.betas[1]), float(self.eps),
+                 hi - lo, st.get("lr", self.lr_dev), float(self.betas[0]), float(self.betas[1]), float(self.eps),
                  step_dev if step_dev is not None else self.step_dev, coef, 1.0)
 
     def _prep(self, batch, st, zero=None):
@@ -344,7 +422,7 @@ class PolicyUpdater:
         loc, sigma = actor.forward_diag(*st["obs"], train=True)
         with torch.no_grad():
             fold_, _mx, dloc, dsigma, _ = m.launch(loc, sigma, None, st["b"], adv, sums=sums, maxes=maxes, defer_fold=True,
-                                                   adv_local=adv_local, beta=st["beta"])
+                                                   adv_local=adv_local, beta=st["beta"], eps=st.get("eps"))
         st.update(loc=loc.detach(), sigma=sigma.detach())
         # the lift's and the fiber basis' backward launches only feed the tail's fold: the first of the two waits for the other and they
         # share ONE launch (ops._tail_pre_offer)
@@ -399,7 +477,7 @@ class PolicyUpdater:
                 with torch.no_grad():
                     zw = st["zw"]
                     sums, maxes, dloc, dsigma, dvalue = m.launch(loc, sigma, value, st["b"], st["adv"], sums=zw[10:22],
-                                                                 maxes=zw[22:23].view(torch.int32), beta=st["beta"])
+                                                                 maxes=zw[22:23].view(torch.int32), beta=st["beta"], eps=st.get("eps"))
                 torch.autograd.backward([loc, sigma], [dloc, dsigma])
                 with torch.no_grad():
                     pipe.bwd3(dvalue)
@@ -425,9 +503,9 @@ class PolicyUpdater:
 
         return [Entry("run", s0), Entry("run", s1), Entry("run", s2), Entry("run", s3), Entry("run_host", lambda: self._finish(st))]
 
-    def _tail_args(self, lo, hi, cnt):
+    def _tail_args(self, st, lo, hi, cnt):
         return dict(grads=self.gflat[lo:hi], params=self.flat[lo:hi], exp_avg=self.exp_avg[lo:hi], exp_avg_sq=self.exp_avg_sq[lo:hi],
-                    lr_dev=self.lr_dev, betas=self.betas, eps=self.eps, step_dev=cnt)
+                    lr_dev=st.get("lr", self.lr_dev), betas=self.betas, eps=self.eps, step_dev=cnt)
 
     def _signal_lane(self):
         """lane_flag[0] = step_dev[0] on the current stream (one tiny launch): the critic's lane may start this step."""
@@ -549,7 +627,7 @@ class PolicyUpdater:
                         o14 = torch.empty(14, device=self.flat.device, dtype=torch.float32)
                         ent = m.entropy_coef if m.entropy_bonus else 0.0
                         # (gated: the lane's closing signal -- see below -- rides on this launch)
-                        done = ops.fold_adam_report(ow, self._tail_args(0, na, self.step_dev),
+                        done = ops.fold_adam_report(ow, self._tail_args(st, 0, na, self.step_dev),
                                                     dict(slots=fold_.slots, batch=fold_.batch, sums=fold_.sums, maxes=fold_.maxes,
                                                          ent_coef=ent, out14=o14), signal=(self.lane_flag, self.step_dev) if (gate and ops.SIGNAL_IN_KERNEL) else None)
                         if done:
@@ -573,7 +651,7 @@ class PolicyUpdater:
             with ops.deferred_folds(), torch.no_grad():
                 for stage in stages:
                     stage()
-                if not (fuse_tail and ops.fold_adam_report(ow, self._tail_args(na, n_all, self.step_dev_c))):
+                if not (fuse_tail and ops.fold_adam_report(ow, self._tail_args(st, na, n_all, self.step_dev_c))):
                     ops.flush_deferred_grads(overwrite=ow)
                     self._adam(st, na, n_all, 1, self.step_dev_c)
                 self._stats_add(st["c_loss"], self.stats_critic)
@@ -650,7 +728,7 @@ class PolicyUpdater:
                     hip.call("grl_trpl_report_record_pairs", self.gbuf[:self._rec], world, st["sums"], st["maxes"], float(ent), o14)
                 else:           # Adam on the reduced slice + the reported values of the delivered records: ONE launch
                     hip.call("grl_adam_report_record_pairs", self.flat[:na], self.gflat[:na], self.exp_avg[:na], self.exp_avg_sq[:na], na,
-                             self.lr_dev, float(self.betas[0]), float(self.betas[1]), float(self.eps), self.step_dev,
+                             st.get("lr", self.lr_dev), float(self.betas[0]), float(self.betas[1]), float(self.eps), self.step_dev,
                              self.gbuf[:self._rec], world, st["sums"], st["maxes"], float(ent), o14)
                 m.after_report(o14)                      # (KL-penalty PPO: every rank adapts on the GLOBAL mean KL -- beta stays equal across the ranks)
                 self._stats_add(o14, self.stats_actor)   # (the GLOBAL values: every rank adds the same numbers, no collective)
@@ -786,6 +864,7 @@ class PolicyUpdater:
     def step_from(self, buf, idx: torch.Tensor) -> Dict[str, torch.Tensor]:
         """One update on the minibatch made of rows ``idx`` (device int64 [B]) of a device-resident ``rollout.RolloutBuffer``.
         With recorded graphs the rows are gathered by ONE launch straight into the static input buffers."""
+        self._schedule_check()   # (in front of the gather as well: nothing is enqueued for a refused update)
         keys = self._rollout_keys(buf)[2]
         jobs = None
         # (recorded without a key that is gathered now, e.g. adv_stats: the plain minibatch makes the step record again)
@@ -850,7 +929,7 @@ class PolicyUpdater:
             return Entry("run", lambda: hip.call("grl_gather_rows_many", *args, row, B), lane, "gather")
         sts, mains, critics = [], [], []
         for j in range(U):
-            st = {"beta": self.beta_table[j:j + 1]}   # (entropy control: step j of a launch reads ITS bound)
+            st = {"beta": self.beta_table[j:j + 1], **self._sched_slots(j)}   # (entropy control, per-update schedule: step j of a launch reads ITS entries)
             actor_lane, (*wait, critic_all) = self._lane_entries(sa, sc, st, bool(gate))
             mains += [gather(ga, j, "m"), *actor_lane]
             critics += [*wait, gather(gc, j, "s"), critic_all]   # (behind the lane's gate, in front of its features)
@@ -1005,13 +1084,18 @@ class PolicyUpdater:
 
     def _advance(self, batch, n, issue):
         """The bookkeeping around ``n`` updates that ``issue()`` enqueues: the loss module's count, the entropy bounds of the updates (from
-        ``batch`` the initial entropy, at the first one), the host's step count -- taken back when issuing raised.  -> what ``issue`` returns."""
+        ``batch`` the initial entropy, at the first one), their learning rates and clip epsilons under a per-update schedule, the host's
+        step count -- taken back when issuing raised.  -> what ``issue`` returns."""
+        self._schedule_check(n)
         self.loss_module._global_steps = self.steps
         self._entropy_prepare(batch, n)
+        lr_before = self._lr
+        self._schedule_prepare(n)
         self.steps += n
         try:
             return issue()
         except BaseException:
+            self._lr = lr_before   # (a per-update schedule: the rate of the last update that WAS issued)
             # the critic lane's gate waits until the DEVICE-side step count (advanced by the actor's feature launch) reaches the HOST's: a
             # step that raised before that launch was enqueued must not leave the host ahead for good -- the next step's wait would
             # never be satisfied and the process would hang on the device instead of raising (ADVICE r5).  After a failure the host count

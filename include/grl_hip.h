@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 /* ABI version (major*10000 + minor*100 + patch); grl_version() returns the value the library was built with. */
-#define GRL_HIP_VERSION 213   /* 213: cfg9[8] accepts 6 and 7, the Euclidean (scale_prec=False) forms of the Frobenius and commutative Wasserstein projections, no signature changed; 212: grl_klpen_fwd_bwd (adaptive KL-penalty PPO objective on the fused loss kernel) and grl_klpen_adapt (its penalty weight's update) added, no existing signature changed; 211: csrc/stats_ops.hip added (grl_stats_accumulate, grl_explained_variance + its scratch query, grl_episode_scan), no existing signature changed; 210: grl_trpl_fwd_bwd_ent (scheduled entropy projection inside the fused TRPL launch) and grl_write_doubles added, no existing signature changed; 209: three exports removed (the device-cursor variant of grl_gather_rows_many, the hipStreamWaitValue32 capability query, the idle spin kernel of calib.hip); 208: cfg9[8] = 4 accepted (non-commuting Wasserstein projection), no signature change; 207: grl_ppo_fwd_bwd added (clipped PPO objective); 206: grl_build_features_noise, grl_step_head_noise[_bf16] added (training noise); 205 (round 6): grl_source_hash added; 204 (round 5): grl_head_fused / grl_head_fused_rows removed, grl_calib_mfma / grl_calib_copy added; the exports are exactly this header */
+#define GRL_HIP_VERSION 214   /* 214: grl_write_floats added (the per-update learning rates and clip epsilons of a recorded program, written by one launch in front of it), no existing signature changed; 213: cfg9[8] accepts 6 and 7, the Euclidean (scale_prec=False) forms of the Frobenius and commutative Wasserstein projections, no signature changed; 212: grl_klpen_fwd_bwd (adaptive KL-penalty PPO objective on the fused loss kernel) and grl_klpen_adapt (its penalty weight's update) added, no existing signature changed; 211: csrc/stats_ops.hip added (grl_stats_accumulate, grl_explained_variance + its scratch query, grl_episode_scan), no existing signature changed; 210: grl_trpl_fwd_bwd_ent (scheduled entropy projection inside the fused TRPL launch) and grl_write_doubles added, no existing signature changed; 209: three exports removed (the device-cursor variant of grl_gather_rows_many, the hipStreamWaitValue32 capability query, the idle spin kernel of calib.hip); 208: cfg9[8] = 4 accepted (non-commuting Wasserstein projection), no signature change; 207: grl_ppo_fwd_bwd added (clipped PPO objective); 206: grl_build_features_noise, grl_step_head_noise[_bf16] added (training noise); 205 (round 6): grl_source_hash added; 204 (round 5): grl_head_fused / grl_head_fused_rows removed, grl_calib_mfma / grl_calib_copy added; the exports are exactly this header */
 int grl_version(void);
 /* The hash of the sources this binary was built from (16 hex digits + NUL into buf; returns the length).  geometry_rl_amd/hip.py
    source_hash() recomputes it from csrc/, this header and the build's flag tables and refuses a library that disagrees. */
@@ -330,6 +330,12 @@ int grl_trpl_fwd_bwd_ent(const double* cfg9, int action_dim, const float* mean, 
 /* (ABI 210) dst[0..n) = host_values[0..n), n <= 16: the values travel as kernel arguments of one small launch, stream-ordered (how the
  * host fills the entropy bounds that recorded launches read; nothing is synchronised) */
 int grl_write_doubles(double* dst, const double* host_values, int n, hipStream_t stream);
+/* (ABI 214) the float counterpart: dst[0..n) = host_values[0..n), n <= 64, by ONE small launch; mirror (optional, device float[1]) receives
+ * host_values[mirror_index] from the same launch.  How the host fills the per-update schedule of a program (PolicyUpdater(anneal_lr=True),
+ * ClipPPOLoss2(anneal_clip_epsilon=True): train.py:263-276) -- entry j of the table is read by the Adam launches of BOTH lanes and by the
+ * PPO loss launch of step j of the program where they read lr_dev / clip_eps otherwise; the mirror is the loss module's own epsilon buffer,
+ * left at the last update's value.  The values are formed on the host (float64, rounded once to float32) and only stored here. */
+int grl_write_floats(float* dst, const float* host_values, int n, float* mirror, int mirror_index, hipStream_t stream);
 /* projection-layer boundary methods for an arbitrary DETACHED target (base_projection_layer.py:292-327 get_trust_region_loss,
  * :332-384 compute_metrics): the same kernel with its projection step skipped.  tgt_S = the target's "std" diagonal as the layer
  * sees it (= covariance diagonal of the policy).  sums[1] = trust_region_coeff * sum measure(p, target), sums[6..9,11] / maxes = the

@@ -9,6 +9,8 @@ ms / step of each (``<variant>_ms_per_step``, ``<variant>_min_max_ms``), B / A (
   python tools/step_ab.py trpl ppo --sizes 512 4096 --steps 20 --blocks 7
   python tools/step_ab.py ppo kl_ppo --count-calls                    # + C-ABI entry-point calls per recorded step of each
   python tools/step_ab.py trpl track_stats_on --sizes 32 512 4096 --blocks 8 --build-order both --reverse-blocks --graphs --calibration
+  python tools/step_ab.py ppo ppo_anneal_on --sizes 32 512 4096 --build-order both --reverse-blocks                    # the per-step program
+  python tools/step_ab.py ppo ppo_anneal_on --sizes 32 512 4096 --build-order both --reverse-blocks --launch-steps 8   # the multi-step launch
 
 The updater built SECOND in a process has measured 3.6 % slower at 4096 frames whatever it runs (entropy control): a
 difference of that size is read from both build orders (--build-order both) and from blocks whose order is reversed every round."""
@@ -34,6 +36,9 @@ VARIANTS = {
     # a linear schedule whose bound stays near the policy's entropy level over the run
     "entropy_on": dict(cfg=dict(entropy_schedule="linear", total_train_steps=10 ** 6, target_entropy=8.5)),
     "track_stats_on": dict(upd=dict(track_stats=True)),
+    # the per-update schedule of train.py:263-276 over a total no run reaches: lr (yardstick: trpl), lr + clip epsilon (yardstick: ppo)
+    "anneal_on": dict(cfg=dict(anneal_lr=True, total_train_steps=10 ** 8)),
+    "ppo_anneal_on": dict(cfg=dict(algorithm="ppo", anneal_lr=True, anneal_clip_epsilon=True, total_train_steps=10 ** 8)),
 }
 
 
@@ -48,7 +53,18 @@ def make(variant, B, dev):
     batch = {k: v.to(dev) for k, v in batch.items()}
     with torch.no_grad():
         actor.forward_diag(*[batch[k] for k in loss.in_features], train=True)   # calibration
-    return agent.PolicyUpdater(loss, lr=cfg.lr, use_graph=True, **VARIANTS[variant].get("upd", {})), batch
+    return agent.PolicyUpdater(loss, use_graph=True, **dict(agent.updater_kwargs(cfg), **VARIANTS[variant].get("upd", {}))), batch
+
+
+def launcher(upd, batch, U):
+    """-> a callable that issues ONE recorded launch of ``U`` steps (run_minibatches' multi-step form, the critic's lane ungated): the batch
+    as a rollout of one time step, every row of the index matrix the whole batch."""
+    from geometry_rl_amd.rollout import RolloutBuffer
+    buf = RolloutBuffer({k: v.unsqueeze(1) for k, v in batch.items()})
+    B = next(iter(batch.values())).shape[0]
+    rows = torch.arange(B, device=upd.flat.device).repeat(U, 1)
+    key = upd._epoch_key(buf, B, U)
+    return lambda: upd._launch_epoch(buf, rows, key, False)
 
 
 def count_calls(upd, batch):
@@ -82,6 +98,8 @@ def main():
     ap.add_argument("--count-calls", action="store_true", help="report the entry-point calls per recorded step of each")
     ap.add_argument("--graphs", action="store_true", help="report the graphs per recorded step of each and whether the outlines are equal")
     ap.add_argument("--calibration", action="store_true", help="print the box calibration (bench.py's two fixed kernels) first")
+    ap.add_argument("--launch-steps", type=int, default=0, help="time the multi-step launch of this many steps (a block = --steps launches) "
+                    "instead of the per-step program")
     a = ap.parse_args()
     if a.a == a.b:
         ap.error("two different variants")
@@ -95,10 +113,14 @@ def main():
         extra = {}
         if a.count_calls:
             extra.update({f"{v}_entry_point_calls_per_step": count_calls(*runs[v]) for v in order})
-        for upd, batch in runs.values():
+        U = max(1, a.launch_steps)
+        issue = {}
+        for v, (upd, batch) in runs.items():
+            upd.step(batch)   # (the first step of a size runs eagerly)
+            issue[v] = launcher(upd, batch, U) if a.launch_steps else (lambda upd=upd, batch=batch: upd.step(batch))
             for _ in range(a.warmup):
-                upd.step(batch)
-            assert upd._program is not None, "the step was not recorded"
+                issue[v]()
+            assert (upd._epoch if a.launch_steps else upd._program) is not None, "the step was not recorded"
         torch.cuda.synchronize()
         times = {v: [] for v in order}
         for r in range(a.blocks):
@@ -108,11 +130,11 @@ def main():
                 upd.join_lanes()
                 e0.record()
                 for _ in range(a.steps):
-                    upd.step(batch)
+                    issue[v]()
                 upd.join_lanes()
                 e1.record()
                 e1.synchronize()
-                times[v].append(e0.elapsed_time(e1) / a.steps)
+                times[v].append(e0.elapsed_time(e1) / (a.steps * U))
         for upd, _ in runs.values():
             if upd.track_stats:
                 assert upd.stats_read()["updates"] == upd.steps, (upd.stats_read()["updates"], upd.steps)
@@ -120,7 +142,7 @@ def main():
             extra["graphs_per_step"] = {v: sum(e.kind == "graph" for e in runs[v][0]._program) for v in order}
             extra["outlines_equal"] = runs[a.a][0].program_outline() == runs[a.b][0].program_outline()
         med = {v: statistics.median(t) for v, t in times.items()}
-        print(json.dumps({"frames": B, "built_first": order[0], "steps_per_block": a.steps, "blocks": a.blocks,
+        print(json.dumps({"frames": B, "built_first": order[0], "steps_per_block": a.steps * U, "steps_per_launch": U, "blocks": a.blocks,
                           **{f"{v}_ms_per_step": round(med[v], 4) for v in med},
                           **{f"{v}_min_max_ms": [round(min(t), 4), round(max(t), 4)] for v, t in times.items()},
                           f"{a.b}_over_{a.a}": round(med[a.b] / med[a.a], 4),
