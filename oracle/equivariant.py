@@ -13,6 +13,14 @@ Every function cites the reference lines it restates.  Abbreviations:
 Parameters are passed as flat dicts keyed by the reference ``state_dict`` names
 (relative to the gnn module), so golden fixtures and the product modules can
 share weights by name.
+
+What pins what (tools/make_golden.py, tests/test_oracle_golden.py): tier1 the grids, the polynomial features and the
+homogeneous Ponita core; tier2b ``hepi_forward`` on graphs from oracle/graph.py; tier2h the wrappers AROUND the cores on
+the batch object the reference's own data class returns -- ``homogeneous_graph`` / ``empn_inputs`` / ``empn_output``
+(= ``empn_forward``, PonitaGCN.one_step: concatenation order, the 2-D branches, to_homogeneous() node and edge order,
+homogeneous_batch, the output mask) and ``hepi_forward`` on a padded rigid batch and on cloth, with the calibration
+statistics taken over the padded, edgeless nodes the reference keeps.  Still a restatement held to no fixture:
+``attentional_aggregation`` beyond its call site (marked there), PonitaGCN(attention=True) (not restated at all).
 """
 import math
 from typing import Dict, List, Tuple
@@ -283,8 +291,9 @@ def ponita_forward(P, x, pos, edge_index, num_layers, prefix="ponita", calibrate
 
 
 def homogeneous_graph(graph: dict, batch_size: int):
-    """ponita_gcn.py:73-83 + PyG to_homogeneous [upstream]: per sample, node types are concatenated
-    in graph["node_types"] order; edges of all types are merged with per-type node offsets.
+    """ponita_gcn.py:73-83 + PyG to_homogeneous [upstream; the edge index PonitaGCN built is in the tier2h
+    fixtures]: per sample, node types are concatenated in graph["node_types"] order; edges of all types are
+    merged with per-type node offsets.
     Returns (edge_index [2,E] over B*n_all nodes, n_all, per-type offsets)."""
     n_per = {t: graph["pos"][t].shape[0] // batch_size for t in graph["node_types"]}
     off, acc = {}, 0
@@ -302,10 +311,9 @@ def homogeneous_graph(graph: dict, batch_size: int):
     return torch.cat(eis, dim=1), n_all, off, n_per
 
 
-def empn_forward(P, graph, scalar_dict, vector_dict, *, dim, output_dim, output_dim_vec, num_layers, batch_size,
-                 calibrate=False):
-    """ponita_gcn.py:88-146 PonitaGCN.one_step."""
-    grid = P["ponita.ori_grid"]
+def empn_inputs(grid, graph, scalar_dict, vector_dict, dim, batch_size):
+    """ponita_gcn.py:94-127: the homogeneous node array -- per sample the node types one after another in graph["node_types"] order,
+    lifted scalars then lifted vectors -- its positions and the merged edge index.  -> (x [B*n_all,O,S+V], pos [B*n_all,dim], edge_index)."""
     xs, ps = [], []
     for t in graph["node_types"]:  # ponita_gcn.py:102-116
         x = lift_features(scalar_dict[t], vector_dict[t], grid, dim)
@@ -314,15 +322,26 @@ def empn_forward(P, graph, scalar_dict, vector_dict, *, dim, output_dim, output_
         ps.append(p[..., :2] if dim == 2 else p)
     x = torch.cat(xs, dim=1)
     pos = torch.cat(ps, dim=1)
-    ei, n_all, off, n_per = homogeneous_graph(graph, batch_size)
-    x = x.reshape(-1, *x.shape[2:])
-    pos = pos.reshape(-1, pos.shape[2])
-    hidden = ponita_forward(P, x, pos, ei, num_layers, "ponita", calibrate)
+    ei, _, _, _ = homogeneous_graph(graph, batch_size)
+    return x.reshape(-1, *x.shape[2:]), pos.reshape(-1, pos.shape[2]), ei
+
+
+def empn_output(P, hidden, graph, *, dim, output_dim, output_dim_vec, batch_size):
+    """ponita_gcn.py:129-146: the read-out on the rows of graph["output_mask_key"], a slice of the per-sample node axis."""
+    _, _, off, n_per = homogeneous_graph(graph, batch_size)
     hidden = hidden.reshape(batch_size, -1, *hidden.shape[1:])
     k = graph["output_mask_key"]
     lat = hidden[:, off[k] : off[k] + n_per[k]]  # ponita_gcn.py:138-141 (mask commutes with the linear ops)
     lat = lat.reshape(-1, *lat.shape[2:])
-    return readout(lat, P["linear.weight"], P["linear.bias"], grid, dim, output_dim, output_dim_vec)
+    return readout(lat, P["linear.weight"], P["linear.bias"], P["ponita.ori_grid"], dim, output_dim, output_dim_vec)
+
+
+def empn_forward(P, graph, scalar_dict, vector_dict, *, dim, output_dim, output_dim_vec, num_layers, batch_size,
+                 calibrate=False):
+    """ponita_gcn.py:88-146 PonitaGCN.one_step."""
+    x, pos, ei = empn_inputs(P["ponita.ori_grid"], graph, scalar_dict, vector_dict, dim, batch_size)
+    hidden = ponita_forward(P, x, pos, ei, num_layers, "ponita", calibrate)
+    return empn_output(P, hidden, graph, dim=dim, output_dim=output_dim, output_dim_vec=output_dim_vec, batch_size=batch_size)
 
 
 # --------------------------------------------------------------------------- parameter init

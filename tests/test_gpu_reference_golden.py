@@ -1,12 +1,18 @@
 """The HIP HEPi against the REFERENCE's own numbers (tests/golden/tier2b_*.npz, written by tools/make_golden.py from the reference
 code): the reference ``state_dict`` is loaded by name (checkpoint compatibility, train.py:336-368 / SURVEY 8f.3: PyG ModuleDict key
 mangling, ``callibrated`` buffers), then first-call outputs, the calibrated weights, post-calibration outputs and every parameter
-gradient are compared at the 1e-4 bar of BASELINE.json -- no oracle in between."""
+gradient are compared at the 1e-4 bar of BASELINE.json -- no oracle in between.
+
+tier2b: HEPi on graphs from the oracle's builder, nothing padded, ``gnn.calibrate`` on the working graph.  tier2h
+(tests/golden/tier2h_*.npz): the reference's data class handed to the reference's PonitaGCN (EMPN) and HEPi, with padded rigid batches,
+and the calibrated state reached through ``actor.forward_diag`` -- policy._maybe_calibrate and its padded graph."""
 import os
 
 import numpy as np
 import pytest
 import torch
+
+import data_fixtures as dfx
 
 pytestmark = pytest.mark.gpu
 
@@ -103,6 +109,91 @@ def test_hepi_matches_reference_fixture(golden_dir, name):
                 close(p.grad, ref, 1e-4 * max(1.0, ref.abs().max().item()), what="grad." + k)
             n += 1
     assert n >= 20
+
+
+def check(what, a, b, atol, rtol=1e-4, ref_distance=None):
+    """``close`` that prints first: the largest error, the share of the bar it uses (max of err / (atol + rtol |ref|)) and, where the
+    fixture has it, how far the reference's own float32 run is from its float64 run for the same tensor."""
+    a, b = a.detach().cpu().double(), b.double()
+    assert a.shape == b.shape, (what, a.shape, b.shape)
+    err = (a - b).abs()
+    used = float((err / (atol + rtol * b.abs())).max()) if b.numel() else 0.0
+    own = "" if ref_distance is None else f", reference fp32 - fp64 {ref_distance:.2e}"
+    print(f"  {what}: max|err| {float(err.max()):.3e}, max|ref| {float(b.abs().max()):.3e}, {used:.2f} of the bar (atol {atol:.1e}, rtol {rtol:.0e}){own}")
+    assert bool((err <= atol + rtol * b.abs()).all()), (what, float(err.max()), float(b.abs().max()))
+
+
+@pytest.mark.parametrize("case", list(dfx.MODEL_CASES))
+def test_actor_matches_reference_model_on_its_data_class(golden_dir, case):
+    """tier2h: the reference's data class handed to the reference's PonitaGCN (EMPN) / HEPi -- padded rigid batches, the 2-D rope, cloth.
+    The agent comes from ``agent.build_agent``, the data class from the recorded names / dims / keywords, the reference state dict is
+    loaded by name, and the calibrated state is reached the way training reaches it: ``actor.forward_diag(*obs, train=True)``, i.e.
+    policy._maybe_calibrate on the PADDED graph (the working graph has dropped the padded points; the reference's statistics run over
+    them).  Rows are in the reference's (sample, gripper) order.  Bars as above: 1e-4 absolute / relative for outputs and calibrated
+    weights, 1e-4 * max(1, max|ref|) for gradients."""
+    from geometry_rl_amd import agent, graph
+    dev = torch.device("cuda:0")
+    fx = dfx.ModelFixture(golden_dir, case)
+    m, z = fx.model, fx.z
+    cls = {"rigid": graph.RigidTasksData, "cloth": graph.ClothTasksData, "rope": graph.RopeTasksData}[fx.family]
+    hd = cls(observation_dim=fx.observation_dim, observation_names=fx.observation_names, training_noise=False, **fx.kwargs, **dfx.ACTOR)
+    cfg = agent.AgentConfig(model="empn" if m["empn"] else "hepi", dim=m["dim"], only_upper_hemisphere=bool(m["upper"]),
+                            output_dim=m["output_dim"], output_dim_vec=m["output_dim_vec"])
+    actor, _, _, _ = agent.build_agent(hd.spec, cfg, device=dev)
+    actor.hyper_data = hd
+    gnn = actor.gnn
+
+    # --- reference checkpoint, by name
+    sd = gnn.state_dict()
+    assert set(fx.init) == set(sd), set(fx.init) ^ set(sd)
+    for k in sd:
+        assert sd[k].shape == fx.init[k].shape, k
+    gnn.load_state_dict({k: v.to(dev) for k, v in fx.init.items()}, strict=True)
+    assert not gnn.calibrated
+
+    obs = [a.to(dev) for a in fx.args()]
+    g, u = hd.build_data(*obs, train=True)
+    assert g.node_types == fx.node_types() and g.compact
+    if fx.family == "rigid":
+        assert g.num_nodes[fx.main] == int(fx.n_valid().sum()) < fx.B * fx.n_per(fx.main)   # the working graph has dropped the padding
+
+    # --- the calibrating call's outputs come from the un-rescaled activations (conv.py:104-105,151-157; ponita.py:178-185)
+    print(case)
+    with torch.no_grad():
+        out0, hid0 = gnn.one_step(g, u)
+    check("out_first_call", out0, z["out_first_call"], 1e-4)
+    check("hidden_first_call", hid0, z["hidden_first_call"], 1e-4)
+
+    # --- the production route to the calibrated state
+    with torch.no_grad():
+        loc, _ = actor.forward_diag(*obs, train=True)
+    for k, v in gnn.state_dict().items():
+        ref = fx.cal[k]
+        if ref.dtype.is_floating_point:
+            check("cal." + k, v, ref, 1e-4, ref_distance=fx.ref_distance("cal." + k) if k in fx.changed else None)
+            assert torch.equal(v.cpu(), fx.init[k]) == (k not in fx.changed), k   # which convolutions calibrate, which stay as loaded
+        else:
+            assert bool(v.cpu()) == bool(ref), k
+    # (that call's own mean is post-calibration here -- the reference's first call still returns the un-rescaled one -- so it is held
+    # against ``out``, computed with the state it has just reached)
+    check("forward_diag mean", loc.reshape(-1, 3), z["out"], 1e-4, ref_distance=fx.ref_distance("out"))
+
+    # --- post-calibration forward + every parameter gradient, from the reference's calibrated state
+    gnn.load_state_dict({k: v.to(dev) for k, v in fx.cal.items()}, strict=True)
+    gnn.zero_grad()
+    out, hid = gnn.one_step(g, u)
+    check("out", out, z["out"], 1e-4, ref_distance=fx.ref_distance("out"))
+    check("hidden", hid, z["hidden"], 1e-4, ref_distance=fx.ref_distance("hidden"))
+    ((out * z["R_out"].to(dev)).sum() + (hid * z["R_hidden"].to(dev)).sum()).backward()
+    n = 0
+    for k, p in gnn.named_parameters():
+        if k in fx.grad:
+            ref = fx.grad[k]
+            check("grad." + k, p.grad, ref, 1e-4 * max(1.0, ref.abs().max().item()))
+            n += 1
+        else:   # the reference gave this parameter no gradient (a skipped convolution, EMPN's unused read_out layer)
+            assert p.grad is None or not bool(p.grad.abs().sum() > 0), k
+    assert n == len(fx.grad) >= 20
 
 
 def test_reference_checkpoint_round_trip(tmp_path):

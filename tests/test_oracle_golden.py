@@ -360,3 +360,154 @@ def test_critic_value_and_gradients_equal_the_reference(golden_dir, case, rank):
         close(p.grad, z[f"{case}.{rank}.grad.{k}"], 1e-5, 1e-4)
         n += 1
     assert n == 14
+
+
+# ------------------------------------------------------------------------------------------------ tier2h: data class INTO the model
+# The reference's data class handed straight to the reference's PonitaGCN (EMPN) / HEPi ``one_step`` (tools/make_golden.py tier2h): the
+# oracle's builders and its restatement of the wrapper (eq.homogeneous_graph / eq.empn_forward, eq.hepi_forward) against the first-call
+# outputs, the calibrated weights, the post-calibration outputs and every gradient, at the bars of the tier2b test above.  The rigid
+# cases pad: the reference's calibration takes its statistics over the edgeless padded nodes too.
+def oracle_model(fx, dtype=torch.float32):
+    """(graph, scalars, vectors, forward(P, graph, s, v, calibrate=False)) of a tier2h case; ``dtype``: of the observations handed to the
+    builders (the float64 run of the reference subtracts the target position in float64 as well)."""
+    spec = oracle_spec(fx)
+    split = gr.split_obs(spec, {k: a.to(dtype) for k, a in fx.obs.items()})
+    topo = gr.build_topology(spec, split, full_graph_obs=False)
+    graph, s, v = gr.build_features(spec, topo, split, dist_as_pos=True)
+    graph["output_mask_key"] = "grippers"
+    m = fx.model
+    if m["empn"]:
+        kw = dict(dim=m["dim"], output_dim=m["output_dim"], output_dim_vec=m["output_dim_vec"], num_layers=2, batch_size=fx.B)
+        return graph, s, v, lambda P, g, s_, v_, calibrate=False: eq.empn_forward(P, g, s_, v_, calibrate=calibrate, **kw)
+    kw = dict(dim=m["dim"], output_dim=m["output_dim"], output_dim_vec=m["output_dim_vec"],
+              rounds=eq.hepi_schedule(spec.edge_types, spec.edge_levels, dfx.HEPI_CODES))
+    return graph, s, v, lambda P, g, s_, v_, calibrate=False: eq.hepi_forward(P, g, s_, v_, calibrate=calibrate, **kw)
+
+
+@pytest.mark.parametrize("case", list(dfx.MODEL_CASES))
+def test_model_graph_equals_the_reference(golden_dir, case):
+    """What the reference model was handed: node types in order, the edge set of every edge type, the output mask; for EMPN also the
+    homogeneous edge index and batch vector PonitaGCN built from it (ponita_gcn.py:65-83) against eq.homogeneous_graph."""
+    fx = dfx.ModelFixture(golden_dir, case)
+    graph, s, v, _ = oracle_model(fx)
+    assert graph["node_types"] == fx.node_types()
+    assert sorted(graph["edge_index"]) == sorted(fx.edge_types())
+    for et, ei in graph["edge_index"].items():
+        assert sorted(zip(ei[0].tolist(), ei[1].tolist())) == fx.edge_set(None, et), et
+    n_per = {t: fx.n_per(t) for t in graph["node_types"]}
+    start = sum(n_per[t] for t in graph["node_types"][:graph["node_types"].index("grippers")])
+    assert fx.z["output_mask"].tolist() == [start, start + n_per["grippers"]]
+    if fx.model["empn"]:
+        ei, n_all, off, _ = eq.homogeneous_graph(graph, fx.B)
+        ref = fx.z["homo_edge_index"]
+        assert sorted(zip(ei[0].tolist(), ei[1].tolist())) == sorted(zip(ref[0].tolist(), ref[1].tolist()))
+        assert n_all == sum(n_per.values()) and off["grippers"] == start
+        assert torch.equal(fx.z["homo_batch"], torch.arange(fx.B).repeat_interleave(n_all))
+    if fx.family == "rigid":   # the case pads: a full sample, one with fewer points than knn_k + 1 (or exactly), one in between
+        nv, P = fx.n_valid(), fx.n_per(fx.main)
+        assert int(nv.max()) == P and int(nv.min()) <= fx.kwargs["knn_k"] and int(nv.min()) < int(nv.median()) < P
+
+
+@pytest.mark.parametrize("case", list(dfx.MODEL_CASES))
+def test_model_forward_backward_calibration_equal_the_reference(golden_dir, case):
+    fx = dfx.ModelFixture(golden_dir, case)
+    graph, s, v, forward = oracle_model(fx)
+    z = fx.z
+
+    P = {k: val.clone() for k, val in fx.init.items()}
+    out0, hid0 = forward(P, graph, s, v, calibrate=True)
+    close(out0, z["out_first_call"], 2e-6)
+    close(hid0, z["hidden_first_call"], 2e-6)
+    for k, val in fx.cal.items():
+        if val.dtype.is_floating_point:
+            close(P[k], val, 2e-6)
+            # which convolutions calibrate: the others (no edges: hetero_fiber_conv.py:48-49) keep their initial weights bit for bit
+            assert torch.equal(P[k], fx.init[k]) == (k not in fx.changed), k
+    assert any("kernel.weight" in k for k in fx.changed)
+
+    # the same in float64 against the reference's float64 run: summation order is all that is left (bar: 1e-10 of the tensor's scale,
+    # float64 rounding 2.2e-16 times a generous 1e5 for the depth of the sums)
+    P64 = {k: (val.double() if val.dtype.is_floating_point else val.clone()) for k, val in fx.init.items()}
+    g64, s64, v64, _ = oracle_model(fx, torch.float64)
+    forward(P64, g64, s64, v64, calibrate=True)
+    for k in fx.changed:
+        if fx.cal64[k].dtype.is_floating_point:
+            close(P64[k], fx.cal64[k], 1e-10, 1e-10)
+    out64, hid64 = forward({k: val.clone() for k, val in fx.cal64.items()}, g64, s64, v64)
+    close(out64, z["out64"], 1e-10, 1e-10)
+    close(hid64, z["hidden64"], 1e-10, 1e-10)
+
+    P = {k: val.clone().requires_grad_(val.dtype.is_floating_point and "ori_grid" not in k) for k, val in fx.cal.items()}
+    out, hid = forward(P, graph, s, v)
+    close(out, z["out"], 2e-6)
+    close(hid, z["hidden"], 2e-6)
+    ((out * z["R_out"]).sum() + (hid * z["R_hidden"]).sum()).backward()
+    for k, val in fx.grad.items():
+        close(P[k].grad, val, 1e-5, 1e-4)
+    assert len(fx.grad) >= 20
+    # a parameter without a recorded gradient got none from the reference (a skipped convolution, EMPN's unused read_out layer)
+    for k, p in P.items():
+        if p.requires_grad and k not in fx.grad:
+            assert p.grad is None or not bool(p.grad.abs().sum() > 0), k
+
+
+# "Has teeth": the two misreadings these fixtures exist for must move the numbers by more than 10x the bar above, on the fixtures'
+# own inputs -- a condition on the INPUTS (point counts), checked with the oracle alone.
+TEETH = 10 * (2e-6 + 1e-5)   # close(a, b, 2e-6) passes up to 2e-6 + 1e-5 * max(1, max|b|); calibrated weights and outputs are below 1
+
+
+def _compact(fx, graph, s, v):
+    """The graph with the padded points of the main node type dropped (valid points keep their order; edges renumbered)."""
+    rows = fx.valid_rows(fx.main)
+    new = torch.full((fx.B * fx.n_per(fx.main),), -1, dtype=torch.long)
+    new[rows] = torch.arange(rows.numel())
+    sub = lambda x: {t: (a[rows] if t == fx.main else a) for t, a in x.items()}
+    ei = {}
+    for et, e in graph["edge_index"].items():
+        e = torch.stack([new[e[0]] if et[0] == fx.main else e[0], new[e[1]] if et[2] == fx.main else e[1]])
+        assert bool((e >= 0).all())
+        ei[et] = e
+    return dict(graph, pos=sub(graph["pos"]), edge_index=ei), sub(s), sub(v), rows
+
+
+@pytest.mark.parametrize("case", [c for c, f in dfx.MODEL_CASES.items() if f == "rigid"])
+def test_calibrating_without_the_padded_points_misses_the_fixture(golden_dir, case):
+    fx = dfx.ModelFixture(golden_dir, case)
+    graph, s, v, forward = oracle_model(fx)
+    P = {k: val.clone() for k, val in fx.init.items()}
+    if fx.model["empn"]:   # (the compact batch is ragged: the homogeneous array is cut after it is laid out)
+        x, pos, ei = eq.empn_inputs(P["ponita.ori_grid"], graph, s, v, fx.model["dim"], fx.B)
+        n_all = x.shape[0] // fx.B
+        keep = torch.ones(fx.B, n_all, dtype=torch.bool)
+        _, _, off, n_per = eq.homogeneous_graph(graph, fx.B)
+        for b, n in enumerate(fx.n_valid().tolist()):
+            keep[b, off[fx.main] + n:off[fx.main] + n_per[fx.main]] = False
+        keep = keep.reshape(-1)
+        new = torch.cumsum(keep, 0) - 1
+        assert bool(keep[ei].all())
+        eq.ponita_forward(P, x[keep], pos[keep], new[ei], 2, "ponita", calibrate=True)
+    else:
+        g2, s2, v2, _ = _compact(fx, graph, s, v)
+        forward(P, g2, s2, v2, calibrate=True)
+    moved = {k: float((P[k] - fx.cal[k]).abs().max()) for k in fx.changed if fx.cal[k].dtype.is_floating_point}
+    print({k: f"{e:.2e}" for k, e in moved.items()})
+    assert max(moved.values()) > TEETH, moved
+
+
+@pytest.mark.parametrize("case", [c for c in dfx.MODEL_CASES if c.startswith("empn")])
+def test_another_node_type_order_in_the_homogeneous_graph_misses_the_fixture(golden_dir, case):
+    """The edge index laid out with the node types in REVERSED order while the node array keeps ponita_gcn.py:102-119's: what a reader
+    gets who takes to_homogeneous() to order the types differently from ``graph.node_types``."""
+    fx = dfx.ModelFixture(golden_dir, case)
+    graph, s, v, _ = oracle_model(fx)
+    m = fx.model
+    P = {k: val.clone() for k, val in fx.cal.items()}
+    x, pos, ei = eq.empn_inputs(P["ponita.ori_grid"], graph, s, v, m["dim"], fx.B)
+    kw = dict(dim=m["dim"], output_dim=m["output_dim"], output_dim_vec=m["output_dim_vec"], batch_size=fx.B)
+    out, _ = eq.empn_output(P, eq.ponita_forward(P, x, pos, ei, 2), graph, **kw)
+    close(out, fx.z["out"], 2e-6)
+    ei_wrong, _, _, _ = eq.homogeneous_graph(dict(graph, node_types=graph["node_types"][::-1]), fx.B)
+    out_wrong, _ = eq.empn_output(P, eq.ponita_forward(P, x, pos, ei_wrong, 2), graph, **kw)
+    moved = float((out_wrong - fx.z["out"]).abs().max())
+    print(f"out moves by {moved:.2e}")
+    assert moved > TEETH, moved

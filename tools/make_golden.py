@@ -20,6 +20,14 @@ section 8c), so three tiers are used:
           critic wrapper (gnn_vf_net.py -> deepsets.py) run as reference code under stubs of the PyG data containers, the two neighbour
           searches and PyG's MLP (install_data_stubs): fixtures tier3_data_<case>.npz and tier3_critic.npz, flagged
           ``generated_under_semantic_stubs``.
+  tier 2h the same data classes handed straight to the reference's PonitaGCN (EMPN) / HEPi ``one_step`` under both sets of stubs --
+          padded rigid batches, the 2-D rope, cloth -- in float32 and float64: tier2h_<case>.npz + tier2h_<case>_grad.npz.
+
+Not in any fixture: variable-length ropes, the rigid builder with knn_to_actuators_k > 0, training noise (see tier3);
+PonitaGCN(attention=True); a model on a data class built with knn_to_actuators_k > 0.
+
+Regenerating: the gradients of the Ponita / HEPi fixtures come out of multi-threaded scatter backward passes and may differ in the last bit
+from run to run; every other array is reproduced exactly.
 
 Only inputs/outputs (arrays) are written; no reference source text is stored.
 """
@@ -725,10 +733,16 @@ def install_data_stubs():
                  ``to()`` is the identity (CPU only); anything else set on the object (``output_mask_key`` ...) is a plain attribute;
                  ``node_offsets``: the start of each node type when the types are laid out one after another in ``node_types`` order
                  (base_data.py:39 reads it -- one semantic beyond the issue's list); ``node_type_subgraph(types)`` drops the other node
-                 types and every edge type that touches one of them, the kept ones stay in their order.
+                 types and every edge type that touches one of them, the kept ones stay in their order; ``num_nodes``: the sum over the
+                 node types; ``edge_index_dict``: edge type -> ``edge_index``, in ``edge_types`` order; ``to_homogeneous()``: ONE graph
+                 whose nodes are the node types laid out one after another in ``node_types`` order and whose ``edge_index`` is the
+                 edge types' concatenated in ``edge_types`` order, each shifted by its source / destination type's offset (the call
+                 site, ponita_gcn.py:78-79, reads nothing else of the result).
     Batch        ``from_data_list``: node attributes concatenated type by type, every ``edge_index`` shifted by the node counts of the
                  samples before it (source row by the source type's, destination row by the destination type's); ``len()`` = number of
-                 graphs; ``batch[0]``: the first sample's stores, restricted to the node types the batch still has.
+                 graphs; ``batch[i]``: sample i's stores cut out of the batch's CURRENT stores (attributes set on the batch later
+                 included) by the node and edge counts the samples came with, ``edge_index`` back in sample-local numbering,
+                 restricted to the node and edge types the batch still has.
     transforms   BaseTransform (``__call__`` -> ``forward``), Compose, Cartesian (pos[row] - pos[col]), Distance (their norm), both with
                  ``norm=False`` only, appended to an existing ``edge_attr``.  Nothing downstream reads that ``edge_attr``.
     functional_transform   a decorator that returns the class unchanged.
@@ -799,6 +813,19 @@ def install_data_stubs():
                 o += s.num_nodes
             return out
 
+        @property
+        def num_nodes(self):
+            return sum(s.num_nodes for s in self._nodes.values())
+
+        @property
+        def edge_index_dict(self):
+            return {e: s.edge_index for e, s in self._edges.items() if "edge_index" in s.keys()}
+
+        def to_homogeneous(self):
+            off = self.node_offsets
+            return Data(edge_index=torch.cat([s.edge_index + torch.tensor([[off[e[0]]], [off[e[2]]]])
+                                              for e, s in self._edges.items()], dim=1))
+
         def _copy(self, deep):
             new = copy.copy(self)
             new.__dict__["_nodes"] = {k: s.copy(deep) for k, s in self._nodes.items()}
@@ -827,7 +854,7 @@ def install_data_stubs():
         @classmethod
         def from_data_list(cls, data_list):
             b = cls()
-            b.__dict__["_num_graphs"], b.__dict__["_first"] = len(data_list), data_list[0]
+            b.__dict__["_num_graphs"] = len(data_list)
             for t in data_list[0].node_types:
                 for k in data_list[0][t].keys():
                     setattr(b[t], k, torch.cat([getattr(d[t], k) for d in data_list], dim=0))
@@ -838,14 +865,32 @@ def install_data_stubs():
             for e in data_list[0].edge_types:
                 b[e].edge_index = torch.cat([d[e].edge_index + torch.tensor([[start[e[0]][i]], [start[e[2]][i]]])
                                              for i, d in enumerate(data_list)], dim=1)
+            estart = {e: [0] for e in data_list[0].edge_types}
+            for d in data_list:
+                for e in estart:
+                    estart[e].append(estart[e][-1] + d[e].edge_index.shape[1])
+            b.__dict__["_node_start"], b.__dict__["_edge_start"] = start, estart
             return b
 
         def __len__(self):
             return self._num_graphs
 
         def _example(self, i):
-            assert i == 0
-            return self._first.node_type_subgraph(self.node_types)
+            d = HeteroData()
+            for t, s in self._nodes.items():
+                lo, hi = self._node_start[t][i], self._node_start[t][i + 1]
+                for k in s.keys():
+                    setattr(d[t], k, getattr(s, k)[lo:hi])
+            for e, s in self._edges.items():
+                lo, hi = self._edge_start[e][i], self._edge_start[e][i + 1]
+                for k in s.keys():
+                    v = getattr(s, k)
+                    if k == "edge_index":
+                        v = v[:, lo:hi] - torch.tensor([[self._node_start[e[0]][i]], [self._node_start[e[2]][i]]])
+                    else:
+                        v = v[lo:hi]
+                    setattr(d[e], k, v)
+            return d
 
     class BaseTransform:
         def __call__(self, data):
@@ -944,6 +989,45 @@ def tie_gap(x, y, k, exclude_self):
     return float(((d[:, k] - d[:, k - 1]) / d[:, k - 1]).min())
 
 
+def rigid_obs(B, P, G, counts, seed, **kw):
+    """make_rigid_obs with the per-sample point counts of the case (padded raw positions zero, as the environment leaves them)."""
+    from geometry_rl_amd import synthetic as syn
+    obs = syn.make_rigid_obs(B, P=P, G=G, E_mesh=4, seed=seed, **kw)
+    n = torch.tensor(counts)
+    g = torch.Generator().manual_seed(1000 + seed)
+    obj = torch.rand(B, P, 3, generator=g) * 2 - 1
+    tgt = obj + 0.3 * (torch.rand(B, 1, 3, generator=g) * 2 - 1)
+    valid = (torch.arange(P)[None, :] < n[:, None]).float()[..., None]
+    pos = obs["position_vectors"].clone()
+    pos[:, 3 * G:3 * (G + P)] = (obj * valid).reshape(B, -1)
+    pos[:, 3 * (G + P):] = (tgt * valid).reshape(B, -1)
+    obs["position_vectors"] = pos
+    obs["infos"][:, 0] = n.float()
+    return obs
+
+
+def case_gap(c, obs):
+    from oracle import graph as gr
+    spec = c["spec"]
+    posv = gr.split_obs(spec, obs)["position_vectors"]
+    B = posv["grippers"].shape[0]
+    counts = c.get("counts", [posv[c["main"]].shape[1]] * B)
+    gap = float("inf")
+    for i in range(B):
+        pts = posv[c["main"]][i][:counts[i]]
+        if spec.family != "cloth":
+            gap = min(gap, tie_gap(pts, pts, c["kw"]["knn_k"], True))
+        if c["kw"].get("knn_to_actuators_k", -1) > 0:
+            gap = min(gap, tie_gap(pts, posv["grippers"][i], c["kw"]["knn_to_actuators_k"], False))
+    return gap
+
+
+def ref_kwargs(c):
+    spec = c["spec"]
+    return dict(observation_dim={g: [(d,) for d in ds] for g, ds in spec.obs_dims.items()},
+                observation_names={g: list(ns) for g, ns in spec.obs_names.items()}, training_noise=False, **c["kw"])
+
+
 def tier3():
     """The reference's RigidTasksData / ClothTasksData / RopeTasksData (imported unmodified, under install_data_stubs) on synthetic
     observations, each case in the two layouts examples/torchrl/builders/utils_algo_graph.py builds -- actor: full_graph_obs=False,
@@ -966,21 +1050,6 @@ def tier3():
     from oracle import graph as gr
     from geometry_rl_amd import synthetic as syn
 
-    def rigid_obs(B, P, G, counts, seed, **kw):
-        """make_rigid_obs with the per-sample point counts of the case (padded raw positions zero, as the environment leaves them)."""
-        obs = syn.make_rigid_obs(B, P=P, G=G, E_mesh=4, seed=seed, **kw)
-        n = torch.tensor(counts)
-        g = torch.Generator().manual_seed(1000 + seed)
-        obj = torch.rand(B, P, 3, generator=g) * 2 - 1
-        tgt = obj + 0.3 * (torch.rand(B, 1, 3, generator=g) * 2 - 1)
-        valid = (torch.arange(P)[None, :] < n[:, None]).float()[..., None]
-        pos = obs["position_vectors"].clone()
-        pos[:, 3 * G:3 * (G + P)] = (obj * valid).reshape(B, -1)
-        pos[:, 3 * (G + P):] = (tgt * valid).reshape(B, -1)
-        obs["position_vectors"] = pos
-        obs["infos"][:, 0] = n.float()
-        return obs
-
     cases = {
         "rigid_g1": dict(cls=RigidTasksData, spec=gr.rigid_spec(P=12, G=1, E_mesh=4), main="object_geometry", counts=[12, 3, 7],
                          obs=lambda s: rigid_obs(3, 12, 1, [12, 3, 7], s), kw=dict(angular_velocity=True, knn_k=3)),
@@ -1000,25 +1069,6 @@ def tier3():
     }
     layouts = {"actor": dict(full_graph_obs=False, dist_as_pos=True, output_mask_key="grippers", concat_input_vector=False),
                "critic": dict(full_graph_obs=True, dist_as_pos=False, output_mask_key=None, concat_input_vector=True)}
-
-    def case_gap(c, obs):
-        spec = c["spec"]
-        posv = gr.split_obs(spec, obs)["position_vectors"]
-        B = posv["grippers"].shape[0]
-        counts = c.get("counts", [posv[c["main"]].shape[1]] * B)
-        gap = float("inf")
-        for i in range(B):
-            pts = posv[c["main"]][i][:counts[i]]
-            if spec.family != "cloth":
-                gap = min(gap, tie_gap(pts, pts, c["kw"]["knn_k"], True))
-            if c["kw"].get("knn_to_actuators_k", -1) > 0:
-                gap = min(gap, tie_gap(pts, posv["grippers"][i], c["kw"]["knn_to_actuators_k"], False))
-        return gap
-
-    def ref_kwargs(c):
-        spec = c["spec"]
-        return dict(observation_dim={g: [(d,) for d in ds] for g, ds in spec.obs_dims.items()},
-                    observation_names={g: list(ns) for g, ns in spec.obs_names.items()}, training_noise=False, **c["kw"])
 
     def record(rec, tag, data, iv, concat):
         rec[f"{tag}.node_types"] = np.array(data.node_types)
@@ -1111,12 +1161,162 @@ def tier3():
     print("tier3 critic:", len(rec), "arrays,", os.path.getsize(path), "bytes")
 
 
+# ----------------------------------------------------------------------------------------------- tier 2h: data class INTO the model
+def tier2h():
+    """The reference's data class handed straight to the reference's model, nothing of ours in between (install_stubs +
+    install_data_stubs): ``build_data(*obs, train=True)`` in the actor layout, then ``one_step`` of PonitaGCN (EMPN, ponita_gcn.py:88-146:
+    lift and concatenation order per node type, the ``[..., :2]`` branches and the zero z column, to_homogeneous() node and edge order,
+    homogeneous_batch, the output mask as a slice of the per-sample node axis) or of HEPi (hepi.py:125-190) on the batch object the data
+    class returned.  The rigid cases pad: the reference keeps the zero-padded points as edgeless nodes, so its one-shot calibration
+    (conv.py:104-105, ponita.py:178-179) takes x.std() over them as well.
+
+      empn_rigid_g2_pad   RigidTasksData P=10 G=2 positions only, counts [10, 6, 3], knn_k=3 -> PonitaGCN with what agent.build_agent
+                          passes for AgentConfig(model="empn"): 16 orientations, 2 layers, hidden 64, degree 2, widening 4, dim 3
+      empn_rope_dim2      RopeTasksData n_links=9 G=2 (three node types, ``target_geometry`` edgeless) -> PonitaGCN(ponita_dim=2)
+      hepi_rigid_g1_pad   RigidTasksData P=12 G=1, counts [12, 3, 7] -> HEPi as in tier2b (upper hemisphere, od = ov = 2); no agent edges:
+                          that convolution is skipped and stays uncalibrated (hetero_fiber_conv.py:48-49)
+      hepi_cloth          ClothTasksData 12 particles, 6 hole points, G=4 -> HEPi as in tier2b (od = ov = 1)
+
+    Two files per case, each below the size limit of a committed file: tier2h_<case>.npz holds ``obs.*``, the constructor keywords and
+    observation names / dims (as tier3), ``model.*`` (the model's keywords), the graph the data class built (``node_types``, ``edge_types``,
+    ``edge_index.*``, ``output_mask``; EMPN: ``homo_edge_index`` / ``homo_batch`` as PonitaGCN cached them), ``init.*``, ``out_first_call`` /
+    ``hidden_first_call``, ``cal.*``, ``out`` / ``hidden``, ``R_out`` / ``R_hidden``, and ``out64`` / ``hidden64`` / ``cal64.*`` from the same model
+    class run in float64 from the same ``init`` on the same observations (the reference's own fp32 error); tier2h_<case>_grad.npz holds
+    ``grad.*``.  ``cal.*`` / ``cal64.*`` hold only the entries the calibrating call CHANGED (asserted: every other entry is bit-identical to
+    ``init``); tests/data_fixtures.py load_tier2h puts the state dicts back together.  Tie-gap rule and seed search as tier3."""
+    install_data_stubs()
+    import copy
+    from geometry_rl.modules.pyg_data.rigid_tasks_data import RigidTasksData
+    from geometry_rl.modules.pyg_data.cloth_tasks_data import ClothTasksData
+    from geometry_rl.modules.pyg_data.rope_tasks_data import RopeTasksData
+    from geometry_rl.modules.pyg_models.hepi import HEPi
+    from geometry_rl.modules.pyg_models.ponita_gcn import PonitaGCN
+    from geometry_rl.modules.pyg_models.ponita.conv import FiberBundleConv
+    from oracle import graph as gr
+    from geometry_rl_amd import synthetic as syn
+
+    cases = {
+        "empn_rigid_g2_pad": dict(cls=RigidTasksData, spec=gr.rigid_spec(P=10, G=2, E_mesh=4, angular_velocity=False, object_velocity=False),
+                                  main="object_geometry", counts=[10, 6, 3],
+                                  obs=lambda s: rigid_obs(3, 10, 2, [10, 6, 3], s, angular_velocity=False, object_velocity=False),
+                                  kw=dict(angular_velocity=False, knn_k=3), model=dict(empn=1, dim=3, upper=0, output_dim=1, output_dim_vec=1)),
+        "empn_rope_dim2": dict(cls=RopeTasksData, spec=gr.rope_spec(n_links=9, G=2), main="links",
+                               obs=lambda s: syn.make_rope_obs(3, n_links=9, G=2, seed=s), kw=dict(knn_k=3),
+                               model=dict(empn=1, dim=2, upper=0, output_dim=1, output_dim_vec=1)),
+        "hepi_rigid_g1_pad": dict(cls=RigidTasksData, spec=gr.rigid_spec(P=12, G=1, E_mesh=4), main="object_geometry", counts=[12, 3, 7],
+                                  obs=lambda s: rigid_obs(3, 12, 1, [12, 3, 7], s), kw=dict(angular_velocity=True, knn_k=3),
+                                  model=dict(empn=0, dim=3, upper=1, output_dim=2, output_dim_vec=2)),
+        "hepi_cloth": dict(cls=ClothTasksData, spec=gr.cloth_spec(n_particles=12, n_hole=6, G=4, E_cloth=4), main="hole_boundary",
+                           obs=lambda s: syn.make_cloth_obs(2, n_particles=12, n_hole=6, G=4, E_cloth=4, seed=s), kw=dict(),
+                           model=dict(empn=0, dim=3, upper=0, output_dim=1, output_dim_vec=1)),
+    }
+    actor = dict(full_graph_obs=False, dist_as_pos=True, output_mask_key="grippers", concat_input_vector=False)
+    codes = [[1, 0], [0, 1], [0, 1]]
+
+    def make_net(c):
+        spec, m = c["spec"], c["model"]
+        n_in = len(spec.node_types) + spec.n_vec
+        if m["empn"]:
+            return PonitaGCN(input_dim_node=n_in, output_dim=m["output_dim"], output_dim_vec=m["output_dim_vec"], num_layers=2, hidden_dim=64,
+                             num_ori=16, degree=2, widening_factor=4, ponita_dim=m["dim"], only_upper_hemisphere=bool(m["upper"]))
+        mp = [[FiberBundleConv(64, 64, 64, groups=64, separable=True, widening_factor=4, aggr="add") if codes[lvl][k] else None
+               for k in range(2)] for lvl in range(3)]
+        return HEPi(input_dim_node=n_in, input_dim_edge=0, hidden_dim=64, latent_dim=64, output_dim=m["output_dim"],
+                    output_dim_vec=m["output_dim_vec"], node_encoder_layers=2, edge_encoder_layers=2, node_decoder_layers=2,
+                    node_type_mapping=None, edge_type_mapping=[tuple(e) for e in spec.edge_types], edge_level_mapping=spec.edge_levels,
+                    message_passing=mp, num_messages=2, device="cpu", num_ori=16, degree=2, ponita_dim=m["dim"],
+                    only_upper_hemisphere=bool(m["upper"]))
+
+    def changed(init, after, what):
+        """The entries of ``after`` that differ from ``init`` (only the calibrated kernels and the ``callibrated`` flags may)."""
+        out = {}
+        for k, v in after.items():
+            if not torch.equal(v, init[k].to(v.dtype)):
+                assert k.endswith(("kernel.weight", "callibrated")), (what, k)
+                out[k] = v.clone()
+        return out
+
+    for name, c in cases.items():
+        seed = 31
+        while case_gap(c, c["obs"](seed)) < TIE_GAP:
+            seed += 1
+        obs = c["obs"](seed)
+        gap = case_gap(c, obs)
+        assert gap >= TIE_GAP, (name, gap)
+        spec = c["spec"]
+        rec = {"obs." + k: v for k, v in obs.items()}
+        for g in spec.obs_names:
+            rec["observation_names." + g] = np.array(spec.obs_names[g])
+            rec["observation_dim." + g] = np.array(spec.obs_dims[g], dtype=np.int64)
+        for k, v in c["kw"].items():
+            rec["kwarg." + k] = np.int64(v)
+        for k, v in c["model"].items():
+            rec["model." + k] = np.int64(v)
+        rec["generated_under_semantic_stubs"] = np.int64(1)
+        rec["tie_gap_min"] = np.float64(min(gap, 1e30))
+
+        torch.manual_seed(77)
+        net = make_net(c)
+        init = {k: v.clone() for k, v in net.state_dict().items()}
+        net64 = copy.deepcopy(net).double()
+        rec.update({"init." + k: v for k, v in init.items()})
+
+        hd = c["cls"](**ref_kwargs(c), **actor)
+        args = [obs[k] for k in spec.in_features]
+        data, iv = hd.build_data(*args, train=True)
+        rec["node_types"] = np.array(data.node_types)
+        rec["edge_types"] = np.array(["|".join(e) for e in data.edge_types])
+        for e in data.edge_types:
+            rec["edge_index." + "|".join(e)] = data[e].edge_index
+        rec["output_mask"] = np.array([data.output_mask.start, data.output_mask.stop], dtype=np.int64)
+        net.train()
+        out0, hid0 = net.one_step(data, iv)     # the calibrating call: its outputs come from the un-rescaled activations
+        rec["out_first_call"], rec["hidden_first_call"] = out0, hid0
+        if c["model"]["empn"]:
+            rec["homo_edge_index"], rec["homo_batch"] = net._homogeneous_edge_index, net._homogeneous_batch
+        cal = changed(init, net.state_dict(), name)
+        rec.update({"cal." + k: v for k, v in cal.items()})
+        net.zero_grad()
+        data, iv = hd.build_data(*args, train=True)
+        out, hid = net.one_step(data, iv)
+        g = torch.Generator().manual_seed(9)
+        Ro, Rh = torch.randn(out.shape, generator=g), torch.randn(hid.shape, generator=g)
+        ((out * Ro).sum() + (hid * Rh).sum()).backward()
+        rec.update({"out": out, "hidden": hid, "R_out": Ro, "R_hidden": Rh})
+        grads = {"grad." + k: p.grad for k, p in net.named_parameters() if p.grad is not None}
+
+        # the same model class in float64 from the same init, on the same (float32-representable) observations
+        hd64 = c["cls"](**ref_kwargs(c), **actor)
+        args64 = [a.double() for a in args]
+        net64.train()
+        with torch.no_grad():
+            net64.one_step(*hd64.build_data(*args64, train=True))
+            cal64 = changed(init, net64.state_dict(), name + " float64")
+            assert set(cal64) == set(cal), (name, set(cal64) ^ set(cal))
+            out64, hid64 = net64.one_step(*hd64.build_data(*args64, train=True))
+        assert out64.dtype == torch.float64 and hid64.dtype == torch.float64
+        rec.update({"cal64." + k: v for k, v in cal64.items()})
+        rec["out64"], rec["hidden64"] = out64, hid64
+
+        path, gpath = os.path.join(OUT, f"tier2h_{name}.npz"), os.path.join(OUT, f"tier2h_{name}_grad.npz")
+        np.savez(path, **npd(rec))
+        np.savez(gpath, **npd(grads))
+        print(f"tier2h {name}: seed {seed}, tie gap {gap:.3g}, {len(rec)} + {len(grads)} arrays, {os.path.getsize(path)} + "
+              f"{os.path.getsize(gpath)} bytes; |out| max {float(out.detach().abs().max()):.3g}, fp32 - fp64: out "
+              f"{float((out.detach() - out64).abs().max()):.2e}, hidden {float((hid.detach() - hid64).abs().max()):.2e}")
+        assert max(os.path.getsize(path), os.path.getsize(gpath)) <= 1 << 20, name
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(4)
     if len(sys.argv) > 1 and sys.argv[1] == "tier3":   # only the tier3 fixtures
         install_stubs()
         tier3()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "tier2h":
+        install_stubs()
+        tier2h()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "tier2f":
         install_stubs()
@@ -1149,5 +1349,6 @@ if __name__ == "__main__":
     tier2f()
     tier2g()
     tier3()
+    tier2h()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
