@@ -380,6 +380,24 @@ GRL_DEVINL void rowred_mma(const RFrags<NTK>& f, f32x16 (&acc)[2][NTK]) {
     }
 }
 
+#if !GRL_PREC
+// The k-th of rowred_mma's MFMAs on its own (k = 0 .. 6 NTK - 1, the same order per accumulator).  An asm MFMA is opaque to the scheduler, which
+// therefore leaves the 32 cycles the matrix pipe is busy with it empty: the fp32 pass issues each one with a piece of plain f32 vector work
+// behind it and a scheduling barrier behind that (the form node_mlp16.hip's dW3 / dW4 loops have) -- plain instructions issue in the shadow.
+template <int NTK>
+GRL_DEVINL void rowred_mma_step(const RFrags<NTK>& f, f32x16 (&acc)[2][NTK], int k) {
+  const int tn = k / (3 * NTK), tk = (k / 3) % NTK, term = k % 3;
+  mfma32_acc(term == 1 ? f.al[tn] : f.ah[tn], term == 2 ? f.bl[tk] : f.bh[tk], acc[tn][tk]);
+}
+// pair k (0 .. 7) of the split of four fragments x[0 .. 3] into hi[2] / lo[2] (words of the operands; split_pair's operations, one pair at a time)
+GRL_DEVINL void split_step(const float4 (&x)[4], u32x4 (&hi)[2], u32x4 (&lo)[2], int k) {
+  const float4& f = x[k >> 1];
+  const float a = (k & 1) ? f.z : f.x, b = (k & 1) ? f.w : f.y;
+  hi[k >> 2][k & 3] = pack_hi(a, b);
+  lo[k >> 2][k & 3] = pack_rn(a - trunc_bf16(a), b - trunc_bf16(b));
+}
+#endif
+
 // GELU value + derivative as packed pairs: one wave per SIMD issues a v_pk_* in the time of a scalar op, and both builds issue the pass's
 // MFMAs in bursts, not between the epilogue's instructions
 GRL_DEVINL void gelu_both4_pk(const float4& x, float4& gv, float4& gpv) {
@@ -688,7 +706,8 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) b2q[nt] = *reinterpret_cast<const float4*>(w.b2s + 16 * nt + 4 * g);
         // dW1 (| db1) of the PREVIOUS pass: its operands were staged at that pass's end (zero tiles before a wave's first pass); the six
-        // MFMAs run beside this pass's first GELU instead of standing alone behind an exposed LDS round trip
+        // MFMAs run beside this pass's invariants (fp32 build; plain-bf16 build: beside its first GELU) instead of standing alone behind an
+        // exposed LDS round trip
         RFrags<1> rf1;
         rowred_load<1>(st, lane, rf1);
         __builtin_amdgcn_sched_barrier(0);
@@ -701,13 +720,47 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
         float dz = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, paz), node)) -
                    __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, poz), k));
         if (p.dim == 2) dz = 0.f;
+#if !GRL_PREC
+        // fp32 build: the six dW1 MFMAs of the previous pass go here, one in front of each piece of the invariants (plain f32 instructions, which
+        // issue in an MFMA's shadow; behind layer 1's MFMAs, where they stood, nothing but the packed GELU was there to fill it).  PIN as below.
+        // The two sums are written as the FMA chains the one-statement form below compiles to (the middle product unfused, then x, then z):
+        // with the statements cut apart the compiler would pick another product to leave unfused, and the invariants would round differently.
+#define PIN_(x) asm volatile("" : "+v"(x))
+#define DW1_STEP(k_) do { __builtin_amdgcn_sched_barrier(0); rowred_mma_step<1>(rf1, accB, k_); } while (0)
+        PIN_(dx); PIN_(dy); PIN_(dz);
+        DW1_STEP(0);
+        PIN_(dx);
+        float a = __builtin_fmaf(dz, gz, __builtin_fmaf(dx, gx, dy * gy));
+        PIN_(a);
+        DW1_STEP(1);
+        PIN_(a);
+        dx = __builtin_fmaf(-a, gx, dx); dy = __builtin_fmaf(-a, gy, dy); dz = __builtin_fmaf(-a, gz, dz);
+        PIN_(dx); PIN_(dy); PIN_(dz);
+        DW1_STEP(2);
+        PIN_(dx);
+        float b = __builtin_amdgcn_sqrtf(__builtin_fmaf(dz, dz, __builtin_fmaf(dx, dx, dy * dy)));   // 1 ulp; the IEEE expansion costs 15 instructions
+        PIN_(b);
+        DW1_STEP(3);
+        PIN_(b);
+        float aa = a * a, ab = a * b, bb = b * b;
+        PIN_(aa); PIN_(ab); PIN_(bb);
+        DW1_STEP(4);
+        PIN_(ab);
+        float aba = ab * a, abb = ab * b;   // (products grouped as the reference's outer products)
+        PIN_(aba); PIN_(abb);
+        DW1_STEP(5);
+        PIN_(a);
+#undef DW1_STEP
+#undef PIN_
+#else
         const float a = dx * gx + dy * gy + dz * gz;
         dx -= a * gx; dy -= a * gy; dz -= a * gz;
         const float b = __builtin_amdgcn_sqrtf(dx * dx + dy * dy + dz * dz);   // 1 ulp; the IEEE expansion costs 15 instructions
+        const float aa = a * a, ab = a * b, bb = b * b, aba = ab * a, abb = ab * b;   // (products grouped as the reference's outer products)
+#endif
         // ---- chain with derivatives
         // polynomial features 4 g .. 4 g + 3 of this lane (ponita.py:233-244), by selects; column 14 carries a one: the dW1 product then
         // leaves db1 in column 14 (W1's image has zeros there)
-        const float aa = a * a, ab = a * b, bb = b * b, aba = ab * a, abb = ab * b;   // (products grouped as the reference's outer products)
         float4 phi;
         phi.x = g0 ? a : g1_ ? ab : g2_ ? aba : bb * a;
         phi.y = g0 ? b : g1_ ? bb : g2_ ? abb : bb * b;
@@ -728,8 +781,8 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
 #if GRL_PREC
         // a 64-deep layer from a resident buffer: four independent two-deep MFMA chains, then the epilogues, then the tail (which refills
         // the buffer for its next use -- behind a scheduling barrier, so every MFMA that reads the buffer has delivered its result first)
-        auto layer64 = [&](int base, const bf16x8 (&ih)[2], const bf16x8 (&il)[2], auto&& epi, auto&& tail) {
-          (void)il;
+        auto layer64 = [&](int base, const bf16x8 (&ih)[2], bf16x8 (&il)[2], auto&& lo_form, auto&& epi, auto&& tail) {
+          (void)il; (void)lo_form;
           LayerFrags& f = (base == 0 || base == 8) ? bufA : bufB;
           f32x4v c[4];
 #pragma unroll
@@ -746,7 +799,9 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
           BAR();
         };
 #else
-        auto layer64 = [&](int base, const bf16x8 (&ih)[2], const bf16x8 (&il)[2], auto&& epi, auto&& tail) {
+        // lo_form(s): forms il[s] from the layer's fp32 input where the producer left only the hi halves (layers 2 and K: their inputs are not
+        // staged before the layer runs) -- the plain f32 instructions of the split issue in the shadow of the eight MFMAs that need ih[s] alone
+        auto layer64 = [&](int base, const bf16x8 (&ih)[2], bf16x8 (&il)[2], auto&& lo_form, auto&& epi, auto&& tail) {
           f32x4v c[4];
 #pragma unroll
           for (int nt = 0; nt < 4; ++nt) c[nt] = base == 0 ? f32x4v{b2q[nt].x, b2q[nt].y, b2q[nt].z, b2q[nt].w} : f32x4v{0.f, 0.f, 0.f, 0.f};
@@ -754,6 +809,7 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
           for (int s_ = 0; s_ < 2; ++s_) {   // (per accumulator the same six products in the same order as the grouped form: bitwise equal)
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) c[nt] = mfma16(buf.h[nt][s_], ih[s_], c[nt]);
+            lo_form(s_);
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) c[nt] = mfma16(buf.l[nt][s_], ih[s_], c[nt]);
 #pragma unroll
@@ -771,9 +827,34 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
           BAR();
         };
 #endif
+        auto lo_none = [](int) {};
 #if !GRL_PREC
+        // a weight-gradient product's twelve MFMAs, the split of the layer's output (eight pairs) in their shadow: one pair behind each of the
+        // first eight.  The layer's packed epilogue stays in front of the first MFMA (a packed f32 instruction does not issue in the shadow).
+        // (volatile asm statements keep their order: an empty one that re-defines a pair's input keeps the pair behind the MFMA in front of it,
+        // one that re-defines its output keeps it in front of the next MFMA -- node_mlp16.hip PIN)
+#define PIN(x) asm volatile("" : "+v"(x))
+        auto rowred_mma_beside_split = [&](const RFrags<2>& f, f32x16 (&acc_)[2][2], float4 (&x)[4], bf16x8 (&hi)[2], bf16x8 (&lo)[2]) {
+          u32x4 h4[2], l4[2];
+          BAR();
+#pragma unroll
+          for (int k_ = 0; k_ < 12; ++k_) {
+            rowred_mma_step<2>(f, acc_, k_);
+            if (k_ < 8) {
+              if (k_ & 1) PIN(x[k_ >> 1].z); else PIN(x[k_ >> 1].x);
+              split_step(x, h4, l4, k_);
+              PIN(h4[k_ >> 2][k_ & 3]); PIN(l4[k_ >> 2][k_ & 3]);
+            }
+            BAR();
+          }
+#pragma unroll
+          for (int s_ = 0; s_ < 2; ++s_) {
+            hi[s_] = __builtin_bit_cast(bf16x8, h4[s_]);
+            lo[s_] = __builtin_bit_cast(bf16x8, l4[s_]);
+          }
+        };
+        float4 g1[4], g2[4];   // layer 1's and layer 2's outputs in fp32: each lives until the NEXT layer has formed its lo halves from it
         {
-          float4 g1[4];
           BAR();
           f32x4v c[4];
 #pragma unroll
@@ -784,12 +865,11 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
           for (int nt = 0; nt < 4; ++nt) c[nt] = mfma16(w1l[nt], ph[0], c[nt]);
 #pragma unroll
           for (int nt = 0; nt < 4; ++nt) c[nt] = mfma16(w1h[nt], pl[0], c[nt]);
-          rowred_mma<1>(rf1, accB);
-          BAR();
+          BAR();   // (dW1's MFMAs of the previous pass: beside the invariants, above)
 #pragma unroll
           for (int nt = 0; nt < 4; ++nt) gelu_both4_pk(v4(c[nt]), g1[nt], gp1[nt]);
-          split_pair(g1[0], g1[1], xh[0], xl[0]);
-          split_pair(g1[2], g1[3], xh[1], xl[1]);
+          xh[0] = split_hi(g1[0], g1[1]);   // (the lo halves: inside layer 2, beside its first MFMAs)
+          xh[1] = split_hi(g1[2], g1[3]);
           BAR();
         }
 #else
@@ -814,14 +894,23 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
         }
 #endif
         B16_PH(1);   // layer 1 (12 MFMA, GELU + derivative, split)
+#if !GRL_PREC
+        layer64(0, xh, xl, [&](int s_) { xl[s_] = split_lo(g1[2 * s_], g1[2 * s_ + 1]); },
+                [&](int nt, const f32x4v& c) { gelu_both4_pk(v4(c), g2[nt], gp2[nt]); },
+                [&]() {
+                  yh[0] = split_hi(g2[0], g2[1]);
+                  yh[1] = split_hi(g2[2], g2[3]);
+                });
+#else
         {
           float4 g2[4];
-          layer64(0, xh, xl, [&](int nt, const f32x4v& c) { gelu_both4_pk(v4(c), g2[nt], gp2[nt]); },
+          layer64(0, xh, xl, lo_none, [&](int nt, const f32x4v& c) { gelu_both4_pk(v4(c), g2[nt], gp2[nt]); },
                   [&]() {
                     split_pair(g2[0], g2[1], yh[0], yl[0]);
                     split_pair(g2[2], g2[3], yh[1], yl[1]);
                   });
         }
+#endif
         B16_PH(2);   // layer 2 (24 MFMA, GELU + derivative, split)
 #if GRL_PREC
         materialise();   // the node's own rows, requested at the node change, are widened here -- first use below
@@ -829,7 +918,41 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
         // ---- K = Wk g2: d x_src row += K * dM;  dK = dM * x_src, staged with g2 for dWk += dK^T g2 (consumed after the dZ2 groups)
         bf16x8 kh[2], kl[2];
         RFrags<2> rf;
-        layer64(4, yh, yl, [&](int nt, const f32x4v& c) { acc[nt] = f4_add_pk(acc[nt], f4_mul_pk(v4(c), dv[nt])); },
+#if !GRL_PREC
+        auto lo_y = [&](int s_) { yl[s_] = split_lo(g2[2 * s_], g2[2 * s_ + 1]); };
+#else
+        auto lo_y = lo_none;
+#endif
+#if !GRL_PREC
+        // dK's hi halves are formed and staged here, its lo halves inside the dZ2 layer (beside that layer's first MFMAs, as xl and yl), where
+        // they are staged and their transposed fragments requested as well: dWk's MFMAs stand behind that layer's epilogue
+        float4 dkf[4];
+        layer64(4, yh, yl, lo_y, [&](int nt, const f32x4v& c) { acc[nt] = f4_add_pk(acc[nt], f4_mul_pk(v4(c), dv[nt])); },
+                [&]() {
+#pragma unroll
+                  for (int nt = 0; nt < 4; ++nt) dkf[nt] = f4_mul_pk(dv[nt], xv[nt]);
+                  kh[0] = split_hi(dkf[0], dkf[1]);
+                  kh[1] = split_hi(dkf[2], dkf[3]);
+                  stage_put_half<2>(st.Ah, kh, r, g);
+                  stage_put<2>(st.Bh, st.Bl, yh, yl, r, g);
+#pragma unroll
+                  for (int t = 0; t < 2; ++t) {
+                    rf.ah[t] = tr_frag(st.Ah, t, lane);
+                    rf.bh[t] = tr_frag(st.Bh, t, lane);
+                    rf.bl[t] = tr_frag(st.Bl, t, lane);
+                  }
+                });
+        auto lo_k = [&](int s_) {
+          kl[s_] = split_lo(dkf[2 * s_], dkf[2 * s_ + 1]);
+          if (s_ == 1) {
+            stage_put_half<2>(st.Al, kl, r, g);
+#pragma unroll
+            for (int t = 0; t < 2; ++t) rf.al[t] = tr_frag(st.Al, t, lane);
+          }
+        };
+#else
+        auto lo_k = lo_none;
+        layer64(4, yh, yl, lo_y, [&](int nt, const f32x4v& c) { acc[nt] = f4_add_pk(acc[nt], f4_mul_pk(v4(c), dv[nt])); },
                 [&]() {
                   split_pair(f4_mul_pk(dv[0], xv[0]), f4_mul_pk(dv[1], xv[1]), kh[0], kl[0]);
                   split_pair(f4_mul_pk(dv[2], xv[2]), f4_mul_pk(dv[3], xv[3]), kh[1], kl[1]);
@@ -837,20 +960,25 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
                   stage_put<2>(st.Bh, st.Bl, yh, yl, r, g);
                   rowred_load<2>(st, lane, rf);
                 });
+#endif
         B16_PH(3);   // K (24 MFMA), d x_src, dK, staging dK | g2, transposed reads issued
         // ---- dZ2 = (Wk^T dK) * gelu'(z2);  db2;  then dWk's MFMAs beside the split of dZ2
         bf16x8 zh[2], zl[2];
         {
           float4 dz2[4];
-          layer64(8, kh, kl,
+          layer64(8, kh, kl, lo_k,
                   [&](int nt, const f32x4v& c) {
                     dz2[nt] = f4_mul_pk(v4(c), gp2[nt]);
                     db2[nt] = f4_add_pk(db2[nt], dz2[nt]);
                   },
                   [&]() {
+#if !GRL_PREC
+                    rowred_mma_beside_split(rf, accK, dz2, zh, zl);
+#else
                     rowred_mma<2>(rf, accK);
                     split_pair(dz2[0], dz2[1], zh[0], zl[0]);
                     split_pair(dz2[2], dz2[3], zh[1], zl[1]);
+#endif
                   });
         }
         B16_PH(4);   // dZ2 (24 MFMA), dWk (12 MFMA 32x32), split dZ2
@@ -862,11 +990,15 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
         bf16x8 uh[2], ul[2];
         {
           float4 dz1[4];
-          layer64(12, zh, zl, [&](int nt, const f32x4v& c) { dz1[nt] = f4_mul_pk(v4(c), gp1[nt]); },
+          layer64(12, zh, zl, lo_none, [&](int nt, const f32x4v& c) { dz1[nt] = f4_mul_pk(v4(c), gp1[nt]); },
                   [&]() {
+#if !GRL_PREC
+                    rowred_mma_beside_split(rf, accA, dz1, uh, ul);
+#else
                     rowred_mma<2>(rf, accA);
                     split_pair(dz1[0], dz1[1], uh[0], ul[0]);
                     split_pair(dz1[2], dz1[3], uh[1], ul[1]);
+#endif
                   });
         }
         B16_PH(5);   // staging dZ2 | g1, dZ1 (24 MFMA), dW2 (12 MFMA 32x32), split dZ1
@@ -884,6 +1016,7 @@ __global__ __launch_bounds__(256, 1) void edge_bwd16_kernel(Bwd16Params bp) {
         }
         B16_PH(6);   // staging dZ1 | phi (their product runs in the next pass)
 #undef BAR
+#undef PIN
       }
     }
     flush(node);                  // the last node with edges (or node 0 of a chunk without any), then the trailing nodes without

@@ -377,6 +377,24 @@ GRL_DEVINL void split_pair(const float4& f0, const float4& f1, bf16x8& hi, bf16x
   hi = __builtin_bit_cast(bf16x8, h);
   lo = __builtin_bit_cast(bf16x8, l);
 }
+#if !GRL_PREC
+// the two halves of split_pair on their own (same operations, same bits): a one-wave kernel forms hi where the fragments are produced and lo
+// beside the first MFMAs that consume hi -- plain f32 instructions issue in an MFMA's shadow, and the lo operand is not needed before the
+// third product of a K-step (edge_conv16.hip layer64)
+GRL_DEVINL bf16x8 split_hi(const float4& f0, const float4& f1) {
+  u32x4 h;
+  h[0] = pack_hi(f0.x, f0.y); h[1] = pack_hi(f0.z, f0.w); h[2] = pack_hi(f1.x, f1.y); h[3] = pack_hi(f1.z, f1.w);
+  return __builtin_bit_cast(bf16x8, h);
+}
+GRL_DEVINL bf16x8 split_lo(const float4& f0, const float4& f1) {
+  u32x4 l;
+  l[0] = pack_rn(f0.x - trunc_bf16(f0.x), f0.y - trunc_bf16(f0.y));
+  l[1] = pack_rn(f0.z - trunc_bf16(f0.z), f0.w - trunc_bf16(f0.w));
+  l[2] = pack_rn(f1.x - trunc_bf16(f1.x), f1.y - trunc_bf16(f1.y));
+  l[3] = pack_rn(f1.z - trunc_bf16(f1.z), f1.w - trunc_bf16(f1.w));
+  return __builtin_bit_cast(bf16x8, l);
+}
+#endif
 template <int K>
 GRL_DEVINL void split_frags(const float4 (&x)[K / 8], bf16x8 (&hi)[K / 16], bf16x8 (&lo)[K / 16]) {
 #pragma unroll

@@ -59,6 +59,16 @@ GRL_DEVINL void stage_put(unsigned short* ih, unsigned short* il, const bf16x8 (
 #endif
   }
 }
+// one image (hi or lo) on its own: the fp32 edge backward stages dK's lo halves a layer later than its hi halves (edge_conv16.hip)
+template <int KS>
+GRL_DEVINL void stage_put_half(unsigned short* img, const bf16x8 (&f)[KS], int r, int g) {
+#pragma unroll
+  for (int s = 0; s < KS; ++s) {
+    const u32x4 h = __builtin_bit_cast(u32x4, f[s]);
+    *reinterpret_cast<uint2*>(img + stg_off(r, 8 * s + g)) = make_uint2(h[0], h[1]);
+    *reinterpret_cast<uint2*>(img + stg_off(r, 8 * s + 4 + g)) = make_uint2(h[2], h[3]);
+  }
+}
 // Weight-gradient accumulators are pinned to the accumulator half of the register file: the MFMA is an asm statement with the tile as
 // a read-write "a" operand (updated in place, never copied), while the files that use it are compiled with
 // -mllvm -amdgpu-mfma-vgpr-form so that the chain's builtin MFMAs keep their results in ordinary VGPRs, where the activation reads them
