@@ -152,7 +152,7 @@ def gae(reward, done, terminated, values, gamma=0.99, lmbda=0.95):
     adv = torch.empty_like(reward)
     tgt = torch.empty_like(reward)
     hip.call("grl_gae_scan", reward.contiguous(), done.to(torch.uint8).contiguous(), terminated.to(torch.uint8).contiguous(),
-             values.contiguous(), adv, tgt, N, T, float(gamma), float(lmbda))
+             values.contiguous(), adv, tgt, N, T, gamma, lmbda)
     return adv, tgt
 
 

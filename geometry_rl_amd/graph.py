@@ -389,7 +389,7 @@ class HyperData:
             # node ranges of the source-sorted CSR, carry equal numbers of edges.  kNN out-degrees vary 0 .. 10: cutting the natural order at
             # node boundaries leaves the slowest wave 25 % over the mean at a 512-frame shard (30 passes for 24), and a one-wave-per-SIMD
             # kernel runs as long as its slowest wave (balanced_node_order).  A function of the topology alone: results stay reproducible.
-            slots = 4 * hip.query("grl_edge_bwd_blocks", int(src.numel()))
+            slots = 4 * hip.query("grl_edge_bwd_blocks", src.numel())
             new_of_old, split_s_int = balanced_node_order(src, n_main, slots)
             new_of_old = new_of_old.to(dev)
             src, dst, cid = new_of_old[src], new_of_old[dst], new_of_old[cid]
@@ -483,7 +483,6 @@ class HyperData:
         """rigid_tasks_data.py / base_data.py:45-55.  Positional obs tensors in ``spec.in_features`` order.  All node features
         (and the raw positions) are written by ONE launch of ``grl_build_features``; with ``train`` and training noise on, that launch
         (``grl_build_features_noise``) also adds the noise of the generator's current draw and advances the draw."""
-        import ctypes
         spec = self.spec
         obs = {k: (v if v.dtype == torch.float32 and v.is_contiguous() else v.float().contiguous())
                for k, v in zip(spec.in_features, args)}
@@ -565,13 +564,13 @@ class HyperData:
             # noise: (host noise words, device state, std, advance) -- the draw advances by one per launch, in stream order
             noise = None
             if noisy:
-                noise = ((ctypes.c_longlong * n_desc)(*nwords), self._noise_state_tensor(dev), self.training_noise_std, int(self._noise_advance))
+                noise = (nwords, self._noise_state_tensor(dev), self.training_noise_std, int(self._noise_advance))
             if ops.HEAD is not None and ops.HEAD.feat is None:   # rides in the merged head launch of this forward (ops.HeadLaunch)
-                ops.HEAD.feat = ((ctypes.c_longlong * len(words))(*words), n_desc, bump, noise)
+                ops.HEAD.feat = (words, n_desc, bump, noise)
             elif noise is not None:
-                hip.call("grl_build_features_noise", (ctypes.c_longlong * len(words))(*words), n_desc, bump, *noise)
+                hip.call("grl_build_features_noise", words, n_desc, bump, *noise)
             else:
-                hip.call("grl_build_features_bump", (ctypes.c_longlong * len(words))(*words), n_desc, bump)
+                hip.call("grl_build_features_bump", words, n_desc, bump)
             self._keepalive = obs  # the launch reads these buffers asynchronously
             graph = GraphBatch(B, list(self.node_type_list), {t: (topo["n_main"] if t == main else B * topo["n_per"][t])
                                                               for t in self.node_type_list}, graph_pos,

@@ -5,9 +5,9 @@ therefore every op of the package) raises.  Tensors are passed as raw device poi
 """
 import ctypes
 import os
+import re
 import subprocess
 import sys
-from typing import Sequence
 
 import torch
 
@@ -36,6 +36,7 @@ VARIANTS = [("edge_conv.hip", ["-DGRL_PREC=1"], ".bf16"), ("edge_conv16.hip", ["
 BUILD_INFO = os.path.join(os.path.dirname(_HERE), "BUILD_INFO.json")
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 HASH_TAG = b"GRL_SOURCE_HASH="
+EXPORT_RE = r"\bint\s+(grl_[a-z0-9_]+)\s*\("   # the entry points of include/grl_hip.h: the names the link's version script exports
 
 
 def _sha(*chunks) -> str:
@@ -75,7 +76,6 @@ def source_hash(root=None) -> str:
 
 def embedded_hash(path) -> str:
     """The source hash a built library carries (read from the file's bytes: no dlopen), or "" for a library without one."""
-    import re
     try:
         m = re.search(HASH_TAG + rb"([0-9a-f]{16})", _read(path))
     except OSError:
@@ -183,8 +183,7 @@ def build(verbose: bool = True, force: bool = False, root=None) -> str:
     if lint_failed:
         raise RuntimeError("ISA lint failed (geometry_rl_amd/isa_lint.py): " + " | ".join(lint_failed))
     # exports = exactly the entry points include/grl_hip.h declares (cross-file helpers such as grl_edge16_launch stay internal)
-    import re
-    names = sorted(set(re.findall(r"\bint\s+(grl_[a-z0-9_]+)\s*\(", open(header).read())))
+    names = sorted(set(re.findall(EXPORT_RE, open(header).read())))
     vs = os.path.join(bdir, "exports.map")
     with open(vs, "w") as f:
         f.write("{\n  global:\n" + "".join(f"    {n};\n" for n in names) + "  local: *;\n};\n")
@@ -209,42 +208,120 @@ def build(verbose: bool = True, force: bool = False, root=None) -> str:
     return lib_path
 
 
-_lib = None
+# ---- the typed boundary: every entry point's argument types come from include/grl_hip.h ------------------------------------------------
+SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "long long": ctypes.c_longlong, "float": ctypes.c_float,
+           "double": ctypes.c_double, "hipStream_t": ctypes.c_void_p}
+_I4, _I8 = {torch.int32, torch.uint32}, {torch.int64, torch.uint64}
+_B1 = {torch.uint8, torch.int8, torch.bool, torch.float8_e4m3fn, torch.float8_e5m2}
+# pointee -> (ctypes element type, the tensor dtypes of its kind and width; None: any)
+POINTEES = {"float": (ctypes.c_float, {torch.float32}), "double": (ctypes.c_double, {torch.float64}), "grl_bf16": (ctypes.c_ushort, {torch.bfloat16}),
+            "int": (ctypes.c_int, _I4), "unsigned": (ctypes.c_uint, _I4), "unsigned int": (ctypes.c_uint, _I4), "long long": (ctypes.c_longlong, _I8),
+            "unsigned long long": (ctypes.c_ulonglong, _I8), "unsigned char": (ctypes.c_ubyte, _B1), "char": (ctypes.c_char, _B1), "void": (None, None)}
+_PASSED_ON = (type(ctypes.byref(ctypes.c_int())), ctypes.c_void_p, ctypes.c_char_p, ctypes._Pointer)
+
+
+class Pointer:
+    """ctypes argument type of one pointer parameter (one subclass per declared type in CTYPES).  It takes None (NULL); a contiguous device
+    tensor of the pointee's kind and width; a ctypes byref / pointer (passed on) or array (its element width checked); and, where the pointee
+    is const (the header's HOST arrays), a list or tuple -- of numbers, or for an array of pointers (``inner``: the element's type) of
+    tensors, None and integer addresses."""
+    decl, elem, dtypes, const, inner = "void*", None, None, False, None
+
+    @classmethod
+    def address(cls, t: torch.Tensor) -> int:
+        if not t.is_contiguous():
+            raise ValueError("non-contiguous tensor passed to a HIP kernel")
+        if cls.dtypes is not None and t.dtype not in cls.dtypes:
+            raise TypeError(f"{cls.decl} does not point at {t.dtype} elements")
+        if not t.is_cuda:
+            raise TypeError(f"{cls.decl} points at device memory, the tensor is on {t.device}")
+        return t.data_ptr()
+
+    @classmethod
+    def from_param(cls, a):
+        if isinstance(a, torch.Tensor):
+            return ctypes.c_void_p(cls.address(a))
+        if a is None or isinstance(a, _PASSED_ON):
+            return a
+        if isinstance(a, ctypes.Array) and (cls.elem is None or ctypes.sizeof(a._type_) == ctypes.sizeof(cls.elem)):
+            return a
+        if isinstance(a, (list, tuple)) and cls.const and cls.elem is not None:
+            return (cls.elem * len(a))(*[cls.inner.address(e) if cls.inner and isinstance(e, torch.Tensor) else e for e in a])
+        what = f"an array of {a._type_.__name__}" if isinstance(a, ctypes.Array) else f"a {type(a).__name__}"
+        raise TypeError(f"{cls.decl} takes None, a device tensor, a ctypes array / pointer{' or a list' if cls.const else ''}, not {what}")
+
+
+CTYPES = dict(SCALARS)   # declared parameter type -> ctypes argument type: the header's whole vocabulary
+for _p, (_elem, _dtypes) in POINTEES.items():
+    for _c in ("", "const "):
+        _t = CTYPES[_c + _p + "*"] = type("Pointer", (Pointer,), dict(decl=_c + _p + "*", elem=_elem, dtypes=_dtypes, const=bool(_c)))
+        CTYPES[_c + _p + "* const*"] = type("Pointer", (Pointer,), dict(decl=_c + _p + "* const*", elem=ctypes.c_void_p, dtypes=set(), const=True, inner=_t))
+
+
+def parse_header(text: str) -> dict:
+    """include/grl_hip.h (or a header in its style) -> {entry point: [(declared type, parameter name, ctypes type)]}.  Every statement is a
+    typedef or ``int grl_x(...)`` over known types and the names are exactly the exported ones: anything else raises and names it."""
+    body = re.sub(r'/\*.*?\*/|^\s*#[^\n]*|extern "C" \{', " ", text, flags=re.S | re.M)
+    decls = {}
+    for stmt in (" ".join(s.split()) for s in body.split(";")):
+        if stmt in ("", "}") or stmt.startswith("typedef "):
+            continue
+        try:
+            name, plist = re.fullmatch(r"int (grl_\w+) ?\((.*)\)", stmt).groups()
+            params = [re.fullmatch(r"(.*\W)(\w+)", p.strip()).groups() for p in plist.split(",") if plist != "void"]
+            decls[name] = [(t.strip(), n, CTYPES[t.strip()]) for t, n in params]
+        except (AttributeError, KeyError) as e:
+            raise ValueError(f"cannot bind the declaration '{stmt}' ({e!r})") from None
+    if set(re.findall(EXPORT_RE, text)) != set(decls):
+        raise ValueError(f"parsed and exported names differ: {sorted(set(re.findall(EXPORT_RE, text)) ^ set(decls))}")
+    return decls
+
+
+def bind(header_text: str, cdll) -> dict:
+    """{name: entry point of ``cdll``} for every declaration of the header, ``restype`` and ``argtypes`` set once, here (``fn.params``: the
+    header's (declared type, parameter name, ctypes type) list)."""
+    entries = {}
+    for name, params in parse_header(header_text).items():
+        fn = entries[name] = getattr(cdll, name)
+        fn.restype, fn.params, fn.argtypes = ctypes.c_int, params, [p[2] for p in params]
+    return entries
+
+
+def invoke(entries: dict, name: str, args) -> int:
+    """entries[name](*args), refusing an undeclared name, a wrong argument count and -- in the header's words -- a wrong argument."""
+    fn = entries.get(name)
+    if fn is None:
+        raise AttributeError(f"{name} is not declared in the header (include/grl_hip.h): no entry point is called untyped")
+    if len(args) != len(fn.params):   # (ctypes itself lets surplus arguments through)
+        raise TypeError(f"{name} takes {len(fn.params)} arguments ({', '.join(p[1] for p in fn.params)}), {len(args)} given")
+    try:
+        return fn(*args)
+    except ctypes.ArgumentError as e:   # ctypes' "argument 3: TypeError: ..." with the header's words for that parameter
+        decl, pname, _ = fn.params[int(str(e).split(":")[0].split()[-1]) - 1]
+        raise (ValueError if ": ValueError: " in str(e) else TypeError)(f"{name}: '{pname}' ({decl}), {e}") from None
+
+
+_lib = _bound = None
 
 
 def lib() -> ctypes.CDLL:
-    global _lib
+    global _lib, _bound
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(
                 f"{LIB_PATH} is missing: the HIP extension must be built (python -c 'import __graft_entry__ as g; g.build()'). "
                 "geometry_rl_amd has no CPU or PyTorch fallback path.")
-        _lib = ctypes.CDLL(LIB_PATH)
+        cdll = ctypes.CDLL(LIB_PATH)
         # the binary must be the one THESE sources build (an explicitly named debugging library -- GRL_LIB, tools/r0*_ab_libs.sh -- is the
         # caller's business; GRL_ALLOW_STALE_LIB=1 switches the check off for bisecting)
         if "GRL_LIB" not in os.environ and os.environ.get("GRL_ALLOW_STALE_LIB", "0") == "0":
             check_library(LIB_PATH)
-        _lib.grl_version.restype = ctypes.c_int
-        if _lib.grl_version() != ABI_VERSION:
-            raise RuntimeError(f"{LIB_PATH} reports ABI version {_lib.grl_version()}, this package binds version {ABI_VERSION} "
+        bound = bind(_read(_pkg_paths()[1]).decode(), cdll)
+        if cdll.grl_version() != ABI_VERSION:
+            raise RuntimeError(f"{LIB_PATH} reports ABI version {cdll.grl_version()}, this package binds version {ABI_VERSION} "
                                "(include/grl_hip.h GRL_HIP_VERSION): rebuild the extension (__graft_entry__.build())")
+        _lib, _bound = cdll, bound
     return _lib
-
-
-def _arg(a):
-    if torch.is_tensor(a):
-        if not a.is_contiguous():
-            raise ValueError("non-contiguous tensor passed to a HIP kernel")
-        return ctypes.c_void_p(a.data_ptr())
-    if a is None:
-        return ctypes.c_void_p(0)
-    if isinstance(a, bool):
-        return ctypes.c_int(int(a))
-    if isinstance(a, int):
-        return ctypes.c_int(a)
-    if isinstance(a, float):
-        return ctypes.c_float(a)
-    return a
 
 
 def stream_ptr() -> ctypes.c_void_p:
@@ -258,14 +335,12 @@ KERNEL_ROWS = {}   # name -> rows (edge x orientation / node x orientation) hand
 
 
 def call(name: str, *args, stream=None, rows: int = 0) -> None:
-    """Launch C-ABI entry point ``name`` on the current stream; raises on a non-zero status."""
-    fn = getattr(lib(), name)
-    fn.restype = ctypes.c_int
+    """Launch C-ABI entry point ``name`` on the current stream; raises on a refused argument (before the launch) and on a non-zero status."""
     timing = KERNEL_TIMES is not None
     if timing:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    rc = fn(*[_arg(a) for a in args], stream if stream is not None else stream_ptr())
+    rc = query(name, *args, stream if stream is not None else stream_ptr())
     if timing:
         e1.record()
         KERNEL_TIMES.setdefault(name, []).append((e0, e1))
@@ -282,17 +357,16 @@ def kernel_time_summary():
 
 def kernel_prof_enable(on: bool) -> None:
     """In-library HIP-event timing of the kernels inside multi-kernel entry points (grl_prof_*)."""
-    lib().grl_prof_enable(ctypes.c_int(int(on)))
+    query("grl_prof_enable", int(on))
 
 
 def kernel_prof_summary():
     """-> {kernel name: (n_launches, total_ms)} from the in-library records (synchronises on each record)."""
-    l = lib()
     out = {}
     buf = ctypes.create_string_buffer(96)
     ms = ctypes.c_float(0.0)
-    for i in range(l.grl_prof_count()):
-        if l.grl_prof_get(ctypes.c_int(i), buf, ctypes.c_int(96), ctypes.byref(ms)) != 0:
+    for i in range(query("grl_prof_count")):
+        if query("grl_prof_get", i, buf, 96, ctypes.byref(ms)) != 0:
             raise RuntimeError("grl_prof_get failed")
         n, t = out.get(buf.value.decode(), (0, 0.0))
         out[buf.value.decode()] = (n + 1, t + ms.value)
@@ -301,9 +375,9 @@ def kernel_prof_summary():
 
 def query(name: str, *args) -> int:
     """Call a pure host-side query entry point (no stream argument)."""
-    fn = getattr(lib(), name)
-    fn.restype = ctypes.c_int
-    return fn(*[_arg(a) for a in args])
+    if _bound is None:
+        lib()
+    return invoke(_bound, name, args)
 
 
 def check_f32(*tensors: torch.Tensor):

@@ -41,7 +41,7 @@ class OneShotRank:
     def all_reduce(self):
         """Enqueue this rank's side on the current stream (every rank must; the kernels meet on the device)."""
         self.seq += 1
-        hip.call("grl_oneshot_allreduce", *self._ptrs, self.rank, self.world, self.n, ctypes.c_uint(self.seq), self.timeout_ms, self.status)
+        hip.call("grl_oneshot_allreduce", *self._ptrs, self.rank, self.world, self.n, self.seq, self.timeout_ms, self.status)
 
     def check(self):
         """Synchronises: raises if a wait of any call since the last check ran into its timeout."""
@@ -61,7 +61,7 @@ def all_reduce_local(ranks: List["OneShotRank"]):
     for r in ranks:
         r.seq = seq
     status = torch.zeros(len(ranks), device=r0.payload.device, dtype=torch.int32)
-    hip.call("grl_oneshot_allreduce_local", *r0._ptrs, r0.world, r0.n, ctypes.c_uint(seq), r0.timeout_ms, status)
+    hip.call("grl_oneshot_allreduce_local", *r0._ptrs, r0.world, r0.n, seq, r0.timeout_ms, status)
     return status
 
 

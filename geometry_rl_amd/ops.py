@@ -5,6 +5,7 @@ forward/backward kernel pair into autograd so the modules in ``geometry_rl_amd.m
 ``nn.Module``s.  No arithmetic of the hot path is done in Python/PyTorch.
 """
 import contextlib
+import ctypes
 from dataclasses import dataclass
 from typing import Optional
 
@@ -125,7 +126,6 @@ def deferred_folds():
 def _launch_folds(jobs, overwrite=False):
     """One launch per <= 64 slabs; every slab of a destination goes into the SAME launch (the kernel sums a destination's slabs in one
     workgroup, in the order given) -- with ``overwrite`` that is a requirement, not just the cheaper form."""
-    import ctypes
     order, by_dst = [], {}
     for j in jobs:                       # group by destination, first-appearance order (the summation order of a destination's slabs)
         k = j[3].data_ptr()
@@ -145,11 +145,14 @@ def _launch_folds(jobs, overwrite=False):
     if cur:
         batches.append(cur)
     for part in batches:
-        n = len(part)
-        hip.call("grl_reduce_partials_multi_ow", n, (ctypes.c_void_p * n)(*[j[0].data_ptr() for j in part]),
-                 (ctypes.c_int * n)(*[j[0].shape[0] for j in part]), (ctypes.c_int * n)(*[j[0].shape[1] for j in part]),
-                 (ctypes.c_int * n)(*[j[1] for j in part]), (ctypes.c_int * n)(*[j[2] for j in part]),
-                 (ctypes.c_void_p * n)(*[j[3].data_ptr() for j in part]), 1 if overwrite else 0)
+        hip.call("grl_reduce_partials_multi_ow", *_fold_args(part), bool(overwrite))
+
+
+def _fold_args(part):
+    """(n_seg, partial, n_rows, ld, start, len, dst): the head of every fold launch's argument list for the (slab, start, length,
+    destination) jobs ``part`` -- the six HOST arrays as plain lists."""
+    return (len(part), [j[0] for j in part], [j[0].shape[0] for j in part], [j[0].shape[1] for j in part], [j[1] for j in part],
+            [j[2] for j in part], [j[3] for j in part])
 
 
 def fold_adam_report(overwrite, adam=None, report=None, signal=None):
@@ -157,7 +160,6 @@ def fold_adam_report(overwrite, adam=None, report=None, signal=None):
     (grl_fold_adam_report).  ``adam``: dict(grads, params, exp_avg, exp_avg_sq, lr_dev, betas, eps, step_dev) or None; ``report``:
     dict(slots, batch, sums, maxes, ent_coef, out14) or None.  Returns False (nothing launched, queue untouched) when the queue does not fit
     one launch -- the caller then takes the separate launches."""
-    import ctypes
     global DEFERRED
     jobs = DEFERRED or []
     if len(jobs) > 64:
@@ -166,21 +168,15 @@ def fold_adam_report(overwrite, adam=None, report=None, signal=None):
     for j in jobs:
         by_dst.setdefault(j[3].data_ptr(), []).append(j)
     part = [j for grp in by_dst.values() for j in grp]
-    n = len(part)
     a, r = adam or {}, report or {}
     if adam is not None:   # every destination must lie inside the flat gradient buffer the optimizer state is parallel to
         lo, hi = a["grads"].data_ptr(), a["grads"].data_ptr() + 4 * a["grads"].numel()
         if any(not (lo <= j[3].data_ptr() and j[3].data_ptr() + 4 * j[2] <= hi) for j in part):
             return False
     sig = list(signal) if signal is not None else [None, None]   # (flag_dst, flag_src): a lane signal written when the launch starts
-    hip.call("grl_fold_adam_report_sig", n, (ctypes.c_void_p * max(n, 1))(*[j[0].data_ptr() for j in part]),
-             (ctypes.c_int * max(n, 1))(*[j[0].shape[0] for j in part]), (ctypes.c_int * max(n, 1))(*[j[0].shape[1] for j in part]),
-             (ctypes.c_int * max(n, 1))(*[j[1] for j in part]), (ctypes.c_int * max(n, 1))(*[j[2] for j in part]),
-             (ctypes.c_void_p * max(n, 1))(*[j[3].data_ptr() for j in part]), 1 if overwrite else 0, 1 if adam is not None else 0,
-             a.get("grads"), a.get("params"), a.get("exp_avg"), a.get("exp_avg_sq"), a.get("lr_dev"),
-             float(a["betas"][0]) if adam else 0.0, float(a["betas"][1]) if adam else 0.0, float(a["eps"]) if adam else 0.0,
-             a.get("step_dev"), r.get("slots"), int(r.get("batch", 0)), r.get("sums"), r.get("maxes"), float(r.get("ent_coef", 0.0)),
-             r.get("out14"), *sig)
+    hip.call("grl_fold_adam_report_sig", *_fold_args(part), bool(overwrite), adam is not None,
+             a.get("grads"), a.get("params"), a.get("exp_avg"), a.get("exp_avg_sq"), a.get("lr_dev"), *a.get("betas", (0, 0)), a.get("eps", 0),
+             a.get("step_dev"), r.get("slots"), r.get("batch", 0), r.get("sums"), r.get("maxes"), r.get("ent_coef", 0), r.get("out14"), *sig)
     if DEFERRED is not None:
         DEFERRED = []
     return True
@@ -189,7 +185,6 @@ def fold_adam_report(overwrite, adam=None, report=None, signal=None):
 def fold_record_pairs(overwrite, slots, batch, rank, world, region) -> bool:
     """Data parallel: the queued folds AND this rank's loss record (as (hi, lo) float pairs in front of the flat gradient) in ONE launch
     (grl_fold_record_pairs) -- both only feed the lane's all-reduce.  False (nothing launched) when the queue does not fit one launch."""
-    import ctypes
     global DEFERRED
     jobs = DEFERRED or []
     if len(jobs) > 64:
@@ -198,11 +193,7 @@ def fold_record_pairs(overwrite, slots, batch, rank, world, region) -> bool:
     for j in jobs:
         by_dst.setdefault(j[3].data_ptr(), []).append(j)
     part = [j for grp in by_dst.values() for j in grp]
-    n = len(part)
-    hip.call("grl_fold_record_pairs", n, (ctypes.c_void_p * max(n, 1))(*[j[0].data_ptr() for j in part]),
-             (ctypes.c_int * max(n, 1))(*[j[0].shape[0] for j in part]), (ctypes.c_int * max(n, 1))(*[j[0].shape[1] for j in part]),
-             (ctypes.c_int * max(n, 1))(*[j[1] for j in part]), (ctypes.c_int * max(n, 1))(*[j[2] for j in part]),
-             (ctypes.c_void_p * max(n, 1))(*[j[3].data_ptr() for j in part]), 1 if overwrite else 0, slots, int(batch), int(rank), int(world), region)
+    hip.call("grl_fold_record_pairs", *_fold_args(part), bool(overwrite), slots, batch, rank, world, region)
     if DEFERRED is not None:
         DEFERRED = []
     return True
@@ -230,9 +221,8 @@ def _emit_grads(partial: torch.Tensor, segments):
     one flat buffer) the sum is accumulated in place and ``None`` is handed to autograd (no AccumulateGrad add kernel);
     otherwise a fresh gradient tensor is returned.  While a DEFERRED queue is installed the leaf segments are only queued (one launch
     for all of them at the end of the backward pass) and the fresh ones are produced at once."""
-    import ctypes
     dev = partial.device
-    outs, dsts, starts, lens, fresh_flags = [], [], [], [], []
+    outs, dsts, fresh_flags = [], [], []
     skip = set()
     for i_, (start, length, shape, t) in enumerate(segments):
         if t is not None and t.is_leaf and not t.requires_grad:
@@ -247,22 +237,18 @@ def _emit_grads(partial: torch.Tensor, segments):
             outs.append(fresh)
             dsts.append(fresh)
             fresh_flags.append(1)
-        starts.append(start)
-        lens.append(length)
     now = [i for i in range(len(segments)) if i not in skip]
     for i in skip:
         outs[i] = None
     if DEFERRED is not None:
-        jobs = [(partial, st, ln, d) for i, (st, ln, d, f) in enumerate(zip(starts, lens, dsts, fresh_flags)) if not f and i not in skip]
+        jobs = [(partial, sg[0], sg[1], d) for i, (sg, d, f) in enumerate(zip(segments, dsts, fresh_flags)) if not f and i not in skip]
         now = [i for i, f in enumerate(fresh_flags) if f and i not in skip]
         DEFERRED.extend(jobs)   # keeps `partial` alive until the flush
     for i0 in range(0, len(now), 8):
         idx = now[i0:i0 + 8]
-        n = len(idx)
         mask = sum(fresh_flags[i] << k for k, i in enumerate(idx))
-        hip.call("grl_reduce_partials_seg", partial, partial.shape[0], partial.shape[1], n,
-                 (ctypes.c_void_p * n)(*[dsts[i].data_ptr() for i in idx]), (ctypes.c_int * n)(*[starts[i] for i in idx]),
-                 (ctypes.c_int * n)(*[lens[i] for i in idx]), mask)
+        hip.call("grl_reduce_partials_seg", partial, partial.shape[0], partial.shape[1], len(idx), [dsts[i] for i in idx],
+                 [segments[i][0] for i in idx], [segments[i][1] for i in idx], mask)
     return outs
 
 
@@ -287,22 +273,11 @@ class HeadLaunch:
         self.keep = []
 
     def launch(self, prec: str = ""):
-        import ctypes
         if self.feat is None and self.fiber is None and self.wimg is None:
             return
         words, n_desc, bump, noise = self.feat if self.feat is not None else (None, 0, None, None)
-        if self.fiber is not None:
-            poly2, P, W, saved, fks = self.fiber
-            n = len(W)
-            fargs = [poly2, *P, (ctypes.c_void_p * n)(*[t.data_ptr() for t in W]), n, saved, (ctypes.c_void_p * n)(*[t.data_ptr() for t in fks])]
-        else:
-            fargs = [None, None, None, None, None, None, 0, None, None]
-        if self.wimg is not None:
-            kinds, ptrs, outs = self.wimg
-            n_img = len(kinds)
-            wargs = [n_img, (ctypes.c_int * n_img)(*kinds), (ctypes.c_void_p * (6 * n_img))(*ptrs), (ctypes.c_void_p * n_img)(*outs)]
-        else:
-            wargs = [0, None, None, None]
+        fargs = self.fiber or [None, None, None, None, None, None, 0, None, None]   # (each role: its entry point's own argument list)
+        wargs = self.wimg or [0, None, None, None]
         if noise is not None:   # (training noise in the feature role: graph.HyperData.build_data)
             hip.call("grl_step_head_noise" + prec, words, n_desc, bump, *noise, *fargs, *wargs)
         else:
@@ -311,23 +286,9 @@ class HeadLaunch:
 
 
 def _tail_pre_launch(lift, fiber):
-    """lift = (prec, T, scal, vec, grid3, dxs, partial, ns, s, v) or None; fiber = (poly2, w2, W, saved, d, partial) or None: ONE launch."""
-    import ctypes
-    prec = lift[0] if lift is not None else ""
-    if lift is not None:
-        _, T, scal, vec, grid3, dxs, lpart, ns, s_, v_ = lift
-        largs = [T, (ctypes.c_void_p * T)(*[a.data_ptr() for a in scal]), (ctypes.c_void_p * T)(*[b.data_ptr() for b in vec]), grid3,
-                 (ctypes.c_void_p * T)(*[(d.data_ptr() if d is not None else 0) for d in dxs]), lpart, ns, s_, v_]
-    else:
-        largs = [0, None, None, None, None, None, None, 0, 0]
-    if fiber is not None:
-        poly2, w2, W, saved, d, fpart = fiber
-        n = len(W)
-        fargs = [poly2, w2, (ctypes.c_void_p * n)(*[t.data_ptr() for t in W]), n, saved,
-                 (ctypes.c_void_p * n)(*[(g.data_ptr() if g is not None else 0) for g in d]), fpart]
-    else:
-        fargs = [None, None, None, 0, None, None, None]
-    hip.call("grl_lift_fiber_basis_bwd" + prec, *largs, *fargs)
+    """lift = (prec, *the arguments of grl_lift_encode_bwd_multi) or None; fiber = the arguments of grl_fiber_basis_bwd or None: ONE launch."""
+    prec, *largs = lift or ("", 0, None, None, None, None, None, None, 0, 0)
+    hip.call("grl_lift_fiber_basis_bwd" + prec, *largs, *(fiber or [None, None, None, 0, None, None, None]))
 
 
 def _tail_pre_offer(kind, job):
@@ -371,7 +332,6 @@ def weight_images(blocks, grid3, basis, prec: str = "", with_backward: bool = Tr
     """One launch for all pre-split weight images of a forward pass.  ``blocks``: [(conv_kernel_weight [64,64], n_dst of the block's edge
     convolution, (gamma, beta, W3, b3, W4, b4) of its ConvNeXt block)]; ``basis`` = (W1, b1, W2, b2) of the shared basis MLP.
     -> [WeightImages] in the order of ``blocks`` (None entries when switched off)."""
-    import ctypes
     if not USE_WEIGHT_IMAGES or not blocks:
         return [None] * len(blocks)
     dev = grid3.device
@@ -381,7 +341,7 @@ def weight_images(blocks, grid3, basis, prec: str = "", with_backward: bool = Tr
     for i, (wk, n_dst, mlp) in enumerate(blocks):
         wk = wk.detach().contiguous()
         edge_src = [w1, b1, w2, b2, wk, grid3]
-        fwd_kind = hip.query("grl_edge_fwd_image_kind", int(n_dst))
+        fwd_kind = hip.query("grl_edge_fwd_image_kind", n_dst)
         if with_backward or fwd_kind == WIMG_EDGE16:
             jobs.append((WIMG_EDGE16, edge_src, i, "e16"))
         if fwd_kind == WIMG_EDGE32:
@@ -402,22 +362,14 @@ def weight_images(blocks, grid3, basis, prec: str = "", with_backward: bool = Tr
         setattr(out[i], member, v)
         views.append(v)
     cap = hip.query("grl_wimg_max_jobs")
+    srcs6 = lambda js: [t for j in js for t in j[1] + [None] * (6 - len(j[1]))]   # srcs [n][6]: a job's sources, unused slots NULL
     if HEAD is not None and HEAD.wimg is None and 0 < len(jobs) <= cap:   # rides in the merged head launch (HeadLaunch)
-        ptrs = []
-        for kind, srcs, _, _ in jobs:
-            ptrs += [t.data_ptr() for t in srcs] + [0] * (6 - len(srcs))
-            HEAD.keep += list(srcs)
-        HEAD.wimg = ([j[0] for j in jobs], ptrs, [v.data_ptr() for v in views])
-        HEAD.keep.append(buf)
+        HEAD.wimg = [len(jobs), [j[0] for j in jobs], srcs6(jobs), views]
+        HEAD.keep += [t for j in jobs for t in j[1]] + [buf]
         return out
     for j0 in range(0, len(jobs), cap):
         part = jobs[j0:j0 + cap]
-        n = len(part)
-        ptrs = []
-        for kind, srcs, _, _ in part:
-            ptrs += [t.data_ptr() for t in srcs] + [0] * (6 - len(srcs))
-        hip.call("grl_weight_images" + prec, n, (ctypes.c_int * n)(*[p_[0] for p_ in part]), (ctypes.c_void_p * (6 * n))(*ptrs),
-                 (ctypes.c_void_p * n)(*[v.data_ptr() for v in views[j0:j0 + n]]))
+        hip.call("grl_weight_images" + prec, len(part), [p_[0] for p_ in part], srcs6(part), views[j0:j0 + len(part)])
     return out
 
 
@@ -455,7 +407,6 @@ class LiftEncodeMulti(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, grid3, w_enc, prec, *sv):
-        import ctypes
         scal, vec = list(sv[0::2]), list(sv[1::2])
         hip.check_f32(grid3, w_enc, *scal, *vec)
         T = len(scal)
@@ -464,10 +415,7 @@ class LiftEncodeMulti(torch.autograd.Function):
             raise ValueError("LiftEncodeMulti: the node types must share the feature widths")
         dev = grid3.device
         xs = [torch.empty(a.shape[0], 16, 64, device=dev, dtype=hip.storage_dtype(prec)) for a in scal]
-        ns = [int(a.shape[0]) for a in scal]
-        hip.call("grl_lift_encode_fwd_multi" + prec, T, (ctypes.c_void_p * T)(*[a.data_ptr() for a in scal]),
-                 (ctypes.c_void_p * T)(*[b.data_ptr() for b in vec]), grid3, w_enc.contiguous(),
-                 (ctypes.c_void_p * T)(*[x.data_ptr() for x in xs]), (ctypes.c_int * T)(*ns), s, v)
+        hip.call("grl_lift_encode_fwd_multi" + prec, T, scal, vec, grid3, w_enc.contiguous(), xs, [a.shape[0] for a in scal], s, v)
         ctx.save_for_backward(grid3, *scal, *vec)
         ctx.kf, ctx.w_enc, ctx.prec, ctx.T, ctx.sv = s + v, w_enc, prec, T, (s, v)
         ctx.set_materialize_grads(False)   # a type whose latent never reaches the loss has no gradient: skipped, not zero-filled
@@ -475,27 +423,23 @@ class LiftEncodeMulti(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *dxs):
-        import ctypes
         grid3, *rest = ctx.saved_tensors
         T = ctx.T
         scal, vec = rest[:T], rest[T:]
         s, v = ctx.sv
         dxs = [d.contiguous() if d is not None else None for d in dxs]
-        for d in dxs:
-            if d is not None:
-                hip.check_latent(ctx.prec, d)
-        ns = (ctypes.c_int * T)(*[int(a.shape[0]) if d is not None else 0 for a, d in zip(scal, dxs)])
+        hip.check_latent(ctx.prec, *dxs)
+        ns = [a.shape[0] if d is not None else 0 for a, d in zip(scal, dxs)]
         blocks = hip.query("grl_lift_bwd_blocks_multi", T, ns)
         if blocks == 0:
             return (None,) * (3 + 2 * T)
         partial = torch.empty(blocks, 64 * ctx.kf, device=grid3.device, dtype=torch.float32)
+        largs = (T, list(scal), list(vec), grid3, dxs, partial, ns, s, v)
         if TAIL_PRE is not None and DEFERRED is not None and _all_leaf_grads([ctx.w_enc]):
             # (the fold of this slab is queued for the lane's tail anyway: the launch may wait for the fiber-basis backward and share its launch)
-            _tail_pre_offer("lift", (ctx.prec, T, list(scal), list(vec), grid3, dxs, partial, ns, s, v))
+            _tail_pre_offer("lift", (ctx.prec, *largs))
         else:
-            hip.call("grl_lift_encode_bwd_multi" + ctx.prec, T, (ctypes.c_void_p * T)(*[a.data_ptr() for a in scal]),
-                     (ctypes.c_void_p * T)(*[b.data_ptr() for b in vec]), grid3,
-                     (ctypes.c_void_p * T)(*[(d.data_ptr() if d is not None else 0) for d in dxs]), partial, ns, s, v)
+            hip.call("grl_lift_encode_bwd_multi" + ctx.prec, *largs)
         (dw,) = _emit_grads(partial, [(0, 64 * ctx.kf, (64, ctx.kf), ctx.w_enc)])
         return (None, dw, None) + (None,) * (2 * T)
 
@@ -648,7 +592,6 @@ class FiberKernels(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, poly, w1, b1, w2, b2, *wfs):
-        import ctypes
         hip.check_f32(poly, w1, b1, w2, b2, *wfs)
         n = len(wfs)
         dev = poly.device
@@ -657,29 +600,28 @@ class FiberKernels(torch.autograd.Function):
         W = [t.contiguous() for t in wfs]
         saved = torch.empty(4, 256, 64, device=dev, dtype=torch.float32)
         fks = [torch.empty(16, 16, 64, device=dev, dtype=torch.float32) for _ in range(n)]
+        fargs = [poly2, *P, W, n, saved, fks]
         if HEAD is not None and HEAD.fiber is None:   # rides in the merged head launch (HeadLaunch)
-            HEAD.fiber = (poly2, P, W, saved, fks)
+            HEAD.fiber = fargs
         else:
-            hip.call("grl_fiber_basis_fwd", poly2, *P, (ctypes.c_void_p * n)(*[t.data_ptr() for t in W]), n, saved,
-                     (ctypes.c_void_p * n)(*[t.data_ptr() for t in fks]))
+            hip.call("grl_fiber_basis_fwd", *fargs)
         ctx.save_for_backward(poly2, P[2], saved, *W)
         ctx.params = (w1, b1, w2, b2) + tuple(wfs)
         return tuple(fks)
 
     @staticmethod
     def backward(ctx, *dfks):
-        import ctypes
         poly2, w2, saved, *W = ctx.saved_tensors
         n = len(W)
         dev = poly2.device
         d = [g.contiguous() if g is not None else None for g in dfks]
         partial = torch.empty(hip.query("grl_fiber_basis_blocks"), hip.query("grl_fiber_basis_partial_size", n), device=dev,
                               dtype=torch.float32)
+        fargs = [poly2, w2, W, n, saved, d, partial]
         if TAIL_PRE is not None and DEFERRED is not None and _all_leaf_grads(ctx.params):
-            _tail_pre_offer("fiber", (poly2, w2, list(W), saved, d, partial))
+            _tail_pre_offer("fiber", fargs)
         else:
-            hip.call("grl_fiber_basis_bwd", poly2, w2, (ctypes.c_void_p * n)(*[t.data_ptr() for t in W]), n, saved,
-                     (ctypes.c_void_p * n)(*[(g.data_ptr() if g is not None else 0) for g in d]), partial)
+            hip.call("grl_fiber_basis_bwd", *fargs)
         pw1, pb1, pw2, pb2, *pwf = ctx.params
         o = n * 4096
         segs = [(i * 4096, 4096, (64, 64), pwf[i]) for i in range(n)]
@@ -757,7 +699,7 @@ class Readout(torch.autograd.Function):
         hidden = torch.empty(n, 64, device=dev, dtype=torch.float32)
         ws_, bs_ = ws.contiguous(), bs.contiguous()
         wd_, bd_ = wd.contiguous(), bd.contiguous()
-        hip.call("grl_readout_fwd", lat, grid3, wd_, bd_, ws_, bs_, float(shift), float(min_std), mean, sigma, hidden, n, od, ov)
+        hip.call("grl_readout_fwd", lat, grid3, wd_, bd_, ws_, bs_, shift, min_std, mean, sigma, hidden, n, od, ov)
         ctx.save_for_backward(lat, grid3, wd_, bd_, ws_, bs_)
         ctx.cfg = (float(shift), od, ov)
         ctx.params = (wd, bd, ws, bs)
@@ -815,12 +757,11 @@ class DeepSetsPipeline:
 
     def fwd2(self):
         w1, b1, g1, be1, w2, b2, w3, b3 = self.P[:8]
-        hip.call("grl_deepsets_fwd2", self.h1, self.stats1, ctypes_double(self.c1), g1, be1, w2, b2, w3, b3, self.z, self.u1,
-                 self.stats2, self.B, self.n)
+        hip.call("grl_deepsets_fwd2", self.h1, self.stats1, self.c1, g1, be1, w2, b2, w3, b3, self.z, self.u1, self.stats2, self.B, self.n)
 
     def fwd3(self):
         g2, be2, w4, b4, wv, bv = self.P[8:]
-        hip.call("grl_deepsets_fwd3", self.u1, self.stats2, ctypes_double(self.c2), g2, be2, w4, b4, wv, bv, self.value, self.B)
+        hip.call("grl_deepsets_fwd3", self.u1, self.stats2, self.c2, g2, be2, w4, b4, wv, bv, self.value, self.B)
         return self.value
 
     def bwd3(self, dvalue):
@@ -832,20 +773,19 @@ class DeepSetsPipeline:
         self.q2 = torch.empty(self.B, 64, device=dev)
         self.q1 = torch.empty(self.B, self.n, 64, device=dev)
         g2, be2, w4, b4, wv, bv = self.P[8:]
-        hip.call("grl_deepsets_bwd3", self.u1, self.stats2, ctypes_double(self.c2), g2, be2, w4, b4, wv, dvalue.contiguous(),
+        hip.call("grl_deepsets_bwd3", self.u1, self.stats2, self.c2, g2, be2, w4, b4, wv, dvalue.contiguous(),
                  self.q2, self.bst2, self.part3, self.B)
 
     def bwd2(self):
         w1, b1, g1, be1, w2, b2, w3, b3 = self.P[:8]
-        hip.call("grl_deepsets_bwd2", self.h1, self.stats1, ctypes_double(self.c1), g1, be1, w2, w3, self.z, self.u1,
-                 self.stats2, ctypes_double(self.c2), self.q2, self.bst2, self.q1, self.bst1, self.part2, self.B, self.n)
+        hip.call("grl_deepsets_bwd2", self.h1, self.stats1, self.c1, g1, be1, w2, w3, self.z, self.u1,
+                 self.stats2, self.c2, self.q2, self.bst2, self.q1, self.bst1, self.part2, self.B, self.n)
 
     def bwd1(self, leaves):
         """Last stage + folding of the partial slabs.  ``leaves``: the 14 parameter tensors in PARAM_ORDER (gradients are
         accumulated in place into ``.grad`` where that buffer exists, see _emit_grads).  Returns the 14 gradients (or None)."""
         d = self.d
-        hip.call("grl_deepsets_bwd1", self.x, self.h1, self.stats1, ctypes_double(self.c1), self.q1, self.bst1, self.part1,
-                 self.B, self.n, d)
+        hip.call("grl_deepsets_bwd1", self.x, self.h1, self.stats1, self.c1, self.q1, self.bst1, self.part1, self.B, self.n, d)
         (pw1, pb1, pg1, pbe1, pw2, pb2, pw3, pb3, pg2, pbe2, pw4, pb4, pwv, pbv) = leaves
         dw4, db4, dwv, dbv, dg2, dbe2 = _emit_grads(self.part3, [(0, 4096, (64, 64), pw4), (4096, 64, (64,), pb4),
                                                                  (4160, 64, (1, 64), pwv), (4352, 1, (1,), pbv),
@@ -884,11 +824,10 @@ def deepsets_values_groups(x: torch.Tensor, params, groups: int, group=None) -> 
     hip.call("grl_deepsets_fwd1_groups", x.contiguous(), w1, b1, h1, slots[0], B, n, d, groups)
     if world > 1:
         dist.all_reduce(slots[0], group=group)
-    hip.call("grl_deepsets_fwd2_groups", h1, slots[0], ctypes_double(float(B * world * n * 64)), g1, be1, w2, b2, w3, b3, z, u1, slots[1], B, n,
-             groups)
+    hip.call("grl_deepsets_fwd2_groups", h1, slots[0], B * world * n * 64, g1, be1, w2, b2, w3, b3, z, u1, slots[1], B, n, groups)
     if world > 1:
         dist.all_reduce(slots[1], group=group)
-    hip.call("grl_deepsets_fwd3_groups", u1, slots[1], ctypes_double(float(B * world * 64)), g2, be2, w4, b4, wv, bv, value, B, groups)
+    hip.call("grl_deepsets_fwd3_groups", u1, slots[1], B * world * 64, g2, be2, w4, b4, wv, bv, value, B, groups)
     return value
 
 
@@ -928,11 +867,6 @@ class DeepSetsValue(torch.autograd.Function):
             dist.all_reduce(pipe.bst1, group=group)
         grads = pipe.bwd1(ctx.leaves)
         return (None,) + tuple(grads) + (None,)
-
-
-def ctypes_double(v: float):
-    import ctypes
-    return ctypes.c_double(v)
 
 
 TRPL_SUM_KEYS = ("loss_objective", "loss_trust_region", "entropy_dist", "loss_critic", "sum_w", "sum_w2", "mean_constraint",
@@ -980,16 +914,13 @@ def _loss_launch(entry, lead, loc, sigma, batch, value, *, old=True, proj_out=No
 def _trpl_cfg(mean_bound, cov_bound, trust_region_coeff, entropy_coef, critic_coef, clip_value, global_batch, proj_type, adv_local):
     """cfg9 of grl_trpl_fwd_bwd[_ent] / grl_trpl_target_terms (host doubles; adv_local: the batch's advantage statistics are summed inside
     the kernel)."""
-    import ctypes
-    return (ctypes.c_double * 10)(mean_bound, cov_bound, trust_region_coeff, entropy_coef, critic_coef, clip_value if clip_value else 0.0,
-                                  1.0 / global_batch, float(global_batch), float(proj_type), 1.0 if adv_local else 0.0)
+    return [mean_bound, cov_bound, trust_region_coeff, entropy_coef, critic_coef, clip_value or 0.0, 1.0 / global_batch, global_batch,
+            proj_type, bool(adv_local)]
 
 
 def _ppo_cfg(entropy_coef, critic_coef, clip_value, global_batch, adv_local):
     """cfg6 of grl_ppo_fwd_bwd / grl_klpen_fwd_bwd (host doubles)."""
-    import ctypes
-    return (ctypes.c_double * 6)(entropy_coef, critic_coef, clip_value if clip_value else 0.0, 1.0 / global_batch, float(global_batch),
-                                 1.0 if adv_local else 0.0)
+    return [entropy_coef, critic_coef, clip_value or 0.0, 1.0 / global_batch, global_batch, bool(adv_local)]
 
 
 def trpl_fwd_bwd(loc, sigma, batch, value, *, mean_bound, cov_bound, trust_region_coeff, entropy_coef, critic_coef, clip_value,
@@ -1008,34 +939,32 @@ def trpl_fwd_bwd(loc, sigma, batch, value, *, mean_bound, cov_bound, trust_regio
         raise ValueError("ent_beta must be a one-element float64 tensor on the policy's device")
     cfg = _trpl_cfg(mean_bound, cov_bound, trust_region_coeff, entropy_coef, critic_coef, clip_value, global_batch, proj_type, adv_local)
     return _loss_launch("grl_trpl_fwd_bwd" if ent_mode is None else "grl_trpl_fwd_bwd_ent", (cfg,), loc, sigma, batch, value,
-                        proj_out=bool(want_projection), trail=() if ent_mode is None else (int(ent_mode), ent_beta), adv_stats=adv_stats,
+                        proj_out=bool(want_projection), trail=() if ent_mode is None else (ent_mode, ent_beta), adv_stats=adv_stats,
                         sums=sums, maxes=maxes, defer_fold=defer_fold)
 
 
 def write_doubles(dst: torch.Tensor, values) -> None:
     """dst[:len(values)] = values (a device float64 tensor, host floats): the values travel as kernel arguments of small launches on the
     current stream (grl_write_doubles, 16 per launch) -- stream-ordered, no staging buffer, no synchronisation."""
-    import ctypes
     vals = [float(v) for v in values]
     if dst.dtype != torch.float64 or not dst.is_cuda or dst.numel() < len(vals):
         raise ValueError("write_doubles: a device float64 tensor with room for the values")
     for i in range(0, len(vals), 16):
         part = vals[i:i + 16]
-        hip.call("grl_write_doubles", dst[i:i + len(part)], (ctypes.c_double * len(part))(*part), len(part))
+        hip.call("grl_write_doubles", dst[i:i + len(part)], part, len(part))
 
 
 def write_floats(dst: torch.Tensor, values, mirror: Optional[torch.Tensor] = None, mirror_index: int = 0) -> None:
     """dst[:len(values)] = values (a device float32 tensor; host floats, each rounded once to float32) by ONE launch on the current stream
     (grl_write_floats, at most 64 values) -- stream-ordered, no staging buffer, no synchronisation.  ``mirror``: a one-element device
     float32 tensor that receives ``values[mirror_index]`` from the same launch."""
-    import ctypes
     vals = [float(v) for v in values]
     hip.check_f32(dst, mirror)
     if not 1 <= len(vals) <= 64 or dst.numel() < len(vals):
         raise ValueError(f"write_floats: 1 .. 64 values into a tensor with room for them, got {len(vals)} for {dst.numel()}")
     if mirror is not None and (mirror.numel() != 1 or mirror.device != dst.device or not 0 <= mirror_index < len(vals)):
         raise ValueError("write_floats: the mirror is a one-element tensor on the table's device, its index one of the values'")
-    hip.call("grl_write_floats", dst, (ctypes.c_float * len(vals))(*vals), len(vals), mirror, int(mirror_index))
+    hip.call("grl_write_floats", dst, vals, len(vals), mirror, mirror_index)
 
 
 def ppo_fwd_bwd(loc, sigma, batch, value, *, clip_epsilon: torch.Tensor, entropy_coef, critic_coef, clip_value, global_batch: int,
@@ -1071,7 +1000,6 @@ def klpen_fwd_bwd(loc, sigma, batch, value, *, beta: torch.Tensor, entropy_coef,
 
 def klpen_thresholds(dtarg: float):
     """(hi, lo) = (dtarg * 1.5, dtarg / 1.5) formed in double and rounded to float32: what the float32 mean KL is compared with."""
-    import ctypes
     return ctypes.c_float(float(dtarg) * 1.5).value, ctypes.c_float(float(dtarg) / 1.5).value
 
 
@@ -1082,7 +1010,7 @@ def klpen_adapt(out14: torch.Tensor, beta: torch.Tensor, dtarg: float, increment
     if out14.numel() < 14 or beta.numel() != 1 or beta.device != out14.device:
         raise ValueError("klpen_adapt: a 14-float report and a one-element beta on one device")
     hi, lo = klpen_thresholds(dtarg)
-    hip.call("grl_klpen_adapt", out14, beta, hi, lo, float(increment), float(decrement))
+    hip.call("grl_klpen_adapt", out14, beta, hi, lo, increment, decrement)
 
 
 def trpl_target_terms(loc, sigma, tgt_mean, tgt_S, *, mean_bound, cov_bound, trust_region_coeff, global_batch: int, proj_type: int = 0):

@@ -6,7 +6,6 @@ Mirror of the transform stack of configs/rigid_insertion_multi_hepi_trpl_cfg.yam
 per axis, shared by all points and environments: geometry_rl/torchrl/envs/transforms.py:63-69,141-163) + ``VecNorm(scalars)`` +
 ``FlattenObservation`` + ``ClipTransform(low, high)`` on raw and normalised groups.  One fused call per group
 (``grl_vecnorm``: column statistics, decayed state update, standardise, clip)."""
-import ctypes
 from typing import Dict, Iterable
 
 import torch
@@ -32,7 +31,7 @@ class ObservationNormalizer:
             self._scratch[K] = torch.empty(hip.query("grl_vecnorm_scratch_bytes", K), device=x.device, dtype=torch.uint8)
         y_norm = torch.empty_like(x) if want_norm else None
         y_clip = torch.empty_like(x) if want_clip else None
-        hip.call("grl_vecnorm", x, ctypes.c_longlong(x.numel() // K), K, self.decay, self.eps, bool(update), self.low, self.high,
+        hip.call("grl_vecnorm", x, x.numel() // K, K, self.decay, self.eps, bool(update), self.low, self.high,
                  self.state[key], self._scratch[K], y_norm, y_clip)
         return y_norm, y_clip
 

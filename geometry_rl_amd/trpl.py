@@ -363,15 +363,13 @@ def trpl_launch(m, loc, sigma, value, batch, adv_stats, sums=None, maxes=None, d
 def value_loss(m, value, batch):
     """The critic's share of the loss on its own (clipped l2 value loss, trpl.py:213-228): -> (dvalue [B], loss_critic float32 0-d, sums
     fp64[2] = summed loss and its mean over the global batch).  One launch; one rank (nothing is all-reduced)."""
-    import ctypes
     B = value.shape[0]
     dev = value.device
     dvalue = torch.empty(B, device=dev, dtype=torch.float32)
     out2 = torch.empty(2, device=dev, dtype=torch.float64)
     mean = torch.empty(1, device=dev, dtype=torch.float32)
     hip.call("grl_value_loss", value.reshape(B).contiguous(), batch["state_value"].reshape(B).contiguous(),
-             batch["value_target"].reshape(B).contiguous(), ctypes.c_double(float(m.clip_value) if m.clip_value is not None else 0.0),
-             ctypes.c_double(float(m.critic_coef)), ctypes.c_double(1.0 / (B * m.world_size)), dvalue, out2, mean, B)
+             batch["value_target"].reshape(B).contiguous(), m.clip_value or 0.0, m.critic_coef, 1.0 / (B * m.world_size), dvalue, out2, mean, B)
     return dvalue, mean[0], out2
 
 
@@ -391,7 +389,7 @@ def report_values(m, slots, B, sums, maxes, out=None):
     metrics dict) like ``loss_values``.  ``out``: the float32[14] buffer to report into."""
     ent_coef = m.entropy_coef if m.entropy_bonus else 0.0
     o = out if out is not None else torch.empty(14, device=sums.device, dtype=torch.float32)
-    hip.call("grl_trpl_report", slots, B, sums, maxes, float(ent_coef), o)
+    hip.call("grl_trpl_report", slots, B, sums, maxes, ent_coef, o)
     return o[0], report_critic(o), report_dict(o, m)[1]
 
 
@@ -400,7 +398,7 @@ def loss_values(m, sums, maxes, out=None):
     are views of its 14-float output (``out``: the float32[14] buffer to report into)."""
     ent_coef = m.entropy_coef if m.entropy_bonus else 0.0
     o = out if out is not None else torch.empty(14, device=sums.device, dtype=torch.float32)
-    hip.call("grl_trpl_loss_values", sums, maxes, float(ent_coef), o)
+    hip.call("grl_trpl_loss_values", sums, maxes, ent_coef, o)
     return o[0], report_critic(o), report_dict(o, m)[1]
 
 

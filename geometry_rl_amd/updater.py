@@ -303,7 +303,7 @@ class PolicyUpdater:
     def _stats_add(self, src, acc):
         """``acc[:n] += src``, ``acc[n] += 1`` on the current stream: the last launch of a lane (no-op without track_stats)."""
         if self.track_stats:
-            hip.call("grl_stats_accumulate", src, int(src.numel()), acc)
+            hip.call("grl_stats_accumulate", src, src.numel(), acc)
 
     def stats_reset(self):
         """Zero the running sums (on the caller's stream: every program joins the critic's lane at its end)."""
@@ -391,9 +391,9 @@ class PolicyUpdater:
         if self.clip:  # train.py:308-310
             sq = st["zw"][23 + i_:24 + i_]
             coef = torch.empty(1, device=self.flat.device, dtype=torch.float32)
-            hip.call("grl_clip_coef", self.gflat[lo:hi], hi - lo, float(self.max_norm), sq, coef)
+            hip.call("grl_clip_coef", self.gflat[lo:hi], hi - lo, self.max_norm, sq, coef)
         hip.call("grl_adam_step_dev", self.flat[lo:hi], self.gflat[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
-                 hi - lo, st.get("lr", self.lr_dev), float(self.betas[0]), float(self.betas[1]), float(self.eps),
+                 hi - lo, st.get("lr", self.lr_dev), *self.betas, self.eps,
                  step_dev if step_dev is not None else self.step_dev, coef, 1.0)
 
     def _prep(self, batch, st, zero=None):
@@ -725,11 +725,11 @@ class PolicyUpdater:
                 ent = m.entropy_coef if m.entropy_bonus else 0.0
                 if self.clip:   # (the clip coefficient needs the reduced gradient's norm first: the separate launches)
                     self._adam(st, 0, na, 0)
-                    hip.call("grl_trpl_report_record_pairs", self.gbuf[:self._rec], world, st["sums"], st["maxes"], float(ent), o14)
+                    hip.call("grl_trpl_report_record_pairs", self.gbuf[:self._rec], world, st["sums"], st["maxes"], ent, o14)
                 else:           # Adam on the reduced slice + the reported values of the delivered records: ONE launch
                     hip.call("grl_adam_report_record_pairs", self.flat[:na], self.gflat[:na], self.exp_avg[:na], self.exp_avg_sq[:na], na,
-                             st.get("lr", self.lr_dev), float(self.betas[0]), float(self.betas[1]), float(self.eps), self.step_dev,
-                             self.gbuf[:self._rec], world, st["sums"], st["maxes"], float(ent), o14)
+                             st.get("lr", self.lr_dev), *self.betas, self.eps, self.step_dev,
+                             self.gbuf[:self._rec], world, st["sums"], st["maxes"], ent, o14)
                 m.after_report(o14)                      # (KL-penalty PPO: every rank adapts on the GLOBAL mean KL -- beta stays equal across the ranks)
                 self._stats_add(o14, self.stats_actor)   # (the GLOBAL values: every rank adds the same numbers, no collective)
 
@@ -872,7 +872,7 @@ class PolicyUpdater:
             jobs = self._gather_jobs(self._static, buf, keys)
         if jobs is None:
             return self.step(buf.rows(idx, keys))
-        hip.call("grl_gather_rows_many", *_job_arrays(jobs), idx, int(idx.numel()))
+        hip.call("grl_gather_rows_many", *_job_arrays(jobs), idx, idx.numel())
         return self.step(self._static)
 
     @staticmethod

@@ -15,7 +15,7 @@ dvalue = torch.randn(B, generator=g).to(dev)
 pipe = ops.DeepSetsPipeline(x, params, 1)
 leaves = [p.clone().requires_grad_(True) for p in params]
 stages = [("fwd1", pipe.fwd1), ("fwd2", pipe.fwd2), ("fwd3", pipe.fwd3), ("bwd3", lambda: pipe.bwd3(dvalue)), ("bwd2", pipe.bwd2),
-          ("bwd1", lambda: hip.call("grl_deepsets_bwd1", pipe.x, pipe.h1, pipe.stats1, ops.ctypes_double(pipe.c1), pipe.q1, pipe.bst1, pipe.part1,
+          ("bwd1", lambda: hip.call("grl_deepsets_bwd1", pipe.x, pipe.h1, pipe.stats1, pipe.c1, pipe.q1, pipe.bst1, pipe.part1,
                                     pipe.B, pipe.n, pipe.d))]
 for _ in range(2):
     for _, f in stages:
