@@ -3,7 +3,7 @@ INFRASTRUCTURE ONLY, a plain module like tests/actor_cases.py; it works on any d
 that each check notices what it is for) and changes no production file.
 
 ``Guarded(poison)`` swaps the name ``torch`` as seen from inside ``geometry_rl_amd.ops`` and ``geometry_rl_amd.graph`` for a proxy that
-forwards every attribute to the real module except ``empty`` and ``empty_like``.  The replacement allocates ``numel + 2 G`` elements,
+forwards every attribute to the real module except ``empty`` and ``empty_like`` (and ``zeros`` / ``zeros_like`` / ``full``, below).  The replacement allocates ``numel + 2 G`` elements,
 fills ALL of them with the poison and hands back the middle as a contiguous view of the requested shape and dtype; the ledger keeps
 (base, view).  ``guard(t, poison)`` does the same for a tensor the test built itself (an input, an upstream gradient, an index array).
 ``ledger.check(results, inputs)`` then asserts
@@ -30,7 +30,18 @@ poison there -- nothing may leave the allocations:
     behind the tensor (the rule for G guarantees that row exists);
   * ``s2d``, indexing the E rows of the per-edge gradient: v = E;
   * a ``rowptr`` over E edges: v = E + 1, i.e. one phantom edge E whose endpoints are the guard words of the edge arrays.
-``guard_edge_set`` applies these to an ``ops.EdgeSet``."""
+``guard_edge_set`` applies these to an ``ops.EdgeSet``.
+
+Buffers a kernel updates IN PLACE (optimiser state, running statistics, a destination that is accumulated into) go through
+``inout(t, poison)`` / ``ledger.inout(t)``: the value in the middle of a poisoned buffer like ``guard``, but exempt from (b) -- the kernel
+is meant to change it.  Its guards are held by (a); the caller lists it among the results, so (c) and the bitwise comparison see it (a
+buffer the test STARTS from the poison, ``poisoned(...)``, shows every element nobody wrote).  The proxy also replaces ``zeros``,
+``zeros_like`` and ``full``: a guarded allocation whose view holds the requested fill and whose guards hold the poison -- the buffers
+kernels write in place are mostly born that way (the flat parameter / gradient / moment buffers, step counters, learning-rate tables).
+They count as interposed for (d).
+
+``Plain`` / ``Wrapped`` / ``three_runs`` are the harness the GPU files share: one case run plain, under ``Guarded(NAN)`` and under
+``Guarded(HUGE)`` from identical inputs, both ledgers checked, every result of both guarded runs bitwise the plain run's."""
 import dataclasses
 import math
 from math import gcd
@@ -109,23 +120,34 @@ class Ledger:
 
     @property
     def wrapped(self):
-        return sum(e.kind == "wrapped" for e in self.entries)
+        """Buffers the test wrapped itself: inputs and in/out buffers."""
+        return sum(e.kind in ("wrapped", "inout") for e in self.entries)
 
-    def _buffer(self, kind, shape, dtype, device, pattern):
+    @property
+    def inouts(self):
+        return sum(e.kind == "inout" for e in self.entries)
+
+    def _buffer(self, kind, shape, dtype, device, pattern, shift=0):
+        """``shift``: the view starts this many elements past the 256-byte boundary a plain allocation starts on (a destination that
+        is a slice at an odd offset of a larger buffer: the kernels' scalar paths); the front guard is that much wider."""
         shape = tuple(int(s) for s in shape)
         numel, G = math.prod(shape), guard_width(shape, dtype)
-        base = torch.empty(numel + 2 * G, dtype=dtype, device=device)
+        assert 0 <= shift < MIN_GUARD, shift
+        base = torch.empty(numel + 2 * G + shift, dtype=dtype, device=device)
         bits_view(base).fill_(pattern)
+        assert (G * base.element_size()) % 256 == 0
+        G += shift
         view = base[G:G + numel].view(shape)
-        assert view.is_contiguous() and view.storage_offset() == G and (G * base.element_size()) % 256 == 0
+        assert view.is_contiguous() and view.storage_offset() == G
         e = _Entry()
         e.kind, e.base, e.view, e.G, e.numel, e.pattern, e.orig = kind, base, view, G, numel, pattern, None
         self.entries.append(e)
         return e
 
-    def allocate(self, shape, dtype, device):
-        """The proxy's ``empty``."""
-        return self._buffer("interposed", shape, dtype, device, poison_bits(dtype, self.poison)).view
+    def allocate(self, shape, dtype, device, fill=None):
+        """The proxy's ``empty``; with ``fill`` its ``zeros`` / ``full``: the view holds the fill, the guards the poison."""
+        view = self._buffer("interposed", shape, dtype, device, poison_bits(dtype, self.poison)).view
+        return view if fill is None else view.fill_(fill)
 
     def guard(self, t, index_of=None):
         """``t`` in the middle of a poisoned buffer of the same layout (detached; the caller sets requires_grad).  ``index_of``: ``t`` is
@@ -141,12 +163,25 @@ class Ledger:
         e.orig = t.clone()
         return e.view
 
-    def check(self, results, inputs=()):
+    def inout(self, t, shift=0):
+        """``t`` in the middle of a poisoned buffer like ``guard``, for a buffer the kernel changes in place: no (b) for it.  The caller
+        lists the returned view among the results.  ``shift``: see ``_buffer``."""
+        t = t.detach().contiguous()
+        e = self._buffer("inout", t.shape, t.dtype, t.device, poison_bits(t.dtype, self.poison), shift)
+        e.view.copy_(t)
+        return e.view
+
+    def check(self, results, inputs=(), direct=False):
         """(a) .. (d) of the module docstring; ``results``: what the op returned and every gradient it produced (nested dicts / lists
         / tuples, None entries skipped); ``inputs``: wrapped tensors of this ledger the caller wants looked at by name -- every wrapped
-        buffer is checked either way, a tensor listed here that the ledger never wrapped is an error."""
-        assert self.interposed >= 1, "(d) no allocation went through the proxy: the interposer is not in the op's path"
-        mine = {e.view.data_ptr() for e in self.entries if e.kind == "wrapped" and e.numel}
+        buffer is checked either way, a tensor listed here that the ledger never wrapped is an error.  ``direct``: the test
+        called the entry point itself and handed it every buffer, so no allocating wrapper is in the path and (d) asks instead that the
+        ledger holds at least one buffer the kernel writes (taken with ``allocate`` or ``inout``)."""
+        if direct:
+            assert any(e.kind in ("interposed", "inout") for e in self.entries), "(d) the ledger holds no buffer the kernel writes"
+        else:
+            assert self.interposed >= 1, "(d) no allocation went through the proxy: the interposer is not in the op's path"
+        mine = {e.view.data_ptr() for e in self.entries if e.kind in ("wrapped", "inout") and e.numel}
         for name, t in flatten(inputs):
             assert t.numel() == 0 or t.data_ptr() in mine, f"(b) input {name} was not wrapped by this ledger"
         for e in self.entries:
@@ -185,7 +220,8 @@ class Ledger:
 
 
 class _TorchProxy:
-    """``torch`` with ``empty`` and ``empty_like`` replaced by guarded, poisoned allocations."""
+    """``torch`` with ``empty`` / ``empty_like`` replaced by guarded, poisoned allocations and ``zeros`` / ``zeros_like`` / ``full`` by
+    guarded allocations that hold the requested fill between poisoned guards."""
 
     def __init__(self, real, ledger):
         self.__dict__["_real"], self.__dict__["_ledger"] = real, ledger
@@ -193,20 +229,39 @@ class _TorchProxy:
     def __getattr__(self, name):
         return getattr(self.__dict__["_real"], name)
 
-    def empty(self, *size, dtype=None, device=None, requires_grad=False, **kw):
+    def _sized(self, name, size, dtype, device, requires_grad, kw, fill=None):
         if kw:
-            raise TypeError(f"footprint: torch.empty({', '.join(kw)}=...) is not interposed")
-        if len(size) == 1 and isinstance(size[0], (tuple, list)):
+            raise TypeError(f"footprint: torch.{name}({', '.join(kw)}=...) is not interposed")
+        if len(size) == 1 and isinstance(size[0], (tuple, list)):   # (torch.Size is a tuple)
             size = tuple(size[0])
         real = self.__dict__["_real"]
         out = self.__dict__["_ledger"].allocate(size, dtype if dtype is not None else real.get_default_dtype(),
-                                                real.device(device) if device is not None else real.device("cpu"))
+                                                real.device(device) if device is not None else real.device("cpu"), fill)
         return out.requires_grad_(True) if requires_grad else out
 
-    def empty_like(self, t, dtype=None, device=None, **kw):
+    def _like(self, name, t, dtype, device, kw, fill=None):
         if kw:
-            raise TypeError(f"footprint: torch.empty_like({', '.join(kw)}=...) is not interposed")
-        return self.__dict__["_ledger"].allocate(t.shape, dtype if dtype is not None else t.dtype, device if device is not None else t.device)
+            raise TypeError(f"footprint: torch.{name}({', '.join(kw)}=...) is not interposed")
+        return self.__dict__["_ledger"].allocate(t.shape, dtype if dtype is not None else t.dtype, device if device is not None else t.device,
+                                                 fill)
+
+    def empty(self, *size, dtype=None, device=None, requires_grad=False, **kw):
+        return self._sized("empty", size, dtype, device, requires_grad, kw)
+
+    def empty_like(self, t, dtype=None, device=None, **kw):
+        return self._like("empty_like", t, dtype, device, kw)
+
+    def zeros(self, *size, dtype=None, device=None, requires_grad=False, **kw):
+        return self._sized("zeros", size, dtype, device, requires_grad, kw, fill=0)
+
+    def zeros_like(self, t, dtype=None, device=None, **kw):
+        return self._like("zeros_like", t, dtype, device, kw, fill=0)
+
+    def full(self, size, fill_value, dtype=None, device=None, requires_grad=False, **kw):
+        if dtype is None:   # torch.full's own inference from the fill value
+            real = self.__dict__["_real"]
+            dtype = real.bool if isinstance(fill_value, bool) else real.int64 if isinstance(fill_value, int) else real.get_default_dtype()
+        return self._sized("full", (size,), dtype, device, requires_grad, kw, fill=fill_value)
 
 
 _ACTIVE = []
@@ -218,9 +273,9 @@ def default_modules():
 
 
 class Guarded:
-    """``with Guarded(poison) as ledger:`` -- inside the block ``torch.empty`` / ``torch.empty_like`` called from ``modules`` (default:
-    geometry_rl_amd.ops and geometry_rl_amd.graph) allocate guarded, poisoned buffers recorded in ``ledger``; nothing outside those modules
-    sees the proxy, and the real module is back when the block ends, however it ends."""
+    """``with Guarded(poison) as ledger:`` -- inside the block ``torch.empty`` / ``empty_like`` / ``zeros`` / ``zeros_like`` / ``full``
+    called from ``modules`` (default: geometry_rl_amd.ops and geometry_rl_amd.graph) allocate guarded buffers recorded in ``ledger`` (poisoned,
+    or holding the requested fill between poisoned guards); nothing outside those modules sees the proxy, and the real module is back when the block ends, however it ends."""
 
     def __init__(self, poison, modules=None):
         self.ledger = Ledger(poison)
@@ -228,9 +283,10 @@ class Guarded:
         self._saved = []
 
     def __enter__(self):
+        for m in self.modules:   # (refused before anything is swapped: a block that fails to start leaves no proxy behind)
+            assert not isinstance(m.torch, _TorchProxy), f"{m.__name__} is already guarded"
         for m in self.modules:
             real = m.torch
-            assert not isinstance(real, _TorchProxy), f"{m.__name__} is already guarded"
             self._saved.append((m, real))
             m.torch = _TorchProxy(real, self.ledger)
         _ACTIVE.append(self.ledger)
@@ -249,6 +305,21 @@ def guard(t, poison, index_of=None):
     assert _ACTIVE, "guard() outside a Guarded block"
     assert _ACTIVE[-1].poison == poison, (_ACTIVE[-1].poison, poison)
     return _ACTIVE[-1].guard(t, index_of)
+
+
+def inout(t, poison):
+    """``Ledger.inout`` in the ledger of the innermost active ``Guarded`` block (whose poison must be ``poison``)."""
+    assert _ACTIVE, "inout() outside a Guarded block"
+    assert _ACTIVE[-1].poison == poison, (_ACTIVE[-1].poison, poison)
+    return _ACTIVE[-1].inout(t)
+
+
+def poisoned(shape, dtype, device, poison):
+    """A plain tensor every element of which holds the poison's bit pattern: what a test starts an in/out buffer from when the kernel has
+    to write all of it (an overwritten destination) -- an element nobody wrote is then reported by (c)."""
+    t = torch.empty(shape, dtype=dtype, device=device)
+    bits_view(t).fill_(poison_bits(dtype, poison))
+    return t
 
 
 def guard_edge_set(es, wrap):
@@ -289,3 +360,85 @@ def unwritten_words(plain, nan_run, huge_run):
     stray = ~hole & ((a != b) | (a != c))
     assert not bool(stray.any()), f"{int(stray.sum())} word(s) are neither the same in all three runs nor unwritten, first at {int(stray.nonzero()[0])}"
     return int(hole.sum())
+
+
+# ------------------------------------------------------------------------------------------------ the run harness of the GPU files
+COUNTS = {}   # op -> [guarded runs, interposed allocations, wrapped buffers] of this process
+
+
+class Plain:
+    """The wrapper of the plain run: fresh copies, plain allocations."""
+    poison = None
+
+    def __call__(self, t, index_of=None):
+        return t.detach().clone()
+
+    def out(self, shape, dtype, device):
+        return torch.zeros(shape, dtype=dtype, device=device)
+
+    def inout(self, t, shift=0):
+        """A buffer the kernel changes in place: a fresh copy (``shift`` elements past a plain allocation's start, as the guarded one)."""
+        t = t.detach().contiguous()
+        out = torch.zeros(t.numel() + shift, dtype=t.dtype, device=t.device)[shift:].view(t.shape)
+        return out.copy_(t)
+
+    def fresh(self, shape, dtype, device, shift=0):
+        """An in/out buffer the kernel has to write in full (an overwritten destination): any contents do for the plain run."""
+        return self.inout(torch.zeros(shape, dtype=dtype, device=device), shift)
+
+
+class Wrapped:
+    """The wrapper of a guarded run: inputs through ``ledger.guard``, buffers the kernel writes through ``ledger.allocate``, buffers it
+    changes in place through ``ledger.inout``."""
+
+    def __init__(self, ledger):
+        self.ledger, self.poison = ledger, ledger.poison
+
+    def __call__(self, t, index_of=None):
+        return self.ledger.guard(t, index_of)
+
+    def out(self, shape, dtype, device):
+        return self.ledger.allocate(shape, dtype, device)
+
+    def inout(self, t, shift=0):
+        return self.ledger.inout(t, shift)
+
+    def fresh(self, shape, dtype, device, shift=0):
+        return self.ledger.inout(poisoned(shape, dtype, device, self.poison), shift)
+
+
+def _sync():
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+
+
+def three_runs(op, label, run, image_holes=None, modules=None, direct=False):
+    """``run(w)`` -> results (nested dicts / lists of tensors); ``w`` wraps every tensor the run hands to an op.  An entry "images" of the
+    results (weight images: byte buffers whose layout has holes on purpose) is held to ``unwritten_words`` and to ``image_holes`` (image
+    name -> the layout's own count of never-written words) instead of (c) and the bitwise comparison; what the kernels compute FROM the
+    images is among the other results.  ``modules``: those of ``Guarded``; ``direct``: that of ``Ledger.check``.  -> the plain run's
+    results."""
+    def split(res):
+        res = dict(res)
+        return res, res.pop("images", None) or {}
+    plain, images = split(run(Plain()))
+    _sync()
+    guarded_images = []
+    for poison in POISONS:
+        with Guarded(poison, modules) as ledger:
+            res, img = split(run(Wrapped(ledger)))
+            _sync()
+        ledger.check(res, direct=direct)
+        bad = same_bits(plain, res)
+        assert not bad, f"{op} {label}: under the {poison} poison these results are not bitwise the plain run's: {bad}"
+        guarded_images.append(img)
+        tot = COUNTS.setdefault(op, [0, 0, 0])
+        tot[0], tot[1], tot[2] = tot[0] + 1, tot[1] + ledger.interposed, tot[2] + ledger.wrapped
+        print(f"footprint {op} {label} [{poison}]: {ledger.interposed} interposed allocations, {ledger.wrapped} wrapped inputs "
+              f"(so far for {op}: {tot[0]} guarded runs, {tot[1]} interposed, {tot[2]} wrapped)")
+    for m, v in images.items():
+        holes = unwritten_words(v, guarded_images[0][m], guarded_images[1][m])
+        print(f"footprint {op} {label}: image {m}: {holes} of {v.numel() // 4} words are never written (padding / unused halves)")
+        assert image_holes is not None and holes == image_holes[m], (m, holes)
+    plain["images"] = images
+    return plain

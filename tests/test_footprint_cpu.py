@@ -204,3 +204,145 @@ def test_unwritten_words_tells_holes_from_strays():
     assert fp.unwritten_words(image(None, False), image(fp.NAN, False), image(fp.HUGE, False)) == 8
     with pytest.raises(AssertionError, match="1 word\\(s\\) are neither the same in all three runs nor unwritten, first at 10"):
         fp.unwritten_words(image(None, True), image(fp.NAN, True), image(fp.HUGE, True))
+
+
+# ------------------------------------------------------------------------------------------------ in/out buffers, zeros / full
+def inplace_standin(state, grad, mistake=None):
+    """An optimiser-like stand-in: state[i] += grad[i] in place, and a step counter taken from ``torch.zeros`` advanced by one."""
+    step = torch.zeros(1, dtype=torch.int32)
+    lr = torch.full((1,), 0.5)
+    n = state.numel() - 1 if mistake == "last_unwritten" else state.numel()
+    state[:n] = state[:n].nan_to_num(0.0, 0.0, 0.0) * 0 + lr * grad[:n] if mistake == "last_unwritten" else state[:n] + lr * grad[:n]
+    step += 1
+    flat, off = raw(state)
+    if mistake == "one_past_the_end":
+        flat[off + state.numel()] = 1.0
+    elif mistake == "one_in_front":
+        flat[off - 1] = 1.0
+    elif mistake == "behind_the_counter":
+        sflat, soff = raw(step)
+        sflat[soff + 1] = 1
+    return step, lr
+
+
+@BOTH
+def test_a_legitimate_in_place_change_of_an_inout_buffer_passes(poison):
+    s0, g0 = torch.arange(10.0), torch.ones(10)
+    with guarded(poison) as ledger:
+        state, grad = fp.inout(s0, poison), fp.guard(g0, poison)
+        step, lr = inplace_standin(state, grad)
+    assert (ledger.interposed, ledger.wrapped, ledger.inouts) == (2, 2, 1)
+    ledger.check({"state": state, "step": step}, [grad, state])
+    assert torch.equal(state, s0 + 0.5) and not torch.equal(state, s0), "changed in place, and no (b) for it"
+    with pytest.raises(AssertionError, match=r"\(b\) a wrapped input was modified"):   # the same change of a guard()ed buffer is (b)
+        with guarded(poison) as other:
+            st = other.guard(s0)
+            inplace_standin(st, g0)
+        other.check({"state": st})
+
+
+@BOTH
+@pytest.mark.parametrize("mistake,where", [("one_past_the_end", "back guard.*0 element\\(s\\) behind the last"),
+                                           ("one_in_front", "front guard.*1 element\\(s\\) in front of the first")])
+def test_a_write_outside_an_inout_buffer_is_reported_by_the_guard_check(poison, mistake, where):
+    with guarded(poison) as ledger:
+        state = ledger.inout(torch.arange(10.0))
+        step, _ = inplace_standin(state, torch.ones(10), mistake)
+    with pytest.raises(AssertionError, match=rf"\(a\) guard words changed: inout buffer of shape \(10,\), torch.float32, {where}"):
+        ledger.check({"state": state, "step": step})
+
+
+@BOTH
+def test_an_element_of_an_inout_buffer_nobody_wrote_is_reported_when_it_started_from_the_poison(poison):
+    """An overwritten destination: the test starts it from the poison (``fp.poisoned``), the kernel has to write all of it."""
+    for mistake in (None, "last_unwritten"):
+        with guarded(poison) as ledger:
+            state = ledger.inout(fp.poisoned((10,), torch.float32, "cpu", poison))
+            assert bool((fp.bits_view(state) == fp.poison_bits(torch.float32, poison)).all())
+            step, _ = inplace_standin(state, torch.ones(10), "last_unwritten")
+            if mistake is None:
+                state[9] = 0.5
+        if mistake is None:
+            ledger.check({"state": state})
+        else:
+            with pytest.raises(AssertionError, match=r"\(c\) result state \(10,\) torch.float32 still holds the poison: 1 element\(s\), first at 9"):
+                ledger.check({"state": state})
+
+
+@BOTH
+def test_zeros_and_full_get_guards_and_hold_the_requested_fill(poison):
+    me = sys.modules[__name__]
+    with guarded(poison) as ledger:
+        z = me.torch.zeros(3, 5, dtype=torch.int32)
+        zl = me.torch.zeros_like(z, dtype=torch.float64)
+        f = me.torch.full((7,), 1.5)
+        fi = me.torch.full((2, 2), 3)
+        zt = me.torch.zeros((4,), requires_grad=True)
+        step, lr = inplace_standin(torch.arange(4.0), torch.ones(4), "behind_the_counter")
+    assert ledger.interposed == 7 and ledger.wrapped == 0
+    assert z.dtype == torch.int32 and z.shape == (3, 5) and bool((z == 0).all()) and zl.dtype == torch.float64 and bool((zl == 0).all())
+    assert f.dtype == torch.float32 and bool((f == 1.5).all()) and fi.dtype == torch.int64 and bool((fi == 3).all())
+    assert zt.requires_grad and bool((zt == 0).all()) and float(lr) == 0.5 and int(step) == 1
+    for e in ledger.entries:
+        want = fp.poison_bits(e.view.dtype, poison)
+        assert e.G >= 4096 and bool((fp.bits_view(e.base[:e.G]) == want).all())
+        assert e is ledger.entries[5] or bool((fp.bits_view(e.base[e.G + e.numel:]) == want).all())
+    with pytest.raises(AssertionError, match=r"\(a\) guard words changed: interposed buffer of shape \(1,\), torch.int32, back guard.*"
+                                             r"0 element\(s\) behind the last"):
+        ledger.check({"z": z, "f": f})
+    with guarded(poison) as clean:
+        z = me.torch.zeros(3)
+    clean.check({"z": z})   # (d): a zero-filled buffer counts as interposed
+
+
+@BOTH
+def test_a_direct_call_needs_a_buffer_the_kernel_writes_in_the_ledger(poison):
+    """(d) where the test calls the entry point itself (no allocating wrapper in the path): an output or an in/out buffer of the ledger."""
+    with fp.Guarded(poison) as ledger:
+        x = ledger.guard(torch.ones(3))
+    with pytest.raises(AssertionError, match=r"\(d\) the ledger holds no buffer the kernel writes"):
+        ledger.check({"y": torch.ones(3)}, [x], direct=True)
+    with fp.Guarded(poison) as ledger:
+        state = ledger.inout(torch.ones(3))
+        state += 1
+    ledger.check({"state": state}, direct=True)
+    with pytest.raises(AssertionError, match=r"\(d\) no allocation went through the proxy"):
+        ledger.check({"state": state})
+
+
+def test_modules_passed_to_guarded_are_restored_on_exit_also_after_an_exception():
+    from geometry_rl_amd import agent, graph, klpen, ops, policy, ppo, rollout, transforms, trpl, updater
+    mods = (ops, graph, updater, trpl, ppo, klpen, agent, policy, transforms, rollout)
+    with fp.Guarded(fp.NAN, modules=mods) as ledger:
+        assert all(isinstance(m.torch, fp._TorchProxy) for m in mods)
+        t = updater.torch.zeros(5)
+        u = rollout.torch.full((2,), 7, dtype=torch.int32)
+        assert ledger.interposed == 2 and bool((t == 0).all()) and bool((u == 7).all())
+    assert all(m.torch is torch for m in mods)
+    with pytest.raises(ZeroDivisionError):
+        with fp.Guarded(fp.HUGE, modules=mods):
+            assert all(m.torch is not torch for m in mods)
+            1 / 0
+    assert all(m.torch is torch for m in mods) and not fp._ACTIVE
+    with pytest.raises(AssertionError, match="is already guarded"):   # a nested block over the same module is refused ...
+        with fp.Guarded(fp.NAN, modules=(updater,)):
+            with fp.Guarded(fp.NAN, modules=(ops, updater)):
+                pass
+    assert all(m.torch is torch for m in mods) and not fp._ACTIVE       # ... and leaves nothing behind either
+
+
+def test_three_runs_on_cpu_tensors_holds_an_inout_buffer_to_the_plain_runs_bits():
+    me = sys.modules[__name__]
+
+    def run(w, mistake=None):
+        state = w.inout(torch.arange(10.0))
+        fresh = w.fresh((10,), torch.float32, "cpu")
+        step, _ = inplace_standin(state, w(torch.ones(10)), mistake if w.poison else None)   # (the plain buffer has no room behind it)
+        inplace_standin(fresh, w(torch.ones(10)), "last_unwritten")
+        fresh[9] = 2.0
+        return {"state": state, "fresh": fresh, "step": step}
+
+    plain = fp.three_runs("standin", "cpu", run, modules=(me,))
+    assert torch.equal(plain["state"], torch.arange(10.0) + 0.5)
+    with pytest.raises(AssertionError, match=r"\(a\) guard words changed: inout buffer"):
+        fp.three_runs("standin", "cpu", lambda w: run(w, "one_past_the_end"), modules=(me,))

@@ -23,7 +23,6 @@ pytestmark = pytest.mark.gpu
 
 BF = torch.bfloat16
 PRECS = pytest.mark.parametrize("prec", ["", "_bf16"], ids=["fp32", "bf16"])
-COUNTS = {}   # op -> [guarded runs, interposed allocations, wrapped inputs] of this process
 
 
 def dev():
@@ -33,29 +32,6 @@ def dev():
 
 def storage(prec):
     return BF if prec else torch.float32
-
-
-class Plain:
-    """The wrapper of the plain run: fresh copies, plain allocations."""
-
-    def __call__(self, t, index_of=None):
-        return t.detach().clone()
-
-    def out(self, shape, dtype, device):
-        return torch.zeros(shape, dtype=dtype, device=device)
-
-
-class Wrapped:
-    """The wrapper of a guarded run: inputs through ``ledger.guard``, buffers the kernel writes through ``ledger.allocate``."""
-
-    def __init__(self, ledger):
-        self.ledger = ledger
-
-    def __call__(self, t, index_of=None):
-        return self.ledger.guard(t, index_of)
-
-    def out(self, shape, dtype, device):
-        return self.ledger.allocate(shape, dtype, device)
 
 
 def image_holes(bf16):
@@ -76,33 +52,8 @@ IMAGE_HOLES = {False: image_holes(False), True: image_holes(True)}
 
 
 def three_runs(op, label, run):
-    """``run(w)`` -> results (nested dicts / lists of tensors); ``w`` wraps every tensor the run hands to an op.  An entry "images" of the
-    results (weight images: byte buffers whose layout has holes on purpose) is held to ``fp.unwritten_words`` instead of (c) and the
-    bitwise comparison; what the kernels compute FROM the images is among the other results."""
-    def split(res):
-        res = dict(res)
-        return res, res.pop("images", None) or {}
-    plain, images = split(run(Plain()))
-    torch.cuda.synchronize()
-    guarded_images = []
-    for poison in fp.POISONS:
-        with fp.Guarded(poison) as ledger:
-            res, img = split(run(Wrapped(ledger)))
-            torch.cuda.synchronize()
-        ledger.check(res)
-        bad = fp.same_bits(plain, res)
-        assert not bad, f"{op} {label}: under the {poison} poison these results are not bitwise the plain run's: {bad}"
-        guarded_images.append(img)
-        tot = COUNTS.setdefault(op, [0, 0, 0])
-        tot[0], tot[1], tot[2] = tot[0] + 1, tot[1] + ledger.interposed, tot[2] + ledger.wrapped
-        print(f"footprint {op} {label} [{poison}]: {ledger.interposed} interposed allocations, {ledger.wrapped} wrapped inputs "
-              f"(so far for {op}: {tot[0]} guarded runs, {tot[1]} interposed, {tot[2]} wrapped)")
-    for m, v in images.items():
-        holes = fp.unwritten_words(v, guarded_images[0][m], guarded_images[1][m])
-        print(f"footprint {op} {label}: image {m}: {holes} of {v.numel() // 4} words are never written (padding / unused halves)")
-        assert holes == IMAGE_HOLES[op.endswith("_bf16")][m], (m, holes)
-    plain["images"] = images
-    return plain
+    """``fp.three_runs`` with the weight images held to the layout's own hole counts of the op's build."""
+    return fp.three_runs(op, label, run, image_holes=IMAGE_HOLES[op.endswith("_bf16")])
 
 
 def leaf(w, t):
