@@ -44,6 +44,9 @@ class AgentConfig:
     max_grad_norm: float = 1.0
     aggr: str = "add"         # "AttentionalAggregation": configs/algorithm/pyg_agent/model/hepi_attention.yaml
     precision: str = "fp32"   # "bf16": BASELINE config 5 -- node latents stored as bf16, one bf16 MFMA per dense product, fp32 accumulation
+    # model "empn" only: the ``attention`` key of configs/algorithm/pyg_agent/model/ponita_gcn.yaml (key / query attention weights on the
+    # messages of every layer, ponita.py:130-137,154-160); fp32, one rank, every layer on the full edge set (ponita_gcn.py)
+    attention: bool = False
     # the actor's HyperData only (configs/rigid_pushing_multi_empn_trpl_cfg.yaml:105-106; every upstream critic config keeps it False)
     training_noise: bool = False
     training_noise_std: float = 0.01
@@ -90,6 +93,9 @@ def build_agent(spec: TaskSpec, cfg: AgentConfig, device="cuda", group=None):
     if cfg.algorithm == "kl_ppo" and cfg.dtarg is None:
         raise ValueError("algorithm 'kl_ppo' needs dtarg (the target KL of configs/algorithm/objective/kl_ppo.yaml): AgentConfig(dtarg=...)")
     n_in = len(spec.node_types) + spec.n_vec  # utils_algo_graph.py:79
+    if cfg.attention and cfg.model != "empn":
+        raise ValueError(f"AgentConfig(attention=True) is the EMPN actor's key / query attention (model='empn'), not model '{cfg.model}' "
+                         "(HEPi's attention variant is aggr='AttentionalAggregation')")
     if cfg.model == "hepi":
         mp = []  # utils_algo_graph.py:29-47: one fresh conv per (level, active round)
         for lvl in range(len(spec.edge_levels)):
@@ -105,10 +111,12 @@ def build_agent(spec: TaskSpec, cfg: AgentConfig, device="cuda", group=None):
         gnn = TransformerVanilla(input_dim_node=len(spec.node_types) + 3 * spec.n_vec, output_dim=64, num_layers=cfg.num_layers,
                                  num_heads=2, hidden_dim=64, dropout=0.0, concat_global=False, device=device)
     elif cfg.model == "empn":
-        from .ponita_gcn import PonitaGCN
+        from .ponita_gcn import PonitaGCN, check_attention_group
+        check_attention_group(cfg.attention, group)
         gnn = PonitaGCN(input_dim_node=n_in, output_dim=cfg.output_dim, output_dim_vec=cfg.output_dim_vec,
                         num_layers=cfg.num_layers, hidden_dim=64, num_ori=cfg.num_ori, ponita_dim=cfg.dim,
-                        only_upper_hemisphere=cfg.only_upper_hemisphere, device=device, precision=cfg.precision)
+                        only_upper_hemisphere=cfg.only_upper_hemisphere, device=device, precision=cfg.precision,
+                        attention=cfg.attention)
     else:
         raise ValueError(cfg.model)
     post_fc = cfg.model == "transformer"

@@ -553,6 +553,80 @@ class SoftmaxAggregate(torch.autograd.Function):
         return dgate, dmsg, None, None
 
 
+class KeyQueryProject(torch.autograd.Function):
+    """k = x Wk^T + bk, q = x Wq^T + bq: x [N,16,64] -> k, q [N,16,128] (ponita.py:130-137,155-156: key_transform / query_transform of
+    SeparableFiberBundleConv(attention=True)).  fp32 build only.  The four leaf gradients go through per-block partials and the fold."""
+
+    @staticmethod
+    def forward(ctx, x, wk, bk, wq, bq):
+        hip.check_f32(x, wk, bk, wq, bq)
+        x = x.contiguous()
+        n_rows = x.shape[0] * 16
+        k = torch.empty(x.shape[0], 16, 128, device=x.device, dtype=torch.float32)   # every row is written by the kernel
+        q = torch.empty(x.shape[0], 16, 128, device=x.device, dtype=torch.float32)
+        args = [a.contiguous() for a in (wk, bk, wq, bq)]
+        hip.attention_call("grl_kq_project_fwd", x, *args, k, q, n_rows, rows=n_rows)
+        ctx.save_for_backward(x, args[0], args[2])
+        ctx.params = (wk, bk, wq, bq)
+        return k, q
+
+    @staticmethod
+    def backward(ctx, dk, dq):
+        x, wk, wq = ctx.saved_tensors
+        n_rows = x.shape[0] * 16
+        partial = torch.empty(hip.attention_query("grl_kq_bwd_blocks", n_rows), hip.attention_query("grl_kq_partial_size"), device=x.device, dtype=torch.float32)
+        dx = torch.empty_like(x)
+        hip.attention_call("grl_kq_project_bwd", x, wk, wq, dk.contiguous(), dq.contiguous(), dx, partial, n_rows, rows=n_rows)
+        pwk, pbk, pwq, pbq = ctx.params
+        dwk, dwq, dbk, dbq = _emit_grads(partial, [(0, 8192, (128, 64), pwk), (8192, 8192, (128, 64), pwq), (16384, 128, (128,), pbk),
+                                                   (16512, 128, (128,), pbq)])
+        return dx, dwk, dbk, dwq, dbq
+
+
+class EdgeAttention(torch.autograd.Function):
+    """x1[d,o,:] = sum_{e->d} a[e,o] msg[e,o,:] with a[e,o] = exp(l - M) / (sum_{e'->d} exp(l' - M) + 1e-6), l[e,o] = <k[src e,o,:],
+    q[dst e,o,:]> / sqrt(128) and M the maximum of l over ALL edges and orientations (ponita.py:21-24,157-161: a global shift that is
+    part of the graph, and 1e-6 -- not the per-destination softmax of ``SoftmaxAggregate``).  ``msg`` rows in destination-sorted edge order
+    (``EdgeMessages``).  An empty edge set launches nothing that reads M and gives zeros with exactly-zero gradients.  fp32 build only."""
+
+    @staticmethod
+    def forward(ctx, k, q, msg, edges: EdgeSet):
+        hip.check_f32(k, q, msg)
+        dev, E = msg.device, edges.n_edges
+        k, q, msg = k.contiguous(), q.contiguous(), msg.contiguous()
+        if k.data_ptr() % 8 or q.data_ptr() % 8:
+            raise ValueError("EdgeAttention: k and q must be 8-byte aligned (the kernels read channel pairs)")
+        logit = torch.empty(E, 16, device=dev, dtype=torch.float32)
+        a = torch.empty(E, 16, device=dev, dtype=torch.float32)
+        comp = torch.empty(edges.n_dst, 16, device=dev, dtype=torch.float32)
+        maxval = torch.empty(1, device=dev, dtype=torch.float32)
+        argmax = torch.empty(1, device=dev, dtype=torch.int32)
+        x1 = torch.empty(edges.n_dst, 16, 64, device=dev, dtype=torch.float32)   # every row is written by the kernel
+        if E > 0:
+            nb = hip.attention_query("grl_attention_blocks", E * 16)
+            pmax = torch.empty(nb, device=dev, dtype=torch.float32)
+            pidx = torch.empty(nb, device=dev, dtype=torch.int32)
+            hip.attention_call("grl_edge_logits_fwd", k, q, edges.src_d, edges.dst_d, E, logit, pmax, pidx, maxval, argmax, rows=E * 16)
+        hip.attention_call("grl_edge_attend_fwd", logit, maxval, msg, edges.rowptr_d, edges.n_dst, a, comp, x1, rows=E * 16)
+        ctx.save_for_backward(k, q, msg, a, comp, argmax)
+        ctx.edges = edges
+        return x1
+
+    @staticmethod
+    def backward(ctx, dx1):
+        k, q, msg, a, comp, argmax = ctx.saved_tensors
+        e = ctx.edges
+        dev, E = msg.device, e.n_edges
+        dmsg = torch.empty_like(msg)
+        dl = torch.empty(E, 16, device=dev, dtype=torch.float32)
+        dk, dq = torch.empty_like(k), torch.empty_like(q)
+        if E > 0:
+            pdm = torch.empty(hip.attention_query("grl_attention_blocks", e.n_dst * 16), device=dev, dtype=torch.float32)
+            hip.attention_call("grl_edge_attend_bwd", a, msg, comp, dx1.contiguous(), e.rowptr_d, e.n_dst, argmax, dmsg, dl, pdm, rows=E * 16)
+        hip.attention_call("grl_edge_logits_bwd", k, q, dl, e.rowptr_d, e.src_d, e.n_dst, e.rowptr_s, e.dst_s, e.s2d, e.n_src, dk, dq, rows=E * 16)
+        return dk, dq, dmsg, None
+
+
 class FiberConv(torch.autograd.Function):
     """x2[n,p,c] = 1/16 sum_o x1[n,o,c] fk[o,p,c] + bias[c]   (reference conv.py:88-90,108-109)."""
 

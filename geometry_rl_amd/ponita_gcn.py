@@ -10,7 +10,14 @@ adds of the partial x1).  Padded points have no edges and never reach the read-o
 graph (geometry_rl_amd/graph.py).  For the same reason the LAST layer only computes what the read-out can see: its edge set holds
 the edges into the read-out nodes, its fiber convolution and ConvNeXt block run on those nodes alone (the reference computes, and
 then never reads, the last layer's output at every other node; its gradient is identically zero) -- ``prune_last_layer=False``
-restores the full last layer."""
+restores the full last layer.
+
+``attention=True`` (ponita.py:130-137,154-160; the ``attention`` key of ponita_gcn.yaml): every layer owns ``key_transform`` /
+``query_transform`` (Linear(64, 128)) and weights its messages by a[e,o] = exp(l - M) / (sum_{e'->dst e} exp(l' - M) + 1e-6) with
+l[e,o] = <k[src e,o], q[dst e,o]> / sqrt(128) and M the maximum over ALL edges of the layer (ops.KeyQueryProject, ops.EdgeAttention).
+M ranges over every edge and reaches the weights through the 1e-6, so dropping edges changes them: with attention every layer runs on
+the full merged edge set and ``prune_last_layer`` is ignored.  fp32 only, one rank only (M and its gradient are batch-global: a
+data-parallel form needs two more collectives)."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -21,12 +28,19 @@ from .hepi import basis_sequential, global_std, make_grid
 
 
 class SeparableFiberBundleConv(nn.Module):
-    """Parameter holder: ponita.py:100-147 (depthwise, no attention)."""
+    """Parameter holder: ponita.py:100-147 (depthwise; ``attention``: the key / query layers of ponita.py:130-137)."""
 
-    def __init__(self, channels, kernel_dim):
+    def __init__(self, channels, kernel_dim, attention=False):
         super().__init__()
         self.kernel = nn.Linear(kernel_dim, channels, bias=False)
         self.fiber_kernel = nn.Linear(kernel_dim, channels, bias=False)
+        self.attention = bool(attention)
+        if self.attention:
+            self.key_transform = nn.Linear(channels, 128)
+            self.query_transform = nn.Linear(channels, 128)
+            for lin in (self.key_transform, self.query_transform):
+                nn.init.xavier_uniform_(lin.weight)
+                nn.init.zeros_(lin.bias)
         self.bias = nn.Parameter(torch.zeros(channels))
         self.register_buffer("callibrated", torch.tensor(False))
 
@@ -34,9 +48,9 @@ class SeparableFiberBundleConv(nn.Module):
 class SeparableFiberBundleConvNext(nn.Module):
     """Parameter holder: ponita.py:195-217 with layer_scale=None."""
 
-    def __init__(self, channels, kernel_dim, widening_factor=4):
+    def __init__(self, channels, kernel_dim, widening_factor=4, attention=False):
         super().__init__()
-        self.conv = SeparableFiberBundleConv(channels, kernel_dim)
+        self.conv = SeparableFiberBundleConv(channels, kernel_dim, attention)
         self.linear_1 = nn.Linear(channels, widening_factor * channels)
         self.linear_2 = nn.Linear(widening_factor * channels, channels)
         self.register_buffer("layer_scale", None)
@@ -47,7 +61,7 @@ class Ponita(nn.Module):
     """Parameter holder with the reference layout (ponita.py:247-325)."""
 
     def __init__(self, input_dim, hidden_dim, output_dim, num_layers, output_dim_vec=0, dim=3, num_ori=16, degree=2,
-                 widening_factor=4, only_upper_hemisphere=False, **ignored):
+                 widening_factor=4, only_upper_hemisphere=False, attention=False, **ignored):
         super().__init__()
         self.dim, self.num_ori = dim, num_ori
         self.register_buffer("ori_grid", make_grid(dim, num_ori, only_upper_hemisphere))
@@ -55,9 +69,19 @@ class Ponita(nn.Module):
         self.fiber_basis_fn = basis_sequential(3, hidden_dim, hidden_dim, degree)
         self.x_embedder = nn.Linear(input_dim, hidden_dim, False)
         self.interaction_layers = nn.ModuleList(
-            [SeparableFiberBundleConvNext(hidden_dim, hidden_dim, widening_factor) for _ in range(num_layers)])
+            [SeparableFiberBundleConvNext(hidden_dim, hidden_dim, widening_factor, attention) for _ in range(num_layers)])
         self.read_out_layers = nn.ModuleList(
             [nn.Linear(hidden_dim, output_dim + output_dim_vec) if i == num_layers - 1 else None for i in range(num_layers)])
+
+
+def check_attention_group(attention: bool, group) -> None:
+    """The attention layer's maximum M and its gradient dM are sums / maxima over the WHOLE batch: on more than one rank they would need an
+    all-reduce(max) of M in the forward and an all-reduce(sum) of dM in the backward, which are not built."""
+    if attention and group is not None:
+        import torch.distributed as dist
+        if dist.get_world_size(group) > 1:
+            raise NotImplementedError("PonitaGCN(attention=True) runs on one rank only: the batch-global maximum M of the attention logits "
+                                      "and its gradient dM need two collectives (all-reduce max of M, all-reduce sum of dM) that are not built")
 
 
 class PonitaGCN(nn.Module):
@@ -65,15 +89,18 @@ class PonitaGCN(nn.Module):
                  widening_factor=4, attention=False, ponita_dim=3, only_upper_hemisphere=False, device="cuda", precision="fp32",
                  prune_last_layer=True, **ignored):
         super().__init__()
-        self.prune_last_layer = prune_last_layer
+        self.attention = bool(attention)
+        self.prune_last_layer = prune_last_layer and not self.attention   # (module docstring: M ranges over every edge of the layer)
         self._merged_cache = {}
         self.precision, self._prec = precision, ("_bf16" if precision == "bf16" else "")
-        if hidden_dim != 64 or num_ori != 16 or degree != 2 or widening_factor != 4 or attention:
+        if hidden_dim != 64 or num_ori != 16 or degree != 2 or widening_factor != 4:
             raise NotImplementedError("HIP kernels are specialised for configs/algorithm/pyg_agent/model/ponita_gcn.yaml")
+        if self.attention and precision != "fp32":
+            raise NotImplementedError("PonitaGCN(attention=True) has fp32 kernels only (csrc/attention_ops.hip): precision='bf16' is not built")
         self.input_dim, self.dim = input_dim_node, ponita_dim
         self.output_dim, self.output_dim_vec = output_dim, output_dim_vec
         self.ponita = Ponita(input_dim_node, hidden_dim, output_dim, num_layers, output_dim_vec, ponita_dim, num_ori, degree,
-                             widening_factor, only_upper_hemisphere)
+                             widening_factor, only_upper_hemisphere, attention=self.attention)
         self.linear = nn.Linear(hidden_dim, output_dim + output_dim_vec)
         self.to(device)
 
@@ -144,8 +171,16 @@ class PonitaGCN(nn.Module):
         x_dst, pos_dst = (x, pos) if lo == 0 else (x[lo:], pos[lo:])
         # x feeds the convolution AND the residual of its own node block: the two gradients are summed inside the fused edge backward
         res = {} if (lo == 0 and torch.is_grad_enabled() and x.requires_grad) else None
-        x1 = ops.EdgeConv.apply(x, pos, pos_dst, grid3, b[1].weight, b[1].bias, b[3].weight, b[3].bias, layer.conv.kernel.weight, es,
-                                self.dim, res, self._prec, wimg)
+        if self.attention:   # un-aggregated messages, then the key/query weights and the sum (always the full edge set: lo == 0)
+            c = layer.conv
+            msg = ops.EdgeMessages.apply(x, pos, pos_dst, grid3, b[1].weight, b[1].bias, b[3].weight, b[3].bias, c.kernel.weight, es,
+                                         self.dim, res, self._prec)
+            k, q = ops.KeyQueryProject.apply(x, c.key_transform.weight, c.key_transform.bias, c.query_transform.weight,
+                                             c.query_transform.bias)
+            x1 = ops.EdgeAttention.apply(k, q, msg, es)
+        else:
+            x1 = ops.EdgeConv.apply(x, pos, pos_dst, grid3, b[1].weight, b[1].bias, b[3].weight, b[3].bias, layer.conv.kernel.weight, es,
+                                    self.dim, res, self._prec, wimg)
         x2 = ops.FiberConv.apply(x1, fk, layer.conv.bias, self._prec)
         if collect is not None:
             collect.update(x1=x1, fk=fk)
@@ -184,7 +219,8 @@ class PonitaGCN(nn.Module):
     @torch.no_grad()
     def calibrate(self, graph_full: GraphBatch, u_dict, group=None) -> None:
         """ponita.py:178-180,187-192: statistics over ALL nodes of the homogeneous graph (all node types, padding included; every layer
-        in full -- no pruning here)."""
+        in full -- no pruning here).  With attention x_1 is the attention-weighted sum; the key / query layers are never rescaled."""
+        check_attention_group(self.attention, group)
         grid3 = self.grid3
         mg = self._merged(graph_full)
         x = ops.LiftEncode.apply(graph_full.scalar_all, graph_full.vec_all, grid3, self.ponita.x_embedder.weight, self._prec)

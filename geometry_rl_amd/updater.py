@@ -175,6 +175,9 @@ class PolicyUpdater:
         self._fold_overwrite = (not getattr(loss_module.actor_network, "post_fc", False)
                                 and not any(getattr(mod, "attention", False) for mod in (gnn.modules() if gnn is not None else [])))
         self._overwrite_checked = not self._fold_overwrite
+        if gnn is not None and hasattr(gnn, "ponita"):   # EMPN key / query attention: one rank only (ponita_gcn.check_attention_group)
+            from .ponita_gcn import check_attention_group
+            check_attention_group(getattr(gnn, "attention", False), group)
         # the critic's lane reduces on a communicator of its own (_plan_dp).  dist.new_group is collective over the WHOLE default group
         # and must be entered by every rank in the same order: ``group`` therefore has to span WORLD (asserted), and a failure propagates
         # -- ranks that disagree on which communicator carries the critic's collectives would deadlock in the first step.

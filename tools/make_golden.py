@@ -22,9 +22,11 @@ section 8c), so three tiers are used:
           ``generated_under_semantic_stubs``.
   tier 2h the same data classes handed straight to the reference's PonitaGCN (EMPN) / HEPi ``one_step`` under both sets of stubs --
           padded rigid batches, the 2-D rope, cloth -- in float32 and float64: tier2h_<case>.npz + tier2h_<case>_grad.npz.
+          ``empn_attention`` (a sub-command of its own, writes only new files): the two EMPN cases with PonitaGCN(attention=True),
+          tier2h_<case>_attention.npz + tier2h_<case>_attention_grad.npz in the same record layout.
 
 Not in any fixture: variable-length ropes, the rigid builder with knn_to_actuators_k > 0, training noise (see tier3);
-PonitaGCN(attention=True); a model on a data class built with knn_to_actuators_k > 0.
+a model on a data class built with knn_to_actuators_k > 0.
 
 Regenerating: the gradients of the Ponita / HEPi fixtures come out of multi-threaded scatter backward passes and may differ in the last bit
 from run to run; every other array is reproduced exactly.
@@ -1162,8 +1164,11 @@ def tier3():
 
 
 # ----------------------------------------------------------------------------------------------- tier 2h: data class INTO the model
-def tier2h():
-    """The reference's data class handed straight to the reference's model, nothing of ours in between (install_stubs +
+def tier2h(attention=False):
+    """``attention``: only the two EMPN cases, with PonitaGCN(attention=True) (ponita.py:130-137,154-160), written to
+    tier2h_<case>_attention.npz / tier2h_<case>_attention_grad.npz; the other fixtures are not touched.
+
+    The reference's data class handed straight to the reference's model, nothing of ours in between (install_stubs +
     install_data_stubs): ``build_data(*obs, train=True)`` in the actor layout, then ``one_step`` of PonitaGCN (EMPN, ponita_gcn.py:88-146:
     lift and concatenation order per node type, the ``[..., :2]`` branches and the zero z column, to_homogeneous() node and edge order,
     homogeneous_batch, the output mask as a slice of the per-sample node axis) or of HEPi (hepi.py:125-190) on the batch object the data
@@ -1212,13 +1217,16 @@ def tier2h():
     }
     actor = dict(full_graph_obs=False, dist_as_pos=True, output_mask_key="grippers", concat_input_vector=False)
     codes = [[1, 0], [0, 1], [0, 1]]
+    if attention:
+        cases = {k + "_attention": dict(c, model=dict(c["model"], attention=1)) for k, c in cases.items() if c["model"]["empn"]}
 
     def make_net(c):
         spec, m = c["spec"], c["model"]
         n_in = len(spec.node_types) + spec.n_vec
         if m["empn"]:
             return PonitaGCN(input_dim_node=n_in, output_dim=m["output_dim"], output_dim_vec=m["output_dim_vec"], num_layers=2, hidden_dim=64,
-                             num_ori=16, degree=2, widening_factor=4, ponita_dim=m["dim"], only_upper_hemisphere=bool(m["upper"]))
+                             num_ori=16, degree=2, widening_factor=4, ponita_dim=m["dim"], only_upper_hemisphere=bool(m["upper"]),
+                             **({"attention": True} if m.get("attention") else {}))
         mp = [[FiberBundleConv(64, 64, 64, groups=64, separable=True, widening_factor=4, aggr="add") if codes[lvl][k] else None
                for k in range(2)] for lvl in range(3)]
         return HEPi(input_dim_node=n_in, input_dim_edge=0, hidden_dim=64, latent_dim=64, output_dim=m["output_dim"],
@@ -1318,6 +1326,10 @@ if __name__ == "__main__":
         install_stubs()
         tier2h()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "empn_attention":   # only the attention-enabled EMPN fixtures (new files)
+        install_stubs()
+        tier2h(attention=True)
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "tier2f":
         install_stubs()
         tier2f()
@@ -1350,5 +1362,6 @@ if __name__ == "__main__":
     tier2g()
     tier3()
     tier2h()
+    tier2h(attention=True)
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))

@@ -39,16 +39,22 @@ VARIANTS = {
     # the per-update schedule of train.py:263-276 over a total no run reaches: lr (yardstick: trpl), lr + clip epsilon (yardstick: ppo)
     "anneal_on": dict(cfg=dict(anneal_lr=True, total_train_steps=10 ** 8)),
     "ppo_anneal_on": dict(cfg=dict(algorithm="ppo", anneal_lr=True, anneal_clip_epsilon=True, total_train_steps=10 ** 8)),
+    # the two-agent EMPN update (bench.py's rigid2_empn workload: ``spec`` = rigid_spec / make_rigid_obs keywords, ``base`` replaces the HEPi
+    # workload's AgentConfig keywords) without and with the key / query attention of ponita_gcn.yaml's ``attention`` key
+    "empn2": dict(spec=dict(G=2), base={}, cfg=dict(model="empn")),
+    "empn2_attention": dict(spec=dict(G=2), base={}, cfg=dict(model="empn", attention=True)),
 }
+HEPI_BASE = dict(only_upper_hemisphere=True, output_dim=2, output_dim_vec=2)
 
 
 def make(variant, B, dev):
     from geometry_rl_amd import agent, graph, synthetic as syn
-    spec = graph.rigid_spec()
-    cfg = agent.AgentConfig(only_upper_hemisphere=True, output_dim=2, output_dim_vec=2, **VARIANTS[variant].get("cfg", {}))
+    spec_kw = VARIANTS[variant].get("spec", {})
+    spec = graph.rigid_spec(**spec_kw)
+    cfg = agent.AgentConfig(**VARIANTS[variant].get("base", HEPI_BASE), **VARIANTS[variant].get("cfg", {}))
     torch.manual_seed(0)
     actor, critic, proj, loss = agent.build_agent(spec, cfg, device=dev)
-    batch = dict(syn.make_rigid_obs(B, seed=1))
+    batch = dict(syn.make_rigid_obs(B, seed=1, **spec_kw))
     batch.update(syn.make_ppo_fields(B, spec.num_actuators * cfg.output_dim_vec * 3, seed=1))
     batch = {k: v.to(dev) for k, v in batch.items()}
     with torch.no_grad():
