@@ -47,6 +47,9 @@ class AgentConfig:
     # model "empn" only: the ``attention`` key of configs/algorithm/pyg_agent/model/ponita_gcn.yaml (key / query attention weights on the
     # messages of every layer, ponita.py:130-137,154-160); fp32, one rank, every layer on the full edge set (ponita_gcn.py)
     attention: bool = False
+    # model "transformer" only: "torch" = stock nn.TransformerEncoder + torch heads (eager updates); "hip" = csrc/transformer_ops.hip, the
+    # encoder as one launch each way and the post_fc head as one, recorded like the other actors (fp32; transformer.py)
+    transformer_kernels: str = "torch"
     # the actor's HyperData only (configs/rigid_pushing_multi_empn_trpl_cfg.yaml:105-106; every upstream critic config keeps it False)
     training_noise: bool = False
     training_noise_std: float = 0.01
@@ -96,6 +99,16 @@ def build_agent(spec: TaskSpec, cfg: AgentConfig, device="cuda", group=None):
     if cfg.attention and cfg.model != "empn":
         raise ValueError(f"AgentConfig(attention=True) is the EMPN actor's key / query attention (model='empn'), not model '{cfg.model}' "
                          "(HEPi's attention variant is aggr='AttentionalAggregation')")
+    if cfg.transformer_kernels not in ("torch", "hip"):
+        raise ValueError(f"AgentConfig(transformer_kernels=...): 'torch' or 'hip', got {cfg.transformer_kernels!r}")
+    if cfg.transformer_kernels == "hip":
+        ref = "configs/algorithm/pyg_agent/model/transformer.yaml"
+        if cfg.model != "transformer":
+            raise NotImplementedError(f"AgentConfig(transformer_kernels='hip') is the transformer baseline actor's switch ({ref}), not "
+                                      f"model '{cfg.model}'")
+        if cfg.precision != "fp32":
+            raise NotImplementedError(f"AgentConfig(transformer_kernels='hip') has fp32 kernels only (csrc/transformer_ops.hip; {ref} runs in "
+                                      f"fp32 and needs no other): precision='{cfg.precision}' is not built")
     if cfg.model == "hepi":
         mp = []  # utils_algo_graph.py:29-47: one fresh conv per (level, active round)
         for lvl in range(len(spec.edge_levels)):
@@ -109,7 +122,8 @@ def build_agent(spec: TaskSpec, cfg: AgentConfig, device="cuda", group=None):
     elif cfg.model == "transformer":   # BASELINE config 1: stock-torch baseline actor + post_fc head on the same loss / critic / updater
         from .transformer import TransformerVanilla
         gnn = TransformerVanilla(input_dim_node=len(spec.node_types) + 3 * spec.n_vec, output_dim=64, num_layers=cfg.num_layers,
-                                 num_heads=2, hidden_dim=64, dropout=0.0, concat_global=False, device=device)
+                                 num_heads=2, hidden_dim=64, dropout=0.0, concat_global=False, device=device,
+                                 kernels=cfg.transformer_kernels)
     elif cfg.model == "empn":
         from .ponita_gcn import PonitaGCN, check_attention_group
         check_attention_group(cfg.attention, group)
@@ -122,6 +136,10 @@ def build_agent(spec: TaskSpec, cfg: AgentConfig, device="cuda", group=None):
     post_fc = cfg.model == "transformer"
     a_data = HyperData(spec, full_graph_obs=False, dist_as_pos=True, output_mask_key=spec.actuator, concat_input_vector=post_fc,
                        training_noise=cfg.training_noise, training_noise_std=cfg.training_noise_std)
+    if cfg.transformer_kernels == "hip":   # tokens per sample = the points of the actor graph's node types: refused here, not in the first step
+        pv = dict(zip(spec.obs_names["position_vectors"], spec.obs_dims["position_vectors"]))
+        gnn.n_tokens = sum(pv[t] // 3 for t in a_data.node_type_list)
+        gnn.check_tokens(gnn.n_tokens)
     A = spec.num_actuators * cfg.output_dim_vec * 3
     actor = GNNGaussianPolicyDiag(gnn=gnn, hyper_data=a_data, action_dim=A, num_actuators=spec.num_actuators, init="orthogonal",
                                   hidden_sizes=(64, 64), contextual_std=True, init_std=cfg.init_std, minimal_std=cfg.minimal_std,

@@ -405,7 +405,7 @@ extern "C" {
 
 // ABI version of this library: major * 10000 + minor * 100 + patch.  Bumped whenever a declared signature changes
 // (include/grl_hip.h GRL_HIP_VERSION must agree: geometry_rl_amd/hip.py checks it at load time).
-int grl_version(void) { return 215; }
+int grl_version(void) { return 216; }
 // dst[0..n) = host_values[0..n), n <= 64, and mirror[0] = host_values[mirror_index] where mirror is given: one small launch whose kernel
 // arguments ARE the values (stream-ordered in front of the program that reads them; nothing is synchronised)
 int grl_write_floats(float* dst, const float* host_values, int n, float* mirror, int mirror_index, hipStream_t stream) {

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("GRL_LIB", os.path.join(_HERE, "libgrl_hip.so"))  # GRL_LIB: debugging builds only
-ABI_VERSION = 215   # include/grl_hip.h GRL_HIP_VERSION
+ABI_VERSION = 216   # include/grl_hip.h GRL_HIP_VERSION
 SOURCES = ["edge_conv.hip", "edge_conv16.hip", "node_ops.hip", "node_mlp.hip", "node_mlp16.hip", "head_ops.hip",
            "critic_ops.hip", "train_ops.hip", "weight_images.hip", "calib.hip", "oneshot.hip", "stats_ops.hip"]
 # The EMPN key / query attention kernels are a library of their own, libgrl_attention.so, declared in csrc/grl_attention.h: the export
@@ -22,6 +22,11 @@ SOURCES = ["edge_conv.hip", "edge_conv16.hip", "node_ops.hip", "node_mlp.hip", "
 ATTENTION_SOURCES = ["attention_ops.hip"]
 ATTENTION_HEADER = "grl_attention.h"
 ATTENTION_LIB_PATH = os.path.join(_HERE, "libgrl_attention.so")
+# The transformer baseline actor's kernels (encoder forward / backward, post_fc head) likewise: libgrl_transformer.so, declared in
+# csrc/grl_transformer.h, bound by transformer_call / transformer_query (ABI 216 of include/grl_hip.h names the addition).
+TRANSFORMER_SOURCES = ["transformer_ops.hip"]
+TRANSFORMER_HEADER = "grl_transformer.h"
+TRANSFORMER_LIB_PATH = os.path.join(_HERE, "libgrl_transformer.so")
 # (source, extra flags, object suffix): the two MFMA files are compiled a second time as the plain-bf16 variant (one MFMA per
 # product instead of three; csrc/grl_common.h GRL_PREC) whose entry points carry the suffix _bf16
 # per-source compiler flags.  edge_conv16.hip: its 512-register backward kernel keeps the chain's MFMA results in VGPRs (the default
@@ -72,7 +77,7 @@ def source_hash(root=None) -> str:
     import json
     csrc, header, lint = _pkg_paths(root)
     names = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
-    parts = [json.dumps([BASE_FLAGS, SOURCES, FILE_FLAGS, VARIANTS, ATTENTION_SOURCES], sort_keys=True)]
+    parts = [json.dumps([BASE_FLAGS, SOURCES, FILE_FLAGS, VARIANTS, ATTENTION_SOURCES, TRANSFORMER_SOURCES], sort_keys=True)]
     for n in names:
         parts += [n, _read(os.path.join(csrc, n))]
     parts += ["grl_hip.h", _read(header), "isa_lint.py", _read(lint)]
@@ -108,36 +113,38 @@ def build(verbose: bool = True, force: bool = False, root=None) -> str:
     csrc, header, lint_py = _pkg_paths(root)
     lib_path = os.path.join(os.path.dirname(csrc), "libgrl_hip.so") if root else LIB_PATH
     att_path = os.path.join(os.path.dirname(csrc), "libgrl_attention.so") if root else ATTENTION_LIB_PATH
+    tf_path = os.path.join(os.path.dirname(csrc), "libgrl_transformer.so") if root else TRANSFORMER_LIB_PATH
     info_path = os.path.join(root, "BUILD_INFO.json") if root else BUILD_INFO
     srcs = [os.path.join(csrc, s) for s in SOURCES if os.path.exists(os.path.join(csrc, s))]
     att_srcs = [os.path.join(csrc, s) for s in ATTENTION_SOURCES]
+    tf_srcs = [os.path.join(csrc, s) for s in TRANSFORMER_SOURCES]
     tree_hash = source_hash(root)
 
     def info(mode, rebuilt, lint=None):
         try:
             with open(info_path, "w") as f:
-                json.dump({"build_mode": mode, "objects_rebuilt": rebuilt, "isa_lint": lint, "objects_total": len(srcs) + len(VARIANTS) + len(att_srcs) + 1,
+                json.dump({"build_mode": mode, "objects_rebuilt": rebuilt, "isa_lint": lint, "objects_total": len(srcs) + len(VARIANTS) + len(att_srcs) + len(tf_srcs) + 1,
                            "library": os.path.relpath(lib_path, os.path.dirname(os.path.dirname(csrc))),
                            "library_bytes": os.path.getsize(lib_path) if os.path.exists(lib_path) else None, "abi_version": ABI_VERSION,
                            "source_hash": tree_hash, "library_source_hash": embedded_hash(lib_path),
                            "forced": bool(force), "time": time.strftime("%Y-%m-%dT%H:%M:%S")}, f, indent=1)
         except OSError:
             pass
-    if not force and embedded_hash(lib_path) == tree_hash and embedded_hash(att_path) == tree_hash:
+    if not force and embedded_hash(lib_path) == tree_hash and embedded_hash(att_path) == tree_hash and embedded_hash(tf_path) == tree_hash:
         info("prebuilt (the libraries' embedded source hash equals the tree's: nothing compiled)", [])
         return lib_path
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     from . import isa_lint
     header_bytes = [_read(os.path.join(csrc, h)) for h in sorted(f for f in os.listdir(csrc) if f.endswith(".h"))]   # every header feeds every object
     lint_bytes = _read(lint_py)
-    objs, att_objs = [], []
+    objs, att_objs, tf_objs = [], [], []
     procs = []
     rebuilt = []
     lint_jobs = []   # (label, assembly file, object, its hash file, its hash) of every object compiled NOW from a source with asm MFMAs
     pending = []     # (hash file, hash) of the other objects compiled now: recorded once hipcc has succeeded
     bdir = os.path.join(csrc, "build")
     os.makedirs(bdir, exist_ok=True)
-    jobs = [(s, [], "") for s in srcs] + [(os.path.join(csrc, s), fl, sfx) for s, fl, sfx in VARIANTS] + [(s, [], "") for s in att_srcs]
+    jobs = [(s, [], "") for s in srcs] + [(os.path.join(csrc, s), fl, sfx) for s, fl, sfx in VARIANTS] + [(s, [], "") for s in att_srcs] + [(s, [], "") for s in tf_srcs]
     for s, flags, sfx in jobs:
         base = os.path.basename(s)
         lint = base in isa_lint.FILES
@@ -146,7 +153,7 @@ def build(verbose: bool = True, force: bool = False, root=None) -> str:
         odir = os.path.join(bdir, base + sfx + ".d") if lint else bdir
         os.makedirs(odir, exist_ok=True)
         o = os.path.join(odir, base + sfx + ".o")
-        (att_objs if s in att_srcs else objs).append(o)
+        (att_objs if s in att_srcs else tf_objs if s in tf_srcs else objs).append(o)
         cmd_flags = BASE_FLAGS + FILE_FLAGS.get(base, []) + flags + (["-save-temps=obj"] if lint else [])
         ohash = _sha(_read(s), *header_bytes, " ".join(cmd_flags), lint_bytes if lint else b"")
         hfile = o + ".srchash"
@@ -222,7 +229,18 @@ def build(verbose: bool = True, force: bool = False, root=None) -> str:
     subprocess.check_call(cmd)
     if embedded_hash(att_path) != tree_hash:
         raise RuntimeError(f"{att_path}: the embedded source hash did not survive the link")
-    info("compiled from source" if len(rebuilt) == len(objs) + len(att_objs) else "incremental (objects whose recorded source hash still matched were kept)", rebuilt, lint_report)
+    # ... and the transformer actor's library, the same way (csrc/grl_transformer.h)
+    tf_names = sorted(set(re.findall(EXPORT_RE, open(os.path.join(csrc, TRANSFORMER_HEADER)).read())))
+    tvs = os.path.join(bdir, "exports_transformer.map")
+    with open(tvs, "w") as f:
+        f.write("{\n  global:\n" + "".join(f"    {n};\n" for n in tf_names) + "  local: *;\n};\n")
+    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + tvs, "-o", tf_path] + tf_objs + [hobj]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    if embedded_hash(tf_path) != tree_hash:
+        raise RuntimeError(f"{tf_path}: the embedded source hash did not survive the link")
+    info("compiled from source" if len(rebuilt) == len(objs) + len(att_objs) + len(tf_objs) else "incremental (objects whose recorded source hash still matched were kept)", rebuilt, lint_report)
     return lib_path
 
 
@@ -360,6 +378,24 @@ def attention_lib() -> dict:
     return _att_bound
 
 
+_tf_bound = None
+
+
+def transformer_lib() -> dict:
+    """The bound entry points of libgrl_transformer.so (csrc/grl_transformer.h), loaded on first use.  No fallback: a missing or stale
+    library raises."""
+    global _tf_bound
+    if _tf_bound is None:
+        if not os.path.exists(TRANSFORMER_LIB_PATH):
+            raise RuntimeError(
+                f"{TRANSFORMER_LIB_PATH} is missing: the HIP extension must be built (python -c 'import __graft_entry__ as g; g.build()'). "
+                "geometry_rl_amd has no CPU or PyTorch fallback path.")
+        if "GRL_LIB" not in os.environ and os.environ.get("GRL_ALLOW_STALE_LIB", "0") == "0":
+            check_library(TRANSFORMER_LIB_PATH)
+        _tf_bound = bind(_read(os.path.join(CSRC, TRANSFORMER_HEADER)).decode(), ctypes.CDLL(TRANSFORMER_LIB_PATH))
+    return _tf_bound
+
+
 def stream_ptr() -> ctypes.c_void_p:
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -378,6 +414,16 @@ def call(name: str, *args, stream=None, rows: int = 0) -> None:
 def attention_call(name: str, *args, stream=None, rows: int = 0) -> None:
     """``call`` for an entry point of libgrl_attention.so (csrc/grl_attention.h)."""
     _launch(attention_query, name, args, stream, rows)
+
+
+def transformer_call(name: str, *args, stream=None, rows: int = 0) -> None:
+    """``call`` for an entry point of libgrl_transformer.so (csrc/grl_transformer.h)."""
+    _launch(transformer_query, name, args, stream, rows)
+
+
+def transformer_query(name: str, *args) -> int:
+    """``query`` for an entry point of libgrl_transformer.so."""
+    return invoke(transformer_lib(), name, args)
 
 
 def attention_query(name: str, *args) -> int:

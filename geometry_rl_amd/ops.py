@@ -801,6 +801,94 @@ class Readout(torch.autograd.Function):
         return dlat, None, dwd, dbd, dws, dbs, None, None, None, None
 
 
+TRANSFORMER_MAX_TOKENS = 256   # csrc/transformer_ops.hip NMAX: one workgroup keeps a sample's per-head K / V / Q rows in LDS
+# (offset, length, shape) of one encoder layer's gradients inside its 25216 floats of a partial row, in the order of the layer's
+# parameters below (csrc/grl_transformer.h grl_transformer_bwd)
+_TF_LAYER_SEGMENTS = ((0, 12288, (192, 64)), (12288, 192, (192,)), (12480, 4096, (64, 64)), (16576, 64, (64,)), (16640, 64, (64,)),
+                      (16704, 64, (64,)), (16768, 4096, (64, 64)), (20864, 64, (64,)), (20928, 4096, (64, 64)), (25024, 64, (64,)),
+                      (25088, 64, (64,)), (25152, 64, (64,)))
+
+
+class TransformerEncode(torch.autograd.Function):
+    """hidden [B*G,64] = fc_out(encoder(embedding(u))[:, m0:m0+G]) for u [B,n,d_in]: torch's post-norm encoder (2 layers, 2 heads, width
+    64, feed-forward 64, no dropout, no mask; transformer_vanilla.py:29-36,87-92) as ONE launch, its backward as one more.
+    ``params``: the 28 tensors in the order of csrc/grl_transformer.h (embedding, per layer in_proj / out_proj / norm1 / linear1 / linear2 /
+    norm2, fc_out).  ``u`` gets no gradient; the 28 leaf gradients go through per-workgroup partial rows and the fold.  fp32 only."""
+
+    @staticmethod
+    def forward(ctx, u, m0: int, G: int, *params):
+        hip.check_f32(u, *params)
+        if len(params) != 28:
+            raise ValueError(f"TransformerEncode takes the encoder's 28 parameter tensors, got {len(params)}")
+        B, n, d_in = u.shape
+        if not 1 <= n <= TRANSFORMER_MAX_TOKENS:
+            raise NotImplementedError(f"TransformerEncode: {n} tokens per sample, the kernels hold 1 .. {TRANSFORMER_MAX_TOKENS}")
+        u = u.contiguous()
+        dev = u.device
+        ps = [p.contiguous() for p in params]
+        saved = torch.empty(15, B * n, 64, device=dev, dtype=torch.float32)    # every row is written by the kernel
+        stats = torch.empty(2, B * n, 6, device=dev, dtype=torch.float32)
+        hidden = torch.empty(B * G, 64, device=dev, dtype=torch.float32)
+        hip.transformer_call("grl_transformer_fwd", u, ps, saved, stats, hidden, B, n, d_in, m0, G, rows=B * n)
+        ctx.save_for_backward(u, saved, stats, *ps)
+        ctx.cfg = (B, n, d_in, m0, G)
+        ctx.params = params
+        return hidden
+
+    @staticmethod
+    def backward(ctx, dhidden):
+        u, saved, stats, *ps = ctx.saved_tensors
+        B, n, d_in, m0, G = ctx.cfg
+        dev = u.device
+        blocks = hip.transformer_query("grl_transformer_blocks", B, n)
+        partial = torch.empty(blocks, hip.transformer_query("grl_transformer_partial_size", d_in), device=dev, dtype=torch.float32)
+        ws = torch.empty(blocks, hip.transformer_query("grl_transformer_group_rows", B, n), hip.transformer_query("grl_transformer_ws_row"), device=dev, dtype=torch.float32)
+        hip.transformer_call("grl_transformer_bwd", u, ps, saved, stats, dhidden.contiguous(), ws, partial, B, n, d_in, m0, G, rows=B * n)
+        p = ctx.params
+        segs = []
+        for l in range(2):
+            segs += [(25216 * l + off, length, shape, p[2 + 12 * l + i]) for i, (off, length, shape) in enumerate(_TF_LAYER_SEGMENTS)]
+        segs += [(50432, 4096, (64, 64), p[26]), (54528, 64, (64,), p[27])]
+        segs = [(54656, 64 * d_in, (64, d_in), p[0]), (54592, 64, (64,), p[1])] + segs
+        return (None, None, None) + tuple(_emit_grads(partial, segs))
+
+
+class PostFcHead(torch.autograd.Function):
+    """mean = hidden Wm^T + bm, sigma = softplus(hidden Ws^T + bs + shift) + min_std for hidden [R,64] and A <= 16 outputs each: both heads
+    of gnn_gaussian_policy_diag.py:65-83 with post_fc=True as one launch (a state-independent std: Ws = 0, bs = the vector)."""
+
+    @staticmethod
+    def forward(ctx, hidden, wm, bm, ws, bs, shift: float, min_std: float):
+        hip.check_f32(hidden, wm, bm, ws, bs)
+        hidden = hidden.contiguous()
+        R, A, dev = hidden.shape[0], wm.shape[0], hidden.device
+        if not 1 <= A <= 16 or ws.shape[0] != A:
+            raise NotImplementedError(f"PostFcHead: {A} outputs per row, the kernels hold 1 .. 16")
+        mean = torch.empty(R, A, device=dev, dtype=torch.float32)
+        sigma = torch.empty(R, A, device=dev, dtype=torch.float32)
+        pre = torch.empty(R, A, device=dev, dtype=torch.float32)
+        args = [a.contiguous() for a in (wm, bm, ws, bs)]
+        hip.transformer_call("grl_postfc_head_fwd", hidden, *args, shift, min_std, mean, sigma, pre, R, A, rows=R)
+        ctx.save_for_backward(hidden, args[0], args[2], pre)
+        ctx.cfg = (float(shift), A)
+        ctx.params = (wm, bm, ws, bs)
+        return mean, sigma
+
+    @staticmethod
+    def backward(ctx, dmean, dsigma):
+        hidden, wm, ws, pre = ctx.saved_tensors
+        shift, A = ctx.cfg
+        R, dev = hidden.shape[0], hidden.device
+        partial = torch.empty(hip.transformer_query("grl_postfc_head_blocks", R), hip.transformer_query("grl_postfc_head_partial_size"), device=dev,
+                              dtype=torch.float32)
+        dhidden = torch.empty_like(hidden)
+        hip.transformer_call("grl_postfc_head_bwd", hidden, wm, ws, pre, shift, dmean.contiguous(), dsigma.contiguous(), dhidden, partial, R, A, rows=R)
+        pwm, pbm, pws, pbs = ctx.params
+        dwm, dbm, dws, dbs = _emit_grads(partial, [(0, A * 64, (A, 64), pwm), (2048, A, (A,), pbm), (1024, A * 64, (A, 64), pws),
+                                                   (2064, A, (A,), pbs)])
+        return dhidden, dwm, dbm, dws, dbs, None, None
+
+
 class DeepSetsPipeline:
     """The six kernels of the DeepSets critic (reference deepsets.py:34-53, gnn_vf_net.py:50-86) as explicit stages.  Between
     fwd1/fwd2, fwd2/fwd3, bwd3/bwd2 and bwd2/bwd1 the whole-tensor LayerNorm sums (``stats`` / ``bst`` halves) have to be summed

@@ -157,8 +157,8 @@ class PolicyUpdater:
         self.stats_critic = torch.zeros(2, device=dev, dtype=torch.float64) if self.track_stats else None
         self._stats_one_stream = False   # the running program is _plan_one_stream: its report carries the critic loss
         self.use_graph = use_graph
-        if use_graph and getattr(loss_module.actor_network, "post_fc", False):
-            # config 1's baseline actor is a stock torch.nn.TransformerEncoder: its launches are torch's own (rocBLAS / hipBLASLt
+        if use_graph and getattr(loss_module.actor_network, "stock_torch_gnn", False):
+            # config 1's baseline actor with kernels="torch" is a stock torch.nn.TransformerEncoder: its launches are torch's own (rocBLAS / hipBLASLt
             # workspaces are not capture-safe on this stack), so that step is issued eagerly -- it is the reference's CPU-sized
             # plumbing case (64 envs x 32 steps), not a throughput path
             self.use_graph, self.mode = False, "eager (stock-torch transformer actor: not recorded)"
@@ -172,6 +172,8 @@ class PolicyUpdater:
         # fold queue: not with the stock torch transformer actor or the attention gate (torch's AccumulateGrad adds into .grad) -- and
         # checked on the first eager step of every updater (``_check_overwrite_coverage``).
         gnn = getattr(loss_module.actor_network, "gnn", None)
+        # The transformer actor on HIP kernels (kernels="hip") keeps the accumulate mode too: ``cls_token`` and the template encoder layer
+        # take no part in the forward, so no fold ever writes their gradients -- they stay the zeros of the buffer, as on the stock path.
         self._fold_overwrite = (not getattr(loss_module.actor_network, "post_fc", False)
                                 and not any(getattr(mod, "attention", False) for mod in (gnn.modules() if gnn is not None else [])))
         self._overwrite_checked = not self._fold_overwrite
@@ -412,7 +414,9 @@ class PolicyUpdater:
             b["var"] = b["covariance_matrix"].diagonal(dim1=-2, dim2=-1).contiguous()
         st["b"] = b
         st["obs"] = [b[k] for k in m.in_features]
-        st["cobs"] = [b[k] for k in m.critic_in_features]
+        # (a multi-step launch hands the actor's lane ITS rollout tensors only: where the actor reads other observation groups than the
+        # critic -- the transformer actor's normalised vectors -- the critic's list is the critic lane's business, built from its own batch)
+        st["cobs"] = [b[k] for k in m.critic_in_features] if all(k in b for k in m.critic_in_features) else None
         st["zw"] = torch.empty(26, device=self.flat.device, dtype=torch.float64)
         st.setdefault("beta", self.beta_table[0:1])   # (entropy control: the bound this step's loss launch reads; _epoch_entries sets entry j)
 

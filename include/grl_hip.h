@@ -21,7 +21,7 @@ extern "C" {
 #endif
 
 /* ABI version (major*10000 + minor*100 + patch); grl_version() returns the value the library was built with. */
-#define GRL_HIP_VERSION 215   /* 215: EMPN key/query attention added as a library of its own (libgrl_attention.so, declared in geometry_rl_amd/csrc/grl_attention.h, bound by geometry_rl_amd/hip.py attention_call / attention_query); this header and the exports of libgrl_hip.so are unchanged; 214: grl_write_floats added (the per-update learning rates and clip epsilons of a recorded program, written by one launch in front of it), no existing signature changed; 213: cfg9[8] accepts 6 and 7, the Euclidean (scale_prec=False) forms of the Frobenius and commutative Wasserstein projections, no signature changed; 212: grl_klpen_fwd_bwd (adaptive KL-penalty PPO objective on the fused loss kernel) and grl_klpen_adapt (its penalty weight's update) added, no existing signature changed; 211: csrc/stats_ops.hip added (grl_stats_accumulate, grl_explained_variance + its scratch query, grl_episode_scan), no existing signature changed; 210: grl_trpl_fwd_bwd_ent (scheduled entropy projection inside the fused TRPL launch) and grl_write_doubles added, no existing signature changed; 209: three exports removed (the device-cursor variant of grl_gather_rows_many, the hipStreamWaitValue32 capability query, the idle spin kernel of calib.hip); 208: cfg9[8] = 4 accepted (non-commuting Wasserstein projection), no signature change; 207: grl_ppo_fwd_bwd added (clipped PPO objective); 206: grl_build_features_noise, grl_step_head_noise[_bf16] added (training noise); 205 (round 6): grl_source_hash added; 204 (round 5): grl_head_fused / grl_head_fused_rows removed, grl_calib_mfma / grl_calib_copy added; the exports are exactly this header */
+#define GRL_HIP_VERSION 216   /* 216: the transformer baseline actor's kernels added as a library of their own (libgrl_transformer.so, declared in geometry_rl_amd/csrc/grl_transformer.h, bound by geometry_rl_amd/hip.py transformer_call / transformer_query); this header's declarations and the exports of libgrl_hip.so are unchanged; 215: EMPN key/query attention added as a library of its own (libgrl_attention.so, declared in geometry_rl_amd/csrc/grl_attention.h, bound by geometry_rl_amd/hip.py attention_call / attention_query); this header and the exports of libgrl_hip.so are unchanged; 214: grl_write_floats added (the per-update learning rates and clip epsilons of a recorded program, written by one launch in front of it), no existing signature changed; 213: cfg9[8] accepts 6 and 7, the Euclidean (scale_prec=False) forms of the Frobenius and commutative Wasserstein projections, no signature changed; 212: grl_klpen_fwd_bwd (adaptive KL-penalty PPO objective on the fused loss kernel) and grl_klpen_adapt (its penalty weight's update) added, no existing signature changed; 211: csrc/stats_ops.hip added (grl_stats_accumulate, grl_explained_variance + its scratch query, grl_episode_scan), no existing signature changed; 210: grl_trpl_fwd_bwd_ent (scheduled entropy projection inside the fused TRPL launch) and grl_write_doubles added, no existing signature changed; 209: three exports removed (the device-cursor variant of grl_gather_rows_many, the hipStreamWaitValue32 capability query, the idle spin kernel of calib.hip); 208: cfg9[8] = 4 accepted (non-commuting Wasserstein projection), no signature change; 207: grl_ppo_fwd_bwd added (clipped PPO objective); 206: grl_build_features_noise, grl_step_head_noise[_bf16] added (training noise); 205 (round 6): grl_source_hash added; 204 (round 5): grl_head_fused / grl_head_fused_rows removed, grl_calib_mfma / grl_calib_copy added; the exports are exactly this header */
 int grl_version(void);
 /* The hash of the sources this binary was built from (16 hex digits + NUL into buf; returns the length).  geometry_rl_amd/hip.py
    source_hash() recomputes it from csrc/, this header and the build's flag tables and refuses a library that disagrees. */

@@ -11,6 +11,8 @@ ms / step of each (``<variant>_ms_per_step``, ``<variant>_min_max_ms``), B / A (
   python tools/step_ab.py trpl track_stats_on --sizes 32 512 4096 --blocks 8 --build-order both --reverse-blocks --graphs --calibration
   python tools/step_ab.py ppo ppo_anneal_on --sizes 32 512 4096 --build-order both --reverse-blocks                    # the per-step program
   python tools/step_ab.py ppo ppo_anneal_on --sizes 32 512 4096 --build-order both --reverse-blocks --launch-steps 8   # the multi-step launch
+  python tools/step_ab.py transformer transformer_hip --sizes 64 512 4096 --reverse-blocks --eager --count-calls       # both as eager steps
+  python tools/step_ab.py transformer transformer_hip --sizes 64 512 4096 --reverse-blocks                             # the HIP variant replayed
 
 The updater built SECOND in a process has measured 3.6 % slower at 4096 frames whatever it runs (entropy control): a
 difference of that size is read from both build orders (--build-order both) and from blocks whose order is reversed every round."""
@@ -43,11 +45,15 @@ VARIANTS = {
     # workload's AgentConfig keywords) without and with the key / query attention of ponita_gcn.yaml's ``attention`` key
     "empn2": dict(spec=dict(G=2), base={}, cfg=dict(model="empn")),
     "empn2_attention": dict(spec=dict(G=2), base={}, cfg=dict(model="empn", attention=True)),
+    # BASELINE config 1's transformer actor (rigid, A = 6): stock torch (its step cannot be recorded: it runs eagerly whatever is asked) and
+    # on HIP kernels.  Compare them with --eager (both as eager upd.step calls) and once more without (the HIP variant replayed)
+    "transformer": dict(base=dict(output_dim=2, output_dim_vec=2), cfg=dict(model="transformer")),
+    "transformer_hip": dict(base=dict(output_dim=2, output_dim_vec=2), cfg=dict(model="transformer", transformer_kernels="hip")),
 }
 HEPI_BASE = dict(only_upper_hemisphere=True, output_dim=2, output_dim_vec=2)
 
 
-def make(variant, B, dev):
+def make(variant, B, dev, use_graph=True):
     from geometry_rl_amd import agent, graph, synthetic as syn
     spec_kw = VARIANTS[variant].get("spec", {})
     spec = graph.rigid_spec(**spec_kw)
@@ -59,7 +65,7 @@ def make(variant, B, dev):
     batch = {k: v.to(dev) for k, v in batch.items()}
     with torch.no_grad():
         actor.forward_diag(*[batch[k] for k in loss.in_features], train=True)   # calibration
-    return agent.PolicyUpdater(loss, use_graph=True, **dict(agent.updater_kwargs(cfg), **VARIANTS[variant].get("upd", {}))), batch
+    return agent.PolicyUpdater(loss, use_graph=use_graph, **dict(agent.updater_kwargs(cfg), **VARIANTS[variant].get("upd", {}))), batch
 
 
 def launcher(upd, batch, U):
@@ -78,16 +84,21 @@ def count_calls(upd, batch):
     torch's own launches are not counted)."""
     from geometry_rl_amd import hip
     upd.step(batch)                       # the first step of a size runs eagerly
-    n, real = [0], hip.call
+    names = ("call", "attention_call", "transformer_call")   # the three libraries' launch functions
+    n, real = [0], {k: getattr(hip, k) for k in names}
 
-    def counting(*args, **kw):
-        n[0] += 1
-        return real(*args, **kw)
-    hip.call = counting
+    def counting(fn):
+        def run(*args, **kw):
+            n[0] += 1
+            return fn(*args, **kw)
+        return run
+    for k in names:
+        setattr(hip, k, counting(real[k]))
     try:
         upd.step(batch)
     finally:
-        hip.call = real
+        for k in names:
+            setattr(hip, k, real[k])
     return n[0]
 
 
@@ -106,7 +117,10 @@ def main():
     ap.add_argument("--calibration", action="store_true", help="print the box calibration (bench.py's two fixed kernels) first")
     ap.add_argument("--launch-steps", type=int, default=0, help="time the multi-step launch of this many steps (a block = --steps launches) "
                     "instead of the per-step program")
+    ap.add_argument("--eager", action="store_true", help="time blocks of eager upd.step calls of both variants (nothing recorded)")
     a = ap.parse_args()
+    if a.eager and a.launch_steps:
+        ap.error("--eager times upd.step calls: no --launch-steps")
     if a.a == a.b:
         ap.error("two different variants")
     dev = torch.device("cuda:0")
@@ -115,7 +129,7 @@ def main():
         print(json.dumps({"box_calibration": {k: v for k, v in bench.box_calibration(dev).items() if k != "what"}}), flush=True)
     orders = {"ab": [(a.a, a.b)], "ba": [(a.b, a.a)], "both": [(a.a, a.b), (a.b, a.a)]}[a.build_order]
     for B, order in [(B, order) for B in a.sizes for order in orders]:
-        runs = {v: make(v, B, dev) for v in order}
+        runs = {v: make(v, B, dev, use_graph=not a.eager) for v in order}
         extra = {}
         if a.count_calls:
             extra.update({f"{v}_entry_point_calls_per_step": count_calls(*runs[v]) for v in order})
@@ -126,7 +140,8 @@ def main():
             issue[v] = launcher(upd, batch, U) if a.launch_steps else (lambda upd=upd, batch=batch: upd.step(batch))
             for _ in range(a.warmup):
                 issue[v]()
-            assert (upd._epoch if a.launch_steps else upd._program) is not None, "the step was not recorded"
+            # (an updater whose mode says "eager" -- asked for with --eager, or the stock-torch transformer actor -- records nothing)
+            assert not upd.mode.startswith("graph") or (upd._epoch if a.launch_steps else upd._program) is not None, "the step was not recorded"
         torch.cuda.synchronize()
         times = {v: [] for v in order}
         for r in range(a.blocks):
@@ -149,6 +164,7 @@ def main():
             extra["outlines_equal"] = runs[a.a][0].program_outline() == runs[a.b][0].program_outline()
         med = {v: statistics.median(t) for v, t in times.items()}
         print(json.dumps({"frames": B, "built_first": order[0], "steps_per_block": a.steps * U, "steps_per_launch": U, "blocks": a.blocks,
+                          **{f"{v}_mode": runs[v][0].mode.split(" ")[0] for v in order},
                           **{f"{v}_ms_per_step": round(med[v], 4) for v in med},
                           **{f"{v}_min_max_ms": [round(min(t), 4), round(max(t), 4)] for v, t in times.items()},
                           f"{a.b}_over_{a.a}": round(med[a.b] / med[a.a], 4),
