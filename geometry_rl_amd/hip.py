@@ -1,7 +1,7 @@
-"""ctypes binding of the C-ABI kernel library ``libgrl_hip.so`` (declared in include/grl_hip.h).
+"""ctypes binding of the C-ABI kernel libraries (``LIBRARIES``: libgrl_hip.so, declared in include/grl_hip.h, and the two satellites).
 
-There is NO fallback: if the shared library is missing or a symbol cannot be resolved the import of this module (and
-therefore every op of the package) raises.  Tensors are passed as raw device pointers + the current HIP stream.
+There is NO fallback: if a shared library is missing or a symbol cannot be resolved the first call into it (and therefore every op of
+the package that needs it) raises.  Tensors are passed as raw device pointers + the current HIP stream.
 """
 import ctypes
 import os
@@ -17,18 +17,11 @@ LIB_PATH = os.environ.get("GRL_LIB", os.path.join(_HERE, "libgrl_hip.so"))  # GR
 ABI_VERSION = 216   # include/grl_hip.h GRL_HIP_VERSION
 SOURCES = ["edge_conv.hip", "edge_conv16.hip", "node_ops.hip", "node_mlp.hip", "node_mlp16.hip", "head_ops.hip",
            "critic_ops.hip", "train_ops.hip", "weight_images.hip", "calib.hip", "oneshot.hip", "stats_ops.hip"]
-# The EMPN key / query attention kernels are a library of their own, libgrl_attention.so, declared in csrc/grl_attention.h: the export
-# list of libgrl_hip.so is exactly include/grl_hip.h, which they leave as it is.  Same flags, same binder (attention_call / attention_query).
-ATTENTION_SOURCES = ["attention_ops.hip"]
-ATTENTION_HEADER = "grl_attention.h"
-ATTENTION_LIB_PATH = os.path.join(_HERE, "libgrl_attention.so")
-# The transformer baseline actor's kernels (encoder forward / backward, post_fc head) likewise: libgrl_transformer.so, declared in
-# csrc/grl_transformer.h, bound by transformer_call / transformer_query (ABI 216 of include/grl_hip.h names the addition).
-TRANSFORMER_SOURCES = ["transformer_ops.hip"]
-TRANSFORMER_HEADER = "grl_transformer.h"
-TRANSFORMER_LIB_PATH = os.path.join(_HERE, "libgrl_transformer.so")
 # (source, extra flags, object suffix): the two MFMA files are compiled a second time as the plain-bf16 variant (one MFMA per
 # product instead of three; csrc/grl_common.h GRL_PREC) whose entry points carry the suffix _bf16
+VARIANTS = [("edge_conv.hip", ["-DGRL_PREC=1"], ".bf16"), ("edge_conv16.hip", ["-DGRL_PREC=1"], ".bf16"),
+            ("node_mlp.hip", ["-DGRL_PREC=1"], ".bf16"), ("node_mlp16.hip", ["-DGRL_PREC=1"], ".bf16"),
+            ("node_ops.hip", ["-DGRL_PREC=1"], ".bf16"), ("weight_images.hip", ["-DGRL_PREC=1"], ".bf16")]
 # per-source compiler flags.  edge_conv16.hip: its 512-register backward kernel keeps the chain's MFMA results in VGPRs (the default
 # selection would put every MFMA result of such a kernel into AGPRs) and pins the weight-gradient tiles to AGPRs itself (asm)
 # node_mlp16.hip additionally without SLP vectorisation: beside the MFMAs of its one wave per SIMD plain f32 instructions overlap with the matrix
@@ -38,9 +31,48 @@ FILE_FLAGS = {"edge_conv16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-
               # the ConvNeXt forward: plain-f32 GELU as well (0.313 vs 0.330 ms per step; the 16-row edge forward, three waves per SIMD, is
               # FASTER with its packed GELU: 0.48 vs 0.52 ms -- docs/history/profiles/r03_ab_forward_gelu_ld1.txt)
               "node_mlp.hip": ["-fno-slp-vectorize", "-DGRL_GELU4_SCALAR=1"]}
-VARIANTS = [("edge_conv.hip", ["-DGRL_PREC=1"], ".bf16"), ("edge_conv16.hip", ["-DGRL_PREC=1"], ".bf16"),
-            ("node_mlp.hip", ["-DGRL_PREC=1"], ".bf16"), ("node_mlp16.hip", ["-DGRL_PREC=1"], ".bf16"),
-            ("node_ops.hip", ["-DGRL_PREC=1"], ".bf16"), ("weight_images.hip", ["-DGRL_PREC=1"], ".bf16")]
+
+
+class Library:
+    """One kernel library: its file beside this module, the header that declares its entry points (= its export list; relative to this
+    package), its plain sources and its variant jobs under csrc/.  Loaded and bound on first use (``load``), never at import."""
+
+    def __init__(self, name, file, header, sources, variants=(), path=None):
+        self.name, self.file, self.header, self.sources, self.variants = name, file, header, list(sources), list(variants)
+        self.path = path or os.path.join(_HERE, file)   # the file ``load`` opens
+        self.cdll = self.entries = None
+
+    def paths(self, root=None):
+        """(library file, header) of this checkout, or of the checkout of this repository at ``root``."""
+        pkg = os.path.join(root, "geometry_rl_amd") if root else _HERE
+        return os.path.join(pkg, self.file) if root else self.path, os.path.normpath(os.path.join(pkg, self.header))
+
+    def load(self) -> dict:
+        """{name: bound entry point} of the library, opened on first use.  No fallback: a missing or stale library raises."""
+        if self.entries is None:
+            if not os.path.exists(self.path):
+                raise RuntimeError(
+                    f"{self.path} is missing: the HIP extension must be built (python -c 'import __graft_entry__ as g; g.build()'). "
+                    "geometry_rl_amd has no CPU or PyTorch fallback path.")
+            # the binary must be the one THESE sources build (an explicitly named debugging library -- GRL_LIB, tools/r0*_ab_libs.sh -- is the
+            # caller's business; GRL_ALLOW_STALE_LIB=1 switches the check off for bisecting)
+            if "GRL_LIB" not in os.environ and os.environ.get("GRL_ALLOW_STALE_LIB", "0") == "0":
+                check_library(self.path)
+            cdll = ctypes.CDLL(self.path)
+            entries = bind(_read(self.paths()[1]).decode(), cdll)
+            if "grl_version" in entries and cdll.grl_version() != ABI_VERSION:   # (the satellites carry no version entry)
+                raise RuntimeError(f"{self.path} reports ABI version {cdll.grl_version()}, this package binds version {ABI_VERSION} "
+                                   "(include/grl_hip.h GRL_HIP_VERSION): rebuild the extension (__graft_entry__.build())")
+            self.cdll, self.entries = cdll, entries
+        return self.entries
+
+
+# The EMPN key / query attention kernels and the transformer baseline actor's kernels (encoder forward / backward, post_fc head) are
+# libraries of their own: the export list of libgrl_hip.so is exactly include/grl_hip.h, which they leave as it is (ABI 216 names the
+# additions).  Same flags, same binder, same ``call`` / ``query``: a name's library is the one whose header declares it.
+MAIN = Library("main", "libgrl_hip.so", "../include/grl_hip.h", SOURCES, VARIANTS, path=LIB_PATH)
+LIBRARIES = [MAIN, Library("attention", "libgrl_attention.so", "csrc/grl_attention.h", ["attention_ops.hip"]),
+             Library("transformer", "libgrl_transformer.so", "csrc/grl_transformer.h", ["transformer_ops.hip"])]
 
 
 BUILD_INFO = os.path.join(os.path.dirname(_HERE), "BUILD_INFO.json")
@@ -64,23 +96,23 @@ def _read(path) -> bytes:
 
 
 def _pkg_paths(root=None):
-    """(csrc directory, include/grl_hip.h, isa_lint.py) of the package tree at ``root`` (default: this checkout)."""
+    """(csrc directory, isa_lint.py) of the package tree at ``root`` (default: this checkout)."""
     pkg = os.path.join(root, "geometry_rl_amd") if root else _HERE
-    return os.path.join(pkg, "csrc"), os.path.join(os.path.dirname(pkg), "include", "grl_hip.h"), os.path.join(pkg, "isa_lint.py")
+    return os.path.join(pkg, "csrc"), os.path.join(pkg, "isa_lint.py")
 
 
 def source_hash(root=None) -> str:
-    """16 hex digits over EVERYTHING libgrl_hip.so is made from: every .hip / .h under csrc/, include/grl_hip.h (the export list), the
-    ISA lint's rules and the flag tables of this module.  ``hip.build()`` embeds it in the library (``grl_source_hash``), ``hip.lib()``
-    recomputes it from the tree and refuses a library that was built from other sources -- modification times play no part (a tree copied
-    to another box has arbitrary ones: VERDICT r5)."""
+    """16 hex digits over EVERYTHING the libraries are made from: every .hip / .h under csrc/, include/grl_hip.h (the export list), the
+    ISA lint's rules and the flag and library tables of this module.  ``hip.build()`` embeds it in every library (``grl_source_hash``),
+    ``Library.load`` recomputes it from the tree and refuses a library that was built from other sources -- modification times play no
+    part (a tree copied to another box has arbitrary ones: VERDICT r5)."""
     import json
-    csrc, header, lint = _pkg_paths(root)
+    csrc, lint = _pkg_paths(root)
     names = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
-    parts = [json.dumps([BASE_FLAGS, SOURCES, FILE_FLAGS, VARIANTS, ATTENTION_SOURCES, TRANSFORMER_SOURCES], sort_keys=True)]
+    parts = [json.dumps([BASE_FLAGS, FILE_FLAGS, [[l.name, l.file, l.header, l.sources, l.variants] for l in LIBRARIES]], sort_keys=True)]
     for n in names:
         parts += [n, _read(os.path.join(csrc, n))]
-    parts += ["grl_hip.h", _read(header), "isa_lint.py", _read(lint)]
+    parts += ["grl_hip.h", _read(MAIN.paths(root)[1]), "isa_lint.py", _read(lint)]
     return _sha(*parts)[:16]
 
 
@@ -104,56 +136,55 @@ def check_library(path=None, root=None) -> str:
 
 
 def build(verbose: bool = True, force: bool = False, root=None) -> str:
-    """Compile every HIP source for gfx950 and link libgrl_hip.so in-tree (hipcc cross-compiles without a GPU).  What is rebuilt is decided
-    by CONTENT: an object is kept when the hash recorded beside it (its source, every header, its flags, the lint rules) still matches, the
-    library when its embedded ``grl_source_hash`` equals ``source_hash()`` of the tree.  Writes BUILD_INFO.json at the repository root
-    ("prebuilt" = nothing compiled).  ``root``: build another checkout of this repository (tests)."""
+    """Compile every HIP source for gfx950 and link the libraries of ``LIBRARIES`` in-tree (hipcc cross-compiles without a GPU).  What is
+    rebuilt is decided by CONTENT: an object is kept when the hash recorded beside it (its source, every header, its flags, the lint rules)
+    still matches, the libraries when their embedded ``grl_source_hash`` equals ``source_hash()`` of the tree.  Writes BUILD_INFO.json at
+    the repository root ("prebuilt" = nothing compiled); -> the main library's path.  ``root``: build another checkout of this repository
+    (tests)."""
     import json
     import time
-    csrc, header, lint_py = _pkg_paths(root)
-    lib_path = os.path.join(os.path.dirname(csrc), "libgrl_hip.so") if root else LIB_PATH
-    att_path = os.path.join(os.path.dirname(csrc), "libgrl_attention.so") if root else ATTENTION_LIB_PATH
-    tf_path = os.path.join(os.path.dirname(csrc), "libgrl_transformer.so") if root else TRANSFORMER_LIB_PATH
-    info_path = os.path.join(root, "BUILD_INFO.json") if root else BUILD_INFO
-    srcs = [os.path.join(csrc, s) for s in SOURCES if os.path.exists(os.path.join(csrc, s))]
-    att_srcs = [os.path.join(csrc, s) for s in ATTENTION_SOURCES]
-    tf_srcs = [os.path.join(csrc, s) for s in TRANSFORMER_SOURCES]
+    csrc, lint_py = _pkg_paths(root)
+    lib_paths = {l.name: l.paths(root)[0] for l in LIBRARIES}
+    lib_path = lib_paths[MAIN.name]
+    top = os.path.dirname(os.path.dirname(csrc))
+    jobs = [(l, s, fl, sfx) for l in LIBRARIES for s, fl, sfx in [(s, [], "") for s in l.sources] + l.variants]
     tree_hash = source_hash(root)
 
     def info(mode, rebuilt, lint=None):
+        size = lambda p: os.path.getsize(p) if os.path.exists(p) else None
         try:
-            with open(info_path, "w") as f:
-                json.dump({"build_mode": mode, "objects_rebuilt": rebuilt, "isa_lint": lint, "objects_total": len(srcs) + len(VARIANTS) + len(att_srcs) + len(tf_srcs) + 1,
-                           "library": os.path.relpath(lib_path, os.path.dirname(os.path.dirname(csrc))),
-                           "library_bytes": os.path.getsize(lib_path) if os.path.exists(lib_path) else None, "abi_version": ABI_VERSION,
+            with open(os.path.join(top, "BUILD_INFO.json") if root else BUILD_INFO, "w") as f:
+                json.dump({"build_mode": mode, "objects_rebuilt": rebuilt, "isa_lint": lint, "objects_total": len(jobs) + 1,
+                           "library": os.path.relpath(lib_path, top), "library_bytes": size(lib_path), "abi_version": ABI_VERSION,
                            "source_hash": tree_hash, "library_source_hash": embedded_hash(lib_path),
+                           "libraries": {n: {"path": os.path.relpath(p, top), "bytes": size(p), "source_hash": embedded_hash(p)}
+                                         for n, p in lib_paths.items()},
                            "forced": bool(force), "time": time.strftime("%Y-%m-%dT%H:%M:%S")}, f, indent=1)
         except OSError:
             pass
-    if not force and embedded_hash(lib_path) == tree_hash and embedded_hash(att_path) == tree_hash and embedded_hash(tf_path) == tree_hash:
+    if not force and all(embedded_hash(p) == tree_hash for p in lib_paths.values()):
         info("prebuilt (the libraries' embedded source hash equals the tree's: nothing compiled)", [])
         return lib_path
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     from . import isa_lint
     header_bytes = [_read(os.path.join(csrc, h)) for h in sorted(f for f in os.listdir(csrc) if f.endswith(".h"))]   # every header feeds every object
     lint_bytes = _read(lint_py)
-    objs, att_objs, tf_objs = [], [], []
+    objs = {l.name: [] for l in LIBRARIES}
     procs = []
     rebuilt = []
     lint_jobs = []   # (label, assembly file, object, its hash file, its hash) of every object compiled NOW from a source with asm MFMAs
     pending = []     # (hash file, hash) of the other objects compiled now: recorded once hipcc has succeeded
     bdir = os.path.join(csrc, "build")
     os.makedirs(bdir, exist_ok=True)
-    jobs = [(s, [], "") for s in srcs] + [(os.path.join(csrc, s), fl, sfx) for s, fl, sfx in VARIANTS] + [(s, [], "") for s in att_srcs] + [(s, [], "") for s in tf_srcs]
-    for s, flags, sfx in jobs:
-        base = os.path.basename(s)
+    for library, base, flags, sfx in jobs:
+        s = os.path.join(csrc, base)
         lint = base in isa_lint.FILES
         # sources with asm MFMAs are compiled with -save-temps into a directory of their own: the assembly the REAL compile leaves behind
         # is what the ISA lint reads (ADVICE r4: a different hipcc or different flags must not get past the hazard check)
         odir = os.path.join(bdir, base + sfx + ".d") if lint else bdir
         os.makedirs(odir, exist_ok=True)
         o = os.path.join(odir, base + sfx + ".o")
-        (att_objs if s in att_srcs else tf_objs if s in tf_srcs else objs).append(o)
+        objs[library.name].append(o)
         cmd_flags = BASE_FLAGS + FILE_FLAGS.get(base, []) + flags + (["-save-temps=obj"] if lint else [])
         ohash = _sha(_read(s), *header_bytes, " ".join(cmd_flags), lint_bytes if lint else b"")
         hfile = o + ".srchash"
@@ -196,11 +227,6 @@ def build(verbose: bool = True, force: bool = False, root=None) -> str:
                 f.write(ohash)
     if lint_failed:
         raise RuntimeError("ISA lint failed (geometry_rl_amd/isa_lint.py): " + " | ".join(lint_failed))
-    # exports = exactly the entry points include/grl_hip.h declares (cross-file helpers such as grl_edge16_launch stay internal)
-    names = sorted(set(re.findall(EXPORT_RE, open(header).read())))
-    vs = os.path.join(bdir, "exports.map")
-    with open(vs, "w") as f:
-        f.write("{\n  global:\n" + "".join(f"    {n};\n" for n in names) + "  local: *;\n};\n")
     # the tree's source hash, embedded: grl_source_hash() hands it out, embedded_hash() finds it in the file's bytes
     hsrc = os.path.join(bdir, "source_hash.cpp")
     with open(hsrc, "w") as f:
@@ -212,39 +238,27 @@ def build(verbose: bool = True, force: bool = False, root=None) -> str:
                 '  if (cap > 0) buf[n] = 0;\n  return n;\n}\n' % len(HASH_TAG))
     hobj = os.path.join(bdir, "source_hash.o")
     subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-fPIC", "-c", hsrc, "-o", hobj])
-    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + vs, "-o", lib_path] + objs + [hobj]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.check_call(cmd)
-    if embedded_hash(lib_path) != tree_hash:
-        raise RuntimeError(f"{lib_path}: the embedded source hash did not survive the link")
-    # the attention library: its own objects, its own export list (csrc/grl_attention.h), the same embedded source hash
-    att_names = sorted(set(re.findall(EXPORT_RE, open(os.path.join(csrc, ATTENTION_HEADER)).read())))
-    avs = os.path.join(bdir, "exports_attention.map")
-    with open(avs, "w") as f:
-        f.write("{\n  global:\n" + "".join(f"    {n};\n" for n in att_names) + "  local: *;\n};\n")
-    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + avs, "-o", att_path] + att_objs + [hobj]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.check_call(cmd)
-    if embedded_hash(att_path) != tree_hash:
-        raise RuntimeError(f"{att_path}: the embedded source hash did not survive the link")
-    # ... and the transformer actor's library, the same way (csrc/grl_transformer.h)
-    tf_names = sorted(set(re.findall(EXPORT_RE, open(os.path.join(csrc, TRANSFORMER_HEADER)).read())))
-    tvs = os.path.join(bdir, "exports_transformer.map")
-    with open(tvs, "w") as f:
-        f.write("{\n  global:\n" + "".join(f"    {n};\n" for n in tf_names) + "  local: *;\n};\n")
-    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + tvs, "-o", tf_path] + tf_objs + [hobj]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.check_call(cmd)
-    if embedded_hash(tf_path) != tree_hash:
-        raise RuntimeError(f"{tf_path}: the embedded source hash did not survive the link")
-    info("compiled from source" if len(rebuilt) == len(objs) + len(att_objs) + len(tf_objs) else "incremental (objects whose recorded source hash still matched were kept)", rebuilt, lint_report)
+
+    def link(library):
+        """Its own objects and the shared source hash; exports = exactly the entry points its header declares (cross-file helpers such
+        as grl_edge16_launch stay internal)."""
+        out, header = library.paths(root)
+        vs = os.path.join(bdir, f"exports_{library.name}.map")
+        with open(vs, "w") as f:
+            f.write("{\n  global:\n" + "".join(f"    {n};\n" for n in sorted(set(re.findall(EXPORT_RE, open(header).read())))) + "  local: *;\n};\n")
+        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + vs, "-o", out] + objs[library.name] + [hobj]
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        subprocess.check_call(cmd)
+        if embedded_hash(out) != tree_hash:
+            raise RuntimeError(f"{out}: the embedded source hash did not survive the link")
+    for library in LIBRARIES:
+        link(library)
+    info("compiled from source" if len(rebuilt) == len(jobs) else "incremental (objects whose recorded source hash still matched were kept)", rebuilt, lint_report)
     return lib_path
 
 
-# ---- the typed boundary: every entry point's argument types come from include/grl_hip.h ------------------------------------------------
+# ---- the typed boundary: every entry point's argument types come from its library's header ------------------------------------------------
 SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "long long": ctypes.c_longlong, "float": ctypes.c_float,
            "double": ctypes.c_double, "hipStream_t": ctypes.c_void_p}
 _I4, _I8 = {torch.int32, torch.uint32}, {torch.int64, torch.uint64}
@@ -327,7 +341,7 @@ def invoke(entries: dict, name: str, args) -> int:
     """entries[name](*args), refusing an undeclared name, a wrong argument count and -- in the header's words -- a wrong argument."""
     fn = entries.get(name)
     if fn is None:
-        raise AttributeError(f"{name} is not declared in the header (include/grl_hip.h): no entry point is called untyped")
+        raise AttributeError(f"{name} is not declared in a header of the kernel libraries: no entry point is called untyped")
     if len(args) != len(fn.params):   # (ctypes itself lets surplus arguments through)
         raise TypeError(f"{name} takes {len(fn.params)} arguments ({', '.join(p[1] for p in fn.params)}), {len(args)} given")
     try:
@@ -337,63 +351,32 @@ def invoke(entries: dict, name: str, args) -> int:
         raise (ValueError if ": ValueError: " in str(e) else TypeError)(f"{name}: '{pname}' ({decl}), {e}") from None
 
 
-_lib = _bound = None
+def entry_index(headers) -> dict:
+    """{entry name: owner} over (owner, header text) pairs; a name that two headers declare raises."""
+    index = {}
+    for owner, text in headers:
+        for name in parse_header(text):
+            if name in index:
+                raise ValueError(f"{name} is declared by two headers: an entry point has one library")
+            index[name] = owner
+    return index
+
+
+_index = None   # {entry name: its Library}, from the headers' text on first use (no library is loaded for it)
+
+
+def query(name: str, *args) -> int:
+    """Call entry point ``name`` of the library whose header declares it, as it stands: a pure host-side query takes no stream argument."""
+    global _index
+    if _index is None:
+        _index = entry_index((l, _read(l.paths()[1]).decode()) for l in LIBRARIES)
+    library = _index.get(name)
+    return invoke(library.load() if library else {}, name, args)
 
 
 def lib() -> ctypes.CDLL:
-    global _lib, _bound
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                f"{LIB_PATH} is missing: the HIP extension must be built (python -c 'import __graft_entry__ as g; g.build()'). "
-                "geometry_rl_amd has no CPU or PyTorch fallback path.")
-        cdll = ctypes.CDLL(LIB_PATH)
-        # the binary must be the one THESE sources build (an explicitly named debugging library -- GRL_LIB, tools/r0*_ab_libs.sh -- is the
-        # caller's business; GRL_ALLOW_STALE_LIB=1 switches the check off for bisecting)
-        if "GRL_LIB" not in os.environ and os.environ.get("GRL_ALLOW_STALE_LIB", "0") == "0":
-            check_library(LIB_PATH)
-        bound = bind(_read(_pkg_paths()[1]).decode(), cdll)
-        if cdll.grl_version() != ABI_VERSION:
-            raise RuntimeError(f"{LIB_PATH} reports ABI version {cdll.grl_version()}, this package binds version {ABI_VERSION} "
-                               "(include/grl_hip.h GRL_HIP_VERSION): rebuild the extension (__graft_entry__.build())")
-        _lib, _bound = cdll, bound
-    return _lib
-
-
-_att_bound = None
-
-
-def attention_lib() -> dict:
-    """The bound entry points of libgrl_attention.so (csrc/grl_attention.h), loaded on first use.  No fallback: a missing or stale
-    library raises."""
-    global _att_bound
-    if _att_bound is None:
-        if not os.path.exists(ATTENTION_LIB_PATH):
-            raise RuntimeError(
-                f"{ATTENTION_LIB_PATH} is missing: the HIP extension must be built (python -c 'import __graft_entry__ as g; g.build()'). "
-                "geometry_rl_amd has no CPU or PyTorch fallback path.")
-        if "GRL_LIB" not in os.environ and os.environ.get("GRL_ALLOW_STALE_LIB", "0") == "0":
-            check_library(ATTENTION_LIB_PATH)
-        _att_bound = bind(_read(os.path.join(CSRC, ATTENTION_HEADER)).decode(), ctypes.CDLL(ATTENTION_LIB_PATH))
-    return _att_bound
-
-
-_tf_bound = None
-
-
-def transformer_lib() -> dict:
-    """The bound entry points of libgrl_transformer.so (csrc/grl_transformer.h), loaded on first use.  No fallback: a missing or stale
-    library raises."""
-    global _tf_bound
-    if _tf_bound is None:
-        if not os.path.exists(TRANSFORMER_LIB_PATH):
-            raise RuntimeError(
-                f"{TRANSFORMER_LIB_PATH} is missing: the HIP extension must be built (python -c 'import __graft_entry__ as g; g.build()'). "
-                "geometry_rl_amd has no CPU or PyTorch fallback path.")
-        if "GRL_LIB" not in os.environ and os.environ.get("GRL_ALLOW_STALE_LIB", "0") == "0":
-            check_library(TRANSFORMER_LIB_PATH)
-        _tf_bound = bind(_read(os.path.join(CSRC, TRANSFORMER_HEADER)).decode(), ctypes.CDLL(TRANSFORMER_LIB_PATH))
-    return _tf_bound
+    MAIN.load()
+    return MAIN.cdll
 
 
 def stream_ptr() -> ctypes.c_void_p:
@@ -407,31 +390,8 @@ KERNEL_ROWS = {}   # name -> rows (edge x orientation / node x orientation) hand
 
 
 def call(name: str, *args, stream=None, rows: int = 0) -> None:
-    """Launch C-ABI entry point ``name`` on the current stream; raises on a refused argument (before the launch) and on a non-zero status."""
-    _launch(query, name, args, stream, rows)
-
-
-def attention_call(name: str, *args, stream=None, rows: int = 0) -> None:
-    """``call`` for an entry point of libgrl_attention.so (csrc/grl_attention.h)."""
-    _launch(attention_query, name, args, stream, rows)
-
-
-def transformer_call(name: str, *args, stream=None, rows: int = 0) -> None:
-    """``call`` for an entry point of libgrl_transformer.so (csrc/grl_transformer.h)."""
-    _launch(transformer_query, name, args, stream, rows)
-
-
-def transformer_query(name: str, *args) -> int:
-    """``query`` for an entry point of libgrl_transformer.so."""
-    return invoke(transformer_lib(), name, args)
-
-
-def attention_query(name: str, *args) -> int:
-    """``query`` for an entry point of libgrl_attention.so."""
-    return invoke(attention_lib(), name, args)
-
-
-def _launch(query, name, args, stream, rows) -> None:
+    """Launch C-ABI entry point ``name`` (of any library) on the current stream; raises on a refused argument (before the launch) and on a
+    non-zero status."""
     timing = KERNEL_TIMES is not None
     if timing:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -467,13 +427,6 @@ def kernel_prof_summary():
         n, t = out.get(buf.value.decode(), (0, 0.0))
         out[buf.value.decode()] = (n + 1, t + ms.value)
     return out
-
-
-def query(name: str, *args) -> int:
-    """Call a pure host-side query entry point (no stream argument)."""
-    if _bound is None:
-        lib()
-    return invoke(_bound, name, args)
 
 
 def check_f32(*tensors: torch.Tensor):

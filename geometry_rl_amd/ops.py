@@ -565,7 +565,7 @@ class KeyQueryProject(torch.autograd.Function):
         k = torch.empty(x.shape[0], 16, 128, device=x.device, dtype=torch.float32)   # every row is written by the kernel
         q = torch.empty(x.shape[0], 16, 128, device=x.device, dtype=torch.float32)
         args = [a.contiguous() for a in (wk, bk, wq, bq)]
-        hip.attention_call("grl_kq_project_fwd", x, *args, k, q, n_rows, rows=n_rows)
+        hip.call("grl_kq_project_fwd", x, *args, k, q, n_rows, rows=n_rows)
         ctx.save_for_backward(x, args[0], args[2])
         ctx.params = (wk, bk, wq, bq)
         return k, q
@@ -574,9 +574,9 @@ class KeyQueryProject(torch.autograd.Function):
     def backward(ctx, dk, dq):
         x, wk, wq = ctx.saved_tensors
         n_rows = x.shape[0] * 16
-        partial = torch.empty(hip.attention_query("grl_kq_bwd_blocks", n_rows), hip.attention_query("grl_kq_partial_size"), device=x.device, dtype=torch.float32)
+        partial = torch.empty(hip.query("grl_kq_bwd_blocks", n_rows), hip.query("grl_kq_partial_size"), device=x.device, dtype=torch.float32)
         dx = torch.empty_like(x)
-        hip.attention_call("grl_kq_project_bwd", x, wk, wq, dk.contiguous(), dq.contiguous(), dx, partial, n_rows, rows=n_rows)
+        hip.call("grl_kq_project_bwd", x, wk, wq, dk.contiguous(), dq.contiguous(), dx, partial, n_rows, rows=n_rows)
         pwk, pbk, pwq, pbq = ctx.params
         dwk, dwq, dbk, dbq = _emit_grads(partial, [(0, 8192, (128, 64), pwk), (8192, 8192, (128, 64), pwq), (16384, 128, (128,), pbk),
                                                    (16512, 128, (128,), pbq)])
@@ -603,11 +603,11 @@ class EdgeAttention(torch.autograd.Function):
         argmax = torch.empty(1, device=dev, dtype=torch.int32)
         x1 = torch.empty(edges.n_dst, 16, 64, device=dev, dtype=torch.float32)   # every row is written by the kernel
         if E > 0:
-            nb = hip.attention_query("grl_attention_blocks", E * 16)
+            nb = hip.query("grl_attention_blocks", E * 16)
             pmax = torch.empty(nb, device=dev, dtype=torch.float32)
             pidx = torch.empty(nb, device=dev, dtype=torch.int32)
-            hip.attention_call("grl_edge_logits_fwd", k, q, edges.src_d, edges.dst_d, E, logit, pmax, pidx, maxval, argmax, rows=E * 16)
-        hip.attention_call("grl_edge_attend_fwd", logit, maxval, msg, edges.rowptr_d, edges.n_dst, a, comp, x1, rows=E * 16)
+            hip.call("grl_edge_logits_fwd", k, q, edges.src_d, edges.dst_d, E, logit, pmax, pidx, maxval, argmax, rows=E * 16)
+        hip.call("grl_edge_attend_fwd", logit, maxval, msg, edges.rowptr_d, edges.n_dst, a, comp, x1, rows=E * 16)
         ctx.save_for_backward(k, q, msg, a, comp, argmax)
         ctx.edges = edges
         return x1
@@ -621,9 +621,9 @@ class EdgeAttention(torch.autograd.Function):
         dl = torch.empty(E, 16, device=dev, dtype=torch.float32)
         dk, dq = torch.empty_like(k), torch.empty_like(q)
         if E > 0:
-            pdm = torch.empty(hip.attention_query("grl_attention_blocks", e.n_dst * 16), device=dev, dtype=torch.float32)
-            hip.attention_call("grl_edge_attend_bwd", a, msg, comp, dx1.contiguous(), e.rowptr_d, e.n_dst, argmax, dmsg, dl, pdm, rows=E * 16)
-        hip.attention_call("grl_edge_logits_bwd", k, q, dl, e.rowptr_d, e.src_d, e.n_dst, e.rowptr_s, e.dst_s, e.s2d, e.n_src, dk, dq, rows=E * 16)
+            pdm = torch.empty(hip.query("grl_attention_blocks", e.n_dst * 16), device=dev, dtype=torch.float32)
+            hip.call("grl_edge_attend_bwd", a, msg, comp, dx1.contiguous(), e.rowptr_d, e.n_dst, argmax, dmsg, dl, pdm, rows=E * 16)
+        hip.call("grl_edge_logits_bwd", k, q, dl, e.rowptr_d, e.src_d, e.n_dst, e.rowptr_s, e.dst_s, e.s2d, e.n_src, dk, dq, rows=E * 16)
         return dk, dq, dmsg, None
 
 
@@ -829,7 +829,7 @@ class TransformerEncode(torch.autograd.Function):
         saved = torch.empty(15, B * n, 64, device=dev, dtype=torch.float32)    # every row is written by the kernel
         stats = torch.empty(2, B * n, 6, device=dev, dtype=torch.float32)
         hidden = torch.empty(B * G, 64, device=dev, dtype=torch.float32)
-        hip.transformer_call("grl_transformer_fwd", u, ps, saved, stats, hidden, B, n, d_in, m0, G, rows=B * n)
+        hip.call("grl_transformer_fwd", u, ps, saved, stats, hidden, B, n, d_in, m0, G, rows=B * n)
         ctx.save_for_backward(u, saved, stats, *ps)
         ctx.cfg = (B, n, d_in, m0, G)
         ctx.params = params
@@ -840,10 +840,10 @@ class TransformerEncode(torch.autograd.Function):
         u, saved, stats, *ps = ctx.saved_tensors
         B, n, d_in, m0, G = ctx.cfg
         dev = u.device
-        blocks = hip.transformer_query("grl_transformer_blocks", B, n)
-        partial = torch.empty(blocks, hip.transformer_query("grl_transformer_partial_size", d_in), device=dev, dtype=torch.float32)
-        ws = torch.empty(blocks, hip.transformer_query("grl_transformer_group_rows", B, n), hip.transformer_query("grl_transformer_ws_row"), device=dev, dtype=torch.float32)
-        hip.transformer_call("grl_transformer_bwd", u, ps, saved, stats, dhidden.contiguous(), ws, partial, B, n, d_in, m0, G, rows=B * n)
+        blocks = hip.query("grl_transformer_blocks", B, n)
+        partial = torch.empty(blocks, hip.query("grl_transformer_partial_size", d_in), device=dev, dtype=torch.float32)
+        ws = torch.empty(blocks, hip.query("grl_transformer_group_rows", B, n), hip.query("grl_transformer_ws_row"), device=dev, dtype=torch.float32)
+        hip.call("grl_transformer_bwd", u, ps, saved, stats, dhidden.contiguous(), ws, partial, B, n, d_in, m0, G, rows=B * n)
         p = ctx.params
         segs = []
         for l in range(2):
@@ -868,7 +868,7 @@ class PostFcHead(torch.autograd.Function):
         sigma = torch.empty(R, A, device=dev, dtype=torch.float32)
         pre = torch.empty(R, A, device=dev, dtype=torch.float32)
         args = [a.contiguous() for a in (wm, bm, ws, bs)]
-        hip.transformer_call("grl_postfc_head_fwd", hidden, *args, shift, min_std, mean, sigma, pre, R, A, rows=R)
+        hip.call("grl_postfc_head_fwd", hidden, *args, shift, min_std, mean, sigma, pre, R, A, rows=R)
         ctx.save_for_backward(hidden, args[0], args[2], pre)
         ctx.cfg = (float(shift), A)
         ctx.params = (wm, bm, ws, bs)
@@ -879,10 +879,10 @@ class PostFcHead(torch.autograd.Function):
         hidden, wm, ws, pre = ctx.saved_tensors
         shift, A = ctx.cfg
         R, dev = hidden.shape[0], hidden.device
-        partial = torch.empty(hip.transformer_query("grl_postfc_head_blocks", R), hip.transformer_query("grl_postfc_head_partial_size"), device=dev,
+        partial = torch.empty(hip.query("grl_postfc_head_blocks", R), hip.query("grl_postfc_head_partial_size"), device=dev,
                               dtype=torch.float32)
         dhidden = torch.empty_like(hidden)
-        hip.transformer_call("grl_postfc_head_bwd", hidden, wm, ws, pre, shift, dmean.contiguous(), dsigma.contiguous(), dhidden, partial, R, A, rows=R)
+        hip.call("grl_postfc_head_bwd", hidden, wm, ws, pre, shift, dmean.contiguous(), dsigma.contiguous(), dhidden, partial, R, A, rows=R)
         pwm, pbm, pws, pbs = ctx.params
         dwm, dbm, dws, dbs = _emit_grads(partial, [(0, A * 64, (A, 64), pwm), (2048, A, (A,), pbm), (1024, A * 64, (A, 64), pws),
                                                    (2064, A, (A,), pbs)])

@@ -53,8 +53,8 @@ def test_no_oracle_import_in_product():
 
 def test_product_fails_loudly_without_extension(monkeypatch, tmp_path):
     from geometry_rl_amd import hip
-    monkeypatch.setattr(hip, "LIB_PATH", str(tmp_path / "missing.so"))
-    monkeypatch.setattr(hip, "_lib", None)
+    monkeypatch.setattr(hip.MAIN, "path", str(tmp_path / "missing.so"))
+    monkeypatch.setattr(hip.MAIN, "entries", None)
     with pytest.raises(RuntimeError, match="no CPU or PyTorch fallback"):
         hip.lib()
 

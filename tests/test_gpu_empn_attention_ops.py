@@ -158,16 +158,16 @@ def test_logits_maximum_and_weights_by_direct_call(case):
     es = _edge_set(case)
     E, n_dst = es.n_edges, case.n_dst
     k, q, msg = case.k.to(d), case.q.to(d), case.msg.to(d)
-    nb = hip.attention_query("grl_attention_blocks", E * 16)
+    nb = hip.query("grl_attention_blocks", E * 16)
     assert nb == min((E * 16 + 3) // 4, 2048)
     nan = float("nan")
     logit, maxval = torch.full((E, 16), nan, device=d), torch.full((1,), nan, device=d)
     pmax, pidx = torch.full((nb,), nan, device=d), torch.full((nb,), -1, device=d, dtype=torch.int32)
     argmax = torch.full((1,), -1, device=d, dtype=torch.int32)
-    hip.attention_call("grl_edge_logits_fwd", k, q, es.src_d, es.dst_d, E, logit, pmax, pidx, maxval, argmax)
+    hip.call("grl_edge_logits_fwd", k, q, es.src_d, es.dst_d, E, logit, pmax, pidx, maxval, argmax)
     a, comp = torch.full((E, 16), nan, device=d), torch.full((n_dst, 16), nan, device=d)
     x1 = torch.full((n_dst, 16, 64), nan, device=d)
-    hip.attention_call("grl_edge_attend_fwd", logit, maxval, msg, es.rowptr_d, n_dst, a, comp, x1)
+    hip.call("grl_edge_attend_fwd", logit, maxval, msg, es.rowptr_d, n_dst, a, comp, x1)
     torch.cuda.synchronize()
     for name, t in (("logit", logit), ("pmax", pmax), ("maxval", maxval), ("a", a), ("comp", comp), ("x1", x1)):
         assert not bool(torch.isnan(t).any()), f"{name}: an element nobody wrote"
@@ -200,16 +200,16 @@ def test_projection_by_direct_call(case):
     import footprint as fp
     from geometry_rl_amd import hip
     d, n = dev(), case.rows
-    blocks, psize = hip.attention_query("grl_kq_bwd_blocks", n), hip.attention_query("grl_kq_partial_size")
+    blocks, psize = hip.query("grl_kq_bwd_blocks", n), hip.query("grl_kq_partial_size")
     assert blocks == ar.kq_bwd_blocks(n) and psize == 2 * 128 * 64 + 2 * 128
     x, ws, Rk, Rq = case.x.to(d), [t.to(d) for t in case.w], case.Rk.to(d), case.Rq.to(d)
 
     def run(w):
         gx, (wk, bk, wq, bq) = w(x), [w(t) for t in ws]
         k, q = w.out((n, 128), torch.float32, d), w.out((n, 128), torch.float32, d)
-        hip.attention_call("grl_kq_project_fwd", gx, wk, bk, wq, bq, k, q, n)
+        hip.call("grl_kq_project_fwd", gx, wk, bk, wq, bq, k, q, n)
         dx, partial = w.out((n, 64), torch.float32, d), w.out((blocks, psize), torch.float32, d)
-        hip.attention_call("grl_kq_project_bwd", gx, wk, wq, w(Rk), w(Rq), dx, partial, n)
+        hip.call("grl_kq_project_bwd", gx, wk, wq, w(Rk), w(Rq), dx, partial, n)
         return {"k": k, "q": q, "dx": dx, "partial": partial}
 
     res = fp.three_runs("kq_project direct", f"{n} rows", run, direct=True)
@@ -230,12 +230,12 @@ def test_calls_that_launch_nothing():
     d = dev()
     f = lambda *s: torch.zeros(*s, device=d)
     i = lambda *s: torch.zeros(*s, device=d, dtype=torch.int32)
-    status = lambda name, *args: hip.attention_query(name, *args, hip.stream_ptr())
+    status = lambda name, *args: hip.query(name, *args, hip.stream_ptr())
     before = [f(1, 16), f(1), i(1), f(1), i(1)]
     assert status("grl_edge_logits_fwd", f(2, 16, 128), f(2, 16, 128), i(1), i(1), 0, *before) == -2
     assert status("grl_edge_attend_bwd", f(1, 16), f(1, 16, 64), f(1, 16), f(1, 16, 64), i(2), 0, i(1), f(1, 16, 64), f(1, 16), f(1)) == -2
-    psize = hip.attention_query("grl_kq_partial_size")
-    assert hip.attention_query("grl_kq_bwd_blocks", 0) == 1
+    psize = hip.query("grl_kq_partial_size")
+    assert hip.query("grl_kq_bwd_blocks", 0) == 1
     partial = torch.full((1, psize), float("nan"), device=d)
     dx = torch.full((1, 64), float("nan"), device=d)
     assert status("grl_kq_project_bwd", f(1, 64), f(128, 64), f(128, 64), f(1, 128), f(1, 128), dx, partial, 0) == 0

@@ -76,9 +76,8 @@ def test_one_eager_update(monkeypatch):
         return {"gradient": upd.gflat.clone(), "parameters": upd.flat.clone(), "loc": out["loc"], "state_value": out["state_value"]}
 
     launched = []
-    real_call, real_att = hip.call, hip.attention_call
+    real_call = hip.call
     monkeypatch.setattr(hip, "call", lambda entry, *a, **k: (launched.append(entry), real_call(entry, *a, **k))[1])
-    monkeypatch.setattr(hip, "attention_call", lambda entry, *a, **k: (launched.append(entry), real_att(entry, *a, **k))[1])
     plain = fp.three_runs("eager update", "empn attention", run)
     assert bool(plain["gradient"].abs().max() > 0)
     names = set(launched)

@@ -75,19 +75,39 @@ def test_too_many_tokens_are_refused_before_any_launch(monkeypatch):
     ps = [p.to(dev) for p in c.params]
     u = torch.zeros(1, 257, 13, device=dev)
     saved, stats, hidden = torch.zeros(15, 257, 64, device=dev), torch.zeros(2, 257, 6, device=dev), torch.full((1, 64), 7.0, device=dev)
-    assert hip.transformer_query("grl_transformer_fwd", u, ps, saved, stats, hidden, 1, 257, 13, 0, 1, hip.stream_ptr()) == -2
-    assert hip.transformer_query("grl_transformer_fwd", u, ps, saved, stats, hidden, 1, 0, 13, 0, 1, hip.stream_ptr()) == -2
-    assert hip.transformer_query("grl_transformer_fwd", u, ps, saved, stats, hidden, 1, 200, 13, 199, 2, hip.stream_ptr()) == -2   # slice past the end
-    assert hip.transformer_query("grl_transformer_fwd", u, ps, saved, stats, hidden, 1, 200, 65, 0, 1, hip.stream_ptr()) == -2
+    assert hip.query("grl_transformer_fwd", u, ps, saved, stats, hidden, 1, 257, 13, 0, 1, hip.stream_ptr()) == -2
+    assert hip.query("grl_transformer_fwd", u, ps, saved, stats, hidden, 1, 0, 13, 0, 1, hip.stream_ptr()) == -2
+    assert hip.query("grl_transformer_fwd", u, ps, saved, stats, hidden, 1, 200, 13, 199, 2, hip.stream_ptr()) == -2   # slice past the end
+    assert hip.query("grl_transformer_fwd", u, ps, saved, stats, hidden, 1, 200, 65, 0, 1, hip.stream_ptr()) == -2
     torch.cuda.synchronize()
     assert float(hidden.min()) == 7.0 and float(saved.abs().max()) == 0.0   # nothing ran
     launched = []
-    real, real_tf = hip.call, hip.transformer_call
+    real = hip.call
     monkeypatch.setattr(hip, "call", lambda entry, *a, **k: (launched.append(entry), real(entry, *a, **k))[1])
-    monkeypatch.setattr(hip, "transformer_call", lambda entry, *a, **k: (launched.append(entry), real_tf(entry, *a, **k))[1])
     with pytest.raises(NotImplementedError):
         ops.TransformerEncode.apply(u, 0, 1, *ps)
     assert launched == []
+
+
+def test_the_one_launch_path_times_every_library():
+    """``hip.KERNEL_TIMES`` (bench.py's roofline leg) sees a launch of each kernel library, once each: grl_stats_accumulate of the main
+    library at n = 1, grl_kq_project_fwd of the attention library at 65 rows (the smallest count whose backward spans two blocks) and
+    grl_postfc_head_fwd of the transformer library at one row."""
+    from geometry_rl_amd import hip
+    dev = torch.device("cuda:0")
+    f = lambda *s: torch.zeros(*s, device=dev)
+    assert hip.query("grl_kq_bwd_blocks", 65) == 2
+    saved = hip.KERNEL_TIMES
+    hip.KERNEL_TIMES = {}
+    try:
+        hip.call("grl_stats_accumulate", f(1), 1, torch.zeros(2, device=dev, dtype=torch.float64))
+        hip.call("grl_kq_project_fwd", f(65, 64), f(128, 64), f(128), f(128, 64), f(128), f(65, 128), f(65, 128), 65, rows=65)
+        hip.call("grl_postfc_head_fwd", f(1, 64), f(1, 64), f(1), f(1, 64), f(1), 0.5, 1e-5, f(1, 1), f(1, 1), f(1, 1), 1, 1, rows=1)
+        summary = hip.kernel_time_summary()
+    finally:
+        hip.KERNEL_TIMES = saved
+    assert sorted(summary) == ["grl_kq_project_fwd", "grl_postfc_head_fwd", "grl_stats_accumulate"]
+    assert all(n == 1 and ms >= 0.0 for n, ms in summary.values()), summary
 
 
 @pytest.mark.parametrize("R,A,contextual", [(1, 1, True), (5, 6, True), (259, 16, True), (70, 6, False)])

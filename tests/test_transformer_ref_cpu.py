@@ -1,7 +1,6 @@
 """tests/transformer_ref.py against torch and the reference fixture, its checker against seeded mistakes, and the CPU-visible side of
-``TransformerVanilla(kernels="hip")``: parameter holders, refusals, the declared entry points (no GPU)."""
+``TransformerVanilla(kernels="hip")``: parameter holders and refusals (no GPU; the kernels' library: tests/test_kernel_libraries_cpu.py)."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -115,44 +114,3 @@ def test_agent_config_refusals():
             agent.build_agent(spec, agent.AgentConfig(model=model, transformer_kernels="hip"), device="cpu")
     with pytest.raises(NotImplementedError, match=ref):   # 1 + 300 tokens per sample
         agent.build_agent(graph.rigid_spec(P=300), agent.AgentConfig(model="transformer", transformer_kernels="hip"), device="cpu")
-
-
-NAMES = ["grl_postfc_head_blocks", "grl_postfc_head_bwd", "grl_postfc_head_fwd", "grl_postfc_head_partial_size", "grl_transformer_blocks",
-         "grl_transformer_bwd", "grl_transformer_fwd", "grl_transformer_group_rows", "grl_transformer_partial_size", "grl_transformer_ws_row"]
-
-
-def test_header_declares_the_new_entry_points_and_their_library_exports_exactly_them():
-    """The kernels are a library of their own, libgrl_transformer.so, declared in geometry_rl_amd/csrc/grl_transformer.h (as the EMPN
-    attention kernels are): include/grl_hip.h keeps its declarations and libgrl_hip.so its export list, ABI 216 names the addition."""
-    import ctypes
-    import subprocess
-    from geometry_rl_amd import hip
-    from test_abi_and_host import declared_symbols
-    hip.build(verbose=False)
-    decls = hip.parse_header(open(os.path.join(hip.CSRC, hip.TRANSFORMER_HEADER)).read())
-    assert sorted(decls) == NAMES
-    for name, params in decls.items():   # launches end in the stream, the size queries take none
-        assert (params[-1:] or [("",)])[-1][0] == ("hipStream_t" if name.endswith(("_fwd", "_bwd")) else "int" if params else "")
-    nm = lambda path: sorted(l.split()[-1] for l in subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True,
-                                                                    check=True).stdout.splitlines() if l.strip())
-    assert nm(hip.TRANSFORMER_LIB_PATH) == NAMES
-    assert hip.embedded_hash(hip.TRANSFORMER_LIB_PATH) == hip.source_hash() == hip.embedded_hash(hip.LIB_PATH)
-    assert not set(NAMES) & set(nm(hip.LIB_PATH)) and not set(NAMES) & set(declared_symbols())
-    text = open(os.path.join(ROOT, "include", "grl_hip.h")).read()
-    assert hip.ABI_VERSION == 216 and int(re.search(r"#define GRL_HIP_VERSION (\d+)", text).group(1)) == 216
-    assert hip.TRANSFORMER_SOURCES == ["transformer_ops.hip"] and "transformer_ops.hip" not in hip.SOURCES + hip.ATTENTION_SOURCES
-    lib = ctypes.CDLL(hip.TRANSFORMER_LIB_PATH)   # host-only queries are callable without a GPU
-    assert lib.grl_transformer_partial_size(15) == 54656 + 64 * 15 and lib.grl_transformer_partial_size(65) == -2
-    assert lib.grl_transformer_ws_row() == 320 and lib.grl_postfc_head_partial_size() == 2080
-    # one sample per group until the batch exceeds the 256 workgroups, then as many as keep a group within 256 rows
-    assert [lib.grl_transformer_group_rows(B, 33) for B in (1, 256, 257, 4096)] == [33, 33, 66, 231]
-    assert [lib.grl_transformer_blocks(B, 33) for B in (1, 256, 257, 4096)] == [1, 256, 129, 256]
-    assert lib.grl_transformer_blocks(4, 257) == -2 and lib.grl_postfc_head_blocks(0) == 1 and lib.grl_postfc_head_blocks(10 ** 6) == 256
-
-
-def test_missing_library_is_an_error(monkeypatch, tmp_path):
-    from geometry_rl_amd import hip
-    monkeypatch.setattr(hip, "TRANSFORMER_LIB_PATH", str(tmp_path / "missing.so"))
-    monkeypatch.setattr(hip, "_tf_bound", None)
-    with pytest.raises(RuntimeError, match="no CPU or PyTorch fallback"):
-        hip.transformer_query("grl_transformer_ws_row")

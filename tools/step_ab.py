@@ -84,21 +84,16 @@ def count_calls(upd, batch):
     torch's own launches are not counted)."""
     from geometry_rl_amd import hip
     upd.step(batch)                       # the first step of a size runs eagerly
-    names = ("call", "attention_call", "transformer_call")   # the three libraries' launch functions
-    n, real = [0], {k: getattr(hip, k) for k in names}
+    n, real = [0], hip.call               # the one launch function of every kernel library
 
-    def counting(fn):
-        def run(*args, **kw):
-            n[0] += 1
-            return fn(*args, **kw)
-        return run
-    for k in names:
-        setattr(hip, k, counting(real[k]))
+    def counting(*args, **kw):
+        n[0] += 1
+        return real(*args, **kw)
+    hip.call = counting
     try:
         upd.step(batch)
     finally:
-        for k in names:
-            setattr(hip, k, real[k])
+        hip.call = real
     return n[0]
 
 
