@@ -77,6 +77,11 @@ class AgentConfig:
     # Both False here (the reference's configs say True): the schedule is opt-in, a caller's own anneal_lr loop keeps working
     anneal_lr: bool = False
     anneal_clip_epsilon: bool = False
+    # the tensordict keys handed positionally to the actor / the critic (``policy.in_features`` / ``value.in_features`` of a task config).
+    # None = the rule below: the family's six (five) groups, the transformer actor with ``norm_`` vectors in the raw slots.  Two configs
+    # (rigid_pushing_multi_transformer, cloth_hanging_multi_transformer) hand their CRITIC the normalised vectors too: refconfig.py
+    actor_in_features: Optional[list] = None
+    critic_in_features: Optional[list] = None
 
 
 def updater_kwargs(cfg: AgentConfig) -> dict:
@@ -151,15 +156,18 @@ def build_agent(spec: TaskSpec, cfg: AgentConfig, device="cuda", group=None):
     critic._network1.group = group
     # config 1 hands its actor the NORMALISED vectors in the raw-vector slots (configs/rigid_insertion_multi_transformer_trpl_cfg.yaml:88-94)
     a_in = [k if k.startswith("norm_") or "vectors" not in k else "norm_" + k for k in spec.in_features] if post_fc else spec.in_features
+    if cfg.actor_in_features is not None:
+        a_in = list(cfg.actor_in_features)
+    c_in = spec.in_features if cfg.critic_in_features is None else list(cfg.critic_in_features)
     if cfg.algorithm == "ppo":   # builders/agent.py:53-64
         loss = ClipPPOLoss2(actor, critic, clip_epsilon=cfg.clip_epsilon, entropy_coef=cfg.entropy_coef, critic_coef=cfg.critic_coef,
                             clip_value=cfg.clip_value, loss_critic_type="l2", normalize_advantage=True, in_features=a_in,
-                            critic_in_features=spec.in_features, group=group, anneal_clip_epsilon=cfg.anneal_clip_epsilon)
+                            critic_in_features=c_in, group=group, anneal_clip_epsilon=cfg.anneal_clip_epsilon)
         return actor, critic, None, loss
     if cfg.algorithm == "kl_ppo":  # builders/agent.py:65-78 (no clip_value: torchrl's class clips no value)
         loss = KLPENPPOLoss(actor, critic, dtarg=cfg.dtarg, beta=cfg.kl_beta, increment=cfg.kl_increment, decrement=cfg.kl_decrement,
                             entropy_coef=cfg.entropy_coef, critic_coef=cfg.critic_coef, loss_critic_type="l2", normalize_advantage=True,
-                            in_features=a_in, critic_in_features=spec.in_features, group=group)
+                            in_features=a_in, critic_in_features=c_in, group=group)
         return actor, critic, None, loss
     projection = KLProjectionLayer(proj_type=cfg.proj_type, mean_bound=cfg.mean_bound, cov_bound=cfg.cov_bound,
                                    trust_region_coeff=cfg.trust_region_coeff, scale_prec=cfg.scale_prec, entropy_schedule=cfg.entropy_schedule or False,
@@ -167,7 +175,7 @@ def build_agent(spec: TaskSpec, cfg: AgentConfig, device="cuda", group=None):
                                    temperature=cfg.temperature, entropy_eq=cfg.entropy_eq, entropy_first=cfg.entropy_first)
     loss = TRPLLoss(actor, critic, projection=projection, entropy_coef=cfg.entropy_coef, critic_coef=cfg.critic_coef,
                     clip_value=cfg.clip_value, loss_critic_type="l2", normalize_advantage=True, in_features=a_in,
-                    critic_in_features=spec.in_features, group=group, entropy_control=bool(cfg.entropy_schedule))
+                    critic_in_features=c_in, group=group, entropy_control=bool(cfg.entropy_schedule))
     return actor, critic, projection, loss
 
 

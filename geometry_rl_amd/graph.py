@@ -601,6 +601,17 @@ _FAMILY = {
 }
 
 
+EDGE_LEVELS = ["internal", "task", "agent"]
+
+
+def family_types(family: str):
+    """(node types, edge types, edge levels) of a task family: the members of the reference's ``NodeType`` / ``EdgeType`` / ``EdgeLevel``
+    classes of ``pyg_data/<family>_tasks_data.py``, in their order (what the builder hands the GNN as its three mappings,
+    builders/utils_algo_graph.py:75-79)."""
+    f = _FAMILY[family]
+    return list(f["node_types"]), [tuple(e) for e in f["edge_types"]], list(EDGE_LEVELS)
+
+
 def spec_from_observation(family: str, observation_dim: Dict, observation_names: Dict, *, knn_k: int = 3,
                           knn_to_actuators_k: int = -1, angular_velocity: bool = True) -> TaskSpec:
     """TaskSpec from the observation manager's ``group_obs_term_dim`` / ``group_obs_term_names`` dictionaries."""

@@ -1315,9 +1315,54 @@ def tier2h(attention=False):
         assert max(os.path.getsize(path), os.path.getsize(gpath)) <= 1 << 20, name
 
 
+def reference_configs():
+    """Re-copy the reference's Hydra config tree (configs/**/*.yaml) to tests/golden/reference_configs/, byte for byte: the files
+    geometry_rl_amd.refconfig composes and the tests read.  Settings only: a file that holds anything but YAML mappings, lists and
+    scalars (a tag, a Python object) fails the copy."""
+    import shutil
+    import yaml
+    src, dst = os.path.join(REF, "configs"), os.path.join(OUT, "reference_configs")
+
+    def plain(node, where):
+        if isinstance(node, dict):
+            for k, v in node.items():
+                if not isinstance(k, str):
+                    raise SystemExit(f"{where}: key {k!r} is no string")
+                plain(v, f"{where}.{k}")
+        elif isinstance(node, list):
+            for i, v in enumerate(node):
+                plain(v, f"{where}[{i}]")
+        elif not (node is None or isinstance(node, (str, int, float, bool))):
+            raise SystemExit(f"{where}: {type(node).__name__} is no YAML scalar")
+
+    files = []
+    for d, _, names in sorted(os.walk(src)):
+        for name in sorted(names):
+            if not name.endswith(".yaml"):
+                raise SystemExit(f"{os.path.join(d, name)}: not a .yaml file")
+            path = os.path.join(d, name)
+            with open(path) as f:
+                text = f.read()
+            if "!!" in text or "!<" in text:
+                raise SystemExit(f"{path}: holds a YAML tag")
+            plain(yaml.safe_load(text), os.path.relpath(path, src))   # safe_load: refuses every tag that builds an object
+            assert os.path.getsize(path) <= 8 << 10, path
+            files.append(path)
+    if os.path.isdir(dst):
+        shutil.rmtree(dst)
+    for path in files:
+        to = os.path.join(dst, os.path.relpath(path, src))
+        os.makedirs(os.path.dirname(to), exist_ok=True)
+        shutil.copyfile(path, to)
+    print(f"reference_configs: {len(files)} files, {sum(os.path.getsize(p) for p in files)} bytes")
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(4)
+    if len(sys.argv) > 1 and sys.argv[1] == "reference_configs":   # only the copy of the config tree (no reference code is imported)
+        reference_configs()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "tier3":   # only the tier3 fixtures
         install_stubs()
         tier3()
