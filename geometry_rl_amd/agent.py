@@ -50,6 +50,9 @@ class AgentConfig:
     # model "transformer" only: "torch" = stock nn.TransformerEncoder + torch heads (eager updates); "hip" = csrc/transformer_ops.hip, the
     # encoder as one launch each way and the post_fc head as one, recorded like the other actors (fp32; transformer.py)
     transformer_kernels: str = "torch"
+    # model "hepi" with aggr="AttentionalAggregation" only: "torch" = the gate network of the attention convolutions as torch modules (a
+    # library GEMM + ReLU under autograd); "hip" = inside the softmax-aggregation launches (csrc/grl_gate.h, fp32; hepi.py)
+    attention_gate: str = "torch"
     # the actor's HyperData only (configs/rigid_pushing_multi_empn_trpl_cfg.yaml:105-106; every upstream critic config keeps it False)
     training_noise: bool = False
     training_noise_std: float = 0.01
@@ -114,6 +117,9 @@ def build_agent(spec: TaskSpec, cfg: AgentConfig, device="cuda", group=None):
         if cfg.precision != "fp32":
             raise NotImplementedError(f"AgentConfig(transformer_kernels='hip') has fp32 kernels only (csrc/transformer_ops.hip; {ref} runs in "
                                       f"fp32 and needs no other): precision='{cfg.precision}' is not built")
+    from .hepi import check_gate_kernels
+    check_gate_kernels(cfg.attention_gate, "AgentConfig(attention_gate=...)", cfg.precision,
+                       cfg.model == "hepi" and cfg.aggr == "AttentionalAggregation" and any(c for lvl in cfg.codes for c in lvl))
     if cfg.model == "hepi":
         mp = []  # utils_algo_graph.py:29-47: one fresh conv per (level, active round)
         for lvl in range(len(spec.edge_levels)):
@@ -123,7 +129,8 @@ def build_agent(spec: TaskSpec, cfg: AgentConfig, device="cuda", group=None):
                    output_dim=cfg.output_dim, output_dim_vec=cfg.output_dim_vec, node_type_mapping=spec.node_types,
                    edge_type_mapping=[tuple(e) for e in spec.edge_types], edge_level_mapping=spec.edge_levels,
                    message_passing=mp, num_messages=len(cfg.codes[0]), device=device, num_ori=cfg.num_ori,
-                   ponita_dim=cfg.dim, only_upper_hemisphere=cfg.only_upper_hemisphere, precision=cfg.precision)
+                   ponita_dim=cfg.dim, only_upper_hemisphere=cfg.only_upper_hemisphere, precision=cfg.precision,
+                   gate_kernels=cfg.attention_gate)
     elif cfg.model == "transformer":   # BASELINE config 1: stock-torch baseline actor + post_fc head on the same loss / critic / updater
         from .transformer import TransformerVanilla
         gnn = TransformerVanilla(input_dim_node=len(spec.node_types) + 3 * spec.n_vec, output_dim=64, num_layers=cfg.num_layers,

@@ -7,6 +7,7 @@
 #include "grl_report.h"
 #include "grl_feat.h"
 #include "grl_wimg_kernel.h"
+#include "grl_gate.h"
 
 namespace {
 
@@ -1101,9 +1102,23 @@ int GRL_ENTRY(grl_fiber_conv_bwd)(const st_t* x1, const float* fk, const st_t* d
   return 0;
 }
 
-// gate [E,16,64] fp32 (the gate network runs as a plain library GEMM), msg [E,16,64] and x1 [n_dst,16,64] in the latent storage type,
-// rowptr [n_dst+1] = destination CSR of the edge set; every row of x1 / dgate / dmsg is written
-int GRL_ENTRY(grl_softmax_aggregate_fwd)(const float* gate, const st_t* msg, const int* rowptr, int n_dst, st_t* x1, hipStream_t stream) {
+// gate [E,16,64] fp32 (the gate network as a library GEMM on the caller's side), msg [E,16,64] and x1 [n_dst,16,64] in the latent storage
+// type, rowptr [n_dst+1] = destination CSR of the edge set; every row of x1 / dgate / dmsg is written.
+// Wg != NULL (fp32 build only): the gate network runs INSIDE the launch (grl_gate.h): gate / dgate must be NULL, Wg [64,64], bg [64],
+// stat [n_dst,16,64,2] (written by the forward, read by the backward), n_blocks = the workgroup count the caller chose (one wave per
+// destination, four per workgroup), partial [n_blocks][64 * 64 + 64] = [dWg | dbg], every row written; dmsg is then the COMPLETE per-edge
+// gradient.  Wg == NULL: the arguments behind x1 / dmsg are ignored.
+int GRL_ENTRY(grl_softmax_aggregate_fwd)(const float* gate, const st_t* msg, const int* rowptr, int n_dst, st_t* x1, const float* Wg,
+                                         const float* bg, float* stat, int n_blocks, hipStream_t stream) {
+  if (Wg) {
+#if GRL_PREC
+    return -2;
+#else
+    if (gate || !bg || !stat || n_blocks < 1) return -2;
+    if (n_dst <= 0) return 0;
+    return gate_softmax_fwd_launch(msg, rowptr, n_dst, x1, Wg, bg, stat, n_blocks, stream);
+#endif
+  }
   if (n_dst <= 0) return 0;
   hipLaunchKernelGGL(softmax_agg_fwd_kernel, dim3(cap_blocks((long long)n_dst * O, 4, 4096)), dim3(256), 0, stream, gate, msg, rowptr,
                      n_dst, x1);
@@ -1111,7 +1126,17 @@ int GRL_ENTRY(grl_softmax_aggregate_fwd)(const float* gate, const st_t* msg, con
   return 0;
 }
 int GRL_ENTRY(grl_softmax_aggregate_bwd)(const float* gate, const st_t* msg, const st_t* x1, const st_t* dx1, const int* rowptr, int n_dst,
-                                         float* dgate, st_t* dmsg, hipStream_t stream) {
+                                         float* dgate, st_t* dmsg, const float* Wg, const float* bg, const float* stat, float* partial,
+                                         int n_blocks, hipStream_t stream) {
+  if (Wg) {
+#if GRL_PREC
+    return -2;
+#else
+    if (gate || dgate || !bg || !stat || !partial || n_blocks < 1) return -2;
+    if (n_dst <= 0) return 0;
+    return gate_softmax_bwd_launch(msg, x1, dx1, rowptr, n_dst, dmsg, Wg, bg, stat, partial, n_blocks, stream);
+#endif
+  }
   if (n_dst <= 0) return 0;
   hipLaunchKernelGGL(softmax_agg_bwd_kernel, dim3(cap_blocks((long long)n_dst * O, 4, 4096)), dim3(256), 0, stream, gate, msg, x1, dx1,
                      rowptr, n_dst, dgate, dmsg);

@@ -57,6 +57,9 @@ class FiberBundleConv(nn.Module):
         if aggr not in ("add", "AttentionalAggregation"):
             raise NotImplementedError("aggr: 'add' (hepi.yaml) or 'AttentionalAggregation' (hepi_attention.yaml)")
         self.attention = aggr == "AttentionalAggregation"
+        # the gate network's kernels: "torch" = gate_nn runs as torch modules (a library GEMM + ReLU under autograd); "hip" = inside the
+        # softmax-aggregation launches (ops.GatedSoftmaxAggregate, fp32 build).  Set through HEPi(gate_kernels=...) / HEPi.set_gate_kernels
+        self.gate_kernels = "torch"
         if self.attention:   # conv.py:21-26: PyG registers the aggregation as ``aggr_module`` with gate_nn = Sequential(Linear, ReLU)
             self.aggr_module = nn.Module()
             self.aggr_module.gate_nn = nn.Sequential(nn.Linear(in_channels, in_channels), nn.ReLU())
@@ -80,6 +83,21 @@ def global_std(t: torch.Tensor, group=None) -> torch.Tensor:
     dist.all_reduce(m, group=group)
     n, mean = m[2], m[0] / m[2]
     return ((m[1] - n * mean * mean) / (n - 1)).clamp_min(0).sqrt().float()
+
+
+def check_gate_kernels(value: str, what: str, precision: str, has_attention: bool) -> None:
+    """The refusals of the attention gate's switch, shared by HEPi, agent.build_agent and refconfig.build_from_config."""
+    ref = "configs/algorithm/pyg_agent/model/hepi_attention.yaml"
+    if value not in ("torch", "hip"):
+        raise ValueError(f"{what}: 'torch' or 'hip', got {value!r}")
+    if value == "hip":
+        hip = what.replace("...", "'hip'")
+        if not has_attention:
+            raise NotImplementedError(f"{hip} is the switch of HEPi's attention convolutions (aggr='AttentionalAggregation', {ref}): "
+                                      "this model has none")
+        if precision != "fp32":
+            raise NotImplementedError(f"{hip} has fp32 kernels only (csrc/grl_gate.h; {ref} runs in fp32 and needs no other): "
+                                      f"precision='{precision}' is not built")
 
 
 def conv_key(edge_type: EdgeType) -> str:
@@ -106,7 +124,7 @@ class HEPi(nn.Module):
                  edge_encoder_layers=2, node_decoder_layers=2, node_type_mapping=None, edge_type_mapping=None,
                  edge_level_mapping=None, message_passing=None, num_messages=2, concat_global=False, shared_processor=False,
                  shared_node_encoder=True, shared_edge_encoder=True, device="cuda", num_ori=16, basis_dim=None, degree=2,
-                 ponita_dim=3, only_upper_hemisphere=False, precision="fp32", **ignored):
+                 ponita_dim=3, only_upper_hemisphere=False, precision="fp32", gate_kernels="torch", **ignored):
         super().__init__()
         if precision not in ("fp32", "bf16"):
             raise ValueError("precision: 'fp32' (split-bf16 products, fp32-accurate) or 'bf16' (one bf16 MFMA per product)")
@@ -132,7 +150,18 @@ class HEPi(nn.Module):
                             level[tuple(et)] = pl
             self.processor.append(HeteroFiberConv(level))
         self.decoder = nn.Linear(latent_dim, output_dim + output_dim_vec)
+        self.set_gate_kernels(gate_kernels)
         self.to(device)
+
+    def set_gate_kernels(self, gate_kernels: str) -> None:
+        """"torch": the attention convolutions' gate_nn runs as torch modules; "hip": csrc/grl_gate.h, inside the softmax-aggregation
+        launches.  Raises for what the HIP kernels do not build.  The parameter holders (``aggr_module.gate_nn.0``) are the same either way."""
+        check_gate_kernels(gate_kernels, "HEPi(gate_kernels=...)", self.precision,
+                           any(c.attention for r in self.processor for _, c in r.items()))
+        self.gate_kernels = gate_kernels
+        for r in self.processor:
+            for _, c in r.items():
+                c.gate_kernels = gate_kernels if c.attention else "torch"
 
     # ------------------------------------------------------------------ helpers
     @property
@@ -194,11 +223,16 @@ class HEPi(nn.Module):
         # x feeds the convolution AND the residual of its own node block: the two gradients are summed inside the d x_src kernel
         res = {} if (x_src is x_dst and prev is None and torch.is_grad_enabled() and x_src.requires_grad) else None
         if getattr(conv, "attention", False):
-            # messages per edge -> gate network (a plain library GEMM + ReLU, autograd) -> per-destination softmax-weighted sum
+            # messages per edge -> gate network (gate_kernels "torch": a plain library GEMM + ReLU, autograd) -> per-destination
+            # softmax-weighted sum
             msg = ops.EdgeMessages.apply(x_src, graph.pos[s], graph.pos[d], grid3, b[1].weight, b[1].bias, b[3].weight, b[3].bias,
                                          conv.kernel.weight, es, self.dim, res, self._prec)
-            gate = conv.aggr_module.gate_nn(msg if msg.dtype == torch.float32 else msg.float())
-            x1 = ops.SoftmaxAggregate.apply(gate, msg, es, self._prec)
+            if conv.gate_kernels == "hip":   # ... inside the aggregation's launches: no gate tensor, no library GEMM
+                lin = conv.aggr_module.gate_nn[0]
+                x1 = ops.GatedSoftmaxAggregate.apply(msg, lin.weight, lin.bias, es, self._prec)
+            else:
+                gate = conv.aggr_module.gate_nn(msg if msg.dtype == torch.float32 else msg.float())
+                x1 = ops.SoftmaxAggregate.apply(gate, msg, es, self._prec)
         else:
             x1 = ops.EdgeConv.apply(x_src, graph.pos[s], graph.pos[d], grid3, b[1].weight, b[1].bias, b[3].weight, b[3].bias,
                                     conv.kernel.weight, es, self.dim, res, self._prec, wimg)

@@ -539,7 +539,7 @@ class SoftmaxAggregate(torch.autograd.Function):
         hip.check_latent(prec, msg)
         x1 = torch.empty(edges.n_dst, 16, 64, device=msg.device, dtype=msg.dtype)
         gate = gate.contiguous()
-        hip.call("grl_softmax_aggregate_fwd" + prec, gate, msg, edges.rowptr_d, edges.n_dst, x1)
+        hip.call("grl_softmax_aggregate_fwd" + prec, gate, msg, edges.rowptr_d, edges.n_dst, x1, None, None, None, 0)
         ctx.save_for_backward(gate, msg, x1)
         ctx.edges, ctx.prec = edges, prec
         return x1
@@ -549,8 +549,49 @@ class SoftmaxAggregate(torch.autograd.Function):
         gate, msg, x1 = ctx.saved_tensors
         dgate, dmsg = torch.empty_like(gate), torch.empty_like(msg)
         hip.call("grl_softmax_aggregate_bwd" + ctx.prec, gate, msg, x1, dx1.contiguous(), ctx.edges.rowptr_d, ctx.edges.n_dst, dgate,
-                 dmsg)
+                 dmsg, None, None, None, None, 0)
         return dgate, dmsg, None, None
+
+
+class GatedSoftmaxAggregate(torch.autograd.Function):
+    """SoftmaxAggregate with the gate network inside the launch: gate = ReLU(msg wg^T + bg) (conv.py:21-26: PyG AttentionalAggregation's
+    gate_nn = Linear + ReLU) is formed tile by tile on the matrix pipe and never stored (csrc/grl_gate.h).  fp32 build only.  The backward
+    returns the COMPLETE per-edge gradient of msg (the softmax's direct part plus the gate network's) and hands d wg / d bg to the fold
+    queue like every other leaf gradient."""
+
+    @staticmethod
+    def blocks(n_dst: int) -> int:
+        """Workgroups of both launches (four destinations in flight each): the caller of the entry points chooses the grid."""
+        return max(1, min(256, -(-n_dst // 4)))
+
+    @staticmethod
+    def forward(ctx, msg, wg, bg, edges: EdgeSet, prec: str = ""):
+        if prec != "":
+            raise NotImplementedError("GatedSoftmaxAggregate: the fused gate network is built in the fp32 build only")
+        hip.check_f32(msg, wg, bg)
+        if tuple(wg.shape) != (64, 64) or tuple(bg.shape) != (64,):
+            raise ValueError("GatedSoftmaxAggregate: gate_nn is Linear(64, 64)")
+        x1 = torch.empty(edges.n_dst, 16, 64, device=msg.device, dtype=torch.float32)
+        stat = torch.empty(edges.n_dst, 16, 64, 2, device=msg.device, dtype=torch.float32)
+        msg, wgc, bgc = msg.contiguous(), wg.contiguous(), bg.contiguous()
+        n_blocks = GatedSoftmaxAggregate.blocks(edges.n_dst)
+        hip.call("grl_softmax_aggregate_fwd", None, msg, edges.rowptr_d, edges.n_dst, x1, wgc, bgc, stat, n_blocks, rows=edges.n_edges * 16)
+        ctx.save_for_backward(msg, x1, stat, wgc, bgc)
+        ctx.edges, ctx.n_blocks, ctx.params = edges, n_blocks, (wg, bg)
+        return x1
+
+    @staticmethod
+    def backward(ctx, dx1):
+        msg, x1, stat, wgc, bgc = ctx.saved_tensors
+        e = ctx.edges
+        dmsg = torch.empty_like(msg)
+        # (without a destination nothing is launched: the rows are then the zeros they would have been)
+        partial = (torch.empty if e.n_dst > 0 else torch.zeros)(ctx.n_blocks, 64 * 64 + 64, device=msg.device, dtype=torch.float32)
+        hip.call("grl_softmax_aggregate_bwd", None, msg, x1, dx1.contiguous(), e.rowptr_d, e.n_dst, None, dmsg, wgc, bgc, stat, partial,
+                 ctx.n_blocks, rows=e.n_edges * 16)
+        wg, bg = ctx.params
+        dwg, dbg = _emit_grads(partial, [(0, 4096, (64, 64), wg), (4096, 64, (64,), bg)])
+        return dmsg, dwg, dbg, None, None
 
 
 class KeyQueryProject(torch.autograd.Function):

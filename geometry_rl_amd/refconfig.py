@@ -580,6 +580,8 @@ def _make_pyg_agent(config, where, observation_dim, observation_names, device, e
         extra.pop("precision", None)
     if model_cls != "TransformerVanilla":
         extra.pop("kernels", None)
+    if model_cls != "HEPi":
+        extra.pop("gate_kernels", None)
     gnn = _build_pyg_model(config["model"], input_dim_node, input_dim_edge, node_types, edge_types, edge_levels, device, extra)
     return gnn, base_data
 
@@ -591,12 +593,12 @@ def _obs_width(observation_dim, key):
 
 
 def build_from_config(cfg, observation_dim, observation_names, action_dim, *, device="cuda", group=None, precision="fp32",
-                      transformer_kernels="torch"):
+                      transformer_kernels="torch", attention_gate="torch"):
     """-> (actor GNNGaussianPolicyDiag, critic BaseCritic, projection | None, loss_module): ``make_ppo_models`` (utils_algo_graph.py:208-276)
     and ``AgentBuilder.build`` (builders/agent.py:31-78) on this package's mirrors, step by step.  ``cfg``: a composed dict or
     ``(config_root, name, overrides)``; ``observation_dim`` / ``observation_names``: the observation manager's ``group_obs_term_dim`` /
     ``_group_obs_term_names`` (what graph.spec_from_observation takes); ``action_dim``: the action space's width.  ``precision`` and
-    ``transformer_kernels`` are this package's own switches (agent.AgentConfig), not the config's."""
+    ``transformer_kernels`` / ``attention_gate`` are this package's own switches (agent.AgentConfig), not the config's."""
     import torch
     from . import policy as _policy, trpl as _trpl
     cfg = _as_cfg(cfg)
@@ -619,11 +621,16 @@ def build_from_config(cfg, observation_dim, observation_names, action_dim, *, de
         raise NotImplementedError(f"transformer_kernels='hip' is the transformer baseline actor's switch, not {model_cls}'s")
     if transformer_kernels == "hip" and precision != "fp32":
         raise NotImplementedError(f"transformer_kernels='hip' has fp32 kernels only (csrc/transformer_ops.hip): precision='{precision}' is not built")
+    if attention_gate != "torch":   # refused here in the switch's own words (HEPi's constructor would refuse the same)
+        from .hepi import check_gate_kernels
+        check_gate_kernels(attention_gate, "attention_gate=...", precision, model_cls == "HEPi" and any(
+            "AttentionalAggregation" in str((m.get("processor") or {}).get("aggr", "")) and any(m.get("code", []))
+            for m in policy_pyg["model"].get("message_passing", [])))
     if model_cls == "PonitaGCN":
         from .ponita_gcn import check_attention_group
         check_attention_group(bool(policy_pyg["model"].get("attention", False)), group)
     gnn, hyper_data = _make_pyg_agent(policy_pyg, "algorithm.policy.pyg_agent", observation_dim, observation_names, device,
-                                      extra=dict(precision=precision, kernels=transformer_kernels))
+                                      extra=dict(precision=precision, kernels=transformer_kernels, gate_kernels=attention_gate))
 
     # ---- :233-243 + _make_probabilistic_actor:123-143
     policy_kwargs = config["policy"]

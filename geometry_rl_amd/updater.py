@@ -169,13 +169,15 @@ class PolicyUpdater:
         self._calib_synced = False                 # (_check_calibrated)
         # Leaf gradients are WRITTEN by the one fold launch at the end of the backward pass (ops.flush_deferred_grads(overwrite=True)) instead
         # of accumulated into a zeroed buffer: no per-step zeroing launch.  Valid while EVERY leaf gradient of the step comes through the
-        # fold queue: not with the stock torch transformer actor or the attention gate (torch's AccumulateGrad adds into .grad) -- and
-        # checked on the first eager step of every updater (``_check_overwrite_coverage``).
+        # fold queue: not with the stock torch transformer actor or an attention gate that runs as torch modules (torch's AccumulateGrad adds
+        # into .grad; gate_kernels="hip" hands the gate's gradients to the queue like every other) -- and checked on the first eager step of
+        # every updater (``_check_overwrite_coverage``).
         gnn = getattr(loss_module.actor_network, "gnn", None)
         # The transformer actor on HIP kernels (kernels="hip") keeps the accumulate mode too: ``cls_token`` and the template encoder layer
         # take no part in the forward, so no fold ever writes their gradients -- they stay the zeros of the buffer, as on the stock path.
         self._fold_overwrite = (not getattr(loss_module.actor_network, "post_fc", False)
-                                and not any(getattr(mod, "attention", False) for mod in (gnn.modules() if gnn is not None else [])))
+                                and not any(getattr(mod, "attention", False) and getattr(mod, "gate_kernels", "torch") == "torch"
+                                            for mod in (gnn.modules() if gnn is not None else [])))
         self._overwrite_checked = not self._fold_overwrite
         if gnn is not None and hasattr(gnn, "ponita"):   # EMPN key / query attention: one rank only (ponita_gcn.check_attention_group)
             from .ponita_gcn import check_attention_group

@@ -107,10 +107,20 @@ int grl_weight_images_bf16(int n, const int* kinds, const float* const* srcs, vo
 /* ---- attention aggregation: FiberBundleConv(aggr="AttentionalAggregation"), ponita/conv.py:21-26,58-61,138-139;
  *      configs/algorithm/pyg_agent/model/hepi_attention.yaml; PyG 2.5.2 AttentionalAggregation / utils.softmax [upstream] ---------------
  * The messages m_e = K_e * x_src[src(e)] are materialised per edge (msg [E,16,64], rows in DESTINATION-sorted edge order), gated by
- * gate = ReLU(Linear(msg)) (a plain library GEMM on the caller's side), and summed per destination with softmax weights:
- * x1[d,o,c] = sum_e softmax_e(gate[e,o,c]) msg[e,o,c].  Backward: grl_softmax_aggregate_bwd hands back d gate and the direct part of
- * d msg; grl_edge_messages_bwd takes the complete per-edge d msg (s2d [E]: row of the i-th SOURCE-sorted edge in the destination-sorted
- * order) and produces d x_src and the five weight-gradient partial rows exactly like grl_edge_conv_bwd. */
+ * gate = ReLU(Linear(msg)), and summed per destination with softmax weights: x1[d,o,c] = sum_e softmax_e(gate[e,o,c]) msg[e,o,c].
+ * grl_edge_messages_bwd takes the complete per-edge d msg (s2d [E]: row of the i-th SOURCE-sorted edge in the destination-sorted
+ * order) and produces d x_src and the five weight-gradient partial rows exactly like grl_edge_conv_bwd.
+ * grl_softmax_aggregate_fwd / _bwd (and their _bf16 twins below) have two forms, selected by Wg.  FOUR ARGUMENT LISTS GREW at their end,
+ * in front of `stream`, under an UNCHANGED ABI number (216): the fwd entries by (Wg, bg, stat, n_blocks), the bwd entries by (Wg, bg,
+ * stat, partial, n_blocks); a library built before the change is refused by its embedded source hash (grl_source_hash).
+ *   Wg == NULL: the gate network is a plain library GEMM + ReLU on the caller's side; gate [E,16,64] is read, the backward hands back
+ *     d gate and the direct part of d msg (alpha dx1).  The arguments behind x1 / dmsg are ignored.
+ *   Wg != NULL (Wg [64,64], bg [64]: gate_nn's Linear; fp32 entries only, the _bf16 twins return -2): the gate network runs inside the
+ *     launch on the matrix pipe (csrc/grl_gate.h) and neither gate nor d gate exists: both must be NULL (-2 otherwise).  The caller
+ *     chooses the grid: n_blocks >= 1 workgroups of four waves, one wave per destination, grid-stride.  stat [n_dst,16,64,2] = (segment
+ *     maximum of the gate, 1 / (sum + 1e-16)) is written by the forward ((0, 0) for a destination without in-edges) and read by the
+ *     backward, whose dmsg is the COMPLETE per-edge gradient alpha dx1 + d pre Wg and whose partial [n_blocks][64 * 64 + 64] =
+ *     [dWg | dbg] rows (every row written) are summed like every other partial. */
 int grl_edge_messages_fwd(const float* x_src, const float* pos_src, const float* pos_dst, const int* rowptr, const int* e_src,
                           const int* e_dst, int n_dst, int n_edges, const float* grid, int dim, const float* W1, const float* b1,
                           const float* W2, const float* b2, const float* Wk, float* msg, hipStream_t stream);
@@ -119,9 +129,11 @@ int grl_edge_messages_bwd(const float* x_src, const float* pos_src, const float*
                           const int* s2d, int n_src, const float* grid, int dim, const float* W1, const float* b1, const float* W2,
                           const float* b2, const float* Wk, const float* dmsg, const float* dres, float* dx_src, float* partial,
                           hipStream_t stream);
-int grl_softmax_aggregate_fwd(const float* gate, const float* msg, const int* rowptr, int n_dst, float* x1, hipStream_t stream);
+int grl_softmax_aggregate_fwd(const float* gate, const float* msg, const int* rowptr, int n_dst, float* x1, const float* Wg,
+                              const float* bg, float* stat, int n_blocks, hipStream_t stream);
 int grl_softmax_aggregate_bwd(const float* gate, const float* msg, const float* x1, const float* dx1, const int* rowptr, int n_dst,
-                              float* dgate, float* dmsg, hipStream_t stream);
+                              float* dgate, float* dmsg, const float* Wg, const float* bg, const float* stat, float* partial,
+                              int n_blocks, hipStream_t stream);
 
 /* ---- reduced-precision twins (BASELINE config 5: rope_shaping_hepi_trpl, "bf16 storage / MFMA, fp32 accumulate") --------------------
  * Same argument lists as the fp32 entry points above / below, with two differences: (1) every dense product is ONE bf16 MFMA (operands
@@ -163,10 +175,11 @@ int grl_edge_messages_bwd_bf16(const grl_bf16* x_src, const float* pos_src, cons
                                const int* s2d, int n_src, const float* grid, int dim, const float* W1, const float* b1,
                                const float* W2, const float* b2, const float* Wk, const grl_bf16* dmsg, const grl_bf16* dres,
                                grl_bf16* dx_src, float* partial, hipStream_t stream);
-int grl_softmax_aggregate_fwd_bf16(const float* gate, const grl_bf16* msg, const int* rowptr, int n_dst, grl_bf16* x1,
-                                   hipStream_t stream);
+int grl_softmax_aggregate_fwd_bf16(const float* gate, const grl_bf16* msg, const int* rowptr, int n_dst, grl_bf16* x1, const float* Wg,
+                                   const float* bg, float* stat, int n_blocks, hipStream_t stream);
 int grl_softmax_aggregate_bwd_bf16(const float* gate, const grl_bf16* msg, const grl_bf16* x1, const grl_bf16* dx1, const int* rowptr,
-                                   int n_dst, float* dgate, grl_bf16* dmsg, hipStream_t stream);
+                                   int n_dst, float* dgate, grl_bf16* dmsg, const float* Wg, const float* bg, const float* stat,
+                                   float* partial, int n_blocks, hipStream_t stream);
 int grl_fiber_conv_fwd_bf16(const grl_bf16* x1, const float* fk, const float* bias, grl_bf16* x2, int n_nodes, hipStream_t stream);
 int grl_fiber_conv_bwd_bf16(const grl_bf16* x1, const float* fk, const grl_bf16* dx2, grl_bf16* dx1, float* partial, int n_nodes,
                             hipStream_t stream);

@@ -13,6 +13,7 @@ ms / step of each (``<variant>_ms_per_step``, ``<variant>_min_max_ms``), B / A (
   python tools/step_ab.py ppo ppo_anneal_on --sizes 32 512 4096 --build-order both --reverse-blocks --launch-steps 8   # the multi-step launch
   python tools/step_ab.py transformer transformer_hip --sizes 64 512 4096 --reverse-blocks --eager --count-calls       # both as eager steps
   python tools/step_ab.py transformer transformer_hip --sizes 64 512 4096 --reverse-blocks                             # the HIP variant replayed
+  python tools/step_ab.py hepi_attn hepi_attn_gate_hip --sizes 512 4096 --reverse-blocks --build-order both --calibration --count-calls
 
 The updater built SECOND in a process has measured 3.6 % slower at 4096 frames whatever it runs (entropy control): a
 difference of that size is read from both build orders (--build-order both) and from blocks whose order is reversed every round."""
@@ -49,6 +50,10 @@ VARIANTS = {
     # on HIP kernels.  Compare them with --eager (both as eager upd.step calls) and once more without (the HIP variant replayed)
     "transformer": dict(base=dict(output_dim=2, output_dim_vec=2), cfg=dict(model="transformer")),
     "transformer_hip": dict(base=dict(output_dim=2, output_dim_vec=2), cfg=dict(model="transformer", transformer_kernels="hip")),
+    # hepi_attention.yaml on the bench.py workload: the gate network of the attention convolutions as torch modules (a library GEMM + ReLU
+    # under autograd, the accumulate mode of the gradient fold) and inside the softmax-aggregation launches (csrc/grl_gate.h, overwrite mode)
+    "hepi_attn": dict(cfg=dict(aggr="AttentionalAggregation")),
+    "hepi_attn_gate_hip": dict(cfg=dict(aggr="AttentionalAggregation", attention_gate="hip")),
 }
 HEPI_BASE = dict(only_upper_hemisphere=True, output_dim=2, output_dim_vec=2)
 
