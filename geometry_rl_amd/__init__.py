@@ -1,7 +1,7 @@
 """ROCm-native policy-update path of geometry_rl (HIP kernels for gfx950).  The loss modules are exported lazily: importing the package
 itself loads nothing."""
 
-_EXPORTS = {"TRPLLoss": "trpl", "ClipPPOLoss2": "ppo", "KLPENPPOLoss": "klpen"}
+_EXPORTS = {"TRPLLoss": "trpl", "ClipPPOLoss2": "ppo", "KLPENPPOLoss": "klpen", "BCLoss": "bc"}
 
 
 def __getattr__(name):

@@ -230,6 +230,17 @@ struct TrplCfg {
 //       mean constraint (column 6, its maximum) is sum (mu - pm)^2.  7 = commutative Wasserstein: cp = sum (So - Sx)^2 = tr(So^2 + Sx^2 -
 //       2 So Sx), pS = (Sx + eta So) / (1 + eta), d cp / d Sx_j = -2 (So_j - Sx_j); regression loss and columns 6, 7 on the detached
 //       projection: md = sum (mu - pm)^2, cd = sum (S - pS)^2, direct gradient 2 (mu - pm), 2 (S - pS).  KL and entropy columns unchanged.
+//       8, 9 = behaviour cloning (behavior_cloning.py:109-125: the actor's mean against a demonstrated action), no RL column at all: only
+//       mean, sigma and action are read, every other input pointer is NULL (trpl_launch refuses the launch otherwise) and no branch below
+//       dereferences it.  With d = mean - action per dimension and se = sum_i d_i^2 per frame:
+//       8 = regression, nn.MSELoss over [B, A]: loss = sum_b se / (B A), d loss / d mean_i = 2 d_i / (B A), d loss / d sigma = 0, WRITTEN
+//       (dsigma is an output like any other).  9 = Gaussian negative log-likelihood (not in the reference; it clones the std with the mean):
+//       nll = 1/2 sum_i d_i^2 / S_i + 1/2 sum_i log S_i + A/2 log 2 pi = -MultivariateNormal(mean, diag(S)).log_prob(action), loss = sum_b nll / B,
+//       d loss / d mean_i = d_i / (S_i B), d loss / d sigma_i = (1 / sigma_i - d_i^2 / sigma_i^3) / B -- the PPO modes' log-probability and its
+//       gradient with the weight d loss / d lw = -1.  Columns of BOTH modes: 0 the optimised loss, 6 sum se (its maximum in maxes[0]),
+//       3 sum se / A (the value-loss column, which no BC launch fills otherwise: the report's second entry is then nn.MSELoss whatever the
+//       mode), 11 sum nll, 2 and 8 the policy's entropy, 4 and 5 one per frame (the report's ESS entry reads 1), 10 the count; 1, 7, 9 and
+//       maxes[1] zero.
 // Covariance projection (KL): eta >= 0 with KL_cov(eta) = cov_bound.  With rho_i = v_i/o_i = (eta+1)/(eta+c_i), c_i = o_i/t_i:
 //   KL = 1/2 sum(rho_i - 1 - log rho_i),  dKL/deta = -1/2 sum (1-c_i)^2 / ((eta+1)(eta+c_i)^2) < 0, KL convex in eta: Newton from eta = 0
 //   approaches the root monotonically from the left (never overshoots).  Phase 1 runs the iteration in fp32 (hardware log2 / reciprocal)
@@ -317,7 +328,8 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
   // sums are all-reduced).
   __shared__ double adv_sh[NW][2];
   double adv_sum0 = 0.0, adv_sum1 = 0.0;
-  if (cfg.adv_local) {
+  constexpr bool BC = PROJ == 8 || PROJ == 9;   // behaviour cloning: no advantage, no old distribution, no value columns
+  if (!BC && cfg.adv_local) {
     for (int k = tid; k < B; k += NT) {
       const double a_ = advantage[k];
       adv_sum0 += a_;
@@ -337,8 +349,8 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
   if (live) {   // (wave-uniform: the frames sit on whole waves)
   const size_t k = (size_t)b * A + ii, kms = (size_t)(b - q_.ms_row0) * A + ii;
   const double mu = mean[kms], sg = sigma[kms], ac = action[k];
-  const double mo = PROJ == 3 ? 0.0 : (double)old_mean[k], So = PROJ == 3 ? 1.0 : (double)old_var[k];   // (PPO: no old distribution)
-  constexpr bool NOPROJ = PROJ == 3 || PROJ == 5;   // the two PPO modes: no projection, no trust-region terms
+  const double mo = PROJ == 3 || BC ? 0.0 : (double)old_mean[k], So = PROJ == 3 || BC ? 1.0 : (double)old_var[k];   // (PPO, BC: no old distribution)
+  constexpr bool NOPROJ = PROJ == 3 || PROJ == 5 || BC;   // the two PPO modes and the BC modes: no projection, no trust-region terms
   const double S = sg * sg;                  // policy covariance diagonal == "std" seen by the projection (trpl.py:241)
   // ---- (ENT) scheduled entropy projection in FRONT of the trust region: the projection below runs on (mu, Sx = alpha S)
   bool e_act = false, e_first = false;
@@ -463,10 +475,10 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
   const double LOG2PI = 1.8378770664093454836;
   const double da = ac - pm;
   const double q = gsum<L>(M(da * da / pS)), sl = gsum<L>(M(log(pS)));
-  const double lw = -0.5 * (q + A * LOG2PI + sl) - (double)old_logp[b];
+  const double lw = -0.5 * (q + A * LOG2PI + sl) - (BC ? 0.0 : (double)old_logp[b]);
   const double ratio = exp(lw);
-  double adv = (double)advantage[b];
-  if ((adv_stats || cfg.adv_local) && cfg.adv_count > 1.0) {
+  double adv = BC ? 0.0 : (double)advantage[b];
+  if (!BC && (adv_stats || cfg.adv_local) && cfg.adv_count > 1.0) {
     const double s0_ = cfg.adv_local ? adv_sum0 : adv_stats[0], s1_ = cfg.adv_local ? adv_sum1 : adv_stats[1];
     const double am = s0_ / cfg.adv_count;
     double var = (s1_ - cfg.adv_count * am * am) / (cfg.adv_count - 1.0);
@@ -524,6 +536,19 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
   acc[9] = (c_ent + ldP) - (c_ent + ldS);
   mmax = (float)acc[6];
   cmax = (float)fmax(acc[7], 0.0);
+  }
+  double bc_d = 0.0;   // BC: mean - action
+  if (BC) {   // behaviour cloning (the header above): lw is the action's log-probability under the policy itself, so nll = -lw
+    bc_d = mu - ac;
+    const double se = gsum<L>(M(bc_d * bc_d));
+    acc[0] = PROJ == 8 ? se / A : -lw;
+    acc[3] = se / A;
+    acc[4] = 1.0;
+    acc[5] = 1.0;
+    acc[6] = se;
+    acc[10] = -lw;
+    mmax = (float)se;
+    w_lw = -1.0;   // d nll / d lw: the gradient below is the NLL's (trpl_launch hands over entropy_coef = 0)
   }
   // ---- gradients of actor_loss = objective + entropy bonus + trust region  (all already scaled by 1/B)
   const double w_obj = w_lw * cfg.inv_batch;
@@ -604,13 +629,14 @@ GRL_DEVINL void trpl_lanes_body(const TrplCfg& cfg, const TrplPtrs& q_, int B, i
     gmu += ctr * 2.0 * (mu - pm);
     gS += ctr * 2.0 * (S - pS);
   }
+  if (PROJ == 8) { gmu = 2.0 * bc_d * cfg.inv_batch / A; gS = 0.0; }   // regression: the mean alone; dsigma is written as zeros
   if (act) {
     dmean[kms] = (float)gmu;
     dsigma[kms] = (float)(gS * 2.0 * sg);
     if (proj_mean_out) { proj_mean_out[k] = (float)pm; proj_var_out[k] = (float)pS; }
   }
   // ---- clipped value loss (trpl.py:213-228, objectives/utils.py:5-28), l2: once per frame
-  if (value) {
+  if (!BC && value) {
     const double V = value[b], Vo = old_value[b], R = value_target[b];
     const double l1 = (V - R) * (V - R);
     double l = l1, g = 2.0 * (V - R);
@@ -810,7 +836,7 @@ __global__ __launch_bounds__(256) void gaussian_sample_kernel(const float* __res
 }
 
 // The ONE host-side launch of the fused loss kernel, behind all five entry points.  mode: the kernel's PROJ (0, 1, 2, 4, 6, 7 the TRPL
-// projections; 3 clipped PPO; 5 KL-penalty PPO); ent: the instance with the entropy stage (TRPL modes only).  Lane width from the action
+// projections; 3 clipped PPO; 5 KL-penalty PPO; 8, 9 behaviour cloning); ent: the instance with the entropy stage (TRPL modes only).  Lane width from the action
 // dimension (<= 4 / 8 / 16), the launch, and -- sums != NULL -- the fold of the slots behind it (sums == NULL: the caller folds later,
 // grl_trpl_fold, on a stream of its choice: the sums are reported values only).  -3: no such instance.
 using TrplKernel = void (*)(TrplCfg, TrplPtrs, int);
@@ -825,6 +851,8 @@ static TrplKernel trpl_kernel_of(int mode, bool ent) {
     case 7: return ent ? trpl_lanes_ent_kernel<L, 7> : trpl_lanes_kernel<L, 7>;
     case 3: return ent ? nullptr : trpl_lanes_kernel<L, 3>;
     case 5: return ent ? nullptr : trpl_lanes_kernel<L, 5>;
+    case 8: return ent ? nullptr : trpl_lanes_kernel<L, 8>;
+    case 9: return ent ? nullptr : trpl_lanes_kernel<L, 9>;
     default: return nullptr;
   }
 }
@@ -906,6 +934,16 @@ static int trpl_launch(const double* cfg9, int action_dim, const float* mean, co
   const TrplCfg c{cfg9[0], cfg9[1], cfg9[2], cfg9[3], cfg9[4], cfg9[5], cfg9[6], cfg9[7], action_dim, (int)cfg9[9]};
   const int proj = (int)cfg9[8];
   if (proj == 3 || proj == 5) return -3;   // (the PPO modes have their own entry points: grl_ppo_fwd_bwd, grl_klpen_fwd_bwd)
+  if (proj == 8 || proj == 9) {   // behaviour cloning: mean, sigma, action -> dmean, dsigma; no instance of it takes an RL column
+    if (old_mean || old_var || old_logp || advantage || value || old_value || value_target || dvalue || proj_mean || proj_var || adv_stats ||
+        tgt_mean || tgt_S)
+      return -3;
+    if (!mean || !sigma || !action || !dmean || !dsigma) return -2;
+    const TrplCfg cb{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, cfg9[6], cfg9[7], action_dim, 0};
+    const TrplPtrs tb{mean, sigma, action, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, dmean, dsigma, nullptr, nullptr,
+                      nullptr, nullptr, slots, nullptr, nullptr, 0, nullptr, ent_beta, 0};
+    return trpl_run(proj, ent_mode >= 0, cb, tb, batch, sums, maxes, stream);
+  }
   const TrplPtrs tp{mean, sigma, action, old_mean, old_var, old_logp, advantage, value, old_value, value_target, dmean, dsigma, dvalue,
                     proj_mean, proj_var, adv_stats, slots, tgt_mean, tgt_S, 0, nullptr, ent_beta, ent_mode < 0 ? 0 : ent_mode};
   return trpl_run(proj, ent_mode >= 0, c, tp, batch, sums, maxes, stream);

@@ -1077,13 +1077,15 @@ TRPL_SUM_KEYS = ("loss_objective", "loss_trust_region", "entropy_dist", "loss_cr
 
 
 def _loss_launch(entry, lead, loc, sigma, batch, value, *, old=True, proj_out=None, trail=(), target=None, adv_stats=None, sums=None,
-                 maxes=None, defer_fold=False):
-    """The one launch of the fused loss kernel behind ``trpl_fwd_bwd`` / ``ppo_fwd_bwd`` / ``klpen_fwd_bwd`` / ``trpl_target_terms``: the
+                 maxes=None, defer_fold=False, clone=None):
+    """The one launch of the fused loss kernel behind ``trpl_fwd_bwd`` / ``ppo_fwd_bwd`` / ``klpen_fwd_bwd`` / ``trpl_target_terms`` /
+    ``bc_fwd_bwd``: the
     workspace (``sums`` fp64[12] / ``maxes`` u32[2] -- the caller's views of its per-step workspace, written in full by the launch, or fresh
     ones --, the per-workgroup ``slots``, ``dloc`` / ``dsigma`` / ``dvalue``), the batch's columns as contiguous [B, A] / [B] arrays, and the
     call of ``entry``(*lead, A, loc, sigma, <columns>, <outputs>, B, *trail).  ``old``: the entry point takes the old distribution;
     ``proj_out`` (not None): it takes the projection outputs (True: allocated here, False: NULL); ``target`` = (mean, S): the argument list of grl_trpl_target_terms
-    (the target in the batch's place, a column of zeros standing in for advantage and old log-prob).
+    (the target in the batch's place, a column of zeros standing in for advantage and old log-prob); ``clone`` = the demonstrated action
+    [B, A]: the argument list of grl_trpl_fwd_bwd in the behaviour-cloning modes (every RL column, output and statistic NULL).
     -> (sums, maxes, dloc, dsigma, dvalue, proj_mean, proj_var); ``defer_fold``: the slots are not folded by this call and ``sums`` comes
     back as the callable that does it (on whatever stream is current when it is called), -> (sums, maxes)."""
     B, A = loc.shape
@@ -1097,6 +1099,8 @@ def _loss_launch(entry, lead, loc, sigma, batch, value, *, old=True, proj_out=No
     pm, pv = (torch.empty_like(loc), torch.empty_like(loc)) if proj_out else (None, None)
     if target is not None:
         args = (*(t.contiguous() for t in target), dloc, dsigma, sums, maxes, slots, torch.zeros(B, device=dev, dtype=torch.float32), B)
+    elif clone is not None:
+        args = (clone.reshape(B, -1).contiguous(), *(None,) * 7, dloc, dsigma, *(None,) * 4, None if defer_fold else sums, maxes, slots, B)
     else:
         mat = lambda k: batch[k].reshape(B, -1).contiguous()
         row = lambda k: batch[k].reshape(B).contiguous()
@@ -1144,6 +1148,25 @@ def trpl_fwd_bwd(loc, sigma, batch, value, *, mean_bound, cov_bound, trust_regio
     return _loss_launch("grl_trpl_fwd_bwd" if ent_mode is None else "grl_trpl_fwd_bwd_ent", (cfg,), loc, sigma, batch, value,
                         proj_out=bool(want_projection), trail=() if ent_mode is None else (ent_mode, ent_beta), adv_stats=adv_stats,
                         sums=sums, maxes=maxes, defer_fold=defer_fold)
+
+
+BC_MODES = {"mse": 8, "nll": 9}   # the fused loss kernel's behaviour-cloning modes (csrc/head_ops.hip, include/grl_hip.h cfg9[8])
+
+
+def bc_fwd_bwd(loc, sigma, action, *, mode, global_batch: int, sums=None, maxes=None, defer_fold: bool = False):
+    """The behaviour-cloning objectives on the fused kernel (grl_trpl_fwd_bwd, modes 8 / 9): ``mode`` "mse" | 8 = the regression of
+    behavior_cloning.py:101,119 (nn.MSELoss of the mean against ``action``; dsigma comes back as zeros), "nll" | 9 = the Gaussian negative
+    log-likelihood of ``action`` under N(loc, diag(sigma^2)).  ``sigma`` is the std as ``forward_diag`` returns it.  Returns (sums fp64[12],
+    maxes u32[2], dloc, dsigma): sums[0] the optimised loss, [6] the squared error (its per-frame maximum in maxes[0]), [3] the squared
+    error / A, [11] the nll, [8] the policy's entropy, [10] the count -- per-frame sums; ``defer_fold`` as in ``trpl_fwd_bwd``."""
+    code = BC_MODES.get(mode, mode)
+    if code not in (8, 9):
+        raise ValueError(f"bc_fwd_bwd(mode=...): 'mse' (8) or 'nll' (9), got {mode!r}")
+    hip.check_f32(loc, sigma, action)
+    if action.numel() != loc.numel() or sigma.shape != loc.shape or action.device != loc.device:
+        raise ValueError(f"the demonstrated action is {tuple(action.shape)}, the policy's mean {tuple(loc.shape)} and std {tuple(sigma.shape)}")
+    cfg = _trpl_cfg(0.0, 0.0, 0.0, 0.0, 0.0, 0.0, global_batch, code, False)
+    return _loss_launch("grl_trpl_fwd_bwd", (cfg,), loc, sigma, None, None, clone=action, sums=sums, maxes=maxes, defer_fold=defer_fold)[:4]
 
 
 def write_doubles(dst: torch.Tensor, values) -> None:

@@ -254,7 +254,18 @@ int grl_readout_bwd(const float* lat, const float* grid, const float* Wd, const 
  *               non-commuting (w2_projection_layer_non_com.py: one joint bound, ten Newton-Schulz steps; precision-scaled) | 6, 7 (ABI 213) the
  *               Euclidean forms (scale_prec=False, projection_utils.py:9-31,70-149) of 1 and 2: mean part sum (mu - mo)^2; 7: covariance
  *               part sum (So - S)^2, regression loss and constraints sum (mu - pm)^2, sum (S - pS)^2; 6: covariance part and regression
- *               loss of 1, reported mean constraint sum (mu - pm)^2.  3 and 5 (the PPO modes' own entry points) are refused,
+ *               loss of 1, reported mean constraint sum (mu - pm)^2.  3 and 5 (the PPO modes' own entry points) are refused.
+ *               8, 9 = behaviour cloning (behavior_cloning.py:109-125), through grl_trpl_fwd_bwd only (grl_trpl_fwd_bwd_ent: -3): the launch
+ *               reads mean, sigma, action and cfg9[6..8] and writes dmean, dsigma, slots (sums, maxes); EVERY other pointer -- old
+ *               distribution, old_logp, advantage, the value columns, dvalue, proj_mean / proj_var, adv_stats -- must be NULL (-3
+ *               otherwise: no instance of these modes takes an RL column).  With d = mean - action, se = sum_i d_i^2 per frame:
+ *               8 regression (nn.MSELoss): loss = sum_b se / (B_global A), dmean = 2 d / (B_global A), dsigma = exact zeros (written);
+ *               9 Gaussian NLL: nll = 1/2 sum_i d_i^2 / sigma_i^2 + sum_i log sigma_i + A/2 log 2 pi, loss = sum_b nll / B_global,
+ *               dmean = d / (sigma^2 B_global), dsigma = (1 / sigma - d^2 / sigma^3) / B_global.  sums of both: [0] the optimised loss,
+ *               [6] sum se (its per-frame maximum in maxes[0]), [3] sum se / A, [11] sum nll, [2] = [8] the policy's entropy, [4] = [5] =
+ *               count (the report's ESS entry reads 1), [10] count, the rest and maxes[1] zero -- grl_trpl_loss_values(entropy_coef = 0):
+ *               out14[0] = out14[12] = loss, [1] nn.MSELoss (se / A, in either mode), [5] mean nll, [6] = [13] mean se, [7] max se,
+ *               [10] entropy,
  *               adv_local: 1 = the advantage statistics are summed inside the kernel from this launch's batch (one rank), 0 = adv_stats}
  * sums fp64[12]: loss_objective, loss_trust_region, entropy(dist), loss_critic, sum w, sum w^2, mean_constraint,
  *               cov_constraint, entropy(p), entropy_diff, count, kl  (per-frame sums; divide by count);  maxes u32[2] (float bits) */

@@ -14,6 +14,7 @@ ms / step of each (``<variant>_ms_per_step``, ``<variant>_min_max_ms``), B / A (
   python tools/step_ab.py transformer transformer_hip --sizes 64 512 4096 --reverse-blocks --eager --count-calls       # both as eager steps
   python tools/step_ab.py transformer transformer_hip --sizes 64 512 4096 --reverse-blocks                             # the HIP variant replayed
   python tools/step_ab.py hepi_attn hepi_attn_gate_hip --sizes 512 4096 --reverse-blocks --build-order both --calibration --count-calls
+  python tools/step_ab.py trpl bc --sizes 4096 --blocks 8 --reverse-blocks --build-order both      # the behaviour-cloning step (bc.BCUpdater)
 
 The updater built SECOND in a process has measured 3.6 % slower at 4096 frames whatever it runs (entropy control): a
 difference of that size is read from both build orders (--build-order both) and from blocks whose order is reversed every round."""
@@ -54,6 +55,9 @@ VARIANTS = {
     # under autograd, the accumulate mode of the gradient fold) and inside the softmax-aggregation launches (csrc/grl_gate.h, overwrite mode)
     "hepi_attn": dict(cfg=dict(aggr="AttentionalAggregation")),
     "hepi_attn_gate_hip": dict(cfg=dict(aggr="AttentionalAggregation", attention_gate="hip")),
+    # the behaviour-cloning step on the same workload (bc.BCUpdater: the actor's lane alone, no critic, no projection): ``bc`` = BCLoss's objective
+    "bc": dict(bc="mse"),
+    "bc_nll": dict(bc="nll"),
 }
 HEPI_BASE = dict(only_upper_hemisphere=True, output_dim=2, output_dim_vec=2)
 
@@ -70,6 +74,9 @@ def make(variant, B, dev, use_graph=True):
     batch = {k: v.to(dev) for k, v in batch.items()}
     with torch.no_grad():
         actor.forward_diag(*[batch[k] for k in loss.in_features], train=True)   # calibration
+    if "bc" in VARIANTS[variant]:
+        from geometry_rl_amd import bc
+        return bc.BCUpdater(bc.BCLoss(actor, objective=VARIANTS[variant]["bc"]), use_graph=use_graph), batch
     return agent.PolicyUpdater(loss, use_graph=use_graph, **dict(agent.updater_kwargs(cfg), **VARIANTS[variant].get("upd", {}))), batch
 
 
@@ -141,7 +148,8 @@ def main():
             for _ in range(a.warmup):
                 issue[v]()
             # (an updater whose mode says "eager" -- asked for with --eager, or the stock-torch transformer actor -- records nothing)
-            assert not upd.mode.startswith("graph") or (upd._epoch if a.launch_steps else upd._program) is not None, "the step was not recorded"
+            recorded = upd._epoch if a.launch_steps else (getattr(upd, "_program", None) or getattr(upd, "_programs", None))
+            assert not upd.mode.startswith("graph") or recorded, "the step was not recorded"
         torch.cuda.synchronize()
         times = {v: [] for v in order}
         for r in range(a.blocks):
@@ -157,7 +165,7 @@ def main():
                 e1.synchronize()
                 times[v].append(e0.elapsed_time(e1) / (a.steps * U))
         for upd, _ in runs.values():
-            if upd.track_stats:
+            if getattr(upd, "track_stats", False):
                 assert upd.stats_read()["updates"] == upd.steps, (upd.stats_read()["updates"], upd.steps)
         if a.graphs:
             extra["graphs_per_step"] = {v: sum(e.kind == "graph" for e in runs[v][0]._program) for v in order}
@@ -167,6 +175,9 @@ def main():
                           **{f"{v}_mode": runs[v][0].mode.split(" ")[0] for v in order},
                           **{f"{v}_ms_per_step": round(med[v], 4) for v in med},
                           **{f"{v}_min_max_ms": [round(min(t), 4), round(max(t), 4)] for v, t in times.items()},
+                          # what two identical runs differ by in this process: a variant's even-numbered blocks against its odd-numbered ones
+                          **{f"{v}_even_minus_odd_blocks_us": round(1000.0 * (statistics.median(t[0::2]) - statistics.median(t[1::2])), 2)
+                             for v, t in times.items() if len(t) > 1},
                           f"{a.b}_over_{a.a}": round(med[a.b] / med[a.a], 4),
                           f"{a.b}_minus_{a.a}_us": round(1000.0 * (med[a.b] - med[a.a]), 2), **extra}), flush=True)
 
