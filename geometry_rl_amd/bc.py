@@ -345,6 +345,61 @@ class BCUpdater:
         hip.call("grl_trpl_loss_values", sums, maxes, 0.0, o14)
         return dict(m.report_dict(o14), loc=loc, sigma=sigma)
 
+    # ---- the whole training state (checkpoint.py), as PolicyUpdater's on the actor alone
+    def _saved_hyper(self) -> dict:
+        return dict(eps=self.eps, betas=self.betas, clip=self.clip, max_norm=self.max_norm, objective=self.loss_module.objective)
+
+    def state_dict(self) -> dict:
+        """Buffers, moments, the ONE step count, the rate, the running sums, the actor's module state (latches, frozen parameters), its
+        noise words and position-built topologies: CPU tensors and plain values.  Synchronises once."""
+        from . import checkpoint as ck
+        if self._released:
+            raise RuntimeError("this BCUpdater was released: its buffers no longer hold the actor's parameters")
+        actor = self.loss_module.actor_network
+        if self.flat.is_cuda:
+            torch.cuda.current_stream().synchronize()
+        if int(self.step_dev) != self.steps:
+            raise RuntimeError(f"the device-side step count is {int(self.step_dev)}, the host's {self.steps}: an update failed while it was "
+                               "issued; this state cannot be resumed bit for bit")
+        cpu = lambda t: t.detach().cpu().clone()
+        return {"version": ck.VERSION, "layout": ck.layout([("actor.", actor)], self.flat), "flat": cpu(self.flat), "exp_avg": cpu(self.exp_avg),
+                "exp_avg_sq": cpu(self.exp_avg_sq), "steps": int(self.steps), "lr": self._lr, "hyper": self._saved_hyper(),
+                "algorithm": {"loss": type(self.loss_module).__name__, "objective": self.loss_module.objective}, "stats": cpu(self.stats),
+                "actor": {k: cpu(v) for k, v in actor.state_dict().items()}, "data": {"actor": ck.data_state(actor.hyper_data)}}
+
+    def load_state_dict(self, sd: dict) -> None:
+        """In place (``copy_``; the actor through ``load_state_dict``, which writes through its views of ``flat``); the recorded programs
+        stay.  ``steps`` and ``step_dev`` take the one saved count (Adam's bias correction reads the device's).  Raises ValueError before
+        anything is written when the layout, the objective, a hyper-parameter or the format version differ."""
+        from . import checkpoint as ck
+        ck.check_version(sd, "BCUpdater.load_state_dict")
+        if self._released:
+            raise RuntimeError("this BCUpdater was released: build a new one and load into it")
+        actor = self.loss_module.actor_network
+        if sd["layout"] != ck.layout([("actor.", actor)], self.flat) or sd["flat"].numel() != self.flat.numel():
+            raise ValueError(f"the saved parameter layout is not this updater's ({len(sd['layout'])} parameters, {sd['flat'].numel()} floats "
+                             f"against {len(self.params)}, {self.flat.numel()})")
+        odd = ck.differing(sd["hyper"], self._saved_hyper())
+        if odd:
+            raise ValueError("the saved run's hyper-parameters differ: " + ", ".join(f"{k} saved {sd['hyper'].get(k)!r}, here "
+                             f"{self._saved_hyper().get(k)!r}" for k in odd))
+        for bad in (ck.module_mismatch(actor, sd["actor"], "actor"), actor.hyper_data.topology_mismatch(sd["data"]["actor"]["topology"])):
+            if bad:
+                raise ValueError(bad)
+        with torch.no_grad():
+            actor.load_state_dict(sd["actor"])
+            self.flat.copy_(sd["flat"])
+            self.exp_avg.copy_(sd["exp_avg"])
+            self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+            self.steps = int(sd["steps"])
+            self.step_dev.fill_(self.steps)
+            self._lr = float(sd["lr"])
+            self.lr_dev.fill_(self._lr)
+            self.stats.copy_(sd["stats"])
+            ck.load_data_state(actor.hyper_data, sd["data"]["actor"], self.flat.device)
+        if not ck.settle_calibration(actor):
+            self._eager_sizes = set()   # (saved before the first training forward: the next step calibrates, which no capture allows)
+
     def release(self):
         """End of the cloning: every parameter becomes an ordinary tensor again (its values kept, its ``.grad`` dropped) and the recorded
         programs are forgotten.  A ``PolicyUpdater`` built afterwards on the same actor finds the cloned values."""
@@ -395,6 +450,7 @@ class BehaviorCloner:
             raise ValueError(f"env-aligned sampling needs mini_batch_size ({self.mini_batch_size}) to be a multiple of the number of "
                              f"training environments ({self.n_train} of {self.N})")
         self.sampling, self.drop_last, self.seed, self.gen = sampling, bool(drop_last), seed, None
+        self.epochs_done = 0   # epochs fitted so far, over every ``fit`` call (and a resumed run's: state_dict)
         self.device = next(iter(data.data.values())).device
 
     def _generator(self):
@@ -429,6 +485,25 @@ class BehaviorCloner:
             out.pop()
         return out
 
+    def _settings(self) -> dict:
+        return dict(N=self.N, T=self.T, n_train=self.n_train, mini_batch_size=self.mini_batch_size, sampling=self.sampling,
+                    drop_last=self.drop_last)
+
+    def state_dict(self) -> dict:
+        """The shuffling generator (or its seed while nothing was drawn), the train / held-out split and the number of epochs fitted."""
+        from . import checkpoint as ck
+        return {"version": ck.VERSION, "settings": self._settings(), "epochs": int(self.epochs_done),
+                "generator": ck.generator_state(self.gen, self.seed)}
+
+    def load_state_dict(self, sd: dict) -> None:
+        from . import checkpoint as ck
+        ck.check_version(sd, "BehaviorCloner.load_state_dict")
+        odd = ck.differing(sd["settings"], self._settings())
+        if odd:
+            raise ValueError(f"the saved cloner's data or split differ at {odd}: saved {sd['settings']}, here {self._settings()}")
+        self.gen, self.seed = ck.restore_generator(sd["generator"], self.device)
+        self.epochs_done = int(sd["epochs"])
+
     def evaluate(self) -> Dict[str, float]:
         """The report on the held-out environments as Python floats (synchronises); {} when nothing is held out."""
         if self.n_train == self.N:
@@ -449,6 +524,7 @@ class BehaviorCloner:
             means = upd.stats_read()   # (the epoch's synchronisation)
             hist["loss"].append(means.get("loss_bc"))
             hist["train"].append(means)
+            self.epochs_done += 1
             if eval_every and epoch > 0 and epoch % eval_every == 0:
                 hist["eval"][epoch] = self.evaluate()
         return hist

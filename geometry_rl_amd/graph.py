@@ -12,7 +12,7 @@ Differences from the reference that do not change any output:
 The topology is built once per batch size and reused for every later batch of that size, like the reference cache
 (rigid_tasks_data.py:254-255).
 """
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, fields
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -300,6 +300,67 @@ class HyperData:
         same environment (``rollout.RolloutDriver`` samples env-aligned for exactly this reason).  Call this before feeding a batch
         of a cached size that breaks the invariant (another env set, shuffled rows, another data-parallel shard offset)."""
         self._cache.clear()
+
+    # ---- cached topology as training state (checkpoint.py).  The kNN neighbourhoods of a size are those of the FIRST batch of that size (the
+    #      invariant above): a run continued in a fresh process would build them from whichever minibatch it meets first, and every later
+    #      update would walk other edges than the run that was never interrupted.
+    def _topology_reads_positions(self) -> bool:
+        """Does a cached topology depend on more than the per-row point counts?  Not for a dense (critic) object, which builds no edges, nor
+        for cloth's fully connected hole boundary without nearest-point task edges: those rebuild bit for bit from any env-aligned batch."""
+        if self.concat_input_vector:
+            return False
+        return self.spec.family != "cloth" or getattr(self.spec, "knn_to_actuators_k", -1) > 0
+
+    def topology_state(self) -> dict:
+        """{batch size: the cached topology as CPU tensors and plain values} of every size whose topology was built from a batch's
+        positions ({} where none is: ``_topology_reads_positions``).  What ``build_data`` derives lazily (``all_order`` ...) is left out."""
+        if not self._topology_reads_positions():
+            return {}
+        cpu = lambda v: v.detach().cpu() if torch.is_tensor(v) else v
+        out = {}
+        for B, topo in self._cache.items():
+            edges = {self.spec.edge_types.index(et): {f.name: cpu(getattr(es, f.name)) for f in fields(es)} for et, es in topo["edges"].items()}
+            nat = topo.get("natural_id")
+            out[int(B)] = dict(n_per=dict(topo["n_per"]), main=topo["main"], gather_main=cpu(topo["gather_main"]), n_main=int(topo["n_main"]),
+                               edges=edges, G=int(topo["G"]), n_valid=cpu(topo["n_valid"]), permuted=bool(topo.get("permuted", False)),
+                               natural_id=None if nat is None else cpu(nat[topo["main"]]))
+        return out
+
+    def topology_mismatch(self, state: dict) -> Optional[str]:
+        """A saved topology against the one already cached for its size: None where none is cached or they are the same edges; else what
+        differs.  A cached topology is never replaced (recorded programs read its arrays): ``reset_cache()`` first."""
+        for B, s in state.items():
+            topo = self._cache.get(int(B))
+            if topo is None:
+                continue
+            same = (torch.equal(topo["gather_main"].cpu(), s["gather_main"])
+                    and {self.spec.edge_types.index(et) for et in topo["edges"]} == set(s["edges"])
+                    and all(torch.equal(es.src_d.cpu(), s["edges"][self.spec.edge_types.index(et)]["src_d"])
+                            and torch.equal(es.rowptr_d.cpu(), s["edges"][self.spec.edge_types.index(et)]["rowptr_d"])
+                            for et, es in topo["edges"].items()))
+            if not same:
+                return (f"the topology cached for batch size {B} has other nodes or edges than the saved one (it was built from another "
+                        "first batch): call reset_cache() on the data object and reset_graph() on the updater before loading")
+        return None
+
+    def load_topology_state(self, state: dict, device) -> None:
+        """Install the saved topologies of the sizes that have none cached (``topology_mismatch`` has compared the others)."""
+        dev = torch.device(device)
+        to = lambda v: v.to(dev) if torch.is_tensor(v) else v
+        n_types = len(self.spec.node_types)
+        for B, s in state.items():
+            if int(B) in self._cache:
+                continue
+            main, n_per = s["main"], dict(s["n_per"])
+            edges = {self.spec.edge_types[i]: ops.EdgeSet(**{k: to(v) for k, v in es.items()}) for i, es in s["edges"].items()}
+            one_hot = {}
+            for t in self.node_type_list:
+                oh = torch.zeros(s["n_main"] if t == main else int(B) * n_per[t], n_types, device=dev)
+                oh[:, self.spec.node_types.index(t)] = 1
+                one_hot[t] = oh
+            self._cache[int(B)] = dict(n_per=n_per, main=main, gather_main=to(s["gather_main"]), n_main=s["n_main"], edges=edges, one_hot=one_hot,
+                                       G=s["G"], n_valid=to(s["n_valid"]), permuted=s["permuted"],
+                                       natural_id=None if s["natural_id"] is None else {main: to(s["natural_id"])})
 
     def check_topology(self, *args) -> None:
         """Raise if the batch's per-row valid point counts differ from those the cached topology of this batch size was built

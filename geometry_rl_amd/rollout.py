@@ -25,7 +25,7 @@ from typing import Dict, Iterator, Optional
 
 import torch
 
-from . import agent as _agent, hip as _hip, updater as _updater
+from . import agent as _agent, checkpoint as _ckpt, hip as _hip, updater as _updater
 from .program import capture
 
 PPO_KEYS = ("action", "loc", "var", "sample_log_prob", "state_value", "advantage", "value_target")
@@ -98,6 +98,20 @@ class EpisodeStats:
                   episode_reward, step_count, self.sums, N, T)
         return episode_reward, step_count
 
+    def state_dict(self) -> dict:
+        """The running return and length of every environment and the last scan's sums (episodes continue across rollouts, and across a
+        resumed run): CPU tensors."""
+        return {"version": _ckpt.VERSION, "N": self.N, "ret_state": self.ret_state.detach().cpu().clone(),
+                "len_state": self.len_state.detach().cpu().clone(), "sums": self.sums.detach().cpu().clone()}
+
+    def load_state_dict(self, sd: dict) -> None:
+        _ckpt.check_version(sd, "EpisodeStats.load_state_dict")
+        if sd["N"] != self.N:
+            raise ValueError(f"the saved episode statistics are those of {sd['N']} environments, these of {self.N}")
+        self.ret_state.copy_(sd["ret_state"])
+        self.len_state.copy_(sd["len_state"])
+        self.sums.copy_(sd["sums"])
+
 
 class RolloutDriver:
     def __init__(self, updater: "_updater.PolicyUpdater", spec, gamma: float = 0.99, lmbda: float = 0.95, ppo_epochs: int = 5,
@@ -119,6 +133,21 @@ class RolloutDriver:
                              "ragged per-sample point counts (object_num_points / links_num_points): pass allow_stale_topology=True to "
                              "reproduce the reference quirk")
         self.sampling = sampling
+
+    def _settings(self) -> dict:
+        return dict(gamma=self.gamma, lmbda=self.lmbda, ppo_epochs=self.ppo_epochs, mini_batch_size=self.mini_batch_size, sampling=self.sampling)
+
+    def state_dict(self) -> dict:
+        """The sampler's generator -- wherever in its sequence it stands, also between two launches of an epoch -- or the seed while no
+        minibatch has been drawn yet; the settings ride along and are compared on loading."""
+        return {"version": _ckpt.VERSION, "settings": self._settings(), "generator": _ckpt.generator_state(self.gen, self.seed)}
+
+    def load_state_dict(self, sd: dict) -> None:
+        _ckpt.check_version(sd, "RolloutDriver.load_state_dict")
+        odd = _ckpt.differing(sd["settings"], self._settings())
+        if odd:
+            raise ValueError(f"the saved driver's settings differ at {odd}: saved {sd['settings']}, here {self._settings()}")
+        self.gen, self.seed = _ckpt.restore_generator(sd["generator"], self.updater.flat.device)
 
     # ---- train.py:134-140,249-251: critic over the T+1 frames of every environment, then the shifted GAE scan
     @torch.no_grad()
@@ -245,6 +274,26 @@ class PolicyActor:
         self.train = bool(train)
         self.gen, self.seed = None, seed
         self._graph, self._static, self._out, self._calls = None, None, None, 0
+        self._resumed = False   # load_state_dict: the next call runs eagerly, like a first call (it may be the process's first)
+
+    def state_dict(self) -> dict:
+        """The sampling generator and the number of calls.  The policy's own state (weights, latches, noise words, topologies) is the
+        updater's part of a training state."""
+        return {"version": _ckpt.VERSION, "deterministic": bool(self.deterministic), "calls": int(self._calls),
+                "generator": _ckpt.generator_state(self.gen, self.seed)}
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Drops the one recorded graph and takes a NEW generator at the saved state (a generator that is registered with a capture is not
+        reliably reseated).  The next call runs eagerly, as a first call does -- in a fresh process it IS the first: the latches are read,
+        a missing topology is built, the noise words are made, none of which a capture allows -- and the call after it records again.
+        Eager and replayed passes launch the same kernels on the same draws: the samples are those of the run that was not interrupted."""
+        _ckpt.check_version(sd, "PolicyActor.load_state_dict")
+        if sd["deterministic"] != bool(self.deterministic):
+            raise ValueError(f"the saved actor was deterministic={sd['deterministic']}, this one is deterministic={self.deterministic}")
+        dev = next(self.policy.parameters()).device
+        self.gen, self.seed = _ckpt.restore_generator(sd["generator"], dev)
+        self._graph, self._static, self._out = None, None, None
+        self._calls, self._resumed = int(sd["calls"]), True
 
     def _pass(self, obs):
         loc, sigma = self.policy.forward_diag(*[obs[k] for k in self.spec.in_features], train=self.train)
@@ -262,7 +311,8 @@ class PolicyActor:
             self.gen = torch.Generator(device=dev)
             self.gen.manual_seed(self.seed)
         self._calls += 1
-        if not self.use_graph or self._calls == 1:
+        resumed, self._resumed = self._resumed, False
+        if not self.use_graph or self._calls == 1 or resumed:
             return self._pass(obs)
         if self._graph is None:
             self._static = {k: obs[k].clone() for k in self.spec.in_features}

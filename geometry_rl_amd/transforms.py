@@ -35,6 +35,33 @@ class ObservationNormalizer:
                  self.state[key], self._scratch[K], y_norm, y_clip)
         return y_norm, y_clip
 
+    def _settings(self) -> dict:
+        return dict(vector_keys=list(self.vector_keys), scalar_keys=list(self.scalar_keys), decay=self.decay, eps=self.eps, low=self.low,
+                    high=self.high)
+
+    def state_dict(self) -> dict:
+        """The running statistics ``[sum | ssq | count]`` of every group seen so far (CPU tensors) and the settings they were gathered under."""
+        from . import checkpoint as ck
+        return {"version": ck.VERSION, "settings": self._settings(), "state": {k: v.detach().cpu().clone() for k, v in self.state.items()}}
+
+    def load_state_dict(self, sd: dict) -> None:
+        """In place where a group's state exists (same width), else a new tensor on this normaliser's device."""
+        from . import checkpoint as ck
+        ck.check_version(sd, "ObservationNormalizer.load_state_dict")
+        odd = ck.differing(sd["settings"], self._settings())
+        if odd:
+            raise ValueError(f"the saved normaliser's settings differ at {odd}: saved {sd['settings']}, here {self._settings()}")
+        bad = [k for k, v in sd["state"].items() if k in self.state and self.state[k].shape != v.shape]
+        if bad:
+            raise ValueError(f"the saved statistics of {bad} have another width than this normaliser's")
+        for k, v in sd["state"].items():
+            if k in self.state:
+                self.state[k].copy_(v)
+            else:
+                self.state[k] = v.to(self.device)
+        for k in [k for k in self.state if k not in sd["state"]]:
+            del self.state[k]   # (a group the saved run had not seen yet starts from zero, as it did there)
+
     def __call__(self, obs: Dict[str, torch.Tensor], update: bool = True) -> Dict[str, torch.Tensor]:
         """obs groups [B, D] (flat, as the loss consumes them) -> same dict with ``norm_<vector key>`` added, scalars normalised in
         place of the raw values (VecNorm without out_keys) and every group clipped."""

@@ -1076,6 +1076,134 @@ class PolicyUpdater:
         self._drop_recordings()
         self._eager_sizes, self.form_by_size, self.form_times = set(), {}, {}
 
+    # ---- the whole training state (checkpoint.py): what makes update n + 1 what it is, most of it outside the modules' state_dict()
+    def _algorithm(self) -> dict:
+        """The objective as plain values: the loss class, the projection's type and flags (a state is loaded into the same algorithm only)."""
+        m = self.loss_module
+        proj = getattr(m, "projection", None)
+        out = {"loss": type(m).__name__, "projection": None}
+        if proj is not None:
+            out.update(projection=proj.proj_type, scale_prec=proj.scale_prec, entropy_schedule=proj.entropy_schedule_type,
+                       entropy_eq=proj.entropy_eq, entropy_first=proj.entropy_first, entropy_control=bool(getattr(m, "entropy_control", False)))
+        return out
+
+    def _saved_hyper(self) -> dict:
+        return dict(self._hyper, anneals_lr=self.anneals_lr, anneals_eps=self.anneals_eps, total_network_updates=self.total_network_updates,
+                    track_stats=self.track_stats)
+
+    def _data_objects(self) -> dict:
+        """The ``HyperData`` of either network: each keeps noise words and cached topologies."""
+        m = self.loss_module
+        hds = {"actor": getattr(m.actor_network, "hyper_data", None),
+               "critic": getattr(getattr(m.critic_network, "_network1", None), "hyper_data", None)}
+        return {k: hd for k, hd in hds.items() if hd is not None}
+
+    def state_dict(self) -> dict:
+        """Everything the next update depends on, as CPU tensors and plain Python values (``checkpoint.save`` writes it; INTEGRATION.md
+        "Saving and resuming a run" lists it).  Joins the lanes and synchronises once; call it between any two ``step`` / ``run_minibatches`` calls.
+        The step count is ONE number, the host's: a state whose device-side count differs (an update that raised while it was issued) is
+        refused, it cannot be continued bit for bit."""
+        from . import checkpoint as ck
+        m = self.loss_module
+        self.join_lanes()
+        if self.flat.is_cuda:
+            torch.cuda.current_stream().synchronize()
+        if int(self.step_dev) != self.steps:
+            raise RuntimeError(f"the device-side step count is {int(self.step_dev)}, the host's {self.steps}: an update failed while it was "
+                               "issued; this state cannot be resumed bit for bit")
+        cpu = lambda t: t.detach().cpu().clone()
+        proj = getattr(m, "projection", None)
+        ent = getattr(proj, "initial_entropy", None)
+        return {
+            "version": ck.VERSION,
+            "layout": ck.layout([("actor.", m.actor_network), ("critic.", m.critic_network)], self.flat), "n_actor": int(self.n_actor),
+            "flat": cpu(self.flat), "exp_avg": cpu(self.exp_avg), "exp_avg_sq": cpu(self.exp_avg_sq),
+            "steps": int(self.steps), "lr": self._lr, "base_lr": self._base_lr,
+            "hyper": self._saved_hyper(), "algorithm": self._algorithm(),
+            "device_scalars": {k: cpu(t) for k, t in m.device_scalars.items()},
+            "initial_entropy": None if ent is None else cpu(torch.as_tensor(ent)),
+            "stats": {"actor": cpu(self.stats_actor), "critic": cpu(self.stats_critic), "one_stream": bool(self._stats_one_stream)} if self.track_stats else None,
+            "actor": {k: cpu(v) for k, v in m.actor_network.state_dict().items()},
+            "critic": {k: cpu(v) for k, v in m.critic_network.state_dict().items()},
+            "data": {k: ck.data_state(hd) for k, hd in self._data_objects().items()},
+            "rank": int(self.rank), "world": int(m.world_size),
+            "form_by_size": {int(k): str(v) for k, v in self.form_by_size.items()},
+        }
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Continue the run ``sd`` (``state_dict()``) was taken from: every value is restored IN PLACE, into the storage the recorded programs
+        read (``copy_``; the modules through ``load_state_dict``, which writes through their views of ``flat``), stream-ordered on the
+        caller's stream behind a join of the lanes.  Nothing recorded is dropped -- ``_program``, ``_static`` and ``_epoch`` stay the
+        objects they were -- and the next update is bit for bit the one the saved run would have issued.
+
+        The one saved step count goes to ``steps``, ``step_dev``, ``step_dev_c`` and ``lane_flag`` alike.  They must never disagree: the
+        recorded Adam launches take their bias correction from ``step_dev`` (actor) and ``step_dev_c`` (critic), a gated critic lane waits
+        until ``lane_flag`` -- which the actor's lane sets to ``step_dev`` -- reaches ``step_dev_c + 1``, and the host forms the entropy
+        bounds and the (lr, clip epsilon) table from ``steps``.  A critic count ahead of the actor's leaves the gate waiting for a signal
+        that does not come (``_advance`` explains the same for the host's count); one behind it releases the lane early and gives the two
+        networks different bias corrections; a host count apart from the device's schedules other rates than Adam's step belongs to.
+
+        Raises ValueError BEFORE anything is written when the layout fingerprint, the algorithm, a hyper-parameter, ``rank`` / ``world`` or
+        the format version differ from this updater's: a resumed run with other settings is another run.  Change settings after loading,
+        through the properties.  ``form_by_size`` is advisory: taken only while this updater has measured nothing itself."""
+        from . import checkpoint as ck
+        m = self.loss_module
+        ck.check_version(sd, "PolicyUpdater.load_state_dict")
+        mine = ck.layout([("actor.", m.actor_network), ("critic.", m.critic_network)], self.flat)
+        if sd["layout"] != mine or sd["n_actor"] != self.n_actor or sd["flat"].numel() != self.flat.numel():
+            odd = [a[0] for a, b in zip(sd["layout"], mine) if a != b][:3]
+            raise ValueError(f"the saved parameter layout is not this updater's ({len(sd['layout'])} parameters, {sd['flat'].numel()} floats, "
+                             f"n_actor {sd['n_actor']} against {len(mine)}, {self.flat.numel()}, {self.n_actor}; first differences {odd})")
+        if sd["algorithm"] != self._algorithm():
+            raise ValueError(f"the saved run's algorithm differs at {ck.differing(sd['algorithm'], self._algorithm())}: saved {sd['algorithm']}, "
+                             f"this updater {self._algorithm()}")
+        odd = ck.differing(sd["hyper"], self._saved_hyper())
+        if odd:
+            raise ValueError("the saved run's hyper-parameters differ: " + ", ".join(f"{k} saved {sd['hyper'].get(k)!r}, here "
+                             f"{self._saved_hyper().get(k)!r}" for k in odd) + " (load into an updater built alike, then change the setting)")
+        if (sd["rank"], sd["world"]) != (self.rank, m.world_size):
+            raise ValueError(f"the state is rank {sd['rank']} of {sd['world']}, this updater rank {self.rank} of {m.world_size}: every rank "
+                             "loads its own file, under the world size it was saved with")
+        if set(sd["device_scalars"]) != set(m.device_scalars) or set(sd["data"]) != set(self._data_objects()):
+            raise ValueError(f"the saved loss scalars {sorted(sd['device_scalars'])} / data objects {sorted(sd['data'])} are not this updater's")
+        for bad in (ck.module_mismatch(m.actor_network, sd["actor"], "actor"), ck.module_mismatch(m.critic_network, sd["critic"], "critic"),
+                    *[hd.topology_mismatch(sd["data"][k]["topology"]) for k, hd in self._data_objects().items()]):
+            if bad:
+                raise ValueError(bad)
+        # ---- nothing above has written; everything below writes in place
+        self.join_lanes()
+        dev = self.flat.device
+        with torch.no_grad():
+            m.actor_network.load_state_dict(sd["actor"])    # (through the views of ``flat``; the policy re-inspects its latches: they are saved true)
+            m.critic_network.load_state_dict(sd["critic"])
+            self.flat.copy_(sd["flat"])
+            self.exp_avg.copy_(sd["exp_avg"])
+            self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+            k = int(sd["steps"])
+            self.steps = m._global_steps = k
+            for t in (self.step_dev, self.step_dev_c, self.lane_flag):
+                t.fill_(k)
+            self._lr, self._base_lr = float(sd["lr"]), float(sd["base_lr"])
+            self.lr_dev.fill_(self._lr)
+            for name, t in m.device_scalars.items():
+                t.copy_(sd["device_scalars"][name])
+            proj = getattr(m, "projection", None)
+            if proj is not None:
+                ent = sd["initial_entropy"]
+                proj.initial_entropy = None if ent is None else ent.to(dev)
+                proj._init_host_src = proj._init_host = None   # (the cached host copy belongs to the value that was there)
+            if self.track_stats:
+                self.stats_actor.copy_(sd["stats"]["actor"])
+                self.stats_critic.copy_(sd["stats"]["critic"])
+                self._stats_one_stream = bool(sd["stats"]["one_stream"])
+            for name, hd in self._data_objects().items():
+                ck.load_data_state(hd, sd["data"][name], dev)
+        self._calib_synced = True   # (the latches and the kernels are the saved run's: no replica calibrates again)
+        if not ck.settle_calibration(m.actor_network):
+            self._eager_sizes = set()   # (saved before the first training forward: the next step calibrates, which no capture allows)
+        if not self.form_by_size:
+            self.form_by_size = dict(sd["form_by_size"])
+
     def _check_calibrated(self):
         """Data parallel: the first training forward of a fresh actor re-initialises the conv kernels from rank-local data
         (conv.py:104-105).  Let it happen once, on every rank, BEFORE the first update, then adopt rank 0's result -- otherwise each
