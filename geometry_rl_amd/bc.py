@@ -7,17 +7,18 @@ loop, the pre-training half of its "clone, then fine-tune with TRPL" workflow --
     BehaviorCloner  the driver over a recorded rollout: the reference's 80/20 split, its shuffled minibatches, per-epoch mean loss.
 
 What is NOT here is the reference's evaluation (``AgentBuilder.eval_model``, behavior_cloning.py:131-137): it steps the simulator.  The
-driver reports the objective on the held-out fifth of the demonstrations instead.  ``PolicyUpdater``, ``RolloutDriver`` and
-``build_agent`` are untouched; ``BCUpdater.release()`` hands the cloned actor over to a ``PolicyUpdater``."""
+driver reports the objective on the held-out fifth of the demonstrations instead.  ``BCUpdater`` is a ``flat.FlatUpdater`` like
+``PolicyUpdater`` (layout, overwrite rule, Adam, static inputs, checkpoint share: flat.py), ``BehaviorCloner`` draws with
+``RolloutDriver``'s sampler (rollout.py); ``BCUpdater.release()`` hands the cloned actor over to a ``PolicyUpdater``."""
 from typing import Dict, Optional
 
 import torch
 
 from . import hip, ops
-from .program import Entry, execute, record
-from .rollout import RolloutBuffer
+from .flat import FlatUpdater, _job_arrays, cpu
+from .program import Entry, record
+from .rollout import RolloutBuffer, check_sampling, env_aligned_rows, seeded_generator
 from .trpl import LossDict, _as_batch, _InjectGrad, _LossBase, _TensorDict, _unwrap
-from .updater import _job_arrays
 
 OBJECTIVES = ("mse", "nll")
 
@@ -84,33 +85,23 @@ class BCLoss(_LossBase):
         return LossDict(out, **extra)
 
 
-def fold_overwrite(actor) -> bool:
-    """PolicyUpdater's rule for writing (not accumulating) the leaf gradients with the one fold launch: every leaf gradient of the pass
-    comes through the fold queue -- not with a post_fc (transformer) actor, whose unused parameters no fold ever writes, nor with an
-    attention gate that runs as torch modules (torch's AccumulateGrad adds into .grad)."""
-    gnn = getattr(actor, "gnn", None)
-    return (not getattr(actor, "post_fc", False)
-            and not any(getattr(mod, "attention", False) and getattr(mod, "gate_kernels", "torch") == "torch"
-                        for mod in (gnn.modules() if gnn is not None else [])))
-
-
-class BCUpdater:
+class BCUpdater(FlatUpdater):
     """One behaviour-cloning update of a ``BCLoss``: behavior_cloning.py:96-99,113-123 -- ``torch.optim.Adam(actor.parameters(), lr=5e-4)``
     with torch's defaults (NB ``eps=1e-8``, not the RL loop's 1e-5), zero_grad, backward, step -- on the ACTOR's trainable parameters alone.
 
-    Layout as PolicyUpdater's: parameters, gradients and both moments are flat fp32 buffers, every parameter starts 16-byte aligned, and
-    ``p.data`` / ``p.grad`` are views of them.  One step, in order: ``forward_diag(train=True)`` (calibration on the first call, training
+    The layout is ``FlatUpdater``'s: parameters, gradients and both moments are flat fp32 buffers, every parameter starts 16-byte aligned,
+    and ``p.data`` / ``p.grad`` are views of them.  One step, in order: ``forward_diag(train=True)`` (calibration on the first call, training
     noise as in the RL step; the step count rides on the feature launch), the loss launch with its fold deferred, ``autograd.backward``,
     then the tail -- the queued gradient folds, Adam with the step count in device memory and the report as ONE launch
-    (``ops.fold_adam_report``) where the folds overwrite and nothing is clipped; else the fold launch (overwrite under PolicyUpdater's
-    rule, accumulate into the zeroed buffer otherwise), ``grl_clip_coef``, ``grl_adam_step_dev`` and the report -- and one
+    (``ops.fold_adam_report``) where the folds overwrite and nothing is clipped; else the fold launch (overwrite under
+    ``flat.fold_overwrite``, accumulate into the zeroed buffer otherwise), ``grl_clip_coef``, ``grl_adam_step_dev`` and the report -- and one
     ``grl_stats_accumulate`` that adds the report to running fp64 sums (``stats_reset`` / ``stats_read``: means without a host
     synchronisation per step).  Every launch is an existing entry point; the loss launch is grl_trpl_fwd_bwd in mode 8 / 9.
 
     ``use_graph=True``: the first step of a minibatch size runs eagerly (topology, calibration, the overwrite check), from the second on
     the step is ONE single-stream hipGraph per size on static inputs, kept per size (a short last minibatch has its own).  ``step_from``
     gathers the rows by one launch (grl_gather_rows_many) straight into the static inputs.  The stock-torch transformer actor runs
-    eagerly, as in PolicyUpdater.  ``release()`` ends the updater: the parameters become ordinary tensors again (values kept), so a
+    eagerly.  ``release()`` ends the updater: the parameters become ordinary tensors again (values kept), so a
     ``PolicyUpdater`` built afterwards on the same actor lays them out anew and finds the cloned values."""
 
     def __init__(self, loss: BCLoss, lr=5e-4, eps=1e-8, betas=(0.9, 0.999), clip_grad_norm=False, max_grad_norm=1.0, use_graph=True,
@@ -120,43 +111,10 @@ class BCUpdater:
         self.loss_module = loss
         actor = loss.actor_network
         self.eps, self.betas, self.clip, self.max_norm = float(eps), tuple(betas), bool(clip_grad_norm), float(max_grad_norm)
-        self.params = [p for p in actor.parameters() if p.requires_grad]
-        pad4 = lambda k: (k + 3) & ~3   # every parameter starts 16-byte aligned (vector loads in the weight-staging prologues)
-        n = sum(pad4(p.numel()) for p in self.params)
-        dev = self.params[0].device
-        self.flat = torch.zeros(n, device=dev, dtype=torch.float32)
-        self.gflat = torch.zeros(n, device=dev, dtype=torch.float32)
-        off = 0
-        for p in self.params:
-            k = p.numel()
-            self.flat[off:off + k].copy_(p.data.reshape(-1))
-            p.data = self.flat[off:off + k].view_as(p)
-            p.grad = self.gflat[off:off + k].view_as(p)
-            off += pad4(k)
-        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
-        self.steps = 0
-        self.step_dev = torch.zeros(1, device=dev, dtype=torch.int32)   # optimizer step, device side (graph replays)
-        self.lr_dev = torch.full((1,), float(lr), device=dev, dtype=torch.float32)   # read by the recorded Adam launches
-        self._lr = float(lr)
-        self.stats = torch.zeros(15, device=dev, dtype=torch.float64)   # running sums of the 14 report values + the number of updates
-        self.use_graph = bool(use_graph)
-        self.mode = "graph" if use_graph else "eager"
-        if use_graph and getattr(actor, "stock_torch_gnn", False):   # torch's own launches are not capture-safe (PolicyUpdater does the same)
-            self.use_graph, self.mode = False, "eager (stock-torch transformer actor: not recorded)"
-        self._programs, self._eager_sizes = {}, set()   # minibatch size -> (program, static inputs, state)
-        self._fold_overwrite = fold_overwrite(actor)
-        self._overwrite_checked = not self._fold_overwrite
+        super().__init__(actor, [[p for p in actor.parameters() if p.requires_grad]], lr, use_graph)
+        self.stats = torch.zeros(15, device=self.flat.device, dtype=torch.float64)   # running sums of the 14 report values + the number of updates
+        self._programs = {}   # minibatch size -> (program, static inputs, state)
         self._released = False
-
-    @property
-    def lr(self) -> float:
-        return self._lr
-
-    @lr.setter
-    def lr(self, value: float):
-        if float(value) != self._lr:
-            self._lr = float(value)
-            self.lr_dev.fill_(self._lr)
 
     def join_lanes(self):
         """Nothing to join: the program has one lane, the caller's stream (PolicyUpdater's method, for tools that time either updater)."""
@@ -183,19 +141,13 @@ class BCUpdater:
         """Fold + [clip +] Adam + report behind the backward: one launch where that is possible, the separate entry points otherwise."""
         n = self.flat.numel()
         ow = self._fold_overwrite
-        adam = dict(grads=self.gflat, params=self.flat, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, lr_dev=self.lr_dev, betas=self.betas,
-                    eps=self.eps, step_dev=self.step_dev)
         report = dict(slots=fold_.slots, batch=fold_.batch, sums=fold_.sums, maxes=fold_.maxes, ent_coef=0.0, out14=o14)
-        if not self.clip and ow and ops.fold_adam_report(ow, adam, report):
+        if not self.clip and ow and ops.fold_adam_report(ow, self._tail_args(0, n, self.lr_dev, self.step_dev), report):
             return
         ops.flush_deferred_grads(overwrite=ow)
-        coef = None
-        if self.clip:   # behavior_cloning.py clips nothing; the option is PolicyUpdater's (train.py:308-310)
-            sq = torch.empty(1, device=self.flat.device, dtype=torch.float64)
-            coef = torch.empty(1, device=self.flat.device, dtype=torch.float32)
-            hip.call("grl_clip_coef", self.gflat, n, self.max_norm, sq, coef)
-        hip.call("grl_adam_step_dev", self.flat, self.gflat, self.exp_avg, self.exp_avg_sq, n, self.lr_dev, *self.betas, self.eps, self.step_dev,
-                 coef, 1.0)
+        # (behavior_cloning.py clips nothing; the option is PolicyUpdater's, with a workspace of this step's own)
+        sq = torch.empty(1, device=self.flat.device, dtype=torch.float64) if self.clip else None
+        self._adam(0, n, lr=self.lr_dev, step_dev=self.step_dev, sq=sq)
         hip.call("grl_trpl_report", fold_.slots, fold_.batch, fold_.sums, fold_.maxes, 0.0, o14)
 
     def _plan(self, batch, st):
@@ -208,18 +160,12 @@ class BCUpdater:
             obs = [batch[k] for k in m.in_features]
             zw = torch.empty(13, device=self.flat.device, dtype=torch.float64)   # loss sums (12) | maxes (2 x u32)
             with ops.deferred_folds():   # the leaf-gradient folds of the backward are queued and executed by the tail
-                hd.bump_next = self.step_dev   # the step count rides on the actor's feature launch
-                loc, sigma = actor.forward_diag(*obs, train=True)
-                assert hd.bump_next is None, "the actor's feature launch did not take the step count"
+                with self._count_rides(hd):
+                    loc, sigma = actor.forward_diag(*obs, train=True)
                 with torch.no_grad():
                     fold_, _mx, dloc, dsigma = m.launch(loc, sigma, batch["action"], sums=zw[:12], maxes=zw[12:13].view(torch.int32),
                                                         defer_fold=True)
-                ops.TAIL_PRE = {} if ops.FUSE_TAIL_PRE else None   # (lift and fiber-basis backward share one launch: PolicyUpdater._actor_head)
-                try:
-                    torch.autograd.backward([loc, sigma], [dloc, dsigma])
-                    ops.flush_tail_pre()
-                finally:
-                    ops.TAIL_PRE = None
+                ops.actor_backward([loc, sigma], [dloc, dsigma])
                 with torch.no_grad():
                     o14 = torch.empty(14, device=self.flat.device, dtype=torch.float32)
                     self._tail(fold_, o14)
@@ -230,33 +176,6 @@ class BCUpdater:
             st["out"] = dict(m.report_dict(st["o14"]), loc=st["loc"], sigma=st["sigma"])
 
         return [Entry("run", run), Entry("run_host", finish)]
-
-    @staticmethod
-    def _do(e: Entry):
-        if e.kind == "graph":
-            e.item.replay()
-        else:
-            e.item()
-
-    def _execute(self, program):
-        execute(program, self._do, lambda: None, lambda label: None)
-
-    def _eager(self, batch):
-        st, hooks, torch_fed = {}, [], []
-        if not self._overwrite_checked:   # overwrite mode: no leaf gradient may arrive through torch's AccumulateGrad (PolicyUpdater._step)
-            hooks = [p.register_hook(lambda g, i=i: torch_fed.append(i) if g is not None else None) for i, p in enumerate(self.params)]
-        try:
-            self._execute(self._plan(batch, st))
-        finally:
-            for h in hooks:
-                h.remove()
-        if hooks:
-            self._overwrite_checked = True
-            if torch_fed:
-                raise RuntimeError(f"{len(set(torch_fed))} parameter(s) received their gradient from torch autograd instead of the fold queue "
-                                   "while BCUpdater runs in overwrite mode (their .grad is never zeroed): this model must be added to the "
-                                   "exceptions of bc.fold_overwrite")
-        return st["out"]
 
     def _compile(self, batch, B):
         m = self.loss_module
@@ -276,33 +195,20 @@ class BCUpdater:
         """One update on ``batch`` (the actor's observation groups and ``action``, [B, ...]) -> the report: ``loss_bc``, ``mse``, ``nll``,
         ``entropy``, ``max_sq_err`` (device scalars, views of the step's report buffer), ``loc`` and ``sigma``."""
         self._check(batch)
+        return self._counted(1, lambda: self._step(batch))
+
+    def _step(self, batch):
         B = int(batch["action"].shape[0])
-        self.steps += 1
-        try:
-            if not self.use_graph or B not in self._eager_sizes:   # the first step of a size always runs eagerly
-                self._eager_sizes.add(B)
-                return self._eager(batch)
-            if B not in self._programs:
-                self._compile(batch, B)
-            program, static, st = self._programs[B]
-            jobs = []
-            for k, v in static.items():
-                src = batch[k]
-                if src is v:
-                    continue
-                if src.shape != v.shape:
-                    raise ValueError(f"minibatch tensor '{k}' has shape {tuple(src.shape)}, the recorded step of {B} frames {tuple(v.shape)}")
-                if src.dtype != v.dtype or not src.is_contiguous() or src.device != v.device:
-                    v.copy_(src)
-                else:
-                    jobs.append((v.data_ptr(), src.data_ptr(), v.numel() * v.element_size()))
-            for i in range(0, len(jobs), 24):
-                hip.call("grl_copy_many", *_job_arrays(jobs[i:i + 24]))
-            self._execute(program)
+        if self._eager_first(B):
+            st = {}
+            self._first_eager(self._plan(batch, st))
             return st["out"]
-        except BaseException:
-            self.steps -= 1
-            raise
+        if B not in self._programs:
+            self._compile(batch, B)
+        program, static, st = self._programs[B]
+        self._refresh(static, batch, f"the recorded step of {B} frames {{}}")
+        self._execute(program)
+        return st["out"]
 
     def step_from(self, buf: RolloutBuffer, idx: torch.Tensor) -> Dict[str, torch.Tensor]:
         """One update on the minibatch made of rows ``idx`` (device int64 [B]) of a device-resident ``RolloutBuffer``.  With a recorded
@@ -311,9 +217,8 @@ class BCUpdater:
         B = int(idx.numel())
         if self.use_graph and B in self._programs:
             static = self._programs[B][1]
-            src = [buf.flat(k) for k in keys]
-            if all(static[k].dtype == v.dtype and static[k][0].numel() == v.shape[1] for k, v in zip(keys, src)):
-                jobs = [(static[k].data_ptr(), v.data_ptr(), v.shape[1] * v.element_size()) for k, v in zip(keys, src)]
+            jobs = self._gather_jobs(static, buf, keys)
+            if jobs is not None:
                 hip.call("grl_gather_rows_many", *_job_arrays(jobs), idx, B)
                 return self.step(static)
         return self.step(buf.rows(idx, keys))
@@ -321,10 +226,7 @@ class BCUpdater:
     def run_minibatches(self, buf: RolloutBuffer, idx_rows) -> Optional[Dict[str, torch.Tensor]]:
         """The updates of consecutive minibatches, ``idx_rows`` [M, B] int64 (or a list of index tensors): the loop of ``step_from``, bit
         for bit (the program has one lane and one graph per step: there is no boundary between two lanes to save).  -> the last report."""
-        out = None
-        for r in idx_rows:
-            out = self.step_from(buf, r)
-        return out
+        return self._step_rows(buf, idx_rows)
 
     @torch.no_grad()
     def evaluate(self, buf: RolloutBuffer, idx: torch.Tensor) -> Dict[str, torch.Tensor]:
@@ -356,14 +258,7 @@ class BCUpdater:
         if self._released:
             raise RuntimeError("this BCUpdater was released: its buffers no longer hold the actor's parameters")
         actor = self.loss_module.actor_network
-        if self.flat.is_cuda:
-            torch.cuda.current_stream().synchronize()
-        if int(self.step_dev) != self.steps:
-            raise RuntimeError(f"the device-side step count is {int(self.step_dev)}, the host's {self.steps}: an update failed while it was "
-                               "issued; this state cannot be resumed bit for bit")
-        cpu = lambda t: t.detach().cpu().clone()
-        return {"version": ck.VERSION, "layout": ck.layout([("actor.", actor)], self.flat), "flat": cpu(self.flat), "exp_avg": cpu(self.exp_avg),
-                "exp_avg_sq": cpu(self.exp_avg_sq), "steps": int(self.steps), "lr": self._lr, "hyper": self._saved_hyper(),
+        return {"version": ck.VERSION, "layout": ck.layout([("actor.", actor)], self.flat), **self._flat_state(), "hyper": self._saved_hyper(),
                 "algorithm": {"loss": type(self.loss_module).__name__, "objective": self.loss_module.objective}, "stats": cpu(self.stats),
                 "actor": {k: cpu(v) for k, v in actor.state_dict().items()}, "data": {"actor": ck.data_state(actor.hyper_data)}}
 
@@ -376,9 +271,7 @@ class BCUpdater:
         if self._released:
             raise RuntimeError("this BCUpdater was released: build a new one and load into it")
         actor = self.loss_module.actor_network
-        if sd["layout"] != ck.layout([("actor.", actor)], self.flat) or sd["flat"].numel() != self.flat.numel():
-            raise ValueError(f"the saved parameter layout is not this updater's ({len(sd['layout'])} parameters, {sd['flat'].numel()} floats "
-                             f"against {len(self.params)}, {self.flat.numel()})")
+        self._check_flat_state(sd, [("actor.", actor)])
         odd = ck.differing(sd["hyper"], self._saved_hyper())
         if odd:
             raise ValueError("the saved run's hyper-parameters differ: " + ", ".join(f"{k} saved {sd['hyper'].get(k)!r}, here "
@@ -388,24 +281,15 @@ class BCUpdater:
                 raise ValueError(bad)
         with torch.no_grad():
             actor.load_state_dict(sd["actor"])
-            self.flat.copy_(sd["flat"])
-            self.exp_avg.copy_(sd["exp_avg"])
-            self.exp_avg_sq.copy_(sd["exp_avg_sq"])
-            self.steps = int(sd["steps"])
-            self.step_dev.fill_(self.steps)
-            self._lr = float(sd["lr"])
-            self.lr_dev.fill_(self._lr)
+            self._load_flat_state(sd)
             self.stats.copy_(sd["stats"])
             ck.load_data_state(actor.hyper_data, sd["data"]["actor"], self.flat.device)
-        if not ck.settle_calibration(actor):
-            self._eager_sizes = set()   # (saved before the first training forward: the next step calibrates, which no capture allows)
+        self._settle_calibration(actor)
 
     def release(self):
-        """End of the cloning: every parameter becomes an ordinary tensor again (its values kept, its ``.grad`` dropped) and the recorded
-        programs are forgotten.  A ``PolicyUpdater`` built afterwards on the same actor finds the cloned values."""
-        for p in self.params:
-            p.data = p.data.clone()
-            p.grad = None
+        """End of the cloning (``FlatUpdater.release``), and the recorded programs are forgotten.  A ``PolicyUpdater`` built afterwards
+        on the same actor finds the cloned values."""
+        super().release()
         self._programs, self._released = {}, True
 
 
@@ -430,14 +314,7 @@ class BehaviorCloner:
 
     def __init__(self, updater: BCUpdater, spec, data: RolloutBuffer, mini_batch_size: int, train_fraction: float = 0.8,
                  sampling: str = "env_aligned", drop_last: bool = False, seed: int = 0, allow_stale_topology: bool = False):
-        if sampling not in ("env_aligned", "uniform"):
-            raise ValueError(sampling)
-        infos = (getattr(spec, "obs_names", None) or {}).get("infos", ())
-        ragged = any(n in infos for n in ("object_num_points", "links_num_points"))
-        if sampling == "uniform" and ragged and not allow_stale_topology:
-            raise ValueError("uniform sampling pairs the topology cached per batch size with rows of other environments; this task has "
-                             "ragged per-sample point counts (object_num_points / links_num_points): pass allow_stale_topology=True to "
-                             "reproduce the reference quirk")
+        check_sampling(spec, sampling, allow_stale_topology)
         self.updater, self.spec, self.data = updater, spec, data
         self.N, self.T = data.N, data.T
         self.n_train = int(train_fraction * self.N)   # behavior_cloning.py:81 on the row-major [N, T] rollout
@@ -453,12 +330,6 @@ class BehaviorCloner:
         self.epochs_done = 0   # epochs fitted so far, over every ``fit`` call (and a resumed run's: state_dict)
         self.device = next(iter(data.data.values())).device
 
-    def _generator(self):
-        if self.gen is None:
-            self.gen = torch.Generator(device=self.device)
-            self.gen.manual_seed(self.seed)
-        return self.gen
-
     def train_rows(self) -> torch.Tensor:
         """The training rows of the flattened [N*T] rollout: the first n_train environments, row-major."""
         return torch.arange(self.n_train * self.T, device=self.device)
@@ -473,14 +344,14 @@ class BehaviorCloner:
         """The index tensors (int64, into the flattened rollout) of one epoch's minibatches: every training row exactly once, the short
         last minibatch kept unless ``drop_last``."""
         mbs, n, T = self.mini_batch_size, self.n_train, self.T
+        self.gen = seeded_generator(self.gen, self.seed, self.device)
         if self.sampling == "uniform":
-            perm = torch.randperm(n * T, device=self.device, generator=self._generator())
+            perm = torch.randperm(n * T, device=self.device, generator=self.gen)
             out = [perm[i:i + mbs] for i in range(0, n * T, mbs)]
         else:
             k = mbs // n
-            perm = torch.argsort(torch.rand(n, T, device=self.device, generator=self._generator()), dim=1)   # per environment, of its time steps
-            idx = (torch.arange(n, device=self.device)[:, None] * T + perm).t().contiguous()                 # [T, n]
-            out = [idx[j:j + k].reshape(-1) for j in range(0, T, k)]                                          # k columns, column after column
+            idx = env_aligned_rows(n, T, self.gen, self.device)         # [T, n]
+            out = [idx[j:j + k].reshape(-1) for j in range(0, T, k)]   # k columns, column after column
         if self.drop_last and out and out[-1].numel() < mbs:
             out.pop()
         return out

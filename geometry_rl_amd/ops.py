@@ -258,7 +258,7 @@ FUSE_HEAD = True
 FUSE_TAIL_PRE = True
 SIGNAL_IN_KERNEL = True   # False: lane signals as 4-byte copy launches of their own
 HEAD = None            # a HeadLaunch while an actor forward that supports it is being issued (policy.GNNGaussianPolicyDiag.forward_diag)
-TAIL_PRE = None        # a dict while PolicyUpdater issues the actor's backward: the first of {lift backward, fiber-basis backward} waits here
+TAIL_PRE = None        # a dict while actor_backward runs: the first of {lift backward, fiber-basis backward} waits here
 PENDING_SIGNAL = None  # (flag_dst, flag_src) int32 tensors: the next FiberConv forward launch writes flag_dst[0] = flag_src[0] when it starts
 
 
@@ -305,6 +305,18 @@ def flush_tail_pre():
     """Issue whatever is still parked (a backward in which only one of the two roles ran)."""
     if TAIL_PRE:
         _tail_pre_launch(TAIL_PRE.pop("lift", None), TAIL_PRE.pop("fiber", None))
+
+
+def actor_backward(outputs, grads):
+    """The actor's backward as the updaters issue it (flat.FlatUpdater): ``torch.autograd.backward`` with TAIL_PRE installed, so the lift's
+    and the fiber basis' backward launches -- which only feed the tail's fold -- share ONE launch, then whatever is still parked."""
+    global TAIL_PRE
+    TAIL_PRE = {} if FUSE_TAIL_PRE else None
+    try:
+        torch.autograd.backward(outputs, grads)
+        flush_tail_pre()
+    finally:
+        TAIL_PRE = None
 
 
 def _all_leaf_grads(tensors):

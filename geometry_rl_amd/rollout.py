@@ -113,6 +113,32 @@ class EpisodeStats:
         self.sums.copy_(sd["sums"])
 
 
+# ---- the sampler without replacement (train.py:128,258), shared by RolloutDriver and bc.BehaviorCloner
+def check_sampling(spec, sampling: str, allow_stale_topology: bool) -> None:
+    """ValueError for an unknown sampler, and for the uniform one on a ragged task unless ``allow_stale_topology``."""
+    if sampling not in ("env_aligned", "uniform"):
+        raise ValueError(sampling)
+    # raggedness, not the task family, is what makes the cached topology wrong for rows of other environments: rigid tasks carry a
+    # per-sample object_num_points, variable-length ropes a per-sample links_num_points (padded nodes are dropped by the CACHED counts)
+    infos = (getattr(spec, "obs_names", None) or {}).get("infos", ())
+    ragged = any(n in infos for n in ("object_num_points", "links_num_points"))
+    if sampling == "uniform" and ragged and not allow_stale_topology:
+        raise ValueError("uniform sampling pairs the topology cached per batch size with rows of other environments; this task has "
+                         "ragged per-sample point counts (object_num_points / links_num_points): pass allow_stale_topology=True to "
+                         "reproduce the reference quirk")
+
+
+def seeded_generator(gen: Optional[torch.Generator], seed: int, device) -> torch.Generator:
+    """``gen``, or while nothing has been drawn yet (None) a new generator on ``device`` seeded with ``seed``."""
+    return gen if gen is not None else torch.Generator(device=device).manual_seed(seed)
+
+
+def env_aligned_rows(n: int, T: int, gen: torch.Generator, device) -> torch.Tensor:
+    """[T, n] int64 row indices into the flattened [n*T] rollout of ``n`` environments: column i of every row belongs to environment i."""
+    perm = torch.argsort(torch.rand(n, T, device=device, generator=gen), dim=1)       # per-environment permutation of time
+    return (torch.arange(n, device=device)[:, None] * T + perm).t().contiguous()
+
+
 class RolloutDriver:
     def __init__(self, updater: "_updater.PolicyUpdater", spec, gamma: float = 0.99, lmbda: float = 0.95, ppo_epochs: int = 5,
                  seed: int = 0, mini_batch_size: Optional[int] = None, sampling: str = "env_aligned",
@@ -122,16 +148,7 @@ class RolloutDriver:
         self.gen = None
         self.seed = seed
         self.mini_batch_size = mini_batch_size   # None: one frame per environment (= num_envs)
-        if sampling not in ("env_aligned", "uniform"):
-            raise ValueError(sampling)
-        # raggedness, not the task family, is what makes the cached topology wrong for rows of other environments: rigid tasks carry a
-        # per-sample object_num_points, variable-length ropes a per-sample links_num_points (padded nodes are dropped by the CACHED counts)
-        infos = (getattr(spec, "obs_names", None) or {}).get("infos", ())
-        ragged = any(n in infos for n in ("object_num_points", "links_num_points"))
-        if sampling == "uniform" and ragged and not allow_stale_topology:
-            raise ValueError("uniform sampling pairs the topology cached per batch size with rows of other environments; this task has "
-                             "ragged per-sample point counts (object_num_points / links_num_points): pass allow_stale_topology=True to "
-                             "reproduce the reference quirk")
+        check_sampling(spec, sampling, allow_stale_topology)
         self.sampling = sampling
 
     def _settings(self) -> dict:
@@ -168,22 +185,16 @@ class RolloutDriver:
         buf.data["advantage"] = adv.reshape(N, T, 1)
         buf.data["value_target"] = tgt.reshape(N, T, 1)
 
-    # ---- sampler without replacement (train.py:128,258)
     def epoch_indices(self, N: int, T: int, device) -> torch.Tensor:
         """[T, N] int64 row indices into the flattened [N*T] rollout: row j = minibatch j."""
-        if self.gen is None:
-            self.gen = torch.Generator(device=device)
-            self.gen.manual_seed(self.seed)
-        perm = torch.argsort(torch.rand(N, T, device=device, generator=self.gen), dim=1)       # per-environment permutation of time
-        return (torch.arange(N, device=device)[:, None] * T + perm).t().contiguous()
+        self.gen = seeded_generator(self.gen, self.seed, device)
+        return env_aligned_rows(N, T, self.gen, device)
 
     def epoch_minibatches(self, N: int, T: int, device):
         """List of int64 index tensors into the flattened [N*T] rollout, one per minibatch of this epoch."""
         mbs = self.mini_batch_size or N
         if self.sampling == "uniform":
-            if self.gen is None:
-                self.gen = torch.Generator(device=device)
-                self.gen.manual_seed(self.seed)
+            self.gen = seeded_generator(self.gen, self.seed, device)
             perm = torch.randperm(N * T, device=device, generator=self.gen)
             return [perm[i:i + mbs] for i in range(0, N * T - mbs + 1, mbs)]
         if mbs % N:

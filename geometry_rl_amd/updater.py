@@ -1,13 +1,15 @@
 """The policy-update driver that replaces the inner loop of ``examples/torchrl/train.py:258-316``: ``PolicyUpdater`` lays one update out
-as a program of ``Entry`` objects and runs it eagerly or recorded into hipGraphs (program.py records and issues programs)."""
+as a program of ``Entry`` objects and runs it eagerly or recorded into hipGraphs (program.py records and issues programs).  The flat
+layout, the overwrite rule of the gradient fold, Adam on a slice, the static inputs and the flat part of a training state are
+``flat.FlatUpdater``'s, shared with behaviour cloning (bc.py); the programs, the lanes and the schedules are here."""
 import contextlib
-import ctypes
 import os
 from typing import Dict, Optional
 
 import torch
 
 from . import hip, ops
+from .flat import FlatUpdater, _job_arrays, cpu
 from .program import Entry, capture, execute, record  # noqa: F401  (capture: re-exported, the collector-side actor's name for it)
 
 _CRITIC_GROUPS = {}   # (id of the actor lane's process group, its ranks) -> the critic lane's communicator
@@ -25,14 +27,7 @@ def total_network_updates(total_frames: int, frames_per_batch: int, ppo_epochs: 
     return (total_frames // frames_per_batch) * ppo_epochs * (frames_per_batch // mini_batch_size)
 
 
-def _job_arrays(jobs):
-    """[(destination pointer, source pointer, bytes)] as the three C arrays and the count that grl_copy_many / grl_gather_rows_many take."""
-    n = len(jobs)
-    return ((ctypes.c_void_p * n)(*[j[0] for j in jobs]), (ctypes.c_void_p * n)(*[j[1] for j in jobs]),
-            (ctypes.c_longlong * n)(*[j[2] for j in jobs]), n)
-
-
-class PolicyUpdater:
+class PolicyUpdater(FlatUpdater):
     """One policy-update step of a TRPLLoss, a ClipPPOLoss2 or a KLPENPPOLoss = loss forward, actor + critic backward, optional clip_grad_norm_ per network, two Adam(lr,
     eps=1e-5) steps (train.py:279-316).  Parameters of both networks live in ONE flat fp32 buffer (gradients likewise), so a
     data-parallel run needs a single RCCL all-reduce of the gradient per step and Adam is a single kernel per optimizer.
@@ -97,48 +92,24 @@ class PolicyUpdater:
         self.form_by_size, self.form_times = {}, {}
 
         self.allow_eager_fallback = allow_eager_fallback   # False: a failed hipGraph capture raises instead of degrading silently
-        self.mode = "graph" if use_graph else "eager"      # what actually runs (bench.py reports it)
         self._hyper = dict(eps=eps, betas=tuple(betas), clip=clip_grad_norm, max_norm=max_grad_norm)
-        a = [p for p in loss_module.actor_network.parameters() if p.requires_grad]
-        c = [p for p in loss_module.critic_network.parameters() if p.requires_grad]
-        self.params = a + c
-        pad4 = lambda k: (k + 3) & ~3   # every parameter starts 16-byte aligned (vector loads in the weight-staging prologues)
-        self.n_actor = sum(pad4(p.numel()) for p in a)
-        n = sum(pad4(p.numel()) for p in self.params)
-        dev = self.params[0].device
-        self.flat = torch.zeros(n, device=dev, dtype=torch.float32)
-        # the flat gradient, with room IN FRONT of it for the ranks' loss records ([world][14] (hi, lo) float pairs, grl_trpl_fold_record_pairs):
-        # data parallel, ``gbuf[:rec + n_actor]`` is ONE all-reduce -- the records ride on the actor's gradient slice
         if group is not None:
             import torch.distributed as dist
             self.rank, n_ranks = dist.get_rank(group), dist.get_world_size(group)
         else:
             self.rank, n_ranks = 0, 1
-        self._rec = 28 * n_ranks
-        self.gbuf = torch.zeros(self._rec + n, device=dev, dtype=torch.float32)
-        self.gflat = self.gbuf[self._rec:]
-        off = 0
-        for p in self.params:
-            k = p.numel()
-            self.flat[off:off + k].copy_(p.data.reshape(-1))
-            p.data = self.flat[off:off + k].view_as(p)
-            p.grad = self.gflat[off:off + k].view_as(p)
-            off += pad4(k)
-        self.exp_avg = torch.zeros_like(self.flat)
-        self.exp_avg_sq = torch.zeros_like(self.flat)
-        self.steps = 0
-        self.step_dev = torch.zeros(1, device=dev, dtype=torch.int32)  # optimizer step, device side (graph replays)
+        # the flat gradient has room IN FRONT of it for the ranks' loss records ([world][14] (hi, lo) float pairs, grl_trpl_fold_record_pairs):
+        # data parallel, ``gbuf[:rec + n_actor]`` is ONE all-reduce -- the records ride on the actor's gradient slice
+        nets = (loss_module.actor_network, loss_module.critic_network)
+        super().__init__(nets[0], [[p for p in net.parameters() if p.requires_grad] for net in nets], lr, use_graph, record_floats=28 * n_ranks)
+        dev = self.flat.device
         self.step_dev_c = torch.zeros(1, device=dev, dtype=torch.int32)  # the same count kept by the critic's lane
         self.lane_flag = torch.zeros(1, device=dev, dtype=torch.int32)   # step count of the last "first edge convolution finished" signal
-        # learning rate, device side: the recorded Adam launches read it, so an annealed rate (train.py:264-271 writes
-        # ``group["lr"] = lr * alpha`` before every iteration; configs/algorithm/optim/default.yaml:5) takes effect under replay
-        self.lr_dev = torch.full((1,), float(lr), device=dev, dtype=torch.float32)
         # entropy bounds, device side (TRPL with entropy control): one entry per step of a launch.  The fused loss launch of step j of a
         # launch reads entry j; the host fills the entries stream-ordered in front of the launch (_entropy_prepare), so recorded programs
         # replay a moving bound unchanged -- the bound is data, like lr_dev
         self.BETA_SLOTS = 64
         self.beta_table = torch.zeros(self.BETA_SLOTS, device=dev, dtype=torch.float64)
-        self._lr = float(lr)
         # the per-update schedule (class docstring): entry j of sched_table = (lr, clip epsilon) of step j of the program about to run.
         # ``_lr`` is then the rate of the last issued update, ``_base_lr`` the rate the schedule starts from
         self.anneals_lr = bool(anneal_lr)
@@ -156,29 +127,11 @@ class PolicyUpdater:
         self.stats_actor = torch.zeros(15, device=dev, dtype=torch.float64) if self.track_stats else None
         self.stats_critic = torch.zeros(2, device=dev, dtype=torch.float64) if self.track_stats else None
         self._stats_one_stream = False   # the running program is _plan_one_stream: its report carries the critic loss
-        self.use_graph = use_graph
-        if use_graph and getattr(loss_module.actor_network, "stock_torch_gnn", False):
-            # config 1's baseline actor with kernels="torch" is a stock torch.nn.TransformerEncoder: its launches are torch's own (rocBLAS / hipBLASLt
-            # workspaces are not capture-safe on this stack), so that step is issued eagerly -- it is the reference's CPU-sized
-            # plumbing case (64 envs x 32 steps), not a throughput path
-            self.use_graph, self.mode = False, "eager (stock-torch transformer actor: not recorded)"
         self._drop_recordings()                    # (nothing is recorded yet: _program, _static, _epoch)
-        self._eager_sizes = set()                  # minibatch sizes whose first, eager step has run (_step)
         self._cstream = None                       # the critic lane's stream, made when a program first needs it (_critic_stream)
         self._loss_ptr = self._loss_storage()      # (_check_loss_storage)
         self._calib_synced = False                 # (_check_calibrated)
-        # Leaf gradients are WRITTEN by the one fold launch at the end of the backward pass (ops.flush_deferred_grads(overwrite=True)) instead
-        # of accumulated into a zeroed buffer: no per-step zeroing launch.  Valid while EVERY leaf gradient of the step comes through the
-        # fold queue: not with the stock torch transformer actor or an attention gate that runs as torch modules (torch's AccumulateGrad adds
-        # into .grad; gate_kernels="hip" hands the gate's gradients to the queue like every other) -- and checked on the first eager step of
-        # every updater (``_check_overwrite_coverage``).
         gnn = getattr(loss_module.actor_network, "gnn", None)
-        # The transformer actor on HIP kernels (kernels="hip") keeps the accumulate mode too: ``cls_token`` and the template encoder layer
-        # take no part in the forward, so no fold ever writes their gradients -- they stay the zeros of the buffer, as on the stock path.
-        self._fold_overwrite = (not getattr(loss_module.actor_network, "post_fc", False)
-                                and not any(getattr(mod, "attention", False) and getattr(mod, "gate_kernels", "torch") == "torch"
-                                            for mod in (gnn.modules() if gnn is not None else [])))
-        self._overwrite_checked = not self._fold_overwrite
         if gnn is not None and hasattr(gnn, "ponita"):   # EMPN key / query attention: one rank only (ponita_gcn.check_attention_group)
             from .ponita_gcn import check_attention_group
             check_attention_group(getattr(gnn, "attention", False), group)
@@ -217,17 +170,10 @@ class PolicyUpdater:
 
     # ---- hyper-parameters.  ``lr`` lives in device memory (no re-recording); the others are baked into recorded launches as
     #      scalars, so changing one drops the recorded program (it is re-recorded by the next step)
-    @property
-    def lr(self) -> float:
-        return self._lr
-
-    @lr.setter
-    def lr(self, value: float):
+    def _schedule_takes_lr(self, value: float) -> bool:
         if self.anneals_lr:   # the schedule's base rate: data of the next fill (_schedule_prepare), no recorded launch reads it
-            self._base_lr = float(value)
-        elif float(value) != self._lr:
-            self._lr = float(value)
-            self.lr_dev.fill_(self._lr)
+            self._base_lr = value
+        return self.anneals_lr
 
     def _set_hyper(self, key, value):
         if self._hyper[key] != value:
@@ -392,16 +338,9 @@ class PolicyUpdater:
                 ib.lins[0].weight, ib.lins[0].bias, ib.norms[0].weight, ib.norms[0].bias, ib.lins[1].weight, ib.lins[1].bias,
                 vf.final.weight, vf.final.bias)
 
-    def _adam(self, st, lo, hi, i_, step_dev=None):
-        """One optimizer's step over its slice [lo, hi) of the flat buffer (train.py:308-316); i_: 0 actor, 1 critic (clip workspace slot)."""
-        coef = None
-        if self.clip:  # train.py:308-310
-            sq = st["zw"][23 + i_:24 + i_]
-            coef = torch.empty(1, device=self.flat.device, dtype=torch.float32)
-            hip.call("grl_clip_coef", self.gflat[lo:hi], hi - lo, self.max_norm, sq, coef)
-        hip.call("grl_adam_step_dev", self.flat[lo:hi], self.gflat[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
-                 hi - lo, st.get("lr", self.lr_dev), *self.betas, self.eps,
-                 step_dev if step_dev is not None else self.step_dev, coef, 1.0)
+    def _adam_of(self, st, lo, hi, i_, step_dev=None):
+        """``_adam`` over [lo, hi) with the step's own rate (a per-update schedule); i_: 0 actor, 1 critic (the slot of the step's clip workspace)."""
+        self._adam(lo, hi, lr=st.get("lr", self.lr_dev), step_dev=self.step_dev if step_dev is None else step_dev, sq=st["zw"][23 + i_:24 + i_])
 
     def _prep(self, batch, st, zero=None):
         """Inputs of a step: the batch with its variance diagonal, the two networks' observation lists, the fp64 workspace
@@ -433,14 +372,7 @@ class PolicyUpdater:
             fold_, _mx, dloc, dsigma, _ = m.launch(loc, sigma, None, st["b"], adv, sums=sums, maxes=maxes, defer_fold=True,
                                                    adv_local=adv_local, beta=st["beta"], eps=st.get("eps"))
         st.update(loc=loc.detach(), sigma=sigma.detach())
-        # the lift's and the fiber basis' backward launches only feed the tail's fold: the first of the two waits for the other and they
-        # share ONE launch (ops._tail_pre_offer)
-        ops.TAIL_PRE = {} if ops.FUSE_TAIL_PRE else None
-        try:
-            torch.autograd.backward([loc, sigma], [dloc, dsigma])
-            ops.flush_tail_pre()
-        finally:
-            ops.TAIL_PRE = None
+        ops.actor_backward([loc, sigma], [dloc, dsigma])
         return fold_
 
     @staticmethod
@@ -503,7 +435,7 @@ class PolicyUpdater:
                 # the two optimizers of train.py:120-127 have identical hyper-parameters and schedules: without per-network gradient
                 # clipping their two Adam steps are ONE launch over the flat buffer (element-wise: the same numbers)
                 for i_, (lo, hi) in enumerate(((0, na), (na, n)) if self.clip else ((0, n),)):
-                    self._adam(st, lo, hi, i_)
+                    self._adam_of(st, lo, hi, i_)
                 o14 = torch.empty(14, device=self.flat.device, dtype=torch.float32) if (self.track_stats or m.keeps_report) else None
                 a_loss, c_loss, mt = loss_values(m, st["sums"], st["maxes"], out=o14)
                 st["lv_main"], st["c_loss"] = (a_loss, mt), c_loss
@@ -511,10 +443,6 @@ class PolicyUpdater:
                 self._stats_add(o14, self.stats_actor)   # (one call: the report carries the critic loss)
 
         return [Entry("run", s0), Entry("run", s1), Entry("run", s2), Entry("run", s3), Entry("run_host", lambda: self._finish(st))]
-
-    def _tail_args(self, st, lo, hi, cnt):
-        return dict(grads=self.gflat[lo:hi], params=self.flat[lo:hi], exp_avg=self.exp_avg[lo:hi], exp_avg_sq=self.exp_avg_sq[lo:hi],
-                    lr_dev=st.get("lr", self.lr_dev), betas=self.betas, eps=self.eps, step_dev=cnt)
 
     def _signal_lane(self):
         """lane_flag[0] = step_dev[0] on the current stream (one tiny launch): the critic's lane may start this step."""
@@ -526,25 +454,24 @@ class PolicyUpdater:
         the critic's lane is signalled right behind the actor's first edge convolution -- by the fiber convolution launched behind it, which
         writes the flag when it starts (ops.FiberConv, ops.SIGNAL_IN_KERNEL), or else by a copy launch of its own."""
         hd = self.loss_module.actor_network.hyper_data
-        hd.bump_next = self.step_dev
-        if gate:
-            def signal():
-                if hd.bump_next is not None:   # the step count has not been advanced yet (a calibrating pass in front of the step's own
-                    return False               # forward): not this edge convolution
-                if ops.SIGNAL_IN_KERNEL:
-                    ops.PENDING_SIGNAL = (self.lane_flag, self.step_dev)
-                else:
-                    self._signal_lane()
-                return True
-            ops.AFTER_EDGE_HOOK = signal
-        try:
-            yield
-        finally:
-            ops.AFTER_EDGE_HOOK = None
-            unsent, ops.PENDING_SIGNAL = ops.PENDING_SIGNAL, None
-        if unsent is not None:   # (no fiber convolution followed the edge convolution: send the signal by itself)
-            self._signal_lane()
-        assert hd.bump_next is None, "the actor's feature launch did not take the step count"
+        with self._count_rides(hd):
+            if gate:
+                def signal():
+                    if hd.bump_next is not None:   # the step count has not been advanced yet (a calibrating pass in front of the step's own
+                        return False               # forward): not this edge convolution
+                    if ops.SIGNAL_IN_KERNEL:
+                        ops.PENDING_SIGNAL = (self.lane_flag, self.step_dev)
+                    else:
+                        self._signal_lane()
+                    return True
+                ops.AFTER_EDGE_HOOK = signal
+            try:
+                yield
+            finally:
+                ops.AFTER_EDGE_HOOK = None
+                unsent, ops.PENDING_SIGNAL = ops.PENDING_SIGNAL, None
+            if unsent is not None:   # (no fiber convolution followed the edge convolution: send the signal by itself)
+                self._signal_lane()
 
     def _critic_wait(self):
         """A gated critic lane's first launch: waits until the actor's lane has signalled THIS step (flag >= the lane's finished steps + 1)."""
@@ -636,14 +563,14 @@ class PolicyUpdater:
                         o14 = torch.empty(14, device=self.flat.device, dtype=torch.float32)
                         ent = m.entropy_coef if m.entropy_bonus else 0.0
                         # (gated: the lane's closing signal -- see below -- rides on this launch)
-                        done = ops.fold_adam_report(ow, self._tail_args(st, 0, na, self.step_dev),
+                        done = ops.fold_adam_report(ow, self._tail_args(0, na, st.get("lr", self.lr_dev), self.step_dev),
                                                     dict(slots=fold_.slots, batch=fold_.batch, sums=fold_.sums, maxes=fold_.maxes,
                                                          ent_coef=ent, out14=o14), signal=(self.lane_flag, self.step_dev) if (gate and ops.SIGNAL_IN_KERNEL) else None)
                         if done:
                             a_loss, mt = m.report_dict(o14)
                     if not done:
                         ops.flush_deferred_grads(overwrite=ow)
-                        self._adam(st, 0, na, 0)
+                        self._adam_of(st, 0, na, 0)
                         keep = self.track_stats or m.keeps_report   # (the report is read again behind this launch)
                         if keep and o14 is None:
                             o14 = torch.empty(14, device=self.flat.device, dtype=torch.float32)
@@ -660,9 +587,9 @@ class PolicyUpdater:
             with ops.deferred_folds(), torch.no_grad():
                 for stage in stages:
                     stage()
-                if not (fuse_tail and ops.fold_adam_report(ow, self._tail_args(st, na, n_all, self.step_dev_c))):
+                if not (fuse_tail and ops.fold_adam_report(ow, self._tail_args(na, n_all, st.get("lr", self.lr_dev), self.step_dev_c))):
                     ops.flush_deferred_grads(overwrite=ow)
-                    self._adam(st, na, n_all, 1, self.step_dev_c)
+                    self._adam_of(st, na, n_all, 1, self.step_dev_c)
                 self._stats_add(st["c_loss"], self.stats_critic)
 
         wait = [Entry("run", self._critic_wait, "s", "critic_gate_wait")] if gate else []
@@ -733,7 +660,7 @@ class PolicyUpdater:
             with torch.no_grad():
                 ent = m.entropy_coef if m.entropy_bonus else 0.0
                 if self.clip:   # (the clip coefficient needs the reduced gradient's norm first: the separate launches)
-                    self._adam(st, 0, na, 0)
+                    self._adam_of(st, 0, na, 0)
                     hip.call("grl_trpl_report_record_pairs", self.gbuf[:self._rec], world, st["sums"], st["maxes"], ent, o14)
                 else:           # Adam on the reduced slice + the reported values of the delivered records: ONE launch
                     hip.call("grl_adam_report_record_pairs", self.flat[:na], self.gflat[:na], self.exp_avg[:na], self.exp_avg_sq[:na], na,
@@ -752,7 +679,7 @@ class PolicyUpdater:
 
         def q_tail():
             with torch.no_grad():
-                self._adam(st, na, n_all, 1, self.step_dev_c)
+                self._adam_of(st, na, n_all, 1, self.step_dev_c)
                 st["c_loss"] = st["vl"][1].float()   # (the all-reduced sum of the ranks' shares, already divided by B_global)
                 self._stats_add(st["c_loss"], self.stats_critic)
 
@@ -853,23 +780,6 @@ class PolicyUpdater:
         st = self._st = {}
         self._program = record(self._plan(self._static, st))
 
-    def _refresh_static(self, batch):
-        """Copy the minibatch into the static input buffers the recorded graphs read: one launch for all tensors."""
-        jobs = []
-        for k, v in self._static.items():
-            src = batch[k]
-            if src is v:
-                continue
-            if src.shape != v.shape:
-                raise ValueError(f"minibatch tensor '{k}' has shape {tuple(src.shape)}, the recorded step was captured for "
-                                 f"{tuple(v.shape)}: call PolicyUpdater.reset_graph() before changing the minibatch size")
-            if src.dtype != v.dtype or not src.is_contiguous() or src.device != v.device:
-                v.copy_(src)  # host-resident / strided / other dtype: the ordinary path
-            else:
-                jobs.append((v.data_ptr(), src.data_ptr(), v.numel() * v.element_size()))
-        for i in range(0, len(jobs), 24):
-            hip.call("grl_copy_many", *_job_arrays(jobs[i:i + 24]))
-
     def step_from(self, buf, idx: torch.Tensor) -> Dict[str, torch.Tensor]:
         """One update on the minibatch made of rows ``idx`` (device int64 [B]) of a device-resident ``rollout.RolloutBuffer``.
         With recorded graphs the rows are gathered by ONE launch straight into the static input buffers."""
@@ -883,14 +793,6 @@ class PolicyUpdater:
             return self.step(buf.rows(idx, keys))
         hip.call("grl_gather_rows_many", *_job_arrays(jobs), idx, idx.numel())
         return self.step(self._static)
-
-    @staticmethod
-    def _gather_jobs(static, buf, keys):
-        """The jobs of one grl_gather_rows_many launch, rows of the rollout's tensors ``keys`` into ``static``; None where one does not fit."""
-        src = [buf.flat(k) for k in keys]
-        if any(static[k].dtype != v.dtype or static[k][0].numel() != v.shape[1] for k, v in zip(keys, src)):
-            return None
-        return [(static[k].data_ptr(), v.data_ptr(), v.shape[1] * v.element_size()) for k, v in zip(keys, src)]
 
     # ---- several minibatch steps per launch (round 6).  A shard-sized step is ~35 dependent launches of 5-15 us; what it pays on top of
     #      them is the boundary of every replay (~13 us between two graph launches on a stream, ~7 us between the eager minibatch gather
@@ -1026,12 +928,6 @@ class PolicyUpdater:
                 j += U
         return self._step_rows(buf, idx_rows[j:], out)
 
-    def _step_rows(self, buf, rows, out=None):
-        """``step_from`` on the rows of ``rows`` [M, B], in order -> the last step's loss dict (``out`` where M = 0)."""
-        for r in rows:
-            out = self.step_from(buf, r)
-        return out
-
     TUNE_ROUNDS = 2   # alternating blocks per form in _tune_form
 
     def tune_minibatches(self, U: Optional[int] = None) -> int:
@@ -1091,6 +987,9 @@ class PolicyUpdater:
         return dict(self._hyper, anneals_lr=self.anneals_lr, anneals_eps=self.anneals_eps, total_network_updates=self.total_network_updates,
                     track_stats=self.track_stats)
 
+    def _named_groups(self) -> list:
+        return [("actor.", self.loss_module.actor_network), ("critic.", self.loss_module.critic_network)]
+
     def _data_objects(self) -> dict:
         """The ``HyperData`` of either network: each keeps noise words and cached topologies."""
         m = self.loss_module
@@ -1106,19 +1005,12 @@ class PolicyUpdater:
         from . import checkpoint as ck
         m = self.loss_module
         self.join_lanes()
-        if self.flat.is_cuda:
-            torch.cuda.current_stream().synchronize()
-        if int(self.step_dev) != self.steps:
-            raise RuntimeError(f"the device-side step count is {int(self.step_dev)}, the host's {self.steps}: an update failed while it was "
-                               "issued; this state cannot be resumed bit for bit")
-        cpu = lambda t: t.detach().cpu().clone()
+        flat_state = self._flat_state()   # (the synchronisation, and the refusal)
         proj = getattr(m, "projection", None)
         ent = getattr(proj, "initial_entropy", None)
         return {
-            "version": ck.VERSION,
-            "layout": ck.layout([("actor.", m.actor_network), ("critic.", m.critic_network)], self.flat), "n_actor": int(self.n_actor),
-            "flat": cpu(self.flat), "exp_avg": cpu(self.exp_avg), "exp_avg_sq": cpu(self.exp_avg_sq),
-            "steps": int(self.steps), "lr": self._lr, "base_lr": self._base_lr,
+            "version": ck.VERSION, "layout": ck.layout(self._named_groups(), self.flat), "n_actor": int(self.n_actor),
+            **flat_state, "base_lr": self._base_lr,
             "hyper": self._saved_hyper(), "algorithm": self._algorithm(),
             "device_scalars": {k: cpu(t) for k, t in m.device_scalars.items()},
             "initial_entropy": None if ent is None else cpu(torch.as_tensor(ent)),
@@ -1149,11 +1041,9 @@ class PolicyUpdater:
         from . import checkpoint as ck
         m = self.loss_module
         ck.check_version(sd, "PolicyUpdater.load_state_dict")
-        mine = ck.layout([("actor.", m.actor_network), ("critic.", m.critic_network)], self.flat)
-        if sd["layout"] != mine or sd["n_actor"] != self.n_actor or sd["flat"].numel() != self.flat.numel():
-            odd = [a[0] for a, b in zip(sd["layout"], mine) if a != b][:3]
-            raise ValueError(f"the saved parameter layout is not this updater's ({len(sd['layout'])} parameters, {sd['flat'].numel()} floats, "
-                             f"n_actor {sd['n_actor']} against {len(mine)}, {self.flat.numel()}, {self.n_actor}; first differences {odd})")
+        self._check_flat_state(sd, self._named_groups())
+        if sd["n_actor"] != self.n_actor:
+            raise ValueError(f"the saved parameter layout is not this updater's (n_actor {sd['n_actor']} against {self.n_actor})")
         if sd["algorithm"] != self._algorithm():
             raise ValueError(f"the saved run's algorithm differs at {ck.differing(sd['algorithm'], self._algorithm())}: saved {sd['algorithm']}, "
                              f"this updater {self._algorithm()}")
@@ -1176,15 +1066,11 @@ class PolicyUpdater:
         with torch.no_grad():
             m.actor_network.load_state_dict(sd["actor"])    # (through the views of ``flat``; the policy re-inspects its latches: they are saved true)
             m.critic_network.load_state_dict(sd["critic"])
-            self.flat.copy_(sd["flat"])
-            self.exp_avg.copy_(sd["exp_avg"])
-            self.exp_avg_sq.copy_(sd["exp_avg_sq"])
-            k = int(sd["steps"])
-            self.steps = m._global_steps = k
-            for t in (self.step_dev, self.step_dev_c, self.lane_flag):
-                t.fill_(k)
-            self._lr, self._base_lr = float(sd["lr"]), float(sd["base_lr"])
-            self.lr_dev.fill_(self._lr)
+            self._load_flat_state(sd)
+            m._global_steps = self.steps
+            for t in (self.step_dev_c, self.lane_flag):
+                t.fill_(self.steps)
+            self._base_lr = float(sd["base_lr"])
             for name, t in m.device_scalars.items():
                 t.copy_(sd["device_scalars"][name])
             proj = getattr(m, "projection", None)
@@ -1199,8 +1085,7 @@ class PolicyUpdater:
             for name, hd in self._data_objects().items():
                 ck.load_data_state(hd, sd["data"][name], dev)
         self._calib_synced = True   # (the latches and the kernels are the saved run's: no replica calibrates again)
-        if not ck.settle_calibration(m.actor_network):
-            self._eager_sizes = set()   # (saved before the first training forward: the next step calibrates, which no capture allows)
+        self._settle_calibration(m.actor_network)
         if not self.form_by_size:
             self.form_by_size = dict(sd["form_by_size"])
 
@@ -1228,16 +1113,14 @@ class PolicyUpdater:
         self._entropy_prepare(batch, n)
         lr_before = self._lr
         self._schedule_prepare(n)
-        self.steps += n
         try:
-            return issue()
+            # ``_counted`` takes the count back when issuing raised.  The critic lane's gate waits until the DEVICE-side step count (advanced by
+            # the actor's feature launch) reaches the HOST's: a step that raised before that launch was enqueued must not leave the host ahead
+            # for good -- the next step's wait would never be satisfied and the process would hang on the device instead of raising (ADVICE
+            # r5).  After a failure the host count is at most the device's: the gate may then release early, it can never be stuck.
+            return self._counted(n, issue)
         except BaseException:
             self._lr = lr_before   # (a per-update schedule: the rate of the last update that WAS issued)
-            # the critic lane's gate waits until the DEVICE-side step count (advanced by the actor's feature launch) reaches the HOST's: a
-            # step that raised before that launch was enqueued must not leave the host ahead for good -- the next step's wait would
-            # never be satisfied and the process would hang on the device instead of raising.  After a failure the host count
-            # is at most the device's: the gate may then release early, it can never be stuck.
-            self.steps -= n
             raise
 
     def step(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -1251,26 +1134,9 @@ class PolicyUpdater:
     def _step(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         B = next(v.shape[0] for v in batch.values() if torch.is_tensor(v))
         self._check_loss_storage()
-        if not self.use_graph or B not in self._eager_sizes:   # the first step of a minibatch size always runs eagerly: it builds the
-            self._eager_sizes.add(B)                           # cached topology of that size and the kernels' one-time attributes
+        if self._eager_first(B):
             st = {}
-            hooks, torch_fed = [], []
-            if not self._overwrite_checked:
-                # overwrite mode (no zeroing launch) is only right while NO leaf gradient arrives through torch's AccumulateGrad, which would
-                # add into a never-zeroed .grad: a hook on a leaf fires exactly for such a gradient (ops' backward functions hand None to
-                # autograd for the leaves whose slabs they queue).  Checked once, on the first eager step.
-                hooks = [p.register_hook(lambda g, i=i: torch_fed.append(i) if g is not None else None) for i, p in enumerate(self.params)]   # (autograd calls a leaf hook with None when a backward function returned no gradient for it)
-            try:
-                self._execute(self._plan(batch, st))
-            finally:
-                for h in hooks:
-                    h.remove()
-            if hooks:
-                self._overwrite_checked = True
-                if torch_fed:
-                    raise RuntimeError(f"{len(set(torch_fed))} parameter(s) received their gradient from torch autograd instead of the fold queue "
-                                       "while PolicyUpdater runs in overwrite mode (their .grad is never zeroed): this model must be added to "
-                                       "the exceptions of PolicyUpdater._fold_overwrite")
+            self._first_eager(self._plan(batch, st))
             return st["out"]
         if self._program is not None and (any(self._static[k].shape != batch[k].shape for k in self._static if k in batch)
                                           or ("adv_stats" in batch) != ("adv_stats" in self._static)):
@@ -1290,7 +1156,8 @@ class PolicyUpdater:
                       "(allow_eager_fallback=True)", file=sys.stderr)
                 self.use_graph, self._program, self._static, self.mode = False, None, None, "eager (graph capture failed)"
                 return self._step(batch)
-        self._refresh_static(batch)
+        self._refresh(self._static, batch, "the recorded step was captured for {}: call PolicyUpdater.reset_graph() before changing the "
+                      "minibatch size")
         self._execute(self._program)
         return self._st["out"]
 
@@ -1304,10 +1171,8 @@ class PolicyUpdater:
             torch.cuda.current_stream().wait_stream(self._cstream)
 
     def _do(self, e: Entry):
-        """Issue one entry on the current stream (tools that time entries wrap this method)."""
-        if e.kind in ("run", "run_host"):
-            e.item()
-        elif e.kind == "graph":
-            e.item.replay()
-        else:   # "sum", the programs' one collective
+        """Issue one entry on the current stream (tools that time entries wrap this method); "sum" is the programs' one collective."""
+        if e.kind == "sum":
             self.all_reduce_sum(e.item(), e.label, e.lane)
+        else:
+            super()._do(e)

@@ -49,25 +49,72 @@ def test_defaults_follow_the_reference():
     assert geometry_rl_amd.BCLoss is bc.BCLoss
 
 
-def test_flat_layout_holds_the_actor_alone():
-    """PolicyUpdater's layout rules on the actor's trainable parameters only: 16-byte aligned starts, p.data / p.grad views of the flat buffers."""
-    from geometry_rl_amd import bc
-    spec, actor = _rigid()
-    want = {k: p.detach().clone() for k, p in actor.named_parameters()}
-    upd = bc.BCUpdater(bc.BCLoss(actor))
-    params = [p for p in actor.parameters() if p.requires_grad]
-    assert [id(p) for p in upd.params] == [id(p) for p in params]
-    assert upd.flat.numel() == sum((p.numel() + 3) & ~3 for p in params) == upd.gflat.numel() == upd.exp_avg.numel() == upd.exp_avg_sq.numel()
+@pytest.mark.parametrize("which", ["bc", "policy"])
+def test_flat_layout_holds_the_actor_alone(which):
+    """FlatUpdater's layout rules under both updaters -- BCUpdater on the actor's trainable parameters only, PolicyUpdater on the actor's
+    followed by the critic's: 16-byte aligned starts, p.data / p.grad views of the flat buffers at one offset, the values kept."""
+    from geometry_rl_amd import agent, bc, graph
+    if which == "bc":
+        spec, actor = _rigid()
+        nets = {"actor": actor}
+    else:
+        torch.manual_seed(0)
+        actor, critic, _, loss = agent.build_agent(graph.rigid_spec(), agent.AgentConfig(only_upper_hemisphere=True, output_dim=2, output_dim_vec=2),
+                                                   device="cpu")
+        nets = {"actor": actor, "critic": critic}
+    named = [(f"{n}.{k}", p) for n, net in nets.items() for k, p in net.named_parameters() if p.requires_grad]
+    want = {k: p.detach().clone() for k, p in named}
+    upd = bc.BCUpdater(bc.BCLoss(actor)) if which == "bc" else agent.PolicyUpdater(loss)
+    pad4 = lambda k: (k + 3) & ~3
+    assert [id(p) for p in upd.params] == [id(p) for _, p in named]
+    assert upd.flat.numel() == sum(pad4(p.numel()) for _, p in named) == upd.gflat.numel() == upd.exp_avg.numel() == upd.exp_avg_sq.numel()
+    if which == "policy":
+        assert upd.n_actor == sum(pad4(p.numel()) for p in actor.parameters() if p.requires_grad)
+        assert upd.gbuf.numel() - upd.gflat.numel() == 28                  # one rank's loss record in front of the gradient
+        assert upd.gflat.data_ptr() - upd.gbuf.data_ptr() == 4 * 28
     lo, hi = upd.flat.data_ptr(), upd.flat.data_ptr() + 4 * upd.flat.numel()
-    for k, p in actor.named_parameters():
+    for k, p in named:
         assert lo <= p.data_ptr() < hi and (p.data_ptr() - lo) % 16 == 0, k
         assert p.grad.data_ptr() - upd.gflat.data_ptr() == p.data_ptr() - lo and p.grad.shape == p.shape, k
         assert torch.equal(p.detach(), want[k]), k
     upd.release()
-    for k, p in actor.named_parameters():
+    for k, p in named:
         assert not (lo <= p.data_ptr() < hi) and p.grad is None and torch.equal(p.detach(), want[k]), k
-    with pytest.raises(RuntimeError):
-        upd.step({})
+    if which == "bc":
+        with pytest.raises(RuntimeError):
+            upd.step({})
+
+
+def test_both_updaters_take_the_overwrite_rule_from_flat():
+    """``flat.fold_overwrite`` is the ONE rule: HEPi overwrites, the attention gate as torch modules accumulates, on HIP kernels it
+    overwrites, the transformer actor accumulates -- and both constructors give what the function gives."""
+    from geometry_rl_amd import agent, bc, flat, graph
+    small = dict(only_upper_hemisphere=True, output_dim=2, output_dim_vec=2)
+    cases = [(dict(small), True), (dict(small, aggr="AttentionalAggregation"), False),
+             (dict(small, aggr="AttentionalAggregation", attention_gate="hip"), True), (dict(small, model="transformer"), False)]
+    for kw, want in cases:
+        made = []
+        for _ in range(2):   # (an actor is laid out by one updater at a time)
+            torch.manual_seed(0)
+            made.append(agent.build_agent(graph.rigid_spec(), agent.AgentConfig(**kw), device="cpu"))
+        (actor_p, _, _, loss_p), (actor_b, *_) = made
+        assert flat.fold_overwrite(actor_p) is want, kw
+        p_upd, b_upd = agent.PolicyUpdater(loss_p), bc.BCUpdater(bc.BCLoss(actor_b))
+        assert p_upd._fold_overwrite is b_upd._fold_overwrite is want, kw
+        assert p_upd._overwrite_checked is b_upd._overwrite_checked is (not want), kw
+    assert not hasattr(bc, "fold_overwrite")
+
+
+def test_cloner_and_driver_share_one_sampler():
+    """N = 4, T = 6, minibatches of 8 (k = 2 permutation columns), seed 3: over two consecutive epochs ``BehaviorCloner`` with every
+    environment training and ``RolloutDriver`` hand out the same index tensors, element for element -- one sampler, one draw order."""
+    from types import SimpleNamespace
+    from geometry_rl_amd.rollout import RolloutDriver
+    c = _cloner(N=4, T=6, mbs=8, train_fraction=1.0, seed=3)
+    drv = RolloutDriver(SimpleNamespace(flat=torch.zeros(1)), c.spec, mini_batch_size=8, seed=3)
+    for _ in range(2):
+        mine, theirs = c.epoch_minibatches(), drv.epoch_minibatches(4, 6, "cpu")
+        assert [i.tolist() for i in mine] == [i.tolist() for i in theirs] and len(mine) == 3 and all(i.numel() == 8 for i in mine)
 
 
 def test_split_by_environment():

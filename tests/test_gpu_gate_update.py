@@ -47,7 +47,7 @@ def test_policy_update_step_gate_hip():
     assert any("gate_nn.0.weight" in k for k, p in actor.named_parameters() if p.grad is not None)
     bad, scales = oc.gradients_off_scale(actor, critic, ref_grads)
     assert not bad, bad
-    upd.step(dbatch)   # (the first eager step: _check_overwrite_coverage runs here)
+    upd.step(dbatch)   # (the first eager step: the overwrite-coverage check runs here)
     assert upd._overwrite_checked and upd._fold_overwrite
     bad = oc.first_step_params_off(actor, critic, oracle, cfg, ref_grads, scales)
     assert not bad, bad
